@@ -50,6 +50,11 @@ def parse(argv=None):
                     "started while it fits into what is left; the measured line is never optional")
     ap.add_argument("--launch-timeout", type=float, default=None, help="self-launched run (--gpus N without WORLD_SIZE): seconds before the "
                     "launcher ends its workers and reports the phase each one was in (default: --budget-s + 120)")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline: the event-timed roofline leg and the closed-form "
+                    "result check, the live counter passes, the secondary workloads (one GPU) and the CPU baseline.  Without it a run sets up, "
+                    "warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the last timed step computed as "
+                    "DIR/<name>.npy (float64, global row order; under 64 MB in all: a matrix above its share as a fixed seeded sample of its rows)")
     ap.add_argument("--probe-transport", default=None, help=argparse.SUPPRESS)  # internal: the child-process trial of one transport
     args = ap.parse_args(argv)
     if args.launch_timeout is None:

@@ -1,6 +1,7 @@
 """The order of a benchmark run: environment, rendezvous, transports (several GPUs), the default route measured in full — from there
 on a complete line is in hand — then whatever the time budget still has room for: other transports, the route search and the
-winner's measurement, counter traffic, the secondary workloads, the CPU baseline."""
+winner's measurement, the outputs of the last timed step (--dump-outputs) and, with --full, counter traffic, the secondary workloads,
+the CPU baseline."""
 import json
 import os
 import sys
@@ -34,7 +35,7 @@ def run(args, make_world=None):
     if getattr(args, "probe_transport", None):
         return transports.probe_main(args)
     for name, default in (("workload", "er"), ("app", "vanilla"), ("transport", "auto"), ("no_secondary", True), ("probe_timeout", 300.0),
-                          ("budget_s", 1200.0)):
+                          ("budget_s", 1200.0), ("full", False), ("dump_outputs", None)):
         if not hasattr(args, name):  # (tests build their own argument namespaces)
             setattr(args, name, default)
 
@@ -223,9 +224,14 @@ def run(args, make_world=None):
                 stopped_early.append("the fastest candidate (%s) was not measured in full: %.0f s left of --budget-s" % (route_name(winner), budget.left()))
 
     out = None
+    if rank == 0 and res["outputs"] is not None:
+        phases.start("dump_outputs")
+        timed.dump_outputs(args.dump_outputs, res["outputs"])
     if rank == 0:
-        phases.start("counter_traffic")
         out = finish_line(res, tuning)
+        fallback.keep(out)
+    if rank == 0 and args.full:
+        phases.start("counter_traffic")
         dur = out["roofline"]["avg_launch_ms"] * 1e-3
         traffic, traffic_source, live = None, None, None
         if n == 1 and not args.no_live_traffic and H.backend_name() == "hip-gfx950":
@@ -256,7 +262,7 @@ def run(args, make_world=None):
         fallback.keep(out)
 
     # ---- one GPU: the other workloads of the reference's harness, bounded, outside the timed region
-    if n == 1 and not args.no_secondary:
+    if n == 1 and args.full and not args.no_secondary:
         phases.start("secondary")
         dog.note("secondary workloads")
         sec = secondary.secondary(args, b)
@@ -266,7 +272,7 @@ def run(args, make_world=None):
             fallback.keep(out)
     # ---- the reference on this box's host cores, beside every line: measured at N = 1 (and left for the runs that follow on this
     # host), quoted at N > 1 — or its bounded sample leg, with the GPU line already in hand
-    if rank == 0 and not args.no_cpu_baseline and out["backend"] == transports.PRODUCT_BACKEND:
+    if rank == 0 and args.full and not args.no_cpu_baseline and out["backend"] == transports.PRODUCT_BACKEND:
         phases.start("cpu_baseline")
         dog.note("CPU baseline (the compiled reference on the host cores)")
         out["cpu_baseline"] = baseline.cpu_baseline_for_line(args, n, budget)

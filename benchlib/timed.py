@@ -8,6 +8,35 @@ from . import checks, common
 from .common import GAT_LAYERS, HBM_PEAK, route_name
 
 
+DUMP_LIMIT = 60 << 20  # bytes of array data --dump-outputs writes in one run (with the .npy headers: under 64 MB)
+
+
+def sample_rows(m, r, n_arrays, limit=DUMP_LIMIT):
+    """Global rows of an m x r float64 output that --dump-outputs writes: all of them when the matrix fits its share of `limit`,
+    else a fixed seeded sample, sorted (the same rows for every run of the same size)."""
+    import numpy as np
+    k = min(m, limit // n_arrays // (8 * r))
+    if k == m:
+        return np.arange(m, dtype=np.int64)
+    return np.sort(np.random.default_rng(12345).choice(m, size=k, replace=False)).astype(np.int64)
+
+
+def operand_b(m, r, nnz):
+    """The constant value of B in the timed loop (A = 1, S = 1).  fusedSpMM overwrites A in place, and with constant operands one call
+    multiplies row i of A by deg_i * R * b^2: b = sqrt(M / (R nnz)) makes that deg_i / (mean degree), so the values the timed steps carry
+    (and --dump-outputs writes) stay of order one over many steps.  The reference's A = B = 0.001 (benchmark_dist.cpp:102-106) shrink
+    them about 80-fold per call at the headline size: exactly zero after some 170 calls."""
+    return (m / (r * max(1, nnz))) ** 0.5
+
+
+def dump_outputs(directory, outputs):
+    """Rank 0: one DIR/<name>.npy per output of the last timed step, float64."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    for name, arr in outputs.items():
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(arr, dtype=np.float64))
+
+
 class Bench:
     """Operator + operands of ONE route at a time, on one of several transports; builds, times and checks it."""
 
@@ -104,7 +133,7 @@ class Bench:
             self.gat_x.fill(0.001)
             self.gat.set_input(self.gat_x)
         else:
-            self.A, self.B = self.op.like_A_matrix(0.001), self.op.like_B_matrix(0.001)
+            self.A, self.B = self.op.like_A_matrix(1.0), self.op.like_B_matrix(operand_b(self.m, args.r, self.nnz))
             self.S, self.buf = self.op.like_S_values(1.0), self.op.like_S_values(0.0)
         self.barrier()
         if self.setup_s is None:
@@ -118,10 +147,61 @@ class Bench:
         else:
             self.op.fusedSpMM(self.A, self.B, self.S, self.buf, self.H.AMAT)
 
+    # -- what a caller of the timed step receives (--dump-outputs)
+    def _global_rows(self, dense, mode, m, rows):
+        """Rows `rows` (sorted global indices) of the distributed matrix `dense`, laid out as op.submatrices(mode) says, in global order;
+        on rank 0 (None elsewhere).  Every element has one owner: the others contribute -inf to a MAX reduction."""
+        import numpy as np
+        got = dense.download().reshape(-1)
+        out = np.full((len(rows), self.op.info()["R"]), -np.inf)
+        off = 0
+        for top, left, rc, cc in self.op.submatrices(mode):
+            keep = int(max(0, min(rc, m - top)))
+            blk = got[off:off + rc * cc].reshape(rc, cc)
+            off += rc * cc
+            lo, hi = np.searchsorted(rows, top), np.searchsorted(rows, top + keep)
+            out[lo:hi, left:left + cc] = blk[rows[lo:hi] - top]
+        if self.dist is not None:
+            t = self.torch.from_numpy(out)
+            self.dist.all_reduce(t, op=self.dist.ReduceOp.MAX)
+            out = t.numpy()
+        if self.rank != 0:
+            return None
+        assert np.isfinite(out).all(), "bench.py --dump-outputs: an element of the output has no owner"
+        return out
+
+    def outputs(self):
+        """What the last step computed, as a caller of the step receives it (collective; a dict on rank 0): vanilla -> A (fusedSpMM's
+        output, Amat), als -> the embeddings A and B, gat -> H, the last layer's output.  A matrix above its share of DUMP_LIMIT is
+        reduced to sample_rows()'s rows."""
+        H, info = self.H, self.op.info()
+        if self.als is not None:
+            A, B = self.op.like_A_matrix(0.0), self.op.like_B_matrix(0.0)
+            self.als.get_embeddings(A, B)
+            mats = [("A", A, H.AMAT, info["M"]), ("B", B, H.BMAT, info["N"])]
+        elif self.gat is not None:
+            r_now = info["R"]
+            self.op.setRValue(GAT_LAYERS[-1][1] * GAT_LAYERS[-1][2])
+            out = H.Dense.create(self.world(), *self.gat.buffer_shape(len(GAT_LAYERS)))
+            self.gat.get_output(out)
+            mats = [("H", out, H.AMAT, info["M"])]
+        else:
+            mats = [("A", self.A, H.AMAT, info["M"])]
+        r = self.op.info()["R"]
+        res = {name: self._global_rows(d, mode, m, sample_rows(m, r, len(mats))) for name, d, mode, m in mats}
+        if self.als is not None:
+            for d in (A, B):
+                d.free()
+        elif self.gat is not None:
+            out.free()
+            self.op.setRValue(r_now)
+        return res if self.rank == 0 else None
+
     # -- the full measurement of the current route
     def measure(self):
-        """warm-up, K timed steps (barrier + device synchronise on both sides, max over ranks), the roofline leg and the check."""
-        args, torch, dist, H = self.args, self.torch, self.dist, self.H
+        """warm-up, K timed steps (barrier + device synchronise on both sides, max over ranks), what the last one computed (--dump-outputs);
+        with --full the roofline leg and the check."""
+        args = self.args
         self.dog.phase("warm-up steps [%s]" % route_name(self.route))
         for _ in range(args.warmup):
             self.step()
@@ -132,6 +212,20 @@ class Bench:
             self.step()
         self.barrier()
         elapsed = self.max_over_ranks(time.perf_counter() - t0)
+        outputs = None
+        if args.dump_outputs:
+            self.dog.phase("outputs of the last timed step [%s]" % route_name(self.route), max(args.watchdog, 600.0))
+            outputs = self.outputs()
+        transport_kind = self.op.json_algorithm_info().get("transport", "?")  # (collective: every rank asks)
+        ranks = self.world().identities()  # (collective) where every rank runs: pid, device ordinal, PCI bus id, the RCCL communicator's view
+        res = {"route": self.route, "elapsed": elapsed, "outputs": outputs, "check": None, "transport_kind": transport_kind, "ranks": ranks}
+        if args.full:
+            res.update(self.roofline_and_check())
+        return res
+
+    def roofline_and_check(self):
+        """--full: the event-bracketed roofline leg and the closed-form result check, after the timed steps of measure()."""
+        args, torch, dist = self.args, self.torch, self.dist
         self.dog.phase("roofline leg and result check [%s]" % route_name(self.route), max(args.watchdog, 600.0))
         # roofline leg (outside the timed region): HIP events around every local kernel launch
         prof_calls = max(2, min(5, args.steps))
@@ -161,31 +255,16 @@ class Bench:
         if not args.no_check:
             check = checks.check(self) if args.app == "vanilla" else checks.check_app(self)
             self.barrier()
-        transport_kind = self.op.json_algorithm_info().get("transport", "?")  # (collective: every rank asks)
-        ranks = self.world().identities()  # (collective) where every rank runs: pid, device ordinal, PCI bus id, the RCCL communicator's view
-        return {"route": self.route, "elapsed": elapsed, "kern_ms": kern_ms, "kern_ms_slowest": kern_ms_slowest, "launches": launches, "prof_calls": prof_calls,
-                "alg_bytes_per_step": alg_bytes_per_step, "check": check, "transport_kind": transport_kind, "ranks": ranks}
+        return {"kern_ms": kern_ms, "kern_ms_slowest": kern_ms_slowest, "launches": launches, "prof_calls": prof_calls,
+                "alg_bytes_per_step": alg_bytes_per_step, "check": check}
 
 
 def compose_line(args, b, res, extra):
-    """The JSON line of one complete measurement (rank 0)."""
+    """The JSON line of one complete measurement (rank 0); `roofline` only when the measurement ran the roofline leg (--full)."""
     H, n = b.H, b.n
     tr, c_now, mode, q = res["route"]
     ms_per_step = res["elapsed"] / args.steps * 1e3
     value = b.nnz * args.r * args.steps / res["elapsed"]
-    launches_per_step = max(1, res["launches"] // res["prof_calls"])
-    dur = res["kern_ms"] / max(1, res["launches"]) * 1e-3  # average launch duration, seconds
-    bytes_per_launch = res["alg_bytes_per_step"] / launches_per_step
-    achieved_kernel = bytes_per_launch / dur if dur > 0 else 0.0
-    # SURVEY 8(d), the whole step: the GLOBAL problem's algorithmic bytes over the driver-timed step (kernels + every exposed shift,
-    # replication and wait — what the reference's elapsed time contains, benchmark_dist.cpp:117-149) against n x the HBM peak
-    per_call = lambda r_: common.fused_bytes(b.nnz, r_, b.m)  # noqa: E731
-    total_bytes = {"vanilla": per_call(args.r), "als": 2 * 12 * per_call(args.r),
-                   "gat": sum(h * per_call(f) for _, f, h in GAT_LAYERS)}[args.app]
-    achieved_step = total_bytes / (ms_per_step * 1e-3) / n  # B/s per GPU
-    kernel_ms_per_step = res["kern_ms_slowest"] / res["prof_calls"]
-    # one GPU: the dominant kernel's own rate (its launches are the step); several GPUs: the step's, exposed communication included
-    achieved = achieved_kernel if n == 1 else achieved_step
     ring_mode_now = None if (n == 1 or mode == "none") else ("mesh fetch + mesh reduce-scatter" if mode == "fusion1" else mode)
     alg_now = "15d_fusion1" if mode == "fusion1" else args.alg
     step_is = {"vanilla": "fused SDDMM->SpMM (fusedSpMM, Amat)", "als": "one ALS step by batched CG (run_cg(1): 24 fused calls)",
@@ -218,32 +297,52 @@ def compose_line(args, b, res, extra):
                    "distinct_devices": distinct,
                    "ranks": [[r["rank"], r["pid"], r["device_ordinal"], r["pci_bus_id"]] + ([r["comm_count"], r["comm_rank"], r["comm_device"]] if "comm_count" in r else [])
                              for r in ranks]},
-        # `achieved` is an ALGORITHMIC rate (SURVEY 8d byte model / measured launch time), not DRAM utilisation: part of every
-        # launch's gathers is served by the 256 MiB Infinity Cache, which sits behind the counters `traffic` comes from
-        "roofline": {"bound": "hbm", "bound_detail": "HBM gather model, Infinity-Cache assisted (DESIGN.md 3.2)",
-                     "achieved": achieved / 1e9, "peak": HBM_PEAK / 1e9, "unit": "GB/s",
-                     "frac": achieved / HBM_PEAK, "traffic": None, "traffic_source": None,
-                     # one GPU: the step IS the dominant kernel's launches; several: SURVEY 8d's whole-step figure, exposed communication counts
-                     "frac_is": "frac_kernel (one GPU)" if n == 1 else "frac_step = total B_fused / ms_per_step / (n_gpus x 8 TB/s)",
-                     "frac_kernel": achieved_kernel / HBM_PEAK, "achieved_kernel": achieved_kernel / 1e9,
-                     "frac_step": achieved_step / HBM_PEAK, "achieved_step_per_gpu": achieved_step / 1e9,
-                     "algorithmic_bytes_per_step_all_gpus": total_bytes,
-                     # the slowest rank's event-bracketed kernel time per step, and what the timed step spends beyond it
-                     "kernel_ms_per_step": kernel_ms_per_step, "exposed_comm_ms": ms_per_step - kernel_ms_per_step,
-                     "kernel": ("row_kernel<fused>, 1 launch per Infinity-Cache panel of B" if n == 1 else
-                                "row_kernel<fused>, 1 launch per visiting block (relay ring)" if ring_mode_now == "relay" else
-                                "row_kernel<fused>, the rank's one block (replication only)" if ring_mode_now is None else
-                                "row_kernel<sddmm> on row ranges + row_kernel<spmm> staging passes (15d_fusion1, mesh)" if mode == "fusion1" else
-                                "row_kernel<fused>: own block + adaptive windowed passes over fetched blocks"),
-                     # device time of a kernel CALL (HIP events around it on the compute stream) divided by the row-kernel launches it made
-                     # (structure plans are cached: a steady-state call launches row kernels only)
-                     "avg_launch_ms": dur * 1e3, "avg_launch_ms_is": "HIP-event time of the call / its row-kernel launches",
-                     "traffic_rate": None,
-                     "compulsory_bytes_per_call": 8 * args.r * (2 * b.m + b.m) + 24 * b.nnz,
-                     "launches_per_step": launches_per_step, "algorithmic_bytes_per_launch": bytes_per_launch,
-                     "model": "nnz*(8R+24) + 16*R*rows per fused call (SURVEY 8d), split evenly over launches"},
     }
+    if "kern_ms" in res:
+        out["roofline"] = roofline(args, b, res, ms_per_step, mode, ring_mode_now)
     if res["check"] is not None:
         out["check"] = res["check"]
     out.update(extra)
     return out
+
+
+def roofline(args, b, res, ms_per_step, mode, ring_mode_now):
+    """`roofline` of a line, from the roofline leg of a --full measurement."""
+    n = b.n
+    launches_per_step = max(1, res["launches"] // res["prof_calls"])
+    dur = res["kern_ms"] / max(1, res["launches"]) * 1e-3  # average launch duration, seconds
+    bytes_per_launch = res["alg_bytes_per_step"] / launches_per_step
+    achieved_kernel = bytes_per_launch / dur if dur > 0 else 0.0
+    # SURVEY 8(d), the whole step: the GLOBAL problem's algorithmic bytes over the driver-timed step (kernels + every exposed shift,
+    # replication and wait — what the reference's elapsed time contains, benchmark_dist.cpp:117-149) against n x the HBM peak
+    per_call = lambda r_: common.fused_bytes(b.nnz, r_, b.m)  # noqa: E731
+    total_bytes = {"vanilla": per_call(args.r), "als": 2 * 12 * per_call(args.r),
+                   "gat": sum(h * per_call(f) for _, f, h in GAT_LAYERS)}[args.app]
+    achieved_step = total_bytes / (ms_per_step * 1e-3) / n  # B/s per GPU
+    kernel_ms_per_step = res["kern_ms_slowest"] / res["prof_calls"]
+    # one GPU: the dominant kernel's own rate (its launches are the step); several GPUs: the step's, exposed communication included
+    achieved = achieved_kernel if n == 1 else achieved_step
+    # `achieved` is an ALGORITHMIC rate (SURVEY 8d byte model / measured launch time), not DRAM utilisation: part of every
+    # launch's gathers is served by the 256 MiB Infinity Cache, which sits behind the counters `traffic` comes from
+    return {"bound": "hbm", "bound_detail": "HBM gather model, Infinity-Cache assisted (DESIGN.md 3.2)",
+            "achieved": achieved / 1e9, "peak": HBM_PEAK / 1e9, "unit": "GB/s",
+            "frac": achieved / HBM_PEAK, "traffic": None, "traffic_source": None,
+            # one GPU: the step IS the dominant kernel's launches; several: SURVEY 8d's whole-step figure, exposed communication counts
+            "frac_is": "frac_kernel (one GPU)" if n == 1 else "frac_step = total B_fused / ms_per_step / (n_gpus x 8 TB/s)",
+            "frac_kernel": achieved_kernel / HBM_PEAK, "achieved_kernel": achieved_kernel / 1e9,
+            "frac_step": achieved_step / HBM_PEAK, "achieved_step_per_gpu": achieved_step / 1e9,
+            "algorithmic_bytes_per_step_all_gpus": total_bytes,
+            # the slowest rank's event-bracketed kernel time per step, and what the timed step spends beyond it
+            "kernel_ms_per_step": kernel_ms_per_step, "exposed_comm_ms": ms_per_step - kernel_ms_per_step,
+            "kernel": ("row_kernel<fused>, 1 launch per Infinity-Cache panel of B" if n == 1 else
+                       "row_kernel<fused>, 1 launch per visiting block (relay ring)" if ring_mode_now == "relay" else
+                       "row_kernel<fused>, the rank's one block (replication only)" if ring_mode_now is None else
+                       "row_kernel<sddmm> on row ranges + row_kernel<spmm> staging passes (15d_fusion1, mesh)" if mode == "fusion1" else
+                       "row_kernel<fused>: own block + adaptive windowed passes over fetched blocks"),
+            # device time of a kernel CALL (HIP events around it on the compute stream) divided by the row-kernel launches it made
+            # (structure plans are cached: a steady-state call launches row kernels only)
+            "avg_launch_ms": dur * 1e3, "avg_launch_ms_is": "HIP-event time of the call / its row-kernel launches",
+            "traffic_rate": None,
+            "compulsory_bytes_per_call": 8 * args.r * (2 * b.m + b.m) + 24 * b.nnz,
+            "launches_per_step": launches_per_step, "algorithmic_bytes_per_launch": bytes_per_launch,
+            "model": "nnz*(8R+24) + 16*R*rows per fused call (SURVEY 8d), split evenly over launches"}

@@ -12,10 +12,11 @@ def _no_constants(name):
     raise ValueError("not strict JSON: %s" % name)
 
 
-def read_line(text, want_record=True):
+def read_line(text, want_record=True, full=True):
     """The ONE line a run prints: at most LINE_LIMIT bytes, strict JSON (no NaN / Infinity), every string bounded, the contract's keys —
     checked for every line any test of this file sees.  Returns the run's FULL record, which the line names in `full_record`
-    (benchlib/line.py: the line is the record's bounded form), so that the tests below keep reading every detail."""
+    (benchlib/line.py: the line is the record's bounded form), so that the tests below keep reading every detail.  `full`: the run
+    was started with --full (a measured line carries `roofline`); a plain run's line carries none of what --full adds."""
     assert len(text.encode()) + 1 <= LINE_LIMIT, len(text)
     line = json.loads(text, parse_constant=_no_constants)
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config"):
@@ -33,8 +34,10 @@ def read_line(text, want_record=True):
             for x in v:
                 yield from strings(x)
     assert max(len(x) for x in strings(line)) <= 300
-    if line.get("value") is not None:
+    if line.get("value") is not None and full:
         assert "roofline" in line and {"bound", "achieved", "peak", "unit", "frac", "traffic"} <= set(line["roofline"])
+    if not full:
+        assert not {"roofline", "check", "secondary", "cpu_baseline"} & set(line), sorted(line)
     if not want_record:
         return line
     assert "full_record" in line, sorted(line)

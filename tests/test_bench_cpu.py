@@ -7,6 +7,7 @@ import subprocess
 import sys
 import time
 
+import numpy as np
 import pytest
 
 from test_gloo_world import ROOT, free_port
@@ -102,7 +103,7 @@ def product_launch(nranks, extra_env=None, probe_timeout="120", extra_args=()):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
     res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(nranks), "--steps", "2", "--warmup", "1", "--logm", "10",
-                          "--edge-factor", "8", "--r", "16", "--no-cpu-baseline", "--probe-timeout", probe_timeout, *extra_args], env=env, capture_output=True, text=True,
+                          "--edge-factor", "8", "--r", "16", "--full", "--no-cpu-baseline", "--probe-timeout", probe_timeout, *extra_args], env=env, capture_output=True, text=True,
                          timeout=900)
     lines = [ln for ln in res.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, (res.returncode, res.stdout[-1500:], res.stderr[-1500:])
@@ -164,7 +165,7 @@ def test_sigterm_to_the_launcher_prints_the_line_in_hand():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
     p = subprocess.Popen([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--logm", "10", "--edge-factor", "8",
-                          "--r", "16", "--no-cpu-baseline", "--probe-timeout", "120"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
+                          "--r", "16", "--full", "--no-cpu-baseline", "--probe-timeout", "120"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
     t0 = time.time()
     for ln in p.stderr:  # trials + bring-up + the first measurement take about 5 s here; then the search (4 s per candidate) is under way
         if "a complete measurement is in hand" in ln:
@@ -199,7 +200,7 @@ def test_a_multi_gpu_line_carries_the_whole_step_roofline_and_the_cpu_baseline(t
 
     def launch(*extra):
         res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "2", "--warmup", "1", "--logm", "10", "--edge-factor", "8",
-                              "--r", "16", "--cpu-logm", "10", "--cpu-trials", "1", "--probe-timeout", "120", "--no-tune", *extra], env=env,
+                              "--r", "16", "--full", "--cpu-logm", "10", "--cpu-trials", "1", "--probe-timeout", "120", "--no-tune", *extra], env=env,
                              capture_output=True, text=True, timeout=900)
         lines = [ln for ln in res.stdout.splitlines() if ln.strip()]
         assert res.returncode == 0 and len(lines) == 1, (res.returncode, res.stdout[-1500:], res.stderr[-1500:])
@@ -314,7 +315,7 @@ def test_the_multi_gpu_product_path_under_torch_distributed_run():
         env.pop(k, None)
     res = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port",
                           str(free_port()), os.path.join(ROOT, "tests", "bench_product_worker.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--logm", "9",
-                          "--edge-factor", "8", "--rvalue", "16", "--no-cpu-baseline", "--probe-timeout", "120"], env=env, capture_output=True, text=True, timeout=900)
+                          "--edge-factor", "8", "--rvalue", "16", "--full", "--no-cpu-baseline", "--probe-timeout", "120"], env=env, capture_output=True, text=True, timeout=900)
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
     assert res.returncode == 0 and len(lines) == 1, (res.returncode, res.stdout[-1000:], res.stderr[-1500:])
     out = read_line(lines[0])
@@ -327,7 +328,7 @@ def self_launch(extra_env, nranks=2, extra_args=()):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
     return subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(nranks), "--steps", "2", "--warmup", "1", "--logm", "10",
-                           "--edge-factor", "8", "--r", "16", "--no-cpu-baseline", *extra_args], env=env, capture_output=True, text=True, timeout=600)
+                           "--edge-factor", "8", "--r", "16", "--full", "--no-cpu-baseline", *extra_args], env=env, capture_output=True, text=True, timeout=600)
 
 
 def test_bench_launches_its_own_workers():
@@ -412,19 +413,19 @@ def test_a_candidate_that_hangs_still_leaves_the_line_in_hand():
     assert out["config"]["mesh_chunks"] == "1,2,2,2,1,1"  # the default route's measurement
 
 
-def run_worker_directly(n, *cli, timeout=600):
+def run_worker_directly(n, *cli, timeout=600, full=True):
     port = free_port()
     procs = []
     for r in range(n):
         env = dict(os.environ, RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE=str(n), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), OMP_NUM_THREADS="2",
                    GLOO_SOCKET_IFNAME="lo")
         procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "tests", "bench_worker.py"), "--gpus", str(n), "--steps", "1", "--warmup", "0",
-                                       "--no-cpu-baseline", "--no-secondary", *cli], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
+                                       *(("--full",) if full else ()), "--no-cpu-baseline", "--no-secondary", *cli], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
     outs = [p.communicate(timeout=timeout) for p in procs]
     assert all(p.returncode == 0 for p in procs), "\n".join(o[1][-1500:] for o in outs)
     lines = [ln for ln in outs[0][0].splitlines() if ln.startswith("{")]
     assert len(lines) == 1, outs[0][0][-1500:]
-    return read_line(lines[0])
+    return read_line(lines[0], full=full)
 
 
 @pytest.mark.parametrize("n,cli,app", [(1, ("--workload", "rmat", "--logm", "9", "--edge-factor", "8", "--r", "16"), "vanilla"),
@@ -455,13 +456,87 @@ def test_matrix_market_workload(tmp_path):
     assert out["data"] == "file" and "g.mtx" in out["config"]["workload"] and out["check"]["ok"] and out["check"]["rows_checked"] == out["config"]["M"]
 
 
+@pytest.mark.parametrize("n", [1, 2])
+def test_a_plain_run_times_its_steps_and_nothing_else(n):
+    """Without --full a run sets up, warms up, times --steps steps and prints the line: `value` and `ms_per_step` come from those steps
+    alone; no roofline leg, result check, secondary workloads or CPU baseline (the run does not even try: --no-cpu-baseline and
+    --no-secondary are not given here)."""
+    port = free_port()
+    procs = []
+    for r in range(n):
+        env = dict(os.environ, RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE=str(n), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), OMP_NUM_THREADS="2",
+                   GLOO_SOCKET_IFNAME="lo")
+        procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "tests", "bench_worker.py"), "--gpus", str(n), "--steps", "3", "--warmup", "1",
+                                       "--logm", "10", "--edge-factor", "8", "--r", "16", "--no-tune"], env=env, stdout=subprocess.PIPE,
+                                      stderr=subprocess.PIPE, text=True))
+    outs = [p.communicate(timeout=600) for p in procs]
+    assert all(p.returncode == 0 for p in procs), "\n".join(o[1][-1500:] for o in outs)
+    lines = [ln for ln in outs[0][0].splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, outs[0][0][-1500:]
+    out = read_line(lines[0], full=False)
+    assert out["steps"] == 3 and out["warmup"] == 1 and out["n_gpus"] == n and out["ms_per_step"] > 0
+    assert out["metric"] == "fused SDDMM+SpMM nnz*R/s" and out["unit"] == "nnz*R/s" and out["higher_is_better"] is True and out["dtype"] == "f64"
+    assert abs(out["value"] - out["config"]["nnz"] * 16 / (out["ms_per_step"] * 1e-3)) <= 1e-9 * out["value"]
+    assert not {"counter_traffic", "secondary", "cpu_baseline"} & set(out["phases_s"]), out["phases_s"]
+
+
+def test_dump_outputs_are_what_the_last_timed_step_computed(tmp_path):
+    """--dump-outputs DIR: A after warm-up + timed steps (fusedSpMM updates A in place from A = 1, B = sqrt(M / (R nnz))), float64, rows in global
+    order — the oracle's fused call applied as often, whatever the number of ranks; the same arguments give the same files."""
+    from oracle import oracle as O
+    rows, cols = O.erdos_renyi(10, 8)
+    a = np.ones((1 << 10, 16))
+    b = np.full((1 << 10, 16), ((1 << 10) / (16 * len(rows))) ** 0.5)
+    want = {}
+    for k in range(1, 4):
+        a = O.fused_a(rows, cols, np.ones(len(rows)), a, b)[0]
+        want[k] = a
+    for n, steps, warmup, d in ((1, 2, 1, "n1"), (1, 2, 1, "n1_again"), (2, 1, 0, "n2"), (2, 1, 0, "n2_full")):
+        out = run_worker_directly(n, "--steps", str(steps), "--warmup", str(warmup), "--logm", "10", "--edge-factor", "8", "--r", "16", "--no-tune",
+                                  "--dump-outputs", str(tmp_path / d), full=d.endswith("full"))
+        assert out["steps"] == steps
+        assert sorted(os.listdir(tmp_path / d)) == ["A.npy"]
+        got = np.load(tmp_path / d / "A.npy")
+        assert got.dtype == np.float64 and got.shape == (1 << 10, 16)
+        ref = want[steps + warmup]
+        assert np.max(np.abs(got - ref)) <= 1e-12 * np.max(np.abs(ref)), (n, steps, warmup)
+    assert np.array_equal(np.load(tmp_path / "n1" / "A.npy"), np.load(tmp_path / "n1_again" / "A.npy"))
+    # what --full adds runs after the timed steps: it does not change what was dumped
+    assert np.array_equal(np.load(tmp_path / "n2" / "A.npy"), np.load(tmp_path / "n2_full" / "A.npy"))
+
+
+@pytest.mark.parametrize("n,app,names", [(1, "als", ["A.npy", "B.npy"]), (2, "gat", ["H.npy"])])
+def test_dump_outputs_of_the_applications(tmp_path, n, app, names):
+    """--app als: the two embeddings after the ALS step; --app gat: the last layer's output of the forward pass (zero: the timed GAT
+    keeps the reference's zero weights)."""
+    cli = ("--logm", "7", "--edge-factor", "4") + (("--r", "16") if app == "als" else ())
+    run_worker_directly(n, "--app", app, *cli, "--no-tune", "--dump-outputs", str(tmp_path / "d"), full=False)
+    assert sorted(os.listdir(tmp_path / "d")) == names
+    for name in names:
+        got = np.load(tmp_path / "d" / name)
+        assert got.dtype == np.float64 and got.shape == (1 << 7, 16 if app == "als" else 256 * 6)
+        assert np.isfinite(got).all() and (np.abs(got).max() > 0) == (app == "als")
+
+
+def test_dump_outputs_sample_large_outputs_by_fixed_rows():
+    """An output above its share of the dump's budget (under 64 MB in all) is written as a fixed, seeded, sorted sample of its rows; a
+    small one whole."""
+    from benchlib import timed
+    assert timed.DUMP_LIMIT + 4 * 128 <= 64e6  # (four .npy headers at most: ALS writes two)
+    rows = timed.sample_rows(1 << 20, 128, 1)
+    assert len(rows) * 128 * 8 == timed.DUMP_LIMIT and np.all(np.diff(rows) > 0) and rows[0] >= 0 and rows[-1] < 1 << 20
+    assert np.array_equal(rows, timed.sample_rows(1 << 20, 128, 1))
+    assert len(timed.sample_rows(1 << 20, 128, 2)) * 2 * 128 * 8 <= timed.DUMP_LIMIT
+    assert np.array_equal(timed.sample_rows(1 << 10, 16, 2), np.arange(1 << 10))
+
+
 def test_secondary_workloads_are_listed_with_their_checks():
     """N = 1: the other workloads of the reference's harness ride in the same JSON line under "secondary", each with its byte
     model, a fraction and a check of its own (toy sizes here; the code is the GPU run's)."""
     port = free_port()
     env = dict(os.environ, RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), OMP_NUM_THREADS="2",
                HNH_BENCH_SECONDARY_SMALL="1")
-    res = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "bench_worker.py"), "--gpus", "1", "--steps", "1", "--warmup", "0", "--no-cpu-baseline",
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "bench_worker.py"), "--gpus", "1", "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline",
                           "--logm", "9", "--edge-factor", "8", "--r", "16"], env=env, capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stderr[-3000:]
     printed = [ln for ln in res.stdout.splitlines() if ln.startswith("{")][0]

@@ -364,7 +364,7 @@ def test_input_side_at_size_matrix_market_to_25d_dense(tmp_path):
         for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
             env.pop(k, None)
         out = subprocess.run([sys.executable, os.path.join(T.ROOT, "bench.py"), "--workload", "mtx:" + path, "--alg", "25d_dense_replicate", "--rvalue", str(r),
-                              "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-secondary", "--no-live-traffic"], env=env, capture_output=True,
+                              "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-secondary", "--no-live-traffic"], env=env, capture_output=True,
                              text=True, timeout=600)
         assert out.returncode == 0, out.stderr[-2000:]
         line = json.loads(out.stdout.strip().splitlines()[-1])

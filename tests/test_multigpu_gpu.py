@@ -90,7 +90,7 @@ def run_bench(n, *extra, timeout=900):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "HNH_BENCH_WORKER"):
         env.pop(k, None)
     return subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "3", "--warmup", "1", "--logm", "16",
-                           "--edge-factor", "32", "--no-cpu-baseline", *extra], env=env, capture_output=True, text=True, timeout=timeout)
+                           "--edge-factor", "32", "--full", "--no-cpu-baseline", *extra], env=env, capture_output=True, text=True, timeout=timeout)
 
 
 @pytest.mark.parametrize("n", [2, 8])
@@ -125,7 +125,7 @@ def test_bench_processes_share_one_gpu(n):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "HNH_BENCH_WORKER"):
         env.pop(k, None)
     res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "2", "--warmup", "1", "--logm", "14",
-                          "--edge-factor", "16", "--r", "32", "--no-cpu-baseline", "--probe-timeout", "240"], env=env, capture_output=True, text=True, timeout=1500)
+                          "--edge-factor", "16", "--r", "32", "--full", "--no-cpu-baseline", "--probe-timeout", "240"], env=env, capture_output=True, text=True, timeout=1500)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, res.stdout[-2000:]
@@ -152,7 +152,7 @@ def test_bench_under_torch_distributed_run_on_one_gpu():
         env.pop(k, None)
     res = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                           "--master-port", str(free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--logm", "14",
-                          "--edge-factor", "16", "--no-cpu-baseline", "--probe-timeout", "240", "--chunks", "2"], env=env,  # (no "--r": the launcher's own
+                          "--edge-factor", "16", "--full", "--no-cpu-baseline", "--probe-timeout", "240", "--chunks", "2"], env=env,  # (no "--r": the launcher's own
                          # option parser takes it for an abbreviation of its --rdzv-* / --role / --run-path options)
                          capture_output=True, text=True, timeout=1500)
     assert res.returncode == 0, res.stderr[-3000:]
@@ -161,6 +161,33 @@ def test_bench_under_torch_distributed_run_on_one_gpu():
     out = read_line(lines[0])
     assert out["n_gpus"] == 2 and out["config"]["transport"] == "ipc-pull" and out["check"]["ok"] and "incomplete" not in out
     assert out["config"]["transport_trials"]["ipc"].startswith("ok (") and "trial failed" not in out["config"]["transport_trials"]["ipc"]
+
+
+def test_bench_plain_run_and_its_outputs_on_one_gpu(tmp_path):
+    """`python bench.py --gpus 1` without --full on the HIP path: the line of the timed steps alone, and --dump-outputs writes A after
+    warm-up + timed steps — the oracle's fused call from A = 1, B = sqrt(M / (R nnz)) applied as often."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    from oracle import oracle as O
+    if gpus() < 1:
+        pytest.skip("needs a GPU")
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "HNH_BENCH_WORKER"):
+        env.pop(k, None)
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--logm", "12",
+                          "--edge-factor", "16", "--r", "32", "--dump-outputs", str(tmp_path / "out")], env=env, capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0, res.stderr[-3000:]
+    lines = [ln for ln in res.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, res.stdout[-2000:]
+    out = read_line(lines[0], full=False)
+    assert out["backend"] == "hip-gfx950" and out["steps"] == 2 and out["ms_per_step"] > 0 and out["value"] > 0
+    got = np.load(tmp_path / "out" / "A.npy")
+    rows, cols = O.erdos_renyi(12, 16)
+    a = np.ones((1 << 12, 32))
+    for _ in range(3):
+        a = O.fused_a(rows, cols, np.ones(len(rows)), a, np.full((1 << 12, 32), ((1 << 12) / (32 * len(rows))) ** 0.5))[0]
+    assert got.dtype == np.float64 and got.shape == a.shape
+    assert np.max(np.abs(got - a)) <= 1e-11 * np.max(np.abs(a))
 
 
 def test_bench_rccl_only_on_one_gpu_ends_with_an_error_line():

@@ -117,6 +117,18 @@ AIDS_SIGNATURES = {
 }
 
 
+# include/hnh_grad.h: the dense kernels of the GAT backward pass, an OPTIONAL group bound only for the product library (the CPU test
+# double under oracle/ does not export it; the host layer binds it with dlsym and reports the missing symbol when it is needed)
+GRAD_SIGNATURES = {
+    "hnh_gemm_tn_f64_workspace": (_i64, [_i64, _i64, _i64]),
+    "hnh_gemm_tn_f64": (_i32, [_vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i32]),
+    "hnh_leaky_relu_grad_f64": (_i32, [_vp, _vp, _vp, _dbl, _i64, _i32]),
+    "hnh_relu_grad_cols_f64": (_i32, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _i32]),
+    "hnh_sum3_cols_f64": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _i64, _i32]),
+    "hnh_transpose_into_f64": (_i32, [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _i32]),
+}
+
+
 class CsrBlock(C.Structure):
     """struct hnh_csr_block"""
     _fields_ = [("rows", C.c_int64), ("nnz", C.c_int64), ("cols", C.c_int64), ("max_row_nnz", C.c_int32), ("reserved", C.c_int32),
@@ -172,6 +184,10 @@ def load(path: str | None = None) -> C.CDLL:
     for name, (res, args) in list(SIGNATURES.items()) + list(AIDS_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype, fn.argtypes = res, args
+    if path is None or os.path.abspath(p) == os.path.abspath(LIB_PATH):
+        for name, (res, args) in GRAD_SIGNATURES.items():
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = res, args
     if path is None:
         _lib = lib
     return lib

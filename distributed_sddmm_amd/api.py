@@ -128,6 +128,9 @@ SIGNATURES = {
     "hnh_gat_get_output": (_i32, [_vp, _vp]),
     "hnh_gat_buffer_shape": (_i32, [_vp, _i32, _pi64]),
     "hnh_gat_forward": (_i32, [_vp]),
+    "hnh_gat_backward": (_i32, [_vp, _vp]),
+    "hnh_gat_get_weight_grad": (_i32, [_vp, _i32, _i32, _vp]),
+    "hnh_gat_get_input_grad": (_i32, [_vp, _vp]),
 }
 
 _lib = None
@@ -637,7 +640,7 @@ class DistributedALS:
 
 
 class GAT:
-    """GAT (gat.hpp): multi-head graph-attention forward pass on top of a DistributedSparse."""
+    """GAT (gat.hpp): multi-head graph-attention forward pass on top of a DistributedSparse, and its backward pass (an addition)."""
 
     def __init__(self, op: DistributedSparse, layers, leaky_relu_alpha: float = 0.2):
         self.op, self.layers = op, [tuple(l) for l in layers]
@@ -668,6 +671,21 @@ class GAT:
 
     def forwardPass(self):
         _check(lib().hnh_gat_forward(self.h), "forwardPass")
+
+    def backwardPass(self, grad_out: Dense):
+        """Gradients of L from grad_out = dL/d(output) (the layout of get_output): needs a forwardPass since the last set_weight /
+        set_input; 15d_fusion1 and 15d_fusion2 with c = 1 only (HnhError otherwise)."""
+        _check(lib().hnh_gat_backward(self.h, grad_out.h), "backwardPass")
+
+    def weight_grad(self, layer: int, head: int) -> np.ndarray:
+        """dL/dW of (layer, head) after backwardPass, summed over every rank (the same on all of them)."""
+        out = np.empty(self.weight_shape(layer, head))
+        _check(lib().hnh_gat_get_weight_grad(self.h, layer, head, out.ctypes.data), "gat_get_weight_grad")
+        return out
+
+    def get_input_grad(self, dx: Dense):
+        """dL/d(input) after backwardPass, in the layout of buffer 0 (set_input's)."""
+        _check(lib().hnh_gat_get_input_grad(self.h, dx.h), "gat_get_input_grad")
 
     def free(self):
         if self.h:

@@ -6,6 +6,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <string>
+#include "hnh_grad.h"
 #include "hnh_kernels.h"
 #ifdef HNH_MEASUREMENT_AIDS
 #include "hnh_measurement_aids.h"
@@ -38,6 +39,10 @@ struct Backend {
     HNH_FN(hnh_ipc_export) HNH_FN(hnh_ipc_open) HNH_FN(hnh_ipc_close) HNH_FN(hnh_ipc_pull) HNH_FN(hnh_ipc_flags_register) HNH_FN(hnh_ipc_flags_unregister)
     HNH_FN(hnh_stream_write_flag) HNH_FN(hnh_stream_wait_flag)
     HNH_FN(hnh_csr_plan_create) HNH_FN(hnh_csr_plan_destroy) HNH_FN(hnh_sddmm_csr_p) HNH_FN(hnh_sddmm_csr_ps) HNH_FN(hnh_spmm_csr_p) HNH_FN(hnh_spmm_csr_pf) HNH_FN(hnh_fused_sddmm_spmm_csr_p)
+    // OPTIONAL group (include/hnh_grad.h): bound when the library exports it, null otherwise (the CPU test double does not);
+    // only GAT::backwardPass needs it, and it fails with an error naming the missing symbol
+    HNH_FN(hnh_gemm_tn_f64_workspace) HNH_FN(hnh_gemm_tn_f64) HNH_FN(hnh_leaky_relu_grad_f64) HNH_FN(hnh_relu_grad_cols_f64)
+    HNH_FN(hnh_sum3_cols_f64) HNH_FN(hnh_transpose_into_f64)
 #ifdef HNH_MEASUREMENT_AIDS
     HNH_FN(hnh_stream_delay_us) HNH_FN(hnh_stream_paced_copy) HNH_FN(hnh_stream_pace_begin) HNH_FN(hnh_stream_pace_end)
 #endif
@@ -45,7 +50,7 @@ struct Backend {
 };
 
 // Loads (once per path) and returns the backend; path == nullptr or "" selects the product HIP library.
-// Calls hnh::fatal() (print + exit(1) / exception) if the library or any symbol is missing.
+// Calls hnh::fatal() (print + exit(1) / exception) if the library or any mandatory symbol is missing.
 Backend* load_backend(const char* path);
 Backend* default_backend();           // the most recently loaded one; loads the HIP library on first use
 std::string default_backend_path();   // <dir of libhnh_host.so>/libhnh_kernels.so

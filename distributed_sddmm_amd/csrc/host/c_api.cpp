@@ -742,13 +742,17 @@ int hnh_gat_weight_shape(hnh_gat* g, int layer, int head, int64_t o[2]) {
     });
 }
 int hnh_gat_set_weight(hnh_gat* g, int layer, int head, const double* host) {
-    return guarded(g->w, [&] { g->g->layers.at(layer).wMats.at(head).copy_from_host(host); });
+    return guarded(g->w, [&] {
+        g->g->layers.at(layer).wMats.at(head).copy_from_host(host);
+        g->g->invalidate_forward();
+    });
 }
 int hnh_gat_set_input(hnh_gat* g, hnh_dense* X) {
     return guarded(g->w, [&] {
         DenseMatrix& b = g->g->buffers.at(0);
         if (b.rows() != X->m.rows() || b.cols() != X->m.cols()) hnh::fatal("Error, GAT input has the wrong shape!");
         b = X->m;
+        g->g->invalidate_forward();
     });
 }
 int hnh_gat_get_output(hnh_gat* g, hnh_dense* out) {
@@ -763,6 +767,31 @@ int hnh_gat_buffer_shape(hnh_gat* g, int index, int64_t o[2]) {
 }
 int hnh_gat_forward(hnh_gat* g) {
     return guarded(g->w, [&] { g->g->forwardPass(); });
+}
+int hnh_gat_backward(hnh_gat* g, hnh_dense* grad_out) {
+    return guarded(g->w, [&] { g->g->backwardPass(grad_out->m); });
+}
+int hnh_gat_get_weight_grad(hnh_gat* g, int layer, int head, double* host) {
+    return guarded(g->w, [&] {
+        GAT& gat = *g->g;
+        const GATLayer& l = gat.layers.at(layer);
+        if (head < 0 || head >= l.num_heads) throw hnh::Error("Error, GAT head index out of range!");
+        if (gat.weight_grads.size() != gat.layers.size() || gat.weight_grads[(size_t)layer].size() == 0)
+            throw hnh::Error("Error, no GAT weight gradient yet: call hnh_gat_backward first!");
+        const DenseMatrix& dW = gat.weight_grads[(size_t)layer];  // input_features x (heads * features_per_head)
+        std::vector<double> all((size_t)dW.size());
+        dW.copy_to_host(all.data());
+        const int64_t k = dW.rows(), ld = dW.cols(), f = l.features_per_head;
+        for (int64_t r = 0; r < k; r++)
+            std::memcpy(host + r * f, all.data() + r * ld + (int64_t)head * f, sizeof(double) * (size_t)f);
+    });
+}
+int hnh_gat_get_input_grad(hnh_gat* g, hnh_dense* out) {
+    return guarded(g->w, [&] {
+        GAT& gat = *g->g;
+        if (gat.input_grads.empty() || gat.input_grads[0].size() == 0) throw hnh::Error("Error, no GAT input gradient yet: call hnh_gat_backward first!");
+        out->m = gat.input_grads[0];
+    });
 }
 
 }  // extern "C"

@@ -10,9 +10,25 @@
 // it is a timing skeleton.  Here alpha defaults to 0.2 and weights are settable; like the reference, the product
 // X * W uses each rank's LOCAL column slice of X (gat.hpp:88), so results are only meaningful for schedules that
 // do not split R (1.5D dense shift), which is what the parity tests use.
+//
+// Backward pass (an addition: the reference's gat.hpp:43-48 leaves it as work in progress).  backwardPass(G), G = dL/d(last
+// output), per head h of layer i from the last layer down, with X = buffers[i], out = buffers[i+1], f = features_per_head:
+//     A = X * W_h, e = SDDMM(A, A)                 recomputed (the fused c = 1 forward never materialises e)
+//     dZ = G[:, h f ..] * [out[:, h f ..] > 0]     hnh_relu_grad_cols_f64
+//     da_ij = <dZ_i, A_j>;  a = LReLU(e), de = da * LReLU'(e)      in S layout and again in ST layout (hnh_leaky_relu_grad_f64)
+//     dA = spmmA(de; A) + spmmB(a^T; dZ) + spmmB(de^T; A)         row side + the two column sides
+// 4 SDDMM and 3 SpMM passes per head through the operator's own calls (S^T lives on other ranks: recomputing in ST layout is the
+// communication-free way to the column sides).  Per layer, with dA_all = [dA_1 .. dA_H] (rows x H f):
+//     dW_all = X^T * dA_all          ONE split-K GEMM (hnh_gemm_tn_f64), summed over the world: every global row lives on one rank
+//     dX = dA_all * [W_1^T; ..; W_H^T]   hnh_gemm_f64: the G of layer i - 1, or the input gradient for layer 0
+// Everything runs on the compute stream.  Supported where the forward pass is oracle.gat_forward's math and R is not split:
+// 15d_fusion1 (any c) and 15d_fusion2 with c = 1.  The dense kernels are the optional group of include/hnh_grad.h.
 #pragma once
+#include "dense_shift_15d.hpp"
 #include "distributed_sparse.hpp"
 #include <cstdlib>
+#include <map>
+#include <tuple>
 
 class GATLayer {
 public:
@@ -101,10 +117,126 @@ public:
             }
         }
         // every product was awaited by the compute stream: nothing is left on the auxiliary stream
+        forward_valid_ = true;
     }
+
+    // The weights or the input changed: the stored activations no longer belong to them (backwardPass refuses until a new forward).
+    void invalidate_forward() { forward_valid_ = false; }
+
+    // Gradients of L with respect to every weight matrix and the input, given G = dL/d(buffers.back()) in that buffer's layout.
+    // Results: weight_grads[i] (input_features x H f of layer i, column block h = dW_h, the same on every rank) and input_grads[i]
+    // (dL/d(buffers[i]); input_grads[0] is the input gradient).  Buffers are allocated on the first call and reused.
+    void backwardPass(const DenseMatrix& grad_out) {
+        check_backward_supported();
+        if (!forward_valid_) throw hnh::Error("Error, GAT backwardPass needs a forwardPass first (and a new one after set_weight / set_input)!");
+        const DenseMatrix& last = buffers.back();
+        if (grad_out.rows() != last.rows() || grad_out.cols() != last.cols()) throw hnh::Error("Error, GAT output gradient has the wrong shape!");
+        if (ones_S_.size() == 0) {
+            ones_S_ = d_ops->like_S_values(1.0);
+            ones_ST_ = d_ops->like_ST_values(1.0);
+            e_S_ = VectorXd(ones_S_.size());
+            d_S_ = VectorXd(ones_S_.size());
+            e_ST_ = VectorXd(ones_ST_.size());
+            d_ST_ = VectorXd(ones_ST_.size());
+        }
+        const int L = (int)layers.size();
+        if ((int)weight_grads.size() != L) {
+            weight_grads.assign((size_t)L, DenseMatrix());
+            input_grads.assign((size_t)L, DenseMatrix());
+        }
+        const DenseMatrix* G = &grad_out;
+        for (int i = L - 1; i >= 0; i--) {
+            backward_layer(i, *G);
+            G = &input_grads[(size_t)i];
+        }
+    }
+
+    std::vector<DenseMatrix> weight_grads, input_grads;
 
 private:
     hnh::World* world_ = nullptr;
+    bool forward_valid_ = false;
+    VectorXd ones_S_, ones_ST_, e_S_, d_S_, e_ST_, d_ST_;  // backward: S values (= 1) and the recomputed / gated value vectors
+    std::map<std::tuple<int, int64_t, int64_t>, DenseMatrix> scratch_;  // backward work buffers by (role, rows, cols)
+
+    DenseMatrix& scratch(int role, int64_t rows, int64_t cols) {
+        DenseMatrix& m = scratch_[std::make_tuple(role, rows, cols)];
+        if (m.rows() != rows || m.cols() != cols) m = DenseMatrix(rows, cols);
+        return m;
+    }
+
+    // Throws hnh::Error (never a wrong number) where the backward pass is not defined or its kernels are missing.
+    void check_backward_supported() {
+        auto* ds = dynamic_cast<Sparse15D_Dense_Shift*>(d_ops);
+        if (ds == nullptr || ds->r_split)
+            throw hnh::Error("Error, GAT backwardPass supports the 1.5D dense-shift schedules only (15d_fusion1, 15d_fusion2 with c = 1), not " +
+                             d_ops->algorithm_name);
+        if (ds->fusionApproach == 2 && ds->c != 1)
+            throw hnh::Error("Error, GAT backwardPass does not support 15d_fusion2 with c > 1 (its forward pass reproduces a quirk of the reference)");
+        const hnh::Backend* be = d_ops->world->be;
+        const std::pair<const void*, const char*> need[] = {
+            {(const void*)be->hnh_gemm_tn_f64_workspace, "hnh_gemm_tn_f64_workspace"}, {(const void*)be->hnh_gemm_tn_f64, "hnh_gemm_tn_f64"},
+            {(const void*)be->hnh_leaky_relu_grad_f64, "hnh_leaky_relu_grad_f64"}, {(const void*)be->hnh_relu_grad_cols_f64, "hnh_relu_grad_cols_f64"},
+            {(const void*)be->hnh_sum3_cols_f64, "hnh_sum3_cols_f64"}, {(const void*)be->hnh_transpose_into_f64, "hnh_transpose_into_f64"}};
+        for (const auto& n : need)
+            if (n.first == nullptr)
+                throw hnh::Error(std::string("Error, GAT backwardPass needs the kernel ") + n.second + ", which the kernel library " + be->path +
+                                 " does not export (include/hnh_grad.h)");
+    }
+
+    // one layer of the backward pass: G = dL/d(buffers[i + 1]) -> weight_grads[i], input_grads[i]
+    void backward_layer(int i, const DenseMatrix& G) {
+        hnh::World* w = d_ops->world;
+        const hnh::Backend* be = w->be;
+        const int S0 = HNH_STREAM_COMPUTE;
+        DenseMatrix& X = buffers[(size_t)i];
+        const DenseMatrix& out = buffers[(size_t)i + 1];
+        const int H = layers[(size_t)i].num_heads, f = layers[(size_t)i].features_per_head;
+        const int64_t rows = X.rows(), k = X.cols(), hf = (int64_t)H * f;
+        if (out.rows() != rows || out.cols() != hf || G.rows() != rows || G.cols() != hf)
+            throw hnh::Error("Error, GAT backwardPass: layer buffers do not have the layer's shape!");
+        DenseMatrix& dA_all = scratch(0, rows, hf);
+        DenseMatrix& Wt = scratch(1, hf, k);
+        d_ops->setRValue(f);
+        for (int h = 0; h < H; h++) {
+            DenseMatrix& Wh = layers[(size_t)i].wMats[(size_t)h];
+            DenseMatrix& A = scratch(2, rows, f);
+            DenseMatrix& dZ = scratch(3, rows, f);
+            DenseMatrix& dArow = scratch(4, rows, f);
+            DenseMatrix& T1 = scratch(5, rows, f);
+            DenseMatrix& T2 = scratch(6, rows, f);
+            w->check(be->hnh_gemm_f64(w->ctx, rows, f, k, X.data(), Wh.data(), A.data(), S0), "hnh_gemm_f64");
+            w->check(be->hnh_relu_grad_cols_f64(w->ctx, dZ.data(), f, G.data(), hf, out.data(), hf, (int64_t)h * f, rows, f, S0),
+                     "hnh_relu_grad_cols_f64");
+            // S layout: e_ij = <A_i, A_j>, da_ij = <dZ_i, A_j>, gate, row side dA_i = sum_j de_ij A_j
+            d_ops->sddmmA(A, A, ones_S_, e_S_);
+            d_ops->sddmmA(dZ, A, ones_S_, d_S_);
+            w->check(be->hnh_leaky_relu_grad_f64(w->ctx, e_S_.data(), d_S_.data(), leaky_relu_alpha, e_S_.size(), S0), "hnh_leaky_relu_grad_f64");
+            d_ops->spmmA(dArow, A, d_S_);
+            // ST layout: the same values on the transpose's nonzeros, column sides sum_i a_ij dZ_i and sum_i de_ij A_i
+            d_ops->sddmmB(A, A, ones_ST_, e_ST_);
+            d_ops->sddmmB(dZ, A, ones_ST_, d_ST_);
+            w->check(be->hnh_leaky_relu_grad_f64(w->ctx, e_ST_.data(), d_ST_.data(), leaky_relu_alpha, e_ST_.size(), S0), "hnh_leaky_relu_grad_f64");
+            d_ops->spmmB(dZ, T1, e_ST_);
+            d_ops->spmmB(A, T2, d_ST_);
+            w->check(be->hnh_sum3_cols_f64(w->ctx, dA_all.data(), hf, (int64_t)h * f, dArow.data(), T1.data(), T2.data(), rows, f, S0),
+                     "hnh_sum3_cols_f64");
+            w->check(be->hnh_transpose_into_f64(w->ctx, Wt.data(), k, (int64_t)h * f, Wh.data(), k, f, S0), "hnh_transpose_into_f64");
+        }
+        // dW_all = X^T dA_all over the local rows, then over every rank (the dense rows of the 1.5D layout are not replicated)
+        DenseMatrix& dW = weight_grads[(size_t)i];
+        if (dW.rows() != k || dW.cols() != hf) dW = DenseMatrix(k, hf);
+        const int64_t need = be->hnh_gemm_tn_f64_workspace(k, hf, rows);
+        DenseMatrix* work = need > 0 ? &scratch(7, need, 1) : nullptr;
+        w->check(be->hnh_gemm_tn_f64(w->ctx, k, hf, rows, X.data(), k, dA_all.data(), hf, dW.data(), hf, work ? work->data() : nullptr,
+                                     need, S0),
+                 "hnh_gemm_tn_f64");
+        w->allreduce_f64(w->world_comm(), dW.data(), (size_t)dW.size(), S0);
+        // dX = dA_all [W_1^T; ..; W_H^T]
+        DenseMatrix& dX = input_grads[(size_t)i];
+        if (dX.rows() != rows || dX.cols() != k) dX = DenseMatrix(rows, k);
+        w->check(be->hnh_gemm_f64(w->ctx, rows, k, hf, dA_all.data(), Wt.data(), dX.data(), S0), "hnh_gemm_f64");
+    }
     DenseMatrix product[2];  // X * W_j of the head in flight and of the next one
     void* ev_input = nullptr;
     void* ev_gemm[2] = {nullptr, nullptr};

@@ -227,6 +227,12 @@ int hnh_gat_set_input(hnh_gat* g, hnh_dense* X);                                
 int hnh_gat_get_output(hnh_gat* g, hnh_dense* out);                               /* buffers.back() (copied) */
 int hnh_gat_buffer_shape(hnh_gat* g, int index, int64_t out2[2]);                 /* buffers[index]          */
 int hnh_gat_forward(hnh_gat* g);                                                  /* forwardPass (gat.hpp:106-112) */
+/* Backward pass (an addition: the reference's gat.hpp:43-48 leaves it as work in progress).  grad_out = dL/d(output) in the layout of
+ * the last buffer.  Needs a forward pass since the last set_weight / set_input; 15d_fusion1 (any c) and 15d_fusion2 with c = 1 only
+ * (HNH_ERR_INVALID otherwise, and when the kernel library lacks the kernels of include/hnh_grad.h). */
+int hnh_gat_backward(hnh_gat* g, hnh_dense* grad_out);
+int hnh_gat_get_weight_grad(hnh_gat* g, int layer, int head, double* host); /* dL/dW (hnh_gat_weight_shape), summed over all ranks */
+int hnh_gat_get_input_grad(hnh_gat* g, hnh_dense* out);                     /* dL/d(buffers[0]) in its layout (copied)          */
 
 #ifdef __cplusplus
 }

@@ -129,6 +129,21 @@ GRAD_SIGNATURES = {
 }
 
 
+# include/hnh_attention.h: neighbourhood-softmax attention of the GAT, a second OPTIONAL group bound only for the product library (the
+# CPU test double does not export it; the host layer binds it with dlsym and names the missing symbol when the softmax mode needs it)
+ATTN_SIGNATURES = {
+    "hnh_attn_softmax_csr_p": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, C.c_uint, _vp, _vp, _i32]),
+    "hnh_softmax_gate_f64": (_i32, [_vp, _vp, _vp, _vp, _vp, _dbl, _i64, _i32]),
+    "hnh_rowdot_cols_f64": (_i32, [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _i32]),
+}
+ATTN_FINISH = 8  # HNH_ATTN_FINISH
+
+
+class AttnState(C.Structure):
+    """struct hnh_attn_state"""
+    _fields_ = [("row_max", _vp), ("row_sum", _vp), ("lse", _vp), ("leaky_alpha", _dbl), ("relu_dst", _vp), ("relu_ld", _i64)]
+
+
 class CsrBlock(C.Structure):
     """struct hnh_csr_block"""
     _fields_ = [("rows", C.c_int64), ("nnz", C.c_int64), ("cols", C.c_int64), ("max_row_nnz", C.c_int32), ("reserved", C.c_int32),
@@ -185,7 +200,7 @@ def load(path: str | None = None) -> C.CDLL:
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype, fn.argtypes = res, args
     if path is None or os.path.abspath(p) == os.path.abspath(LIB_PATH):
-        for name, (res, args) in GRAD_SIGNATURES.items():
+        for name, (res, args) in list(GRAD_SIGNATURES.items()) + list(ATTN_SIGNATURES.items()):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
     if path is None:

@@ -131,6 +131,7 @@ SIGNATURES = {
     "hnh_gat_backward": (_i32, [_vp, _vp]),
     "hnh_gat_get_weight_grad": (_i32, [_vp, _i32, _i32, _vp]),
     "hnh_gat_get_input_grad": (_i32, [_vp, _vp]),
+    "hnh_gat_set_attention": (_i32, [_vp, _i32]),
 }
 
 _lib = None
@@ -642,11 +643,22 @@ class DistributedALS:
 class GAT:
     """GAT (gat.hpp): multi-head graph-attention forward pass on top of a DistributedSparse, and its backward pass (an addition)."""
 
-    def __init__(self, op: DistributedSparse, layers, leaky_relu_alpha: float = 0.2):
+    ATTENTION = {"none": 0, "softmax": 1}  # HNH_GAT_ATTENTION_NONE / _SOFTMAX
+
+    def __init__(self, op: DistributedSparse, layers, leaky_relu_alpha: float = 0.2, attention: str = "none"):
         self.op, self.layers = op, [tuple(l) for l in layers]
         spec = (C.c_int * (3 * len(layers)))(*[x for l in self.layers for x in l])
         self.h = _vp()
         _check(lib().hnh_gat_create(op.h, len(layers), spec, leaky_relu_alpha, C.byref(self.h)), "gat_create")
+        if attention != "none":
+            self.set_attention(attention)
+
+    def set_attention(self, mode: str):
+        """"none" (the default: the LeakyReLU scores are the edge weights) or "softmax" (normalised over each row's neighbourhood;
+        15d_fusion2 with c = 1 only, forwardPass raises HnhError elsewhere).  A change invalidates the stored forward pass."""
+        if mode not in self.ATTENTION:
+            raise ValueError("attention must be one of %s, not %r" % (sorted(self.ATTENTION), mode))
+        _check(lib().hnh_gat_set_attention(self.h, self.ATTENTION[mode]), "gat_set_attention")
 
     def weight_shape(self, layer: int, head: int):
         o = (C.c_int64 * 2)()

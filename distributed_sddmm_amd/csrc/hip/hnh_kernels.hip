@@ -27,6 +27,7 @@
 #include <new>
 #include <cstdint>
 #include "hnh_ctx.hpp"
+#include "hnh_attention.h"
 
 namespace {
 
@@ -182,9 +183,10 @@ struct Unroll {
 
 // kFusedCg = kFused whose row epilogue also performs the CG updates of hnh_cg_update or the ReLU delivery of
 // hnh_fused_extras::relu_dst; its own instance so that the plain fused kernel's register allocation (and with it its
-// occupancy) is not touched by code it never runs
-enum class Op { kSddmm, kSpmm, kFused, kFusedCg };
-constexpr bool fused_op(Op o) { return o == Op::kFused || o == Op::kFusedCg; }
+// occupancy) is not touched by code it never runs.  kFusedSoftmax = the neighbourhood-softmax pass of hnh_attention.h (online
+// softmax over the row's LeakyReLU scores, row state in Extras::row_max / row_sum), its own instance for the same reason.
+enum class Op { kSddmm, kSpmm, kFused, kFusedCg, kFusedSoftmax };
+constexpr bool fused_op(Op o) { return o == Op::kFused || o == Op::kFusedCg || o == Op::kFusedSoftmax; }
 
 // ---------------------------------------------------------------- the row kernel (sddmm / spmm / fused)
 //
@@ -226,6 +228,10 @@ struct Extras {
     // epilogue: deliver max(row, 0) to relu_dst[row * relu_ld + column] instead of storing the row to Out (GAT head output)
     double* relu_dst = nullptr;
     int64_t relu_ld = 0;
+    // kFusedSoftmax (hnh_attn_state): the rows' running max and sum, and the log-sum-exp the finishing launch writes
+    double* row_max = nullptr;
+    double* row_sum = nullptr;
+    double* lse = nullptr;
 };
 
 template <int LPR>
@@ -283,6 +289,14 @@ __device__ __forceinline__ void process_row(int64_t row, int beg, int end, bool 
             if constexpr (OP != Op::kSddmm) {
                 if (!atomic_out && !(flags & HNH_FUSED_OUT_OVERWRITE)) load_w_stream<W>(acc[v], Out + row * ld + coff[v]);
             }
+        }
+    }
+    // kFusedSoftmax: the row's running max and sum (hnh_attention.h); a launch continues from them, an overwriting one starts empty
+    double m_run = -__builtin_inf(), l_run = 0.0;
+    if constexpr (OP == Op::kFusedSoftmax) {
+        if (!(flags & HNH_FUSED_OUT_OVERWRITE)) {
+            m_run = ex.row_max[row];
+            l_run = ex.row_sum[row];
         }
     }
     // the gathered operand: byte address of column col0 of its row 0, and its row pitch in bytes
@@ -368,7 +382,45 @@ __device__ __forceinline__ void process_row(int64_t row, int beg, int end, bool 
                 wgt = 0.0;
             }
         }
-        if constexpr (OP != Op::kSddmm) {
+        if constexpr (OP == Op::kFusedSoftmax) {
+            // online softmax, nonzero by nonzero in row order: wgt is the score s of nonzero `mine`.  Every lane walks the prefix max
+            // over the batch (starting from the row's running max) and keeps the values before / after its own nonzero, then computes
+            // its nonzero's rescale factor f = exp(M_prev - M) and weight p = exp(s - M); the axpy below applies them in order.
+            const double s = have ? wgt : -__builtin_inf();
+            double run = m_run, mprev = m_run, mcur = m_run;
+#pragma unroll
+            for (int u = 0; u < U; u++) {
+                const double t = group_bcast<LPR>(s, u * SUB);
+                const double nx = t > run ? t : run;
+                if (lig / SUB == u) { mprev = run; mcur = nx; }
+                run = nx;
+            }
+            // (the empty state: (-inf) - (-inf) never reaches exp)
+            const double fac = (mcur == mprev) ? 1.0 : (mprev == -__builtin_inf() ? 0.0 : exp(mprev - mcur));
+            const double pw = have ? exp(s - mcur) : 0.0;
+            m_run = run;
+#pragma unroll
+            for (int u = 0; u < U; u++) {
+                const double fu = group_bcast<LPR>(fac, u * SUB);
+                const double pu = group_bcast<LPR>(pw, u * SUB);
+                if (fu != 1.0) {  // the running max rose (uniform over the group; rare after the first few nonzeros)
+#pragma unroll
+                    for (int v = 0; v < VEC; v++)
+#pragma unroll
+                        for (int w = 0; w < W; w++) acc[v][w] *= fu;
+                    l_run *= fu;
+                }
+                l_run += pu;
+#pragma unroll
+                for (int v = 0; v < VEC; v++)
+#pragma unroll
+                    for (int w = 0; w < W; w++) acc[v][w] = fma(pu, y[u][v][w], acc[v][w]);
+            }
+#pragma unroll
+            for (int v = 0; v < VEC; v++)
+#pragma unroll
+                for (int w = 0; w < W; w++) asm volatile("" : "+v"(acc[v][w]));
+        } else if constexpr (OP != Op::kSddmm) {
 #pragma unroll
             for (int u = 0; u < U; u++) {
                 const double wu = group_bcast<LPR>(wgt, u * SUB);
@@ -667,8 +719,27 @@ __device__ __forceinline__ void process_row(int64_t row, int beg, int end, bool 
     }
     }  // !NARROW
 
+    if constexpr (OP == Op::kFusedSoftmax) {
+        // the row's state leaves with every launch (also the finishing one: the state after a pass does not depend on its grouping)
+        if (lig == 0) {
+            ex.row_max[row] = m_run;
+            ex.row_sum[row] = l_run;
+        }
+        if (flags & kInternalEpilogue) {  // finish: o = Out / l through the ReLU into the head's column block, and lse; Out is scratch
+            const bool live = l_run > 0.0;
+#pragma unroll
+            for (int v = 0; v < VEC; v++) {
+                double o[W];
+#pragma unroll
+                for (int w = 0; w < W; w++) o[w] = live ? fmax(acc[v][w] / l_run, 0.0) : 0.0;
+                if (act[v]) store_w_stream<W>(ex.relu_dst + row * ex.relu_ld + coff[v], o);
+            }
+            if (lig == 0) ex.lse[row] = live ? m_run + log(l_run) : 0.0;
+            return;
+        }
+    }
     if constexpr (OP != Op::kSddmm) {
-        if (fused_op(OP) && (flags & kInternalEpilogue) && !atomic_out) {  // the row is complete in this launch
+        if (fused_op(OP) && OP != Op::kFusedSoftmax && (flags & kInternalEpilogue) && !atomic_out) {  // the row is complete in this launch
             double part = 0.0;
 #pragma unroll
             for (int v = 0; v < VEC; v++)
@@ -1720,9 +1791,11 @@ int launch_row(hnh_ctx* ctx, hipStream_t st, const LongCtl& lc, int64_t rows, co
     hipLaunchKernelGGL((row_kernel<OP, LPR, VEC, W, EXACT, NARROW>), dim3((unsigned)blocks), dim3(kBlock), lds_pad, st, rows, rowptr, beg_ptr, end_ptr,
                        colidx, values, svalues, X, Y, Out, ld, col0, ncols, flags, ex);
     if (int rc = hnh::check_hip(ctx, hipGetLastError(), "row_kernel launch")) return rc;
+    if constexpr (OP == Op::kFusedSoftmax) return HNH_OK;  // (hub rows are never split: dispatch_row prepares no long-row list)
     if (lc.enabled && run_long) {  // hub rows once per pass (after the last column panel), over their whole length
         // (the segments are plain fused work whatever epilogue the closing launch carries: the kFused instance)
-        constexpr Op LOP = (OP == Op::kFusedCg) ? Op::kFused : OP;
+        // (never reached by kFusedSoftmax, which returned above: mapping it to kFused keeps a long-row instance of it from being compiled)
+        constexpr Op LOP = (OP == Op::kFusedCg || OP == Op::kFusedSoftmax) ? Op::kFused : OP;
         // 256 CUs x 4 resident workgroups; items are spread round-robin over all groups of the grid
         double* partials = (OP != Op::kSddmm) ? lc.partials : nullptr;
         hipLaunchKernelGGL((long_row_kernel<LOP, LPR, VEC, W, EXACT, NARROW>), dim3((unsigned)ctx->long_grid), dim3(kBlock), 0, st, lc.items, lc.count,
@@ -1757,6 +1830,15 @@ int launch_shape(hnh_ctx* ctx, hipStream_t st, const LongCtl& lc, const Shape& s
 #define HNH_CASE(L, V)                                                                                                     \
     if (s.lpr == L && s.vec == V)                                                                                          \
         return launch_row<OP, L, V, 2, true>(ctx, st, lc, rows, rowptr, beg_ptr, end_ptr, colidx, values, svalues, X, Y, Out, R, 0, R, flags, ex, run_long);
+#define HNH_NX(V, WW)                                                                                                      \
+    if (s.w == WW && R <= 64 * WW * V)                                                                                     \
+        return launch_row<OP, 64, V, WW, false>(ctx, st, lc, rows, rowptr, beg_ptr, end_ptr, colidx, values, svalues, X, Y, Out, R, 0, R, flags, ex, run_long);
+    if constexpr (OP == Op::kFusedSoftmax) {
+        // exact widths 64 / 128 / 256 (the GAT's heads), every other one-pass width bounds-checked
+        if (s.exact) { HNH_CASE(32, 1) HNH_CASE(64, 1) HNH_CASE(64, 2) }
+        HNH_NX(1, 2) HNH_NX(2, 2) HNH_NX(4, 2) HNH_NX(1, 1) HNH_NX(2, 1) HNH_NX(4, 1)
+        return -1;
+    } else {
     if (s.exact) {
         // narrow rows with line-aligned CSR streams: the line-granular instances (process_row, NARROW)
         if (ctx->narrow_rows && (s.lpr == 4 || s.lpr == 8 || s.lpr == 16) && s.vec == 1 && aligned128(colidx) && aligned128(values) &&
@@ -1771,18 +1853,16 @@ int launch_shape(hnh_ctx* ctx, hipStream_t st, const LongCtl& lc, const Shape& s
         HNH_CASE(64, 2) HNH_CASE(64, 3) HNH_CASE(64, 4) HNH_CASE(32, 3) HNH_CASE(32, 5) HNH_CASE(32, 7)
         return hnh::fail(ctx, HNH_ERR_UNSUPPORTED, "no kernel instance for this shape");
     }
-#undef HNH_CASE
     if constexpr (OP == Op::kFusedCg) return hnh::fail(ctx, HNH_ERR_UNSUPPORTED, "the CG epilogue has exact-width instances only");
     // Widths that are not a supported exact multiple: one bounds-checked pass when the row fits the widest
     // instance (R <= 512 even / 256 odd)
-#define HNH_NX(V, WW)                                                                                                      \
-    if (s.w == WW && R <= 64 * WW * V)                                                                                     \
-        return launch_row<OP, 64, V, WW, false>(ctx, st, lc, rows, rowptr, beg_ptr, end_ptr, colidx, values, svalues, X, Y, Out, R, 0, R, flags, ex, run_long);
     if constexpr (OP != Op::kFusedCg) {
         HNH_NX(1, 2) HNH_NX(2, 2) HNH_NX(4, 2) HNH_NX(1, 1) HNH_NX(2, 1) HNH_NX(4, 1)
     }
-#undef HNH_NX
     return -1;
+    }
+#undef HNH_CASE
+#undef HNH_NX
 }
 
 // launch_shape for the launch that completes the output rows: with the in-launch epilogue (kInternalEpilogue in `flags`) and CG
@@ -1823,9 +1903,11 @@ int dispatch_row(hnh_ctx* ctx, hipStream_t st, int sidx, const Shape& s, int64_t
         }
     }
     LongCtl lc;
-    if (int rc = prepare_long(ctx, st, sidx, rows, rowptr, nnz, max_row_nnz, (OP != Op::kSddmm) ? (int64_t)R : 0, &lc,
-                              win == nullptr || win->last != 0, plan))
-        return rc;
+    // (the softmax pass walks hub rows whole, one group each: a row's scores are combined in row order, never by segments)
+    if (OP != Op::kFusedSoftmax)
+        if (int rc = prepare_long(ctx, st, sidx, rows, rowptr, nnz, max_row_nnz, (OP != Op::kSddmm) ? (int64_t)R : 0, &lc,
+                                  win == nullptr || win->last != 0, plan))
+            return rc;
     if (!lc.enabled || ctx->row_waves_cap > 0) lc.lds_pad = row_occupancy_pad(ctx, s, rows, nnz, max_row_nnz);  // (hub rows = a skewed block)
     const bool single_pass = s.exact || R <= 64 * s.w * 4;
     // the epilogue can ride in the launches that complete the rows: short rows are completed by ONE group of the row kernel, hub rows
@@ -1834,7 +1916,9 @@ int dispatch_row(hnh_ctx* ctx, hipStream_t st, int sidx, const Shape& s, int64_t
     const bool extra_rows_ok = s.w == 1 || ((ex.cg_x == nullptr || (aligned16(ex.cg_x) && aligned16(ex.cg_r))) &&
                                             (ex.relu_dst == nullptr || (aligned16(ex.relu_dst) && ex.relu_ld % 2 == 0)));  // 16-byte row accesses
     const bool hubs_ok = !lc.enabled || (lc.partials != nullptr && lc.partial_items >= lc.capacity);
-    const bool epilogue_in_launch = hubs_ok && single_pass && ((ex.cg_x == nullptr && ex.relu_dst == nullptr) || (s.exact && extra_rows_ok));
+    const bool epilogue_in_launch = (OP == Op::kFusedSoftmax)  // (its caller checked the ReLU destination's alignment into the shape)
+                                        ? single_pass
+                                        : hubs_ok && single_pass && ((ex.cg_x == nullptr && ex.relu_dst == nullptr) || (s.exact && extra_rows_ok));
     if (win != nullptr) {
         // a caller-defined window of every row; hub rows stay whole and go to the long-row pass with the pass's last window,
         // which is also where a row epilogue can run inside the launch
@@ -1845,7 +1929,7 @@ int dispatch_row(hnh_ctx* ctx, hipStream_t st, int sidx, const Shape& s, int64_t
         const unsigned f = flags | ((epilogue_done != nullptr && *epilogue_done) ? kInternalEpilogue : 0u);
         const int rcw = launch_closing<OP>(ctx, st, lc, s, rows, rowptr, beg_ptr, end_ptr, colidx, values, svalues, X, Y, Out, R, f, ex, last);
         if (rcw != -1) return rcw;
-        if (OP == Op::kFused) return hnh::fail(ctx, HNH_ERR_UNSUPPORTED, "fused fallback is composed by the caller");
+        if (OP == Op::kFused || OP == Op::kFusedSoftmax) return hnh::fail(ctx, HNH_ERR_UNSUPPORTED, "fused fallback is composed by the caller");
         const int wtile = 64 * s.w;
         for (int col0 = 0; col0 < R; col0 += wtile) {
             const int ncols = (R - col0 < wtile) ? (R - col0) : wtile;
@@ -1946,7 +2030,7 @@ int dispatch_row(hnh_ctx* ctx, hipStream_t st, int sidx, const Shape& s, int64_t
     const int rc1 = launch_closing<OP>(ctx, st, lc, s, rows, rowptr, rowptr, rowptr + 1, colidx, values, svalues, X, Y, Out, R, flags | epi, ex);
     if (rc1 != -1) return rc1;
     // ... else column tiles; SDDMM partial dot products accumulate into `values` tile by tile
-    if (OP == Op::kFused) return hnh::fail(ctx, HNH_ERR_UNSUPPORTED, "fused fallback is composed by the caller");
+    if (OP == Op::kFused || OP == Op::kFusedSoftmax) return hnh::fail(ctx, HNH_ERR_UNSUPPORTED, "fused fallback is composed by the caller");
     const int tile = 64 * s.w;
     for (int col0 = 0; col0 < R; col0 += tile) {
         const int ncols = (R - col0 < tile) ? (R - col0) : tile;
@@ -2548,6 +2632,122 @@ int hnh_expand_rowptr(hnh_ctx* ctx, int64_t rows, const int32_t* rowptr, int32_t
     const int64_t blocks = (rows * 64 + kBlock - 1) / kBlock;
     hipLaunchKernelGGL(expand_rowptr_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, ctx->streams[stream], rows, rowptr, row_idx);
     return hnh::check_hip(ctx, hipGetLastError(), "expand_rowptr_kernel launch");
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- neighbourhood-softmax attention (include/hnh_attention.h)
+namespace {
+// a block without any nonzero: the state reset of HNH_FUSED_OUT_OVERWRITE and the finish of HNH_ATTN_FINISH, as process_row does them
+// for a row whose piece is empty (one wave per row)
+__global__ __launch_bounds__(kBlock) void attn_empty_rows_kernel(int64_t rows, double* __restrict__ Out, int R, unsigned flags, Extras ex) {
+    const int64_t row = ((int64_t)blockIdx.x * kBlock + threadIdx.x) / 64;
+    const int lane = threadIdx.x % 64;
+    if (row >= rows) return;
+    const bool fresh = (flags & HNH_FUSED_OUT_OVERWRITE) != 0, finish = (flags & kInternalEpilogue) != 0;
+    const double m = fresh ? -__builtin_inf() : ex.row_max[row];
+    const double l = fresh ? 0.0 : ex.row_sum[row];
+    for (int c = lane; c < R; c += 64) {
+        const double a = fresh ? 0.0 : Out[row * R + c];
+        if (finish) ex.relu_dst[row * ex.relu_ld + c] = l > 0.0 ? fmax(a / l, 0.0) : 0.0;
+        else Out[row * R + c] = a;
+    }
+    if (lane == 0) {
+        ex.row_max[row] = m;
+        ex.row_sum[row] = l;
+        if (finish) ex.lse[row] = l > 0.0 ? m + log(l) : 0.0;
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void softmax_gate_kernel(double* __restrict__ e_to_a, double* __restrict__ da_to_de, const double* __restrict__ lse,
+                                                              const double* __restrict__ delta, double alpha, int64_t n) {
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
+        const double e = e_to_a[i];
+        const double s = e > 0.0 ? e : alpha * e;
+        const double a = exp(s - lse[i]);
+        e_to_a[i] = a;
+        da_to_de[i] = a * (da_to_de[i] - delta[i]) * (e > 0.0 ? 1.0 : alpha);
+    }
+}
+
+// out[r] = <dZ[r, :cols], O[r, col0 : col0 + cols]>, one wave per row
+__global__ __launch_bounds__(kBlock) void rowdot_cols_kernel(double* __restrict__ out, const double* __restrict__ dZ, int64_t ld_dz,
+                                                             const double* __restrict__ O, int64_t ld_o, int64_t col0, int64_t rows, int64_t cols) {
+    const int64_t row = ((int64_t)blockIdx.x * kBlock + threadIdx.x) / 64;
+    const int lane = threadIdx.x % 64;
+    if (row >= rows) return;
+    double s = 0.0;
+    for (int64_t c = lane; c < cols; c += 64) s = fma(dZ[row * ld_dz + c], O[row * ld_o + col0 + c], s);
+    s = group_sum<64>(s);
+    if (lane == 0) out[row] = s;
+}
+}  // namespace
+
+extern "C" {
+
+int hnh_attn_softmax_csr_p(hnh_ctx* ctx, const hnh_csr_block* b, double* values, const double* X, const double* Y, double* Out, int R,
+                           unsigned flags, const hnh_attn_state* state, const hnh_csr_window* window, int stream) {
+    HNH_ENTER(ctx, stream);
+    const char* who = "hnh_attn_softmax_csr_p";
+    if (!b || !state) return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": null block or state");
+    if (int rc = check_common(ctx, b->rows, R, who)) return rc;
+    if (flags & ~(HNH_FUSED_VALUES_OVERWRITE | HNH_FUSED_OUT_OVERWRITE | HNH_ATTN_FINISH)) return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": unknown flag");
+    const bool finish = (flags & HNH_ATTN_FINISH) != 0;
+    if (finish && window != nullptr && !window->last) return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": the finish belongs to the last window");
+    if (!state->row_max || !state->row_sum || !state->lse || !state->relu_dst) return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": null state pointer");
+    if (state->relu_ld < R) return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": relu_ld is narrower than R");
+    if (b->rows == 0) return HNH_OK;
+    if (!Out) return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": null pointer");
+    Extras ex;
+    ex.leaky_alpha = state->leaky_alpha;
+    ex.relu_dst = state->relu_dst;
+    ex.relu_ld = state->relu_ld;
+    ex.row_max = state->row_max;
+    ex.row_sum = state->row_sum;
+    ex.lse = state->lse;
+    hipStream_t st = ctx->streams[stream];
+    if (b->rowptr == nullptr) {  // a block without nonzeros
+        if (b->nnz > 0) return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": null rowptr");
+        const unsigned f = (flags & HNH_FUSED_OUT_OVERWRITE) | (finish ? kInternalEpilogue : 0u);
+        hipLaunchKernelGGL(attn_empty_rows_kernel, dim3((unsigned)((b->rows * 64 + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, b->rows, Out, R, f, ex);
+        return hnh::check_hip(ctx, hipGetLastError(), "attn_empty_rows_kernel launch");
+    }
+    if (!b->col_idx || !values || !X || !Y) return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": null pointer");
+    if (X == Out || Y == Out) return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": Out aliases an input");
+    // one shape for every call of a pass (the row state is continued across them, and the scores' rounding depends on the shape): the
+    // ReLU destination is part of every call's state
+    const Shape s = pick_shape(R, aligned16(X) && aligned16(Y) && aligned16(Out) && aligned16(state->relu_dst) && state->relu_ld % 2 == 0);
+    if (!(s.exact || R <= 256 * s.w))
+        return hnh::fail(ctx, HNH_ERR_UNSUPPORTED, std::string(who) + ": width beyond the one-pass instances (a softmax cannot be composed of two passes)");
+    bool done = false;
+    const unsigned f = (flags & (HNH_FUSED_VALUES_OVERWRITE | HNH_FUSED_OUT_OVERWRITE)) | HNH_FUSED_LEAKY_RELU;
+    if (int rc = dispatch_row<Op::kFusedSoftmax>(ctx, st, stream, s, b->rows, b->nnz, b->max_row_nnz, window ? -1 : b->cols, b->rowptr, b->col_idx, values,
+                                                 nullptr, X, Y, Out, R, f, ex, finish ? &done : nullptr, window, b->plan))
+        return rc;
+    if (finish && !done) return hnh::fail(ctx, HNH_ERR_UNSUPPORTED, std::string(who) + ": the finish did not run inside the pass");
+    return HNH_OK;
+}
+
+int hnh_softmax_gate_f64(hnh_ctx* ctx, double* e_to_a, double* da_to_de, const double* lse, const double* delta, double alpha, int64_t n,
+                         int stream) {
+    HNH_ENTER(ctx, stream);
+    if (n < 0) return hnh::fail(ctx, HNH_ERR_INVALID, "hnh_softmax_gate_f64: bad size");
+    if (n == 0) return HNH_OK;
+    if (!e_to_a || !da_to_de || !lse || !delta) return hnh::fail(ctx, HNH_ERR_INVALID, "hnh_softmax_gate_f64: null pointer");
+    hipLaunchKernelGGL(softmax_gate_kernel, dim3(ew_grid(n)), dim3(kBlock), 0, ctx->streams[stream], e_to_a, da_to_de, lse, delta, alpha, n);
+    return hnh::check_hip(ctx, hipGetLastError(), "softmax_gate_kernel launch");
+}
+
+int hnh_rowdot_cols_f64(hnh_ctx* ctx, double* out, const double* dZ, int64_t ld_dz, const double* O, int64_t ld_o, int64_t col0, int64_t rows,
+                        int64_t cols, int stream) {
+    HNH_ENTER(ctx, stream);
+    if (rows < 0 || cols < 0 || col0 < 0 || ld_dz < cols || ld_o < col0 + cols) return hnh::fail(ctx, HNH_ERR_INVALID, "hnh_rowdot_cols_f64: bad size");
+    if (rows == 0) return HNH_OK;
+    if (!out || !dZ || !O) return hnh::fail(ctx, HNH_ERR_INVALID, "hnh_rowdot_cols_f64: null pointer");
+    hipLaunchKernelGGL(rowdot_cols_kernel, dim3((unsigned)((rows * 64 + kBlock - 1) / kBlock)), dim3(kBlock), 0, ctx->streams[stream], out, dZ, ld_dz, O,
+                       ld_o, col0, rows, cols);
+    return hnh::check_hip(ctx, hipGetLastError(), "rowdot_cols_kernel launch");
 }
 
 }  // extern "C"

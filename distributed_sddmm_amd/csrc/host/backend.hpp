@@ -6,6 +6,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <string>
+#include "hnh_attention.h"
 #include "hnh_grad.h"
 #include "hnh_kernels.h"
 #ifdef HNH_MEASUREMENT_AIDS
@@ -43,6 +44,8 @@ struct Backend {
     // only GAT::backwardPass needs it, and it fails with an error naming the missing symbol
     HNH_FN(hnh_gemm_tn_f64_workspace) HNH_FN(hnh_gemm_tn_f64) HNH_FN(hnh_leaky_relu_grad_f64) HNH_FN(hnh_relu_grad_cols_f64)
     HNH_FN(hnh_sum3_cols_f64) HNH_FN(hnh_transpose_into_f64)
+    // OPTIONAL group (include/hnh_attention.h), bound the same way: only the GAT's softmax attention needs it
+    HNH_FN(hnh_attn_softmax_csr_p) HNH_FN(hnh_softmax_gate_f64) HNH_FN(hnh_rowdot_cols_f64)
 #ifdef HNH_MEASUREMENT_AIDS
     HNH_FN(hnh_stream_delay_us) HNH_FN(hnh_stream_paced_copy) HNH_FN(hnh_stream_pace_begin) HNH_FN(hnh_stream_pace_end)
 #endif

@@ -284,6 +284,19 @@ public:
         return true;
     }
 
+    // Neighbourhood-softmax attention (include/hnh_attention.h) in one fused pass: Out's rows are the running accumulators, `state`
+    // holds the rows' running max / sum, the log-sum-exp and the ReLU destination.  Returns false, having done nothing, where a row's
+    // nonzeros are not all summed by this rank's own launches (only approach 2 with c = 1 has such a pass).  Not a virtual of
+    // Distributed_Sparse: that would change the vtable of every schedule, which drivers compiled against the previous headers embed.
+    bool fusedSoftmax_out(DenseMatrix& localA, DenseMatrix& localB, MatMode mode, DenseMatrix& Out, const hnh_attn_state& state) {
+        if (fusionApproach != 2 || c != 1) return false;  // (c > 1 reduce-scatters partial rows: a softmax cannot be summed that way)
+        DenseMatrix& Xin = (mode == Amat) ? localA : localB;
+        if (Out.rows() != Xin.rows() || Out.cols() != Xin.cols() || Out.data() == Xin.data())
+            hnh::fatal("Error, fusedSoftmax_out needs a separate output of the input's shape!");
+        fused_pass(Xin, mode == Amat ? localB : localA, mode == Amat ? S.get() : ST.get(), &Out, 0u, nullptr, &state);
+        return true;
+    }
+
 private:
     // ---- merged layout helpers
     // visiting step of global block column b on this rank (block_at(k) == b), or -1 when the rank never visits it
@@ -444,8 +457,9 @@ private:
 
     // One pass of shifts with the fused kernel on every visiting block.  target == nullptr: the result replaces
     // Xin (the reference's in-place fusedSpMM); otherwise it is written to *target and Xin survives.
+    // softmax != nullptr: the neighbourhood-softmax instance (KernelImplementation::softmax_local) instead of the fused pair, c == 1 only.
     void fused_pass(DenseMatrix& Xin, DenseMatrix& moving, SpmatLocal* choice, DenseMatrix* target, unsigned act_flag,
-                    const hnh_fused_extras* extras) {
+                    const hnh_fused_extras* extras, const hnh_attn_state* softmax = nullptr) {
         DenseMatrix* Arole = &Xin;
         DenseMatrix* Brole = &moving;
         const int n = p / c;
@@ -473,26 +487,31 @@ private:
         const unsigned base = HNH_FUSED_VALUES_OVERWRITE | act_flag;
         bool out_fresh = true;
         // the fused kernel on one block (or one window of it); `ex` = what the call applies besides the multiplication
-        auto fused_on = [&](int block_id, DenseMatrix& Y, int window, int window_end, const hnh_fused_extras* ex) {
+        // (closing: the call that completes the rows; a softmax pass always makes it, and its first call, to reset and finish the row state)
+        auto fused_on = [&](int block_id, DenseMatrix& Y, int window, int window_end, bool closing) {
+            const hnh_fused_extras* ex = closing ? last : act;
             CSRLocal* blk = choice->csr_blocks[block_id];
-            if (blk == nullptr && ex == act) return;  // nothing to multiply and no epilogue to run
+            if (blk == nullptr && ex == act && !(softmax && (closing || out_fresh))) return;  // nothing to multiply and no epilogue to run
             if (blk != nullptr) {
                 blk->window = window;
                 blk->window_end = window_end;
             }
-            kernel->fused_local(*choice, *rowOperand, Y, *accum, block_id, base | (out_fresh ? HNH_FUSED_OUT_OVERWRITE : 0u), ex);
+            const unsigned flags = base | (out_fresh ? HNH_FUSED_OUT_OVERWRITE : 0u);
+            const bool done = softmax ? kernel->softmax_local(*choice, *rowOperand, Y, *accum, block_id, flags, *softmax, closing)
+                                      : (kernel->fused_local(*choice, *rowOperand, Y, *accum, block_id, flags, ex), true);
             if (blk != nullptr) blk->window = blk->window_end = -1;
+            if (!done) throw hnh::Error("Error, the kernel implementation has no softmax attention pass (KernelImplementation::softmax_local)!");
             out_fresh = false;
         };
 
         if (merged) {
             walk_merged(choice, Brole, [&](int block_id, DenseMatrix& Y, int window, int window_end, bool is_last) {
-                fused_on(block_id, Y, window, window_end, is_last ? last : act);
+                fused_on(block_id, Y, window, window_end, is_last);
             });
         } else {
             ring_readonly(Brole, n, [&](int i, DenseMatrix& cur) {
                 auto t = phase_begin("Computation Time");
-                fused_on(block_at(i), cur, -1, -1, (i == n - 1) ? last : act);
+                fused_on(block_at(i), cur, -1, -1, i == n - 1);
                 phase_end(t);
             });
         }

@@ -23,12 +23,21 @@
 //     dX = dA_all * [W_1^T; ..; W_H^T]   hnh_gemm_f64: the G of layer i - 1, or the input gradient for layer 0
 // Everything runs on the compute stream.  Supported where the forward pass is oracle.gat_forward's math and R is not split:
 // 15d_fusion1 (any c) and 15d_fusion2 with c = 1.  The dense kernels are the optional group of include/hnh_grad.h.
+//
+// Attention mode (an addition): HNH_GAT_ATTENTION_NONE (the default) uses the LeakyReLU scores raw, as above;
+// HNH_GAT_ATTENTION_SOFTMAX normalises them over each row's neighbourhood (Velickovic et al.):
+//     s_ij = LeakyReLU(<A_i, A_j>),  lse_i = log sum_j exp(s_ij),  a_ij = exp(s_ij - lse_i),  out[:, h f ..] = ReLU(sum_j a_ij A_j)
+// in ONE fused pass per head with an online softmax (include/hnh_attention.h; lse kept per (layer, head)).  Its backward pass is the
+// one above with a in place of LeakyReLU(e) and, with delta_i = <dZ_i, out_i> and the lse and delta broadcast onto the nonzeros by
+// width-1 SDDMMs in both layouts, de_ij = a_ij (da_ij - delta_i) LeakyReLU'(e_ij) (hnh_softmax_gate_f64).  15d_fusion2 with c = 1
+// only: on every other schedule a row's nonzeros are summed across ranks, which a softmax cannot be.
 #pragma once
 #include "dense_shift_15d.hpp"
 #include "distributed_sparse.hpp"
 #include <cstdlib>
 #include <map>
 #include <tuple>
+#include "hnh_dist.h"
 
 class GATLayer {
 public:
@@ -74,6 +83,15 @@ public:
     GAT(const GAT&) = delete;
     GAT& operator=(const GAT&) = delete;
 
+    // HNH_GAT_ATTENTION_NONE | HNH_GAT_ATTENTION_SOFTMAX (include/hnh_dist.h); a change invalidates the stored forward pass
+    int attention() const { return attention_; }
+    void set_attention(int mode) {
+        if (mode != HNH_GAT_ATTENTION_NONE && mode != HNH_GAT_ATTENTION_SOFTMAX)
+            throw hnh::Error("Error, unknown GAT attention mode " + std::to_string(mode) + " (none = 0, softmax = 1)!");
+        if (mode != attention_) invalidate_forward();
+        attention_ = mode;
+    }
+
     // Computes the j'th self-attention head of the i'th layer (gat.hpp:83-104)
     void computeSelfAttentionHead(int i, int j) {
         DenseMatrix A;
@@ -86,6 +104,7 @@ public:
     // between two product buffers; the layers' outputs are the reference's, bit for bit (same kernels, same operands).
     // HNH_GAT_SERIAL=1: the reference's order on one stream (A/B measurements).
     void forwardPass() {
+        if (attention_ == HNH_GAT_ATTENTION_SOFTMAX) check_softmax_supported();
         if (std::getenv("HNH_GAT_SERIAL") != nullptr) {
             for (size_t i = 0; i < layers.size(); i++)
                 for (int j = 0; j < layers[i].num_heads; j++) computeSelfAttentionHead((int)i, j);
@@ -139,6 +158,12 @@ public:
             e_ST_ = VectorXd(ones_ST_.size());
             d_ST_ = VectorXd(ones_ST_.size());
         }
+        if (attention_ == HNH_GAT_ATTENTION_SOFTMAX && lse_S_.size() != ones_S_.size()) {
+            lse_S_ = VectorXd(ones_S_.size());
+            delta_S_ = VectorXd(ones_S_.size());
+            lse_ST_ = VectorXd(ones_ST_.size());
+            delta_ST_ = VectorXd(ones_ST_.size());
+        }
         const int L = (int)layers.size();
         if ((int)weight_grads.size() != L) {
             weight_grads.assign((size_t)L, DenseMatrix());
@@ -156,6 +181,12 @@ public:
 private:
     hnh::World* world_ = nullptr;
     bool forward_valid_ = false;
+    int attention_ = HNH_GAT_ATTENTION_NONE;
+    // softmax attention: the rows' running max / sum (reused by every head, which run one after the other on the compute stream), the
+    // log-sum-exp of every (layer, head), and for the backward pass a column of ones and the broadcasts of lse and delta onto the nonzeros
+    DenseMatrix row_max_, row_sum_, ones_col_;
+    std::vector<std::vector<DenseMatrix>> lse_;
+    VectorXd lse_S_, delta_S_, lse_ST_, delta_ST_;
     VectorXd ones_S_, ones_ST_, e_S_, d_S_, e_ST_, d_ST_;  // backward: S values (= 1) and the recomputed / gated value vectors
     std::map<std::tuple<int, int64_t, int64_t>, DenseMatrix> scratch_;  // backward work buffers by (role, rows, cols)
 
@@ -182,6 +213,29 @@ private:
             if (n.first == nullptr)
                 throw hnh::Error(std::string("Error, GAT backwardPass needs the kernel ") + n.second + ", which the kernel library " + be->path +
                                  " does not export (include/hnh_grad.h)");
+        if (attention_ == HNH_GAT_ATTENTION_SOFTMAX) {
+            const std::pair<const void*, const char*> need_attn[] = {
+                {(const void*)be->hnh_softmax_gate_f64, "hnh_softmax_gate_f64"}, {(const void*)be->hnh_rowdot_cols_f64, "hnh_rowdot_cols_f64"}};
+            for (const auto& n : need_attn)
+                if (n.first == nullptr)
+                    throw hnh::Error(std::string("Error, GAT backwardPass with softmax attention needs the kernel ") + n.second +
+                                     ", which the kernel library " + be->path + " does not export (include/hnh_attention.h)");
+        }
+    }
+
+    // Throws hnh::Error (never a wrong number) where softmax attention is not defined or its kernel is missing: a row's softmax needs
+    // all of the row's nonzeros summed by this rank's own launches, which only 15d_fusion2 with c = 1 does (15d_fusion1 reduce-scatters
+    // over the mesh; c > 1, the 2.5D schedules and the sparse shift reduce across ranks too).
+    void check_softmax_supported() {
+        auto* ds = dynamic_cast<Sparse15D_Dense_Shift*>(d_ops);
+        if (ds == nullptr || ds->r_split || ds->fusionApproach != 2 || ds->c != 1)
+            throw hnh::Error("Error, GAT softmax attention supports 15d_fusion2 with c = 1 only, not " +
+                             (ds ? "15d_fusion" + std::to_string(ds->fusionApproach) + " (" + d_ops->algorithm_name + ")" : d_ops->algorithm_name) +
+                             " with c = " + std::to_string(d_ops->c) + ": its rows are summed across ranks");
+        const hnh::Backend* be = d_ops->world->be;
+        if (be->hnh_attn_softmax_csr_p == nullptr)
+            throw hnh::Error(std::string("Error, GAT softmax attention needs the kernel hnh_attn_softmax_csr_p, which the kernel library ") + be->path +
+                             " does not export (include/hnh_attention.h)");
     }
 
     // one layer of the backward pass: G = dL/d(buffers[i + 1]) -> weight_grads[i], input_grads[i]
@@ -208,15 +262,39 @@ private:
             w->check(be->hnh_gemm_f64(w->ctx, rows, f, k, X.data(), Wh.data(), A.data(), S0), "hnh_gemm_f64");
             w->check(be->hnh_relu_grad_cols_f64(w->ctx, dZ.data(), f, G.data(), hf, out.data(), hf, (int64_t)h * f, rows, f, S0),
                      "hnh_relu_grad_cols_f64");
+            const bool softmax = attention_ == HNH_GAT_ATTENTION_SOFTMAX;
+            if (softmax) {
+                // delta_i = <dZ_i, out_i> (= <dZ_i, o_i>: dZ is 0 where out is), then lse_i and delta_i onto the nonzeros of both layouts:
+                // width-1 SDDMMs whose first operand is the S-row side in both, so S^T gets the per-row scalars from the rank that owns them
+                DenseMatrix& delta = scratch(8, rows, 1);
+                w->check(be->hnh_rowdot_cols_f64(w->ctx, delta.data(), dZ.data(), f, out.data(), hf, (int64_t)h * f, rows, f, S0),
+                         "hnh_rowdot_cols_f64");
+                DenseMatrix& lse = lse_.at((size_t)i).at((size_t)h);
+                if (ones_col_.rows() != rows) ones_col_ = DenseMatrix::Constant(rows, 1, 1.0);
+                d_ops->setRValue(1);
+                d_ops->sddmmA(lse, ones_col_, ones_S_, lse_S_);
+                d_ops->sddmmA(delta, ones_col_, ones_S_, delta_S_);
+                d_ops->sddmmB(lse, ones_col_, ones_ST_, lse_ST_);
+                d_ops->sddmmB(delta, ones_col_, ones_ST_, delta_ST_);
+                d_ops->setRValue(f);
+            }
+            // the gate: e -> a (LeakyReLU(e), or its softmax weight), da -> de
+            auto gate = [&](VectorXd& e, VectorXd& d, VectorXd& lse_nz, VectorXd& delta_nz) {
+                if (softmax)
+                    w->check(be->hnh_softmax_gate_f64(w->ctx, e.data(), d.data(), lse_nz.data(), delta_nz.data(), leaky_relu_alpha, e.size(), S0),
+                             "hnh_softmax_gate_f64");
+                else
+                    w->check(be->hnh_leaky_relu_grad_f64(w->ctx, e.data(), d.data(), leaky_relu_alpha, e.size(), S0), "hnh_leaky_relu_grad_f64");
+            };
             // S layout: e_ij = <A_i, A_j>, da_ij = <dZ_i, A_j>, gate, row side dA_i = sum_j de_ij A_j
             d_ops->sddmmA(A, A, ones_S_, e_S_);
             d_ops->sddmmA(dZ, A, ones_S_, d_S_);
-            w->check(be->hnh_leaky_relu_grad_f64(w->ctx, e_S_.data(), d_S_.data(), leaky_relu_alpha, e_S_.size(), S0), "hnh_leaky_relu_grad_f64");
+            gate(e_S_, d_S_, lse_S_, delta_S_);
             d_ops->spmmA(dArow, A, d_S_);
             // ST layout: the same values on the transpose's nonzeros, column sides sum_i a_ij dZ_i and sum_i de_ij A_i
             d_ops->sddmmB(A, A, ones_ST_, e_ST_);
             d_ops->sddmmB(dZ, A, ones_ST_, d_ST_);
-            w->check(be->hnh_leaky_relu_grad_f64(w->ctx, e_ST_.data(), d_ST_.data(), leaky_relu_alpha, e_ST_.size(), S0), "hnh_leaky_relu_grad_f64");
+            gate(e_ST_, d_ST_, lse_ST_, delta_ST_);
             d_ops->spmmB(dZ, T1, e_ST_);
             d_ops->spmmB(A, T2, d_ST_);
             w->check(be->hnh_sum3_cols_f64(w->ctx, dA_all.data(), hf, (int64_t)h * f, dArow.data(), T1.data(), T2.data(), rows, f, S0),
@@ -262,6 +340,27 @@ private:
         hnh::World* w = d_ops->world;
         d_ops->setRValue(layers[i].features_per_head);
         DenseMatrix& out = buffers[i + 1];
+
+        if (attention_ == HNH_GAT_ATTENTION_SOFTMAX) {
+            // one fused pass with the online softmax (include/hnh_attention.h): the head's ReLU output leaves the finishing launch
+            // straight into its column block, lse into this head's vector; H carries the unnormalised rows between the launches
+            const int64_t rows = A.rows();
+            if (row_max_.rows() != rows) {
+                row_max_ = DenseMatrix(rows, 1);
+                row_sum_ = DenseMatrix(rows, 1);
+            }
+            if (lse_.size() != layers.size()) lse_.assign(layers.size(), std::vector<DenseMatrix>());
+            std::vector<DenseMatrix>& lse = lse_[(size_t)i];
+            if (lse.size() != (size_t)layers[i].num_heads) lse.assign((size_t)layers[i].num_heads, DenseMatrix());
+            if (lse[(size_t)j].rows() != rows) lse[(size_t)j] = DenseMatrix(rows, 1);
+            DenseMatrix H(A.rows(), A.cols());
+            const hnh_attn_state st = {row_max_.data(), row_sum_.data(), lse[(size_t)j].data(), leaky_relu_alpha,
+                                       out.data() + (int64_t)j * A.cols(), (int64_t)out.cols()};
+            auto* ds = dynamic_cast<Sparse15D_Dense_Shift*>(d_ops);
+            if (ds == nullptr || !ds->fusedSoftmax_out(A, A, Amat, H, st))
+                throw hnh::Error("Error, GAT softmax attention supports 15d_fusion2 with c = 1 only, not " + d_ops->algorithm_name);
+            return;
+        }
 
         // Schedules with a single fused pass (1.5D dense shift, local kernel fusion, c = 1: its shifts are empty and
         // the attention matrix is not exported) do SDDMM, LeakyReLU and SpMM in ONE gather of the neighbours' rows.

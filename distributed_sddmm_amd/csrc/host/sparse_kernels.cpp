@@ -114,6 +114,46 @@ size_t StandardKernel::fused_local(SpmatLocal& S, DenseMatrix& A, DenseMatrix& B
     return 0;
 }
 
+bool KernelImplementation::softmax_local(SpmatLocal& S, DenseMatrix& A, DenseMatrix& B, DenseMatrix& Out, int block, unsigned flags,
+                                         const hnh_attn_state& state, bool finish) {
+    StandardKernel* k = dynamic_cast<StandardKernel*>(this);
+    return k != nullptr && k->softmax_block(S, A, B, Out, block, flags, state, finish);
+}
+
+// The softmax instance of the fused pass (include/hnh_attention.h), next to fused_local: same block and window handling, the finish
+// belongs to the pass's last call (win.last when windows are selected).
+bool StandardKernel::softmax_block(SpmatLocal& S, DenseMatrix& A, DenseMatrix& B, DenseMatrix& Out, int block, unsigned flags,
+                                   const hnh_attn_state& state, bool finish) {
+    hnh::World* w = S.world;
+    if (w->be->hnh_attn_softmax_csr_p == nullptr)
+        throw hnh::Error(std::string("Error, softmax attention needs the kernel hnh_attn_softmax_csr_p, which the kernel library ") + w->be->path +
+                         " does not export (include/hnh_attention.h)");
+    if (A.cols() != B.cols() || Out.cols() != A.cols()) hnh::fatal("Error, fused operands must have the same number of columns!");
+    if (Out.rows() != A.rows()) hnh::fatal("Error, the softmax pass needs an output of the row operand's shape!");
+    CSRLocal* blk = S.csr_blocks[block];
+    const unsigned f = flags | (finish ? HNH_ATTN_FINISH : 0u);
+    if (blk == nullptr || blk->num_coords == 0) {  // nothing to multiply; the state reset and the finish still apply
+        hnh_csr_block none = {};
+        none.rows = Out.rows();
+        none.cols = -1;
+        w->check(w->be->hnh_attn_softmax_csr_p(w->ctx, &none, nullptr, A.data(), B.data(), Out.data(), (int)A.cols(), f & ~HNH_FUSED_VALUES_OVERWRITE,
+                                               &state, nullptr, HNH_STREAM_COMPUTE),
+                 "hnh_attn_softmax_csr_p");
+        return true;
+    }
+    if (blk->transpose) hnh::fatal("Error, local matrix is transposed, can't perform the fused SDDMM+SpMM");
+    begin(w);
+    hnh_csr_window win;
+    const hnh_csr_block desc = blk->block_args();
+    const bool windowed = blk->window_args(&win);
+    if (windowed && finish && !win.last) hnh::fatal("Error, the softmax finish belongs to the block's last window!");
+    w->check(w->be->hnh_attn_softmax_csr_p(w->ctx, &desc, blk->getActive()->values, A.data(), B.data(), Out.data(), (int)A.cols(), f, &state,
+                                           windowed ? &win : nullptr, HNH_STREAM_COMPUTE),
+             "hnh_attn_softmax_csr_p");
+    end(w, (profile && !windowed) ? w->be->hnh_panel_count(w->ctx, desc.rows, desc.nnz, desc.cols, (int)A.cols(), desc.max_row_nnz) : 1);
+    return true;
+}
+
 void StandardKernel::begin(hnh::World* w) {
     if (!profile) return;
     if (evw_ != nullptr && evw_ != w) hnh::fatal("Error, a profiled StandardKernel belongs to one world!");

@@ -54,6 +54,17 @@ public:
         return n;
     }
 
+    // Neighbourhood-softmax attention (include/hnh_attention.h, the GAT's softmax mode) on one block, or the selected window(s) of it:
+    // continues every row's running state (state.row_max / row_sum and the rows of Out) and, with `finish` (the pass's last call,
+    // which a schedule makes also when the block is absent), writes the rows' ReLU output and log-sum-exp.  flags: as fused_local's
+    // (HNH_FUSED_OUT_OVERWRITE starts every row from the empty state).  Returns false, having done nothing, when the implementation
+    // has no such pass: every implementation but StandardKernel (and its subclasses), so plugins written against the reference are
+    // untouched.  NOT virtual, on purpose: a new virtual would change the vtables of KernelImplementation and StandardKernel, which
+    // drivers compiled against the previous headers embed (the vtable of StandardKernel is copied into such an executable at load time,
+    // at the size it had when the driver was linked).
+    bool softmax_local(SpmatLocal& S, DenseMatrix& A, DenseMatrix& B, DenseMatrix& Out, int block, unsigned flags, const hnh_attn_state& state,
+                       bool finish);
+
     // Row windows (CSRLocal::window): a schedule may select one column range of a block before calling the kernels, to
     // work on data that arrives piece by piece.  An implementation that honours CSRLocal::window says so here; for the
     // others (plugins written against the reference's two pure virtuals) the schedule waits for the whole block instead.
@@ -127,6 +138,9 @@ public:
     size_t spmm_local(SpmatLocal& S, DenseMatrix& A, DenseMatrix& B, MatMode mode, int block) override;
     size_t fused_local(SpmatLocal& S, DenseMatrix& A, DenseMatrix& B, DenseMatrix& Out, int block, unsigned flags,
                        const hnh_fused_extras* extras = nullptr) override;
+    // KernelImplementation::softmax_local's pass (non-virtual: see there)
+    bool softmax_block(SpmatLocal& S, DenseMatrix& A, DenseMatrix& B, DenseMatrix& Out, int block, unsigned flags, const hnh_attn_state& state,
+                       bool finish);
     ~StandardKernel() override;
 
 private:

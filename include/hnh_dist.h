@@ -233,6 +233,13 @@ int hnh_gat_forward(hnh_gat* g);                                                
 int hnh_gat_backward(hnh_gat* g, hnh_dense* grad_out);
 int hnh_gat_get_weight_grad(hnh_gat* g, int layer, int head, double* host); /* dL/dW (hnh_gat_weight_shape), summed over all ranks */
 int hnh_gat_get_input_grad(hnh_gat* g, hnh_dense* out);                     /* dL/d(buffers[0]) in its layout (copied)          */
+/* Attention mode (an addition).  NONE (the default of hnh_gat_create): the LeakyReLU scores are the edge weights, as in the
+ * reference.  SOFTMAX: they are normalised over each row's neighbourhood, a_ij = exp(s_ij - lse_i), forward and backward; 15d_fusion2
+ * with c = 1 only (the forward pass returns HNH_ERR_INVALID elsewhere, and when the kernel library lacks include/hnh_attention.h).
+ * A change of mode invalidates the stored forward pass. */
+#define HNH_GAT_ATTENTION_NONE 0
+#define HNH_GAT_ATTENTION_SOFTMAX 1
+int hnh_gat_set_attention(hnh_gat* g, int mode);
 
 #ifdef __cplusplus
 }

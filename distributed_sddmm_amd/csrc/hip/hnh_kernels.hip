@@ -2719,7 +2719,9 @@ int hnh_attn_softmax_csr_p(hnh_ctx* ctx, const hnh_csr_block* b, double* values,
     // ReLU destination is part of every call's state
     const Shape s = pick_shape(R, aligned16(X) && aligned16(Y) && aligned16(Out) && aligned16(state->relu_dst) && state->relu_ld % 2 == 0);
     if (!(s.exact || R <= 256 * s.w))
-        return hnh::fail(ctx, HNH_ERR_UNSUPPORTED, std::string(who) + ": width beyond the one-pass instances (a softmax cannot be composed of two passes)");
+        return hnh::fail(ctx, HNH_ERR_UNSUPPORTED, std::string(who) + ": width " + std::to_string(R) +
+                                                       " beyond the one-pass instances (R <= 512 even with X, Y, Out and relu_dst 16-byte aligned and relu_ld "
+                                                       "even, R <= 256 otherwise; a softmax cannot be composed of two passes)");
     bool done = false;
     const unsigned f = (flags & (HNH_FUSED_VALUES_OVERWRITE | HNH_FUSED_OUT_OVERWRITE)) | HNH_FUSED_LEAKY_RELU;
     if (int rc = dispatch_row<Op::kFusedSoftmax>(ctx, st, stream, s, b->rows, b->nnz, b->max_row_nnz, window ? -1 : b->cols, b->rowptr, b->col_idx, values,

@@ -232,6 +232,14 @@ private:
             throw hnh::Error("Error, GAT softmax attention supports 15d_fusion2 with c = 1 only, not " +
                              (ds ? "15d_fusion" + std::to_string(ds->fusionApproach) + " (" + d_ops->algorithm_name + ")" : d_ops->algorithm_name) +
                              " with c = " + std::to_string(d_ops->c) + ": its rows are summed across ranks");
+        // a head is one pass over its columns (include/hnh_attention.h); its operands are whole allocations and column blocks at an even
+        // offset of an even pitch when f is even, so the 16-byte condition of the 512 limit holds for every even f
+        for (const GATLayer& L : layers) {
+            const int f = L.features_per_head;
+            if (f > 512 || (f % 2 != 0 && f > 256))
+                throw hnh::Error("Error, GAT softmax attention supports heads of at most 512 features (256 when odd), not " + std::to_string(f) +
+                                 ": a row's softmax is one pass over its columns (include/hnh_attention.h)");
+        }
         const hnh::Backend* be = d_ops->world->be;
         if (be->hnh_attn_softmax_csr_p == nullptr)
             throw hnh::Error(std::string("Error, GAT softmax attention needs the kernel hnh_attn_softmax_csr_p, which the kernel library ") + be->path +

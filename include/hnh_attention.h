@@ -40,8 +40,10 @@ typedef struct hnh_attn_state {
 /* One softmax-attention pass over a block (or a window of it), X = the row operand, Y = the gathered operand (R columns each),
  * Out = the running accumulator (rows x R; undefined after the finishing call).  values[e] receives s_e (the activated score).
  * b->rowptr == NULL: a block of b->rows rows without any nonzero (the flags' state reset and the finish still apply).
- * Widths: R in {64, 128, 256} run exact-width instances, R <= 512 (even) / 256 (odd) bounds-checked ones; wider rows return
- * HNH_ERR_UNSUPPORTED.  Hub rows are walked whole by one group, never split (bit-identical results at any grouping). */
+ * Widths: one pass over the row's R columns.  R in {64, 128, 256} run exact-width instances and every other R <= 512 a bounds-checked
+ * one, but an R above 256 only when R is even, X, Y, Out and state->relu_dst are 16-byte aligned and state->relu_ld is even (the
+ * 16-byte instances); otherwise R <= 256.  Wider rows return HNH_ERR_UNSUPPORTED and write nothing.  A block without nonzeros
+ * (rowptr == NULL) takes any R.  Hub rows are walked whole by one group, never split (bit-identical results at any grouping). */
 int hnh_attn_softmax_csr_p(hnh_ctx* ctx, const hnh_csr_block* b, double* values, const double* X, const double* Y, double* Out, int R,
                            unsigned flags, const hnh_attn_state* state, const hnh_csr_window* window, int stream);
 

@@ -9,7 +9,10 @@ it appears):
 Backward, from G = dL/d(out):
     dZ    = G[:, cols] * [out[:, cols] > 0],   delta_i = <dZ_i, o_i>
     ds_ij = a_ij (<dZ_i, A_j> - delta_i),      de_ij = ds_ij * LeakyReLU'_alpha(e_ij)
-    dA    = S_de A  +  S_a^T dZ  +  S_de^T A,  dW_h = X^T dA,  dX += dA W_h^T"""
+    dA    = S_de A  +  S_a^T dZ  +  S_de^T A,  dW_h = X^T dA,  dX += dA W_h^T
+attention_ld is attention() in extended precision (the kernel tests' reference); max_rises finds where a row's running max rises."""
+import math
+
 import numpy as np
 import scipy.sparse as sp
 
@@ -41,6 +44,70 @@ def attention(rows, cols, m, y_rows, y_cols, alpha: float):
     s = leaky(np.einsum("ij,ij->i", y_rows[rows], y_cols[cols]), alpha)
     a, lse = row_softmax(rows, m, s)
     return _smat(rows, cols, a, m) @ y_cols, lse, s
+
+
+def attention_ld(rows, cols, m, y_rows, y_cols, alpha: float, chunk: int = 8192, fsum=None):
+    """attention() with the scores, max, sum, lse and o in np.longdouble: (o, lse, s) as longdouble arrays.  Where longdouble is no
+    wider than fp64 (or fsum=True) the sums of a row (l and every column of o) are taken with math.fsum instead."""
+    ld = np.longdouble
+    wide = not fsum if fsum is not None else np.finfo(ld).eps <= 1e-18
+    order = np.argsort(rows, kind="stable")
+    r, c = np.asarray(rows)[order], np.asarray(cols)[order]
+    xr, yc = np.asarray(y_rows, dtype=ld), np.asarray(y_cols, dtype=ld)
+    n = len(r)
+    s = np.empty(n, dtype=ld)
+    for e0 in range(0, n, chunk):
+        e1 = min(n, e0 + chunk)
+        s[e0:e1] = np.sum(xr[r[e0:e1]] * yc[c[e0:e1]], axis=1)
+    s = np.maximum(s, ld(0)) + np.minimum(s, ld(0)) * ld(alpha)
+    rowptr = np.concatenate([[0], np.cumsum(np.bincount(r, minlength=m))])
+    mx = np.full(m, -np.inf, dtype=ld)
+    np.maximum.at(mx, r, s)
+    ex = np.exp(s - mx[r])
+    tot = np.zeros(m, dtype=ld)
+    live = rowptr[1:] > rowptr[:-1]
+    if wide:
+        np.add.at(tot, r, ex)
+    else:
+        for i in np.nonzero(live)[0]:
+            tot[i] = math.fsum(ex[rowptr[i]:rowptr[i + 1]])
+    lse = np.zeros(m, dtype=ld)
+    lse[live] = mx[live] + np.log(tot[live])
+    a = np.exp(s - lse[r])
+    o = np.zeros((m, yc.shape[1]), dtype=ld)
+    r0 = 0
+    while r0 < m:  # whole rows, about `chunk` nonzeros at a time
+        r1 = max(r0 + 1, int(np.searchsorted(rowptr, rowptr[r0] + chunk, side="right")) - 1)
+        r1 = min(r1, m)
+        e0, e1 = rowptr[r0], rowptr[r1]
+        if e1 > e0:
+            contrib = a[e0:e1, None] * yc[c[e0:e1]]
+            nz = np.nonzero(live[r0:r1])[0]
+            if wide:
+                o[r0 + nz] = np.add.reduceat(contrib, rowptr[r0 + nz] - e0, axis=0)
+            else:
+                for i in nz:
+                    seg = contrib[rowptr[r0 + i] - e0:rowptr[r0 + i + 1] - e0]
+                    o[r0 + i] = [math.fsum(seg[:, k]) for k in range(seg.shape[1])]
+        r0 = r1
+    s_out = np.empty(n, dtype=ld)
+    s_out[order] = s
+    return o, lse, s_out
+
+
+def max_rises(rowptr, s):
+    """Per row, the positions (0-based within the row, in row order) where the prefix max of the scores s rises strictly: the
+    nonzeros at which the online softmax rescales its state.  Position 0 of a non-empty row always counts (it leaves the empty state)."""
+    s = np.asarray(s)
+    out = []
+    for i in range(len(rowptr) - 1):
+        seg = s[rowptr[i]:rowptr[i + 1]]
+        if len(seg) == 0:
+            out.append(np.zeros(0, dtype=np.int64))
+            continue
+        before = np.concatenate([[-np.inf], np.maximum.accumulate(seg)[:-1]])
+        out.append(np.nonzero(seg > before)[0])
+    return out
 
 
 def forward(rows, cols, m, x, layers, alpha: float, weights=None, keep: bool = False):

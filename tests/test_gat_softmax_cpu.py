@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import gat_softmax_ref as R
+import softmax_schedules as S
 import hnh_testlib as T
 from distributed_sddmm_amd import _kernels as K
 from distributed_sddmm_amd import api as H
@@ -184,3 +185,101 @@ def test_softmax_refuses_unsupported_schedules(alg, p, c):
         return True
 
     assert all(H.run_spmd(p, rank))
+
+
+# ------------------------------------------------------------------------------------------------ the kernel tests' reference and inputs
+@pytest.mark.parametrize("width,scale,fsum,tol", [(7, 1.0, None, 1e-13), (100, 1.0, None, 1e-13), (5, 1.0, True, 1e-13), (16, 40.0, None, 1e-12)])
+def test_extended_reference_matches_fp64(width, scale, fsum, tol):
+    """attention_ld (longdouble, or math.fsum where longdouble is fp64) against the fp64 attention(); with scores up to +-1e3 the fp64
+    weights exp(s - lse) carry the rounding of s (a few 1e-13), which is what the extended reference removes."""
+    rng = np.random.default_rng(width)
+    m = 300
+    deg = rng.integers(0, 30, m)
+    deg[::7] = 0
+    deg[3] = 700
+    rows = np.repeat(np.arange(m), deg)
+    cols = rng.integers(0, m, len(rows))
+    x, y = rng.uniform(-1, 1, (m, width)) * scale, rng.uniform(-1, 1, (m, width)) * scale
+    perm = rng.permutation(len(rows))  # the reference takes the nonzeros in any order
+    o, lse, s = R.attention(rows[perm], cols[perm], m, x, y, T.GAT_ALPHA)
+    o_ld, lse_ld, s_ld = R.attention_ld(rows[perm], cols[perm], m, x, y, T.GAT_ALPHA, chunk=1000, fsum=fsum)
+    assert o_ld.dtype == np.longdouble and lse_ld.dtype == np.longdouble
+    assert T.rel(np.float64(o_ld), o) <= tol and T.rel(np.float64(s_ld), s) <= 1e-13
+    assert np.all(np.abs(np.float64(lse_ld) - lse) <= 1e-13 * np.maximum(1.0, np.abs(lse))) and np.all(lse_ld[deg == 0] == 0)
+    if scale > 1:
+        assert np.abs(s).max() > 700.0
+
+
+def test_max_rises():
+    rowptr = np.array([0, 0, 1, 5, 9])
+    s = np.array([3.0, 1.0, 2.0, 2.0, 5.0, -2.0, 0.0, 0.0, -1.0])
+    got = R.max_rises(rowptr, s)
+    assert [list(g) for g in got] == [[], [0], [0, 1, 3], [0, 1]]
+
+
+def test_forced_schedules_rise_where_designed():
+    """The designed inputs of tests/softmax_schedules.py: every row's running max rises exactly where its schedule says, and the
+    schedules reach what they are for (a spike at every k <= 18, a hub row's last nonzero, every window and panel start, ties with the
+    max, rises beyond exp's range)."""
+    m = 4096
+    rowptr, colidx, x, y, rises, group = S.build(m, 16, 3)
+    rows = np.repeat(np.arange(m), np.diff(rowptr))
+    assert all(np.all(np.diff(colidx[rowptr[i]:rowptr[i + 1]]) >= 0) for i in range(m)), "columns sorted within a row"
+    _, _, s = R.attention(rows, colidx.astype(np.int64), m, x, y, T.GAT_ALPHA)
+    got = R.max_rises(rowptr, s)
+    for i in range(m):
+        assert np.array_equal(got[i], rises[i]), (i, group[i], got[i], rises[i])
+    g = np.array(group)
+    deg = np.diff(rowptr)
+    assert np.count_nonzero(deg == 0) > m // 20
+    mono = np.nonzero((g == "monotone") & (deg > 0))[0]
+    assert all(len(rises[i]) == deg[i] for i in mono) and deg[mono].max() >= 300
+    spike = [i for i in np.nonzero(g == "spike")[0] if deg[i] > 0]
+    ks = {int(rises[i][-1]) if len(rises[i]) > 1 else 0 for i in spike}
+    assert set(range(19)) <= ks
+    hub = [i for i in spike if deg[i] >= 600]
+    assert hub and all(rises[i][-1] == deg[i] - 1 for i in hub)
+    assert any(deg[i] >= 60 and rises[i][-1] >= deg[i] - 8 for i in spike), "a rise late in a row"
+    for name, bounds in (("window", S.window_bounds(m, 6)), ("panel", S.panel_bounds(m, 5))):
+        starts = set()
+        for i in np.nonzero(g == name)[0]:
+            c = colidx[rowptr[i]:rowptr[i + 1]]
+            starts |= {int(np.searchsorted(bounds, c[u], side="right")) - 1 for u in rises[i]}
+            assert len(rises[i]) == len(set(np.searchsorted(bounds, c, side="right")))
+        assert starts == set(range(len(bounds) - 1))
+        assert max(len(rises[i]) for i in np.nonzero(g == name)[0]) == len(bounds) - 1
+    for i in np.nonzero((g == "ties") | (g == "tie_spike"))[0]:
+        assert deg[i] == 0 or list(rises[i]) == [0]
+    assert deg[(g == "ties")].max() >= 300 and len(np.unique(s[np.isin(rows, np.nonzero(g == "ties")[0])])) == 1
+
+    def tie_spike(i):  # a score equal to the row's max right after a lower one: f == 1 at a local spike
+        seg = s[rowptr[i]:rowptr[i + 1]]
+        return len(seg) > 2 and np.any((seg[2:] == seg[0]) & (seg[1:-1] < seg[0]))
+
+    tie_rows = np.nonzero(g == "tie_spike")[0]
+    assert sum(tie_spike(i) for i in tie_rows) > len(tie_rows) // 2
+    jumps = [np.diff(np.maximum.accumulate(s[rowptr[i]:rowptr[i + 1]]))[rises[i][1:] - 1] for i in np.nonzero(g == "jump")[0] if len(rises[i]) > 1]
+    assert min(j.min() for j in jumps) > 745.0 and any(len(j) == 2 for j in jumps)
+
+
+@pytest.mark.parametrize("layers,refused", [([(16, 301, 2)], True), ([(16, 514, 1)], True), ([(16, 8, 2), (16, 257, 1)], True),
+                                            ([(16, 512, 1)], False), ([(16, 255, 2)], False)])
+def test_softmax_names_the_width_limit(layers, refused):
+    """A softmax head is one pass over its columns: f <= 512 (even) or 255 (odd).  Refused before any kernel is needed (the test
+    double has none: an accepted width gets as far as naming the missing kernel)."""
+    H.load_backend(T.ORACLE_BACKEND)
+    case = T.case_inputs("er8_r16")
+
+    def rank(world):
+        sp = H.SpmatLocal.from_global(world, case["M"], case["N"], case["rows"], case["cols"], np.ones(len(case["rows"])))
+        d = H.DistributedSparse(world, "15d_fusion2", sp, 16, 1)
+        gnn = H.GAT(d, layers, T.GAT_ALPHA, attention="softmax")
+        with pytest.raises(H.HnhError, match="at most 512 features" if refused else "hnh_attn_softmax_csr_p") as e:
+            gnn.forwardPass()
+        if refused:
+            assert str(max(f for _, f, _ in layers)) in str(e.value)
+        for h in (gnn, d, sp):
+            h.free()
+        return True
+
+    assert all(H.run_spmd(1, rank))

@@ -60,9 +60,10 @@ def mixed_degrees(m, seed):
     return d
 
 
-def softmax_pass(ctx, rowptr, colidx, x, y, alpha, groups=None, nwin=6):
+def softmax_pass(ctx, rowptr, colidx, x, y, alpha, groups=None, nwin=6, off=2):
     """One softmax pass through hnh_attn_softmax_csr_p.  groups = None: one call over whole rows; else a list of (first, end) window
-    ranges covering [0, nwin) of nwin column windows, one call each.  Returns (relu output, lse, row_max, row_sum, values)."""
+    ranges covering [0, nwin) of nwin column windows, one call each.  The head's block starts at column `off` of a relu_dst of pitch
+    R + 4 (an odd off: 8-byte aligned only, the W = 1 instances).  Returns (relu output, lse, row_max, row_sum, values)."""
     lib = ctx.lib
     m, R_ = x.shape
     nnz = int(rowptr[-1])
@@ -74,7 +75,7 @@ def softmax_pass(ctx, rowptr, colidx, x, y, alpha, groups=None, nwin=6):
     rmax, rsum, lse = (ctx.upload(np.full(m, 5.0)) for _ in range(3))
     dst = ctx.upload(np.full((m, ld), 7.0))
     blk = K.CsrBlock(m, nnz, m, int(np.diff(rowptr).max()), 0, drp.ptr, dci.ptr, None)
-    st = K.AttnState(rmax.ptr, rsum.ptr, lse.ptr, alpha, dst.ptr + 2 * 8, ld)
+    st = K.AttnState(rmax.ptr, rsum.ptr, lse.ptr, alpha, dst.ptr + off * 8, ld)
     base = K.FUSED_VALUES_OVERWRITE
     if groups is None:
         ctx.check(lib.hnh_attn_softmax_csr_p(ctx.h, C.byref(blk), vals.ptr, dx.ptr, dy.ptr, out.ptr, R_, base | K.FUSED_OUT_OVERWRITE | K.ATTN_FINISH,
@@ -91,21 +92,27 @@ def softmax_pass(ctx, rowptr, colidx, x, y, alpha, groups=None, nwin=6):
         split.free()
     ctx.sync()
     d = dst.get()
-    assert np.all(d[:, :2] == 7.0) and np.all(d[:, 2 + R_:] == 7.0), "columns outside the head's block are not written"
-    res = (d[:, 2:2 + R_], lse.get(), rmax.get(), rsum.get(), vals.get()[:nnz])
+    assert np.all(d[:, :off] == 7.0) and np.all(d[:, off + R_:] == 7.0), "columns outside the head's block are not written"
+    res = (d[:, off:off + R_], lse.get(), rmax.get(), rsum.get(), vals.get()[:nnz])
     for a in (drp, dci, dx, dy, out, vals, rmax, rsum, lse, dst):
         a.free()
     return res
 
 
-def check_against_numpy(got, rows, colidx, m, x, y):
-    o, lse, s = R.attention(rows, colidx.astype(np.int64), m, x, y, ALPHA)
+def check_against_numpy(got, rows, colidx, m, x, y, sels=None):
+    """The pass against the extended-precision reference (gat_softmax_ref.attention_ld): output, lse, scores and the row state.  sels =
+    boolean row masks: the output and lse bounds hold over each group of rows on its own (groups whose scales differ)."""
+    o, lse, s = (np.float64(v) for v in R.attention_ld(rows, colidx.astype(np.int64), m, x, y, ALPHA))
     live = np.bincount(rows, minlength=m) > 0
     assert np.all(np.isfinite(got[0])) and np.all(np.isfinite(got[1]))
-    assert T.rel(got[0], np.maximum(o, 0.0)) <= 1e-12, T.rel(got[0], np.maximum(o, 0.0))
-    assert np.max(np.abs(got[1] - lse)) <= 1e-12 * max(1.0, np.abs(lse).max()) and np.all(got[1][~live] == 0.0)
+    for sel in (sels if sels is not None else [np.ones(m, dtype=bool)]):
+        assert T.rel(got[0][sel], np.maximum(o[sel], 0.0)) <= 1e-12, T.rel(got[0][sel], np.maximum(o[sel], 0.0))
+        assert np.max(np.abs(got[1][sel] - lse[sel])) <= 1e-12 * max(1.0, np.abs(lse[sel]).max()) and np.all(got[1][~live] == 0.0)
     assert T.rel(got[4], s) <= 1e-13
     assert np.all(got[2][~live] == -np.inf) and np.all(got[3][~live] == 0.0)
+    mx = np.full(m, -np.inf)
+    np.maximum.at(mx, rows, s)
+    assert np.max(np.abs(got[2][live] - mx[live]), initial=0.0) <= 1e-13 * max(1.0, np.abs(s).max()) and np.all(got[3][live] >= 1.0)
 
 
 @pytest.mark.parametrize("width", [1, 2, 7, 16, 64, 100, 128, 256])
@@ -134,7 +141,12 @@ def test_scores_beyond_the_range_of_exp(ctx, width):
     check_against_numpy(got, rows, colidx, m, x, y)
 
 
-@pytest.mark.parametrize("width", [7, 64, 256])
+# one width per instance of the softmax pass (launch_shape<Op::kFusedSoftmax>), the earlier three included: exact (32,1,2) 64,
+# (64,1,2) 128, (64,2,2) 256; bounds-checked NX(1,2) 16 / 100, NX(2,2) 200, NX(4,2) 300, NX(1,1) 7, NX(2,1) 101, NX(4,1) 201
+INSTANCE_WIDTHS = [7, 16, 64, 100, 101, 128, 200, 201, 256, 300]
+
+
+@pytest.mark.parametrize("width", INSTANCE_WIDTHS)
 def test_forced_panels_are_bit_identical(monkeypatch, width):
     """Column panels (several launches over every row) continue the row state nonzero by nonzero: the same bits as one launch."""
     m = 4096
@@ -155,7 +167,7 @@ def test_forced_panels_are_bit_identical(monkeypatch, width):
     check_against_numpy(five, rows, colidx, m, x, y)
 
 
-@pytest.mark.parametrize("width", [16, 128, 256])
+@pytest.mark.parametrize("width", INSTANCE_WIDTHS)
 def test_grouping_independence(ctx, width):
     """The same block walked with its 6 windows grouped as 1, 2 or 5 launches (and window by window): bit-identical outputs, lse,
     row state and scores — what a launch-local state merged at the end would not give."""

@@ -139,6 +139,27 @@ ATTN_SIGNATURES = {
 ATTN_FINISH = 8  # HNH_ATTN_FINISH
 
 
+# include/hnh_attn_grad.h: the fused backward pass of the GAT's attention, a third OPTIONAL group bound only for the product library
+ATTN_GRAD_SIGNATURES = {
+    "hnh_attn_grad_row_csr_p": (_i32, [_vp, _vp, _vp, C.c_uint, _vp, _i32]),
+    "hnh_attn_grad_col_csr_p": (_i32, [_vp, _vp, _vp, C.c_uint, _vp, _i32]),
+    "hnh_attn_grad_pack_f64": (_i32, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i32, _i32]),
+}
+ATTN_GRAD_MAX_F = 256  # HNH_ATTN_GRAD_MAX_F
+ERR_UNSUPPORTED = 4    # HNH_ERR_UNSUPPORTED
+
+
+def attn_grad_packed_width(f: int, softmax: bool) -> int:
+    """HNH_ATTN_GRAD_PACKED_WIDTH"""
+    return 2 * (f + (f & 1)) + (2 if softmax else 0)
+
+
+class AttnGrad(C.Structure):
+    """struct hnh_attn_grad"""
+    _fields_ = [("X", _vp), ("ld_x", _i64), ("dZ", _vp), ("ld_dz", _i64), ("lse", _vp), ("delta", _vp), ("Y", _vp), ("ld_y", _i64),
+                ("Out", _vp), ("ld_out", _i64), ("f", _i32), ("softmax", _i32), ("leaky_alpha", _dbl)]
+
+
 class AttnState(C.Structure):
     """struct hnh_attn_state"""
     _fields_ = [("row_max", _vp), ("row_sum", _vp), ("lse", _vp), ("leaky_alpha", _dbl), ("relu_dst", _vp), ("relu_ld", _i64)]
@@ -200,7 +221,7 @@ def load(path: str | None = None) -> C.CDLL:
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype, fn.argtypes = res, args
     if path is None or os.path.abspath(p) == os.path.abspath(LIB_PATH):
-        for name, (res, args) in list(GRAD_SIGNATURES.items()) + list(ATTN_SIGNATURES.items()):
+        for name, (res, args) in list(GRAD_SIGNATURES.items()) + list(ATTN_SIGNATURES.items()) + list(ATTN_GRAD_SIGNATURES.items()):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
     if path is None:

@@ -132,6 +132,7 @@ SIGNATURES = {
     "hnh_gat_get_weight_grad": (_i32, [_vp, _i32, _i32, _vp]),
     "hnh_gat_get_input_grad": (_i32, [_vp, _vp]),
     "hnh_gat_set_attention": (_i32, [_vp, _i32]),
+    "hnh_gat_set_backward": (_i32, [_vp, _i32]),
 }
 
 _lib = None
@@ -645,13 +646,17 @@ class GAT:
 
     ATTENTION = {"none": 0, "softmax": 1}  # HNH_GAT_ATTENTION_NONE / _SOFTMAX
 
-    def __init__(self, op: DistributedSparse, layers, leaky_relu_alpha: float = 0.2, attention: str = "none"):
+    BACKWARD = {"unfused": 0, "fused": 1}  # HNH_GAT_BACKWARD_UNFUSED / _FUSED
+
+    def __init__(self, op: DistributedSparse, layers, leaky_relu_alpha: float = 0.2, attention: str = "none", backward: str = "unfused"):
         self.op, self.layers = op, [tuple(l) for l in layers]
         spec = (C.c_int * (3 * len(layers)))(*[x for l in self.layers for x in l])
         self.h = _vp()
         _check(lib().hnh_gat_create(op.h, len(layers), spec, leaky_relu_alpha, C.byref(self.h)), "gat_create")
         if attention != "none":
             self.set_attention(attention)
+        if backward != "unfused":
+            self.set_backward(backward)
 
     def set_attention(self, mode: str):
         """"none" (the default: the LeakyReLU scores are the edge weights) or "softmax" (normalised over each row's neighbourhood;
@@ -659,6 +664,13 @@ class GAT:
         if mode not in self.ATTENTION:
             raise ValueError("attention must be one of %s, not %r" % (sorted(self.ATTENTION), mode))
         _check(lib().hnh_gat_set_attention(self.h, self.ATTENTION[mode]), "gat_set_attention")
+
+    def set_backward(self, mode: str):
+        """"unfused" (the default: seven operator calls per head) or "fused" (two passes per head, include/hnh_attn_grad.h; 15d_fusion2
+        with c = 1 and heads of at most 256 features only, backwardPass raises HnhError elsewhere).  Needs no new forward pass."""
+        if mode not in self.BACKWARD:
+            raise ValueError("backward must be one of %s, not %r" % (sorted(self.BACKWARD), mode))
+        _check(lib().hnh_gat_set_backward(self.h, self.BACKWARD[mode]), "gat_set_backward")
 
     def weight_shape(self, layer: int, head: int):
         o = (C.c_int64 * 2)()

@@ -28,6 +28,7 @@
 #include <cstdint>
 #include "hnh_ctx.hpp"
 #include "hnh_attention.h"
+#include "hnh_attn_grad.h"
 
 namespace {
 
@@ -1886,12 +1887,8 @@ int panel_count(const hnh_ctx* ctx, int64_t cols, int R) {
     return (int)(p < 1 ? 1 : (p > most ? most : p));
 }
 
-// cols: number of rows of the gathered operand (= columns of the sparse block), or < 0 when unknown (no panels)
-template <Op OP>
-int dispatch_row(hnh_ctx* ctx, hipStream_t st, int sidx, const Shape& s, int64_t rows, int64_t nnz, int max_row_nnz, int64_t cols,
-                 const int32_t* rowptr, const int32_t* colidx, double* values, const double* svalues, const double* X,
-                 const double* Y, double* Out, int R, unsigned flags, const Extras& ex = Extras(), bool* epilogue_done = nullptr,
-                 const hnh_csr_window* win = nullptr, hnh_csr_plan* plan = nullptr) {
+// a structure plan belongs to the first block it is used with (checked on every use)
+int adopt_plan(hnh_ctx* ctx, hnh_csr_plan* plan, int64_t rows, int64_t nnz, const int32_t* rowptr, const int32_t* colidx) {
     if (plan != nullptr) {
         if (plan->rowptr == nullptr) {  // first use: the plan is this block's from now on
             plan->rowptr = rowptr;
@@ -1902,6 +1899,64 @@ int dispatch_row(hnh_ctx* ctx, hipStream_t st, int sidx, const Shape& s, int64_t
             return hnh::fail(ctx, HNH_ERR_INVALID, "the structure plan belongs to another block");
         }
     }
+    return HNH_OK;
+}
+
+// the per-row boundaries of `panels` column panels of a block (see panel_split_kernel): from the block's plan when it has one
+// (computed once per block and width class), else from the stream's scratch; *split stays null for one panel
+int panel_split_rows(hnh_ctx* ctx, hipStream_t st, int sidx, hnh_csr_plan* plan, int64_t rows, int64_t cols, const int32_t* rowptr,
+                     const int32_t* colidx, int panels, int32_t** split_out) {
+    const size_t need = (size_t)(panels - 1) * (size_t)rows * sizeof(int32_t);
+    const int width = (int)((cols + panels - 1) / panels);
+    int32_t* split = nullptr;
+    if (panels == 1) {
+        // (one panel per slab: the rows' own boundaries)
+    } else if (plan != nullptr) {
+        // the boundaries depend on the structure and (panels, width) only: computed once per block and width class
+        hnh_csr_plan::Split* slot = nullptr;
+        for (auto& sp : plan->splits)
+            if (sp.split != nullptr && sp.panels == panels && sp.width == width) slot = &sp;
+        if (slot == nullptr) {
+            slot = &plan->splits[0];
+            for (auto& sp : plan->splits)
+                if (sp.split == nullptr || (slot->split != nullptr && sp.age < slot->age)) slot = &sp;
+            HNH_TRY_HIP(ctx, hipStreamSynchronize(st));
+            if (slot->split) HNH_TRY_HIP(ctx, hipFree(slot->split));
+            slot->split = nullptr;
+            HNH_TRY_HIP(ctx, hipMalloc((void**)&slot->split, need));
+            slot->panels = panels;
+            slot->width = width;
+            hipLaunchKernelGGL(panel_split_kernel, dim3((unsigned)((rows + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, rows, rowptr, colidx,
+                               panels, width, slot->split);
+            if (int rc = hnh::check_hip(ctx, hipGetLastError(), "panel_split_kernel launch")) return rc;
+            HNH_TRY_HIP(ctx, hipStreamSynchronize(st));  // once per block and width class: later calls may run on any stream
+        }
+        slot->age = ++plan->clock;
+        split = slot->split;
+    } else {
+        if (ctx->panel_cap[sidx] < need) {
+            HNH_TRY_HIP(ctx, hipStreamSynchronize(st));
+            if (ctx->panel_split[sidx]) HNH_TRY_HIP(ctx, hipFree(ctx->panel_split[sidx]));
+            ctx->panel_split[sidx] = nullptr;
+            HNH_TRY_HIP(ctx, hipMalloc(&ctx->panel_split[sidx], need));
+            ctx->panel_cap[sidx] = need;
+        }
+        split = static_cast<int32_t*>(ctx->panel_split[sidx]);
+        hipLaunchKernelGGL(panel_split_kernel, dim3((unsigned)((rows + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, rows, rowptr, colidx, panels,
+                           width, split);
+        if (int rc = hnh::check_hip(ctx, hipGetLastError(), "panel_split_kernel launch")) return rc;
+    }
+    *split_out = split;
+    return HNH_OK;
+}
+
+// cols: number of rows of the gathered operand (= columns of the sparse block), or < 0 when unknown (no panels)
+template <Op OP>
+int dispatch_row(hnh_ctx* ctx, hipStream_t st, int sidx, const Shape& s, int64_t rows, int64_t nnz, int max_row_nnz, int64_t cols,
+                 const int32_t* rowptr, const int32_t* colidx, double* values, const double* svalues, const double* X,
+                 const double* Y, double* Out, int R, unsigned flags, const Extras& ex = Extras(), bool* epilogue_done = nullptr,
+                 const hnh_csr_window* win = nullptr, hnh_csr_plan* plan = nullptr) {
+    if (int rc = adopt_plan(ctx, plan, rows, nnz, rowptr, colidx)) return rc;
     LongCtl lc;
     // (the softmax pass walks hub rows whole, one group each: a row's scores are combined in row order, never by segments)
     if (OP != Op::kFusedSoftmax)
@@ -1963,46 +2018,8 @@ int dispatch_row(hnh_ctx* ctx, hipStream_t st, int sidx, const Shape& s, int64_t
     const int panels = slab_w ? ((!lc.enabled || ctx->panels_with_hubs) ? panel_count(ctx, cols, slab_w) : 1)
                               : ((single_pass && (!lc.enabled || ctx->panels_with_hubs)) ? panel_count(ctx, cols, R) : 1);
     if (panels > 1 || slab_w) {
-        const size_t need = (size_t)(panels - 1) * (size_t)rows * sizeof(int32_t);
-        const int width = (int)((cols + panels - 1) / panels);
         int32_t* split = nullptr;
-        if (panels == 1) {
-            // (one panel per slab: the rows' own boundaries)
-        } else if (plan != nullptr) {
-            // the boundaries depend on the structure and (panels, width) only: computed once per block and width class
-            hnh_csr_plan::Split* slot = nullptr;
-            for (auto& sp : plan->splits)
-                if (sp.split != nullptr && sp.panels == panels && sp.width == width) slot = &sp;
-            if (slot == nullptr) {
-                slot = &plan->splits[0];
-                for (auto& sp : plan->splits)
-                    if (sp.split == nullptr || (slot->split != nullptr && sp.age < slot->age)) slot = &sp;
-                HNH_TRY_HIP(ctx, hipStreamSynchronize(st));
-                if (slot->split) HNH_TRY_HIP(ctx, hipFree(slot->split));
-                slot->split = nullptr;
-                HNH_TRY_HIP(ctx, hipMalloc((void**)&slot->split, need));
-                slot->panels = panels;
-                slot->width = width;
-                hipLaunchKernelGGL(panel_split_kernel, dim3((unsigned)((rows + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, rows, rowptr, colidx,
-                                   panels, width, slot->split);
-                if (int rc = hnh::check_hip(ctx, hipGetLastError(), "panel_split_kernel launch")) return rc;
-                HNH_TRY_HIP(ctx, hipStreamSynchronize(st));  // once per block and width class: later calls may run on any stream
-            }
-            slot->age = ++plan->clock;
-            split = slot->split;
-        } else {
-            if (ctx->panel_cap[sidx] < need) {
-                HNH_TRY_HIP(ctx, hipStreamSynchronize(st));
-                if (ctx->panel_split[sidx]) HNH_TRY_HIP(ctx, hipFree(ctx->panel_split[sidx]));
-                ctx->panel_split[sidx] = nullptr;
-                HNH_TRY_HIP(ctx, hipMalloc(&ctx->panel_split[sidx], need));
-                ctx->panel_cap[sidx] = need;
-            }
-            split = static_cast<int32_t*>(ctx->panel_split[sidx]);
-            hipLaunchKernelGGL(panel_split_kernel, dim3((unsigned)((rows + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, rows, rowptr, colidx, panels,
-                               width, split);
-            if (int rc = hnh::check_hip(ctx, hipGetLastError(), "panel_split_kernel launch")) return rc;
-        }
+        if (int rc = panel_split_rows(ctx, st, sidx, plan, rows, cols, rowptr, colidx, panels, &split)) return rc;
         for (int sl = 0; sl < nslabs; sl++)
             for (int q = 0; q < panels; q++) {
                 const int32_t* beg_ptr = (q == 0) ? rowptr : split + (size_t)(q - 1) * rows;
@@ -2753,3 +2770,6 @@ int hnh_rowdot_cols_f64(hnh_ctx* ctx, double* out, const double* dZ, int64_t ld_
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------- fused attention backward (include/hnh_attn_grad.h)
+#include "hnh_attn_grad_kernels.hpp"

@@ -771,6 +771,9 @@ int hnh_gat_forward(hnh_gat* g) {
 int hnh_gat_set_attention(hnh_gat* g, int mode) {
     return guarded(g->w, [&] { g->g->set_attention(mode); });
 }
+int hnh_gat_set_backward(hnh_gat* g, int mode) {
+    return guarded(g->w, [&] { g->g->set_backward(mode); });
+}
 int hnh_gat_backward(hnh_gat* g, hnh_dense* grad_out) {
     return guarded(g->w, [&] { g->g->backwardPass(grad_out->m); });
 }

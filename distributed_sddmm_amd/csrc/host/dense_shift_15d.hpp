@@ -297,6 +297,46 @@ public:
         return true;
     }
 
+    // One pass of the fused attention backward (include/hnh_attn_grad.h): the row pass over S (`moving` = A, this->R = f wide) or, with
+    // `column_side`, the column pass over S^T (`moving` = the packed operand, this->R = its width: the caller sets the schedule's R to
+    // the MOVING operand's width, which is what the landing buffers and the fetch are sized by; the row operand and the output are
+    // narrower and addressed through args' leading dimensions).  The own block runs first, then the fetched blocks window by window or
+    // in adaptive groups as their chunks land, exactly as the fused forward pass.  `overwrite`: the output rows start from zero.
+    // Returns false, having done nothing, where a rank's own launches do not see all of a row's nonzeros (only approach 2 with c = 1).
+    // Not a virtual of Distributed_Sparse, for fusedSoftmax_out's reason.
+    bool attnGrad_pass(bool column_side, DenseMatrix& moving, const hnh_attn_grad& args, int64_t out_rows, bool overwrite) {
+        if (fusionApproach != 2 || c != 1) return false;
+        if (moving.cols() != R) hnh::fatal("Error, attnGrad_pass: the schedule's R must be the moving operand's width!");
+        SpmatLocal* choice = column_side ? ST.get() : S.get();
+        const int n = p / c;
+        bool fresh = overwrite;
+        auto on = [&](int block_id, DenseMatrix& Y, int window, int window_end) {
+            CSRLocal* blk = choice->csr_blocks[block_id];
+            if (blk == nullptr && !fresh) return;  // nothing to add
+            if (blk != nullptr) {
+                blk->window = window;
+                blk->window_end = window_end;
+            }
+            hnh_attn_grad a = args;
+            a.Y = Y.data();
+            a.ld_y = Y.cols();
+            const bool done = kernel->attn_grad_local(*choice, block_id, a, column_side, fresh ? HNH_FUSED_OUT_OVERWRITE : 0u, out_rows);
+            if (blk != nullptr) blk->window = blk->window_end = -1;
+            if (!done) throw hnh::Error("Error, the kernel implementation has no fused attention backward pass (KernelImplementation::attn_grad_local)!");
+            fresh = false;
+        };
+        if (merged) {
+            walk_merged(choice, &moving, [&](int block_id, DenseMatrix& Y, int window, int window_end, bool) { on(block_id, Y, window, window_end); });
+        } else {
+            ring_readonly(&moving, n, [&](int i, DenseMatrix& cur) {
+                auto t = phase_begin("Computation Time");
+                on(block_at(i), cur, -1, -1);
+                phase_end(t);
+            });
+        }
+        return true;
+    }
+
 private:
     // ---- merged layout helpers
     // visiting step of global block column b on this rank (block_at(k) == b), or -1 when the rank never visits it

@@ -31,6 +31,15 @@
 // one above with a in place of LeakyReLU(e) and, with delta_i = <dZ_i, out_i> and the lse and delta broadcast onto the nonzeros by
 // width-1 SDDMMs in both layouts, de_ij = a_ij (da_ij - delta_i) LeakyReLU'(e_ij) (hnh_softmax_gate_f64).  15d_fusion2 with c = 1
 // only: on every other schedule a row's nonzeros are summed across ranks, which a softmax cannot be.
+//
+// Backward mode (an addition): HNH_GAT_BACKWARD_UNFUSED (the default) is the pass above, seven operator calls per head.
+// HNH_GAT_BACKWARD_FUSED computes the same dA = dArow + T1 + T2 in TWO passes per head (include/hnh_attn_grad.h):
+//     row pass over S       A_i, dZ_i, lse_i, delta_i in registers, one gather of A_j: e, da, the gate and dA_i += de_ij A_j
+//     column pass over S^T  A_j in registers, one gather of the packed P_i = [A_i | dZ_i | lse_i delta_i]: e, da, the gate with the
+//                           gathered row's scalars, and dA_j += a_ij dZ_i + de_ij A_i
+// straight into the head's column block of dA_all: no value vectors, no gate launches, no width-1 SDDMMs, no sum3.  15d_fusion2 with
+// c = 1 only (the condition of the fused forward: a rank's own launches see all of a row's nonzeros and no output row is summed
+// across ranks), heads of at most HNH_ATTN_GRAD_MAX_F features.  Switching the mode needs no new forward pass.
 #pragma once
 #include "dense_shift_15d.hpp"
 #include "distributed_sparse.hpp"
@@ -92,6 +101,14 @@ public:
         attention_ = mode;
     }
 
+    // HNH_GAT_BACKWARD_UNFUSED | HNH_GAT_BACKWARD_FUSED (include/hnh_dist.h); the stored forward pass serves either
+    int backward() const { return backward_; }
+    void set_backward(int mode) {
+        if (mode != HNH_GAT_BACKWARD_UNFUSED && mode != HNH_GAT_BACKWARD_FUSED)
+            throw hnh::Error("Error, unknown GAT backward mode " + std::to_string(mode) + " (unfused = 0, fused = 1)!");
+        backward_ = mode;
+    }
+
     // Computes the j'th self-attention head of the i'th layer (gat.hpp:83-104)
     void computeSelfAttentionHead(int i, int j) {
         DenseMatrix A;
@@ -150,7 +167,8 @@ public:
         if (!forward_valid_) throw hnh::Error("Error, GAT backwardPass needs a forwardPass first (and a new one after set_weight / set_input)!");
         const DenseMatrix& last = buffers.back();
         if (grad_out.rows() != last.rows() || grad_out.cols() != last.cols()) throw hnh::Error("Error, GAT output gradient has the wrong shape!");
-        if (ones_S_.size() == 0) {
+        const bool fused = backward_ == HNH_GAT_BACKWARD_FUSED;  // (no per-nonzero vectors in that mode)
+        if (!fused && ones_S_.size() == 0) {
             ones_S_ = d_ops->like_S_values(1.0);
             ones_ST_ = d_ops->like_ST_values(1.0);
             e_S_ = VectorXd(ones_S_.size());
@@ -158,7 +176,7 @@ public:
             e_ST_ = VectorXd(ones_ST_.size());
             d_ST_ = VectorXd(ones_ST_.size());
         }
-        if (attention_ == HNH_GAT_ATTENTION_SOFTMAX && lse_S_.size() != ones_S_.size()) {
+        if (!fused && attention_ == HNH_GAT_ATTENTION_SOFTMAX && lse_S_.size() != ones_S_.size()) {
             lse_S_ = VectorXd(ones_S_.size());
             delta_S_ = VectorXd(ones_S_.size());
             lse_ST_ = VectorXd(ones_ST_.size());
@@ -182,6 +200,7 @@ private:
     hnh::World* world_ = nullptr;
     bool forward_valid_ = false;
     int attention_ = HNH_GAT_ATTENTION_NONE;
+    int backward_ = HNH_GAT_BACKWARD_UNFUSED;
     // softmax attention: the rows' running max / sum (reused by every head, which run one after the other on the compute stream), the
     // log-sum-exp of every (layer, head), and for the backward pass a column of ones and the broadcasts of lse and delta onto the nonzeros
     DenseMatrix row_max_, row_sum_, ones_col_;
@@ -198,6 +217,7 @@ private:
 
     // Throws hnh::Error (never a wrong number) where the backward pass is not defined or its kernels are missing.
     void check_backward_supported() {
+        if (backward_ == HNH_GAT_BACKWARD_FUSED) check_fused_backward_supported();
         auto* ds = dynamic_cast<Sparse15D_Dense_Shift*>(d_ops);
         if (ds == nullptr || ds->r_split)
             throw hnh::Error("Error, GAT backwardPass supports the 1.5D dense-shift schedules only (15d_fusion1, 15d_fusion2 with c = 1), not " +
@@ -221,6 +241,29 @@ private:
                     throw hnh::Error(std::string("Error, GAT backwardPass with softmax attention needs the kernel ") + n.second +
                                      ", which the kernel library " + be->path + " does not export (include/hnh_attention.h)");
         }
+    }
+
+    // The fused backward mode's own conditions, checked before anything is launched: its kernel group first, then the schedule (a rank's
+    // own launches must see all of a row's nonzeros and no output row may be summed across ranks: 15d_fusion2 with c = 1, the condition
+    // of the fused forward), then the head widths.
+    void check_fused_backward_supported() {
+        const hnh::Backend* be = d_ops->world->be;
+        const std::pair<const void*, const char*> need[] = {{(const void*)be->hnh_attn_grad_row_csr_p, "hnh_attn_grad_row_csr_p"},
+                                                            {(const void*)be->hnh_attn_grad_col_csr_p, "hnh_attn_grad_col_csr_p"},
+                                                            {(const void*)be->hnh_attn_grad_pack_f64, "hnh_attn_grad_pack_f64"}};
+        for (const auto& n : need)
+            if (n.first == nullptr)
+                throw hnh::Error(std::string("Error, GAT backwardPass in fused mode needs the kernel ") + n.second + ", which the kernel library " +
+                                 be->path + " does not export (include/hnh_attn_grad.h)");
+        auto* ds = dynamic_cast<Sparse15D_Dense_Shift*>(d_ops);
+        if (ds == nullptr || ds->r_split || ds->fusionApproach != 2 || ds->c != 1)
+            throw hnh::Error("Error, GAT fused backward supports 15d_fusion2 with c = 1 only, not " +
+                             (ds ? "15d_fusion" + std::to_string(ds->fusionApproach) + " (" + d_ops->algorithm_name + ")" : d_ops->algorithm_name) +
+                             " with c = " + std::to_string(d_ops->c) + ": its rows are summed across ranks");
+        for (const GATLayer& L : layers)
+            if (L.features_per_head > HNH_ATTN_GRAD_MAX_F)
+                throw hnh::Error("Error, GAT fused backward supports heads of at most " + std::to_string(HNH_ATTN_GRAD_MAX_F) + " features, not " +
+                                 std::to_string(L.features_per_head) + " (include/hnh_attn_grad.h)");
     }
 
     // Throws hnh::Error (never a wrong number) where softmax attention is not defined or its kernel is missing: a row's softmax needs
@@ -264,13 +307,55 @@ private:
             DenseMatrix& Wh = layers[(size_t)i].wMats[(size_t)h];
             DenseMatrix& A = scratch(2, rows, f);
             DenseMatrix& dZ = scratch(3, rows, f);
-            DenseMatrix& dArow = scratch(4, rows, f);
-            DenseMatrix& T1 = scratch(5, rows, f);
-            DenseMatrix& T2 = scratch(6, rows, f);
             w->check(be->hnh_gemm_f64(w->ctx, rows, f, k, X.data(), Wh.data(), A.data(), S0), "hnh_gemm_f64");
             w->check(be->hnh_relu_grad_cols_f64(w->ctx, dZ.data(), f, G.data(), hf, out.data(), hf, (int64_t)h * f, rows, f, S0),
                      "hnh_relu_grad_cols_f64");
             const bool softmax = attention_ == HNH_GAT_ATTENTION_SOFTMAX;
+            if (backward_ == HNH_GAT_BACKWARD_FUSED) {
+                // two passes straight into the head's column block of dA_all (include/hnh_attn_grad.h)
+                auto* ds = dynamic_cast<Sparse15D_Dense_Shift*>(d_ops);
+                const double* lse = nullptr;
+                const double* delta = nullptr;
+                if (softmax) {
+                    DenseMatrix& dl = scratch(8, rows, 1);
+                    w->check(be->hnh_rowdot_cols_f64(w->ctx, dl.data(), dZ.data(), f, out.data(), hf, (int64_t)h * f, rows, f, S0), "hnh_rowdot_cols_f64");
+                    delta = dl.data();
+                    lse = lse_.at((size_t)i).at((size_t)h).data();
+                }
+                const int pw = HNH_ATTN_GRAD_PACKED_WIDTH(f, softmax);
+                DenseMatrix& P = scratch(9, rows, pw);
+                w->check(be->hnh_attn_grad_pack_f64(w->ctx, P.data(), pw, A.data(), f, dZ.data(), f, lse, delta, rows, f, S0), "hnh_attn_grad_pack_f64");
+                hnh_attn_grad g = {};
+                g.X = A.data();
+                g.ld_x = f;
+                g.dZ = dZ.data();
+                g.ld_dz = f;
+                g.lse = lse;
+                g.delta = delta;
+                g.Out = dA_all.data() + (int64_t)h * f;
+                g.ld_out = hf;
+                g.f = f;
+                g.softmax = softmax ? 1 : 0;
+                g.leaky_alpha = leaky_relu_alpha;
+                bool ok = ds != nullptr && ds->attnGrad_pass(false, A, g, rows, true);  // row side: dA_i = sum_j de_ij A_j
+                if (ok) {
+                    // column side onto the same rows; the moving operand is the packed one, so the schedule runs at ITS width for this pass
+                    d_ops->setRValue(pw);
+                    try {
+                        ok = ds->attnGrad_pass(true, P, g, rows, false);
+                    } catch (...) {
+                        d_ops->setRValue(f);
+                        throw;
+                    }
+                    d_ops->setRValue(f);
+                }
+                if (!ok) throw hnh::Error("Error, GAT fused backward supports 15d_fusion2 with c = 1 only, not " + d_ops->algorithm_name);
+                w->check(be->hnh_transpose_into_f64(w->ctx, Wt.data(), k, (int64_t)h * f, Wh.data(), k, f, S0), "hnh_transpose_into_f64");
+                continue;
+            }
+            DenseMatrix& dArow = scratch(4, rows, f);
+            DenseMatrix& T1 = scratch(5, rows, f);
+            DenseMatrix& T2 = scratch(6, rows, f);
             if (softmax) {
                 // delta_i = <dZ_i, out_i> (= <dZ_i, o_i>: dZ is 0 where out is), then lse_i and delta_i onto the nonzeros of both layouts:
                 // width-1 SDDMMs whose first operand is the S-row side in both, so S^T gets the per-row scalars from the rank that owns them

@@ -154,6 +154,38 @@ bool StandardKernel::softmax_block(SpmatLocal& S, DenseMatrix& A, DenseMatrix& B
     return true;
 }
 
+bool KernelImplementation::attn_grad_local(SpmatLocal& S, int block, const hnh_attn_grad& args, bool column_side, unsigned flags, int64_t rows) {
+    StandardKernel* k = dynamic_cast<StandardKernel*>(this);
+    return k != nullptr && k->attn_grad_block(S, block, args, column_side, flags, rows);
+}
+
+// The two passes of the fused attention backward (include/hnh_attn_grad.h), next to fused_local: same block and window handling.
+bool StandardKernel::attn_grad_block(SpmatLocal& S, int block, const hnh_attn_grad& args, bool column_side, unsigned flags, int64_t rows) {
+    hnh::World* w = S.world;
+    auto fn = column_side ? w->be->hnh_attn_grad_col_csr_p : w->be->hnh_attn_grad_row_csr_p;
+    const char* name = column_side ? "hnh_attn_grad_col_csr_p" : "hnh_attn_grad_row_csr_p";
+    if (fn == nullptr)
+        throw hnh::Error(std::string("Error, the fused attention backward needs the kernel ") + name + ", which the kernel library " + w->be->path +
+                         " does not export (include/hnh_attn_grad.h)");
+    CSRLocal* blk = S.csr_blocks[block];
+    if (blk == nullptr || blk->num_coords == 0) {  // nothing to add; overwritten output rows still have to hold zeros afterwards
+        hnh_csr_block none = {};
+        none.rows = rows;
+        none.cols = -1;
+        w->check(fn(w->ctx, &none, &args, flags, nullptr, HNH_STREAM_COMPUTE), name);
+        return true;
+    }
+    if (blk->transpose) hnh::fatal("Error, local matrix is transposed, can't perform the fused attention backward");
+    begin(w);
+    hnh_csr_window win;
+    const hnh_csr_block desc = blk->block_args();
+    if (desc.rows != rows) hnh::fatal("Error, the fused attention backward needs an output of the block's rows!");
+    const bool windowed = blk->window_args(&win);
+    w->check(fn(w->ctx, &desc, &args, flags, windowed ? &win : nullptr, HNH_STREAM_COMPUTE), name);
+    end(w, (profile && !windowed) ? w->be->hnh_panel_count(w->ctx, desc.rows, desc.nnz, desc.cols, column_side ? 2 * args.f : args.f, desc.max_row_nnz) : 1);
+    return true;
+}
+
 void StandardKernel::begin(hnh::World* w) {
     if (!profile) return;
     if (evw_ != nullptr && evw_ != w) hnh::fatal("Error, a profiled StandardKernel belongs to one world!");

@@ -65,6 +65,13 @@ public:
     bool softmax_local(SpmatLocal& S, DenseMatrix& A, DenseMatrix& B, DenseMatrix& Out, int block, unsigned flags, const hnh_attn_state& state,
                        bool finish);
 
+    // One pass of the fused attention backward (include/hnh_attn_grad.h, the GAT's fused backward mode) on one block, or the selected
+    // window(s) of it: the row pass over a block of S, or with `column_side` the column pass over a block of S^T whose gathered operand
+    // is the packed one.  `args` carries the operands with their leading dimensions (args.Y = the gathered operand the schedule hands
+    // in); rows = the rows of the output (used when the block is absent: HNH_FUSED_OUT_OVERWRITE still has to leave zeros).  Returns
+    // false, having done nothing, when the implementation has no such pass.  NOT virtual, for softmax_local's reason.
+    bool attn_grad_local(SpmatLocal& S, int block, const hnh_attn_grad& args, bool column_side, unsigned flags, int64_t rows);
+
     // Row windows (CSRLocal::window): a schedule may select one column range of a block before calling the kernels, to
     // work on data that arrives piece by piece.  An implementation that honours CSRLocal::window says so here; for the
     // others (plugins written against the reference's two pure virtuals) the schedule waits for the whole block instead.
@@ -141,6 +148,8 @@ public:
     // KernelImplementation::softmax_local's pass (non-virtual: see there)
     bool softmax_block(SpmatLocal& S, DenseMatrix& A, DenseMatrix& B, DenseMatrix& Out, int block, unsigned flags, const hnh_attn_state& state,
                        bool finish);
+    // KernelImplementation::attn_grad_local's pass (non-virtual: see there)
+    bool attn_grad_block(SpmatLocal& S, int block, const hnh_attn_grad& args, bool column_side, unsigned flags, int64_t rows);
     ~StandardKernel() override;
 
 private:

@@ -240,6 +240,13 @@ int hnh_gat_get_input_grad(hnh_gat* g, hnh_dense* out);                     /* d
 #define HNH_GAT_ATTENTION_NONE 0
 #define HNH_GAT_ATTENTION_SOFTMAX 1
 int hnh_gat_set_attention(hnh_gat* g, int mode);
+/* Backward mode (an addition).  UNFUSED (the default of hnh_gat_create): seven operator calls per head (4 SDDMM, 3 SpMM) with their
+ * per-nonzero value vectors.  FUSED: the same gradients from two passes per head (include/hnh_attn_grad.h: one gather per layout);
+ * 15d_fusion2 with c = 1 and heads of at most 256 features only — hnh_gat_backward fails elsewhere, naming the schedule or the
+ * limit, or the missing symbol when the kernel library lacks the group.  An unknown mode fails; switching needs no new forward pass. */
+#define HNH_GAT_BACKWARD_UNFUSED 0
+#define HNH_GAT_BACKWARD_FUSED 1
+int hnh_gat_set_backward(hnh_gat* g, int mode);
 
 #ifdef __cplusplus
 }

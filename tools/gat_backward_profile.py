@@ -1,13 +1,18 @@
 """Development tool: time the GAT backward pass against its forward pass on one GPU, and the split-K weight-gradient GEMM alone.
 
-    python tools/gat_backward_profile.py [logm] [alg]          forward and backward ms per head (benchmark_dist.cpp:93-95 layers,
+    python tools/gat_backward_profile.py [logm] [alg] [--backward unfused|fused|both]
+                                                               forward and backward ms per head (benchmark_dist.cpp:93-95 layers,
                                                                Erdos-Renyi 2^logm vertices, edge factor 32), then hnh_gemm_tn_f64
-                                                               at 1024 x 1024 x 2^logm
+                                                               at 1024 x 1024 x 2^logm.  Backward mode "both" (the default; 15d_fusion2
+                                                               only, 15d_fusion1 has the un-fused pass alone) times the un-fused and
+                                                               the fused pass in the same run: both warmed up, then alternating, each
+                                                               pass between two device synchronisations; mean and min .. max are printed
     python tools/gat_backward_profile.py --stats <dir>         the backward pass split into sparse passes, GEMMs and element-wise
                                                                kernels, from the *kernel_stats.csv of a run of this tool with
-                                                               HNH_PROFILE_BACKWARD_ONLY=1 under `rocprofv3 --kernel-trace --stats`
+                                                               HNH_PROFILE_BACKWARD_ONLY=1 (and one --backward mode) under
+                                                               `rocprofv3 --kernel-trace --stats`
 """
-import csv, glob, os, sys, time
+import csv, glob, os, re, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
@@ -22,7 +27,14 @@ def stats(d):
     for f in files:
         for row in csv.DictReader(open(f)):
             name, ns, calls = row["Name"], float(row["TotalDurationNs"]), int(row["Calls"])
-            if "gemm_tn" in name:
+            ag = re.search(r"attn_grad_(row|long)_kernel<\s*(\d)", name)
+            if ag:  # the two passes of the fused backward mode (include/hnh_attn_grad.h), hub-row segments with their pass
+                g = "fused backward: column pass over S^T (packed gather)" if ag.group(2) == "1" else "fused backward: row pass over S"
+            elif "attn_grad_reduce" in name:
+                g = "fused backward: hub-row segment sums"
+            elif "attn_grad_pack" in name:
+                g = "fused backward: pack P = [A | dZ | lse delta]"
+            elif "gemm_tn" in name:
                 g = "TN GEMM (dW = X^T dA, split-K + reduce)"
             elif "gemm_f64" in name:
                 g = "NN GEMM (A = X W, dX = dA W^T)"
@@ -45,8 +57,16 @@ def main():
         return
     from distributed_sddmm_amd import api as H, _kernels as K
     assert H.load_backend(None) == "hip-gfx950"
-    logm = int(sys.argv[1]) if len(sys.argv) > 1 else 18
-    algs = [sys.argv[2]] if len(sys.argv) > 2 else ["15d_fusion2", "15d_fusion1"]
+    argv = list(sys.argv)
+    backward = "both"
+    if "--backward" in argv:
+        i = argv.index("--backward")
+        backward = argv[i + 1]
+        del argv[i:i + 2]
+    if backward not in ("unfused", "fused", "both"):
+        sys.exit("--backward takes unfused, fused or both")
+    logm = int(argv[1]) if len(argv) > 1 else 18
+    algs = [argv[2]] if len(argv) > 2 else ["15d_fusion2", "15d_fusion1"]
     backward_only = os.environ.get("HNH_PROFILE_BACKWARD_ONLY") == "1"
     w = H.World.single(0)
     sp = H.SpmatLocal.load_tuples(w, False, logm, 32)
@@ -66,8 +86,11 @@ def main():
         gnn.set_input(x)
         g = H.Dense.create(w, *gnn.buffer_shape(len(layers)))
         g.fill(1.0)
+        modes = ["unfused"] if alg != "15d_fusion2" else (["unfused", "fused"] if backward == "both" else [backward])
         gnn.forwardPass()
-        gnn.backwardPass(g)  # allocates the backward buffers
+        for mode in modes:  # allocates each mode's buffers and warms it up
+            gnn.set_backward(mode)
+            gnn.backwardPass(g)
         w.sync()
         reps = 1 if backward_only else 3
         t = time.perf_counter()
@@ -75,13 +98,24 @@ def main():
             gnn.forwardPass()
         w.sync()
         fwd = (time.perf_counter() - t) / reps
-        t = time.perf_counter()
-        for _ in range(reps):
-            gnn.backwardPass(g)
-        w.sync()
-        bwd = (time.perf_counter() - t) / reps
-        print("GAT [%s] 2^%d vertices, %d nnz, %d heads: forward %.1f ms (%.2f per head), backward %.1f ms (%.2f per head), ratio %.2f"
-              % (alg, logm, nnz, heads, fwd * 1e3, fwd * 1e3 / heads, bwd * 1e3, bwd * 1e3 / heads, bwd / fwd))
+        times = {mode: [] for mode in modes}
+        for _ in range(reps):  # alternating, every pass between two device synchronisations
+            for mode in modes:
+                gnn.set_backward(mode)
+                w.sync()
+                t = time.perf_counter()
+                gnn.backwardPass(g)
+                w.sync()
+                times[mode].append(time.perf_counter() - t)
+        for mode in modes:
+            bwd = float(np.mean(times[mode]))
+            print("GAT [%s, backward %s] 2^%d vertices, %d nnz, %d heads: forward %.1f ms (%.2f per head), backward %.1f ms (%.2f per head; "
+                  "min %.1f .. max %.1f over %d), ratio %.2f"
+                  % (alg, mode, logm, nnz, heads, fwd * 1e3, fwd * 1e3 / heads, bwd * 1e3, bwd * 1e3 / heads, min(times[mode]) * 1e3,
+                     max(times[mode]) * 1e3, reps, bwd / fwd))
+        if len(modes) == 2:
+            u, f = float(np.mean(times["unfused"])), float(np.mean(times["fused"]))
+            print("GAT [%s] un-fused / fused backward: %.2f x (%.1f -> %.1f ms)" % (alg, u / f, u * 1e3, f * 1e3))
         for h in (g, x, gnn, op):
             h.free()
     if backward_only:

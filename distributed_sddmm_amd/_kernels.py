@@ -160,6 +160,36 @@ class AttnGrad(C.Structure):
                 ("Out", _vp), ("ld_out", _i64), ("f", _i32), ("softmax", _i32), ("leaky_alpha", _dbl)]
 
 
+# include/hnh_attn_additive.h: additive (a1, a2) attention scores of the GAT, forward and backward; a fourth OPTIONAL group bound only
+# for the product library
+ATTN_ADD_SIGNATURES = {
+    "hnh_attn_add_fwd_csr_p": (_i32, [_vp, _vp, _vp, C.c_uint, _vp, _i32]),
+    "hnh_attn_add_row_csr_p": (_i32, [_vp, _vp, _vp, C.c_uint, _vp, _i32]),
+    "hnh_attn_add_col_csr_p": (_i32, [_vp, _vp, _vp, C.c_uint, _vp, _i32]),
+    "hnh_attn_add_scores_f64": (_i32, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i32, _i32]),
+    "hnh_attn_add_pack_f64": (_i32, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i32, _i32]),
+    "hnh_attn_add_update_f64": (_i32, [_vp, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i32, _i32]),
+}
+ATTN_ADD_MAX_F = 256  # HNH_ATTN_ADD_MAX_F
+
+
+def attn_add_scored_width(f: int) -> int:
+    """HNH_ATTN_ADD_SCORED_WIDTH: [A (0) | s t]"""
+    return f + (f & 1) + 2
+
+
+def attn_add_packed_width(f: int) -> int:
+    """HNH_ATTN_ADD_PACKED_WIDTH: [dZ (0) | s lse delta 0]"""
+    return f + (f & 1) + 4
+
+
+class AttnAdd(C.Structure):
+    """struct hnh_attn_add"""
+    _fields_ = [("M", _vp), ("ld_m", _i64), ("dZ", _vp), ("ld_dz", _i64), ("lse", _vp), ("delta", _vp), ("Y", _vp), ("ld_y", _i64),
+                ("Out", _vp), ("ld_out", _i64), ("vec", _vp), ("ld_vec", _i64), ("row_max", _vp), ("row_sum", _vp), ("relu_dst", _vp),
+                ("relu_ld", _i64), ("f", _i32), ("leaky_alpha", _dbl)]
+
+
 class AttnState(C.Structure):
     """struct hnh_attn_state"""
     _fields_ = [("row_max", _vp), ("row_sum", _vp), ("lse", _vp), ("leaky_alpha", _dbl), ("relu_dst", _vp), ("relu_ld", _i64)]
@@ -221,7 +251,8 @@ def load(path: str | None = None) -> C.CDLL:
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype, fn.argtypes = res, args
     if path is None or os.path.abspath(p) == os.path.abspath(LIB_PATH):
-        for name, (res, args) in list(GRAD_SIGNATURES.items()) + list(ATTN_SIGNATURES.items()) + list(ATTN_GRAD_SIGNATURES.items()):
+        for name, (res, args) in list(GRAD_SIGNATURES.items()) + list(ATTN_SIGNATURES.items()) + list(ATTN_GRAD_SIGNATURES.items()) + \
+                list(ATTN_ADD_SIGNATURES.items()):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
     if path is None:

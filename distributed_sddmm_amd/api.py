@@ -133,6 +133,9 @@ SIGNATURES = {
     "hnh_gat_get_input_grad": (_i32, [_vp, _vp]),
     "hnh_gat_set_attention": (_i32, [_vp, _i32]),
     "hnh_gat_set_backward": (_i32, [_vp, _i32]),
+    "hnh_gat_set_score": (_i32, [_vp, _i32]),
+    "hnh_gat_set_attn_vectors": (_i32, [_vp, _i32, _i32, _vp, _vp]),
+    "hnh_gat_get_attn_grads": (_i32, [_vp, _i32, _i32, _vp, _vp]),
 }
 
 _lib = None
@@ -648,7 +651,10 @@ class GAT:
 
     BACKWARD = {"unfused": 0, "fused": 1}  # HNH_GAT_BACKWARD_UNFUSED / _FUSED
 
-    def __init__(self, op: DistributedSparse, layers, leaky_relu_alpha: float = 0.2, attention: str = "none", backward: str = "unfused"):
+    SCORE = {"dot": 0, "additive": 1}  # HNH_GAT_SCORE_DOT / _ADDITIVE
+
+    def __init__(self, op: DistributedSparse, layers, leaky_relu_alpha: float = 0.2, attention: str = "none", backward: str = "unfused",
+                 score: str = "dot"):
         self.op, self.layers = op, [tuple(l) for l in layers]
         spec = (C.c_int * (3 * len(layers)))(*[x for l in self.layers for x in l])
         self.h = _vp()
@@ -657,6 +663,8 @@ class GAT:
             self.set_attention(attention)
         if backward != "unfused":
             self.set_backward(backward)
+        if score != "dot":
+            self.set_score(score)
 
     def set_attention(self, mode: str):
         """"none" (the default: the LeakyReLU scores are the edge weights) or "softmax" (normalised over each row's neighbourhood;
@@ -671,6 +679,31 @@ class GAT:
         if mode not in self.BACKWARD:
             raise ValueError("backward must be one of %s, not %r" % (sorted(self.BACKWARD), mode))
         _check(lib().hnh_gat_set_backward(self.h, self.BACKWARD[mode]), "gat_set_backward")
+
+    def set_score(self, mode: str):
+        """"dot" (the default: e_ij = LeakyReLU(<A_i, A_j>)) or "additive" (e_ij = LeakyReLU(<A_i, a1> + <A_j, a2>) with the vectors of
+        set_attention_vectors, include/hnh_attn_additive.h; attention "softmax" on 15d_fusion2 with c = 1 and heads of at most 256
+        features only, forwardPass / backwardPass raise HnhError elsewhere).  With "additive" there is one backward implementation:
+        set_backward is not consulted.  A change invalidates the stored forward pass."""
+        if mode not in self.SCORE:
+            raise ValueError("score must be one of %s, not %r" % (sorted(self.SCORE), mode))
+        _check(lib().hnh_gat_set_score(self.h, self.SCORE[mode]), "gat_set_score")
+
+    def set_attention_vectors(self, layer: int, head: int, a1: np.ndarray, a2: np.ndarray):
+        """The additive score's vectors of (layer, head): features_per_head entries each, zero until set.  Invalidates the stored
+        forward pass like set_weight."""
+        f = self.layers[layer][1]
+        a1 = np.ascontiguousarray(a1, dtype=np.float64)
+        a2 = np.ascontiguousarray(a2, dtype=np.float64)
+        assert a1.shape == (f,) and a2.shape == (f,)
+        _check(lib().hnh_gat_set_attn_vectors(self.h, layer, head, a1.ctypes.data, a2.ctypes.data), "gat_set_attn_vectors")
+
+    def attention_grad(self, layer: int, head: int):
+        """(dL/da1, dL/da2) of (layer, head) after backwardPass with score "additive", summed over every rank."""
+        f = self.layers[layer][1]
+        da1, da2 = np.empty(f), np.empty(f)
+        _check(lib().hnh_gat_get_attn_grads(self.h, layer, head, da1.ctypes.data, da2.ctypes.data), "gat_get_attn_grads")
+        return da1, da2
 
     def weight_shape(self, layer: int, head: int):
         o = (C.c_int64 * 2)()

@@ -1,0 +1,636 @@
+// Additive (a1, a2) attention scores of the GAT (include/hnh_attn_additive.h): three sibling templates of the row kernel.  Included at the
+// end of hnh_kernels.hip, after hnh_attn_grad_kernels.hpp, whose machinery they use as it is (AgUnroll, the hub-row segment scheme with
+// attn_grad_reduce_kernel / attn_grad_zero_rows_kernel, plans, Infinity-Cache panels) next to the row kernels' transposed butterfly and
+// group broadcast; kept apart from process_row and attn_grad_process so that none of the existing instances changes by a register.
+//
+//   PASS 0  forward over S:        s_i and the row's softmax state in registers; gathers M_j = [A_j | s_j t_j]; z = s_i + t_j (no dot product,
+//                                  no butterfly), the online-softmax step of kFusedSoftmax, acc = acc f + p A_j
+//   PASS 1  backward row pass:     dZ_i, s_i, lse_i, delta_i in registers; gathers M_j; da = <dZ_i, A_j> (butterfly), gate, ds_i += dz
+//   PASS 2  backward column pass:  A_j, t_j in registers; gathers Q_i = [dZ_i | s_i lse_i delta_i]; da = <A_j, dZ_i>, gate with the
+//                                  gathered row's scalars, acc += a dZ_i, dt_j += dz
+// Lane layout and batches as in attn_grad_process: U nonzeros per batch in one of two register buffers; lane group lig / SUB owns
+// nonzero lig / SUB of the batch for the per-nonzero scalar work (one exp per lane and batch), whose results are handed round with group
+// broadcasts.  The scalars of a gathered row come with one 16-byte load from column fp of that row.
+#pragma once
+
+namespace {
+
+struct AaArgs {  // hnh_attn_add as the kernels take it
+    const double* M;
+    const double* dZ;
+    const double* delta;
+    const double* Y;
+    double* lse;
+    double* Out;
+    double* vec;
+    double* row_max;
+    double* row_sum;
+    double* relu_dst;
+    int64_t ld_m, ld_dz, ld_y, ld_out, ld_vec, relu_ld;
+    int f, fp;  // fp = f rounded up to even: column of the scalars in a scored / packed row
+    double alpha;
+};
+
+template <int PASS, int LPR, int VEC, int W, bool EXACT>
+__device__ __forceinline__ void attn_add_process(int64_t row, int beg, int end, const int32_t* __restrict__ colidx, const AaArgs& a,
+                                                 unsigned flags, int lig, double* part_row) {
+    constexpr int U = AgUnroll<0, LPR, VEC, W>::value;
+    constexpr int SUB = LPR / U;  // lanes that own the same nonzero of a batch
+    static_assert(SUB >= 1, "needs U <= LPR");
+    bool act[VEC];
+    int coff[VEC];
+    unsigned lane_off[VEC];
+#pragma unroll
+    for (int v = 0; v < VEC; v++) {
+        const int c = (v * LPR + lig) * W;
+        act[v] = EXACT ? true : (c < a.f);
+        coff[v] = c;
+        lane_off[v] = (unsigned)c * (unsigned)sizeof(double);
+    }
+    const bool fresh = part_row != nullptr || (flags & HNH_FUSED_OUT_OVERWRITE);
+
+    double x[PASS == 0 ? 1 : VEC][W], acc[PASS == 1 ? 1 : VEC][W];
+#pragma unroll
+    for (int v = 0; v < VEC; v++) {
+#pragma unroll
+        for (int w = 0; w < W; w++) {
+            if constexpr (PASS != 0) x[v][w] = 0.0;
+            if constexpr (PASS != 1) acc[v][w] = 0.0;
+        }
+        if (act[v]) {
+            if constexpr (PASS == 1) load_w_stream<W>(x[v], a.dZ + row * a.ld_dz + coff[v]);
+            if constexpr (PASS == 2) load_w_stream<W>(x[v], a.M + row * a.ld_m + coff[v]);
+            if constexpr (PASS != 1)
+                if (!fresh) load_w_stream<W>(acc[v], a.Out + row * a.ld_out + coff[v]);
+        }
+    }
+    // the own row's scalars: s_i (forward, row pass) or t_j (column pass); lse_i, delta_i (row pass)
+    const double own = a.M[row * a.ld_m + a.fp + (PASS == 2 ? 1 : 0)];
+    double lse_i = 0.0, delta_i = 0.0;
+    if constexpr (PASS == 1) {
+        lse_i = a.lse[row];
+        delta_i = a.delta[row];
+    }
+    double m_run = -__builtin_inf(), l_run = 0.0;  // forward: the row's running max and sum (hnh_attention.h)
+    double dsum = 0.0;                             // backward: the row's scalar sum (ds_i or dt_j)
+    if constexpr (PASS == 0) {
+        if (!fresh) {
+            m_run = a.row_max[row];
+            l_run = a.row_sum[row];
+        }
+    } else {
+        if (!fresh) dsum = a.vec[row * a.ld_vec];
+    }
+    const uint64_t g_base = reinterpret_cast<uint64_t>(a.Y);
+    const uint64_t ld_bytes = (uint64_t)a.ld_y * sizeof(double);
+    const unsigned sc_bytes = (unsigned)a.fp * (unsigned)sizeof(double);
+
+    struct Batch {
+        double y[U][VEC][W];
+        double sa[U][2];                    // [s t] of a scored row, [s lse] of a packed one
+        double sb[PASS == 2 ? U : 1][2];    // [delta 0] of a packed row
+    };
+
+    auto load_idx = [&](auto full, int e, int (&c)[U]) {
+        constexpr bool FULL = decltype(full)::value;
+        if constexpr (LPR == 64) {
+#pragma unroll
+            for (int u = 0; u < U; u++) c[u] = (FULL || e + u < end) ? colidx[e + u] : -1;
+        } else {
+            const int my = e + (lig % U);
+            const int cv = (FULL || my < end) ? colidx[my] : -1;
+#pragma unroll
+            for (int u = 0; u < U; u++) c[u] = __shfl(cv, u, LPR);
+        }
+    };
+    auto gather = [&](auto full, const int (&c)[U], Batch& b) {
+        constexpr bool FULL = decltype(full)::value;
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const bool live = FULL || c[u] >= 0;
+            uint64_t rowp = g_base + (uint64_t)(unsigned)(live ? c[u] : 0) * ld_bytes;
+            if constexpr (LPR == 64) {  // wave-uniform: SGPR base + VGPR offset
+                const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)rowp);
+                const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)(rowp >> 32));
+                rowp = ((uint64_t)hi << 32) | lo;
+            }
+#pragma unroll
+            for (int v = 0; v < VEC; v++) {
+#pragma unroll
+                for (int w = 0; w < W; w++) b.y[u][v][w] = 0.0;
+                if (live && act[v]) {
+                    unsigned off = lane_off[v];
+                    if constexpr (LPR == 64) asm volatile("" : "+v"(off));
+                    load_w_global<W>(b.y[u][v], rowp, off);
+                }
+            }
+            b.sa[u][0] = 0.0;
+            b.sa[u][1] = 0.0;
+            if (live) load_w_global<2>(b.sa[u], rowp, sc_bytes);  // (16-byte aligned: an even pitch, fp even)
+            if constexpr (PASS == 2) {
+                b.sb[u][0] = 0.0;
+                b.sb[u][1] = 0.0;
+                if (live) load_w_global<2>(b.sb[u], rowp, sc_bytes + 16u);
+            }
+        }
+    };
+    auto compute = [&](auto full, int e, const Batch& b) {
+        constexpr bool FULL = decltype(full)::value;
+        const int umine = lig / SUB;
+        const bool have = FULL || e + umine < end;
+        double q0 = 0.0, q1 = 0.0, q2 = 0.0;  // the scalars of this lane's nonzero
+#pragma unroll
+        for (int u = 0; u < U; u++)
+            if (u == umine) {
+                q0 = b.sa[u][0];
+                q1 = b.sa[u][1];
+                if constexpr (PASS == 2) q2 = b.sb[u][0];
+            }
+        const double z = PASS == 2 ? q0 + own : own + q1;  // s_i + t_j
+        const double slope = z > 0.0 ? 1.0 : a.alpha;
+        const double ev = z * slope;
+        if constexpr (PASS == 0) {
+            // the online-softmax step of kFusedSoftmax (process_row), nonzero by nonzero in row order
+            const double s = have ? ev : -__builtin_inf();
+            double run = m_run, mprev = m_run, mcur = m_run;
+#pragma unroll
+            for (int u = 0; u < U; u++) {
+                const double t = group_bcast<LPR>(s, u * SUB);
+                const double nx = t > run ? t : run;
+                if (umine == u) { mprev = run; mcur = nx; }
+                run = nx;
+            }
+            const double fac = (mcur == mprev) ? 1.0 : (mprev == -__builtin_inf() ? 0.0 : exp(mprev - mcur));
+            const double pw = have ? exp(s - mcur) : 0.0;
+            m_run = run;
+#pragma unroll
+            for (int u = 0; u < U; u++) {
+                const double fu = group_bcast<LPR>(fac, u * SUB);
+                const double pu = group_bcast<LPR>(pw, u * SUB);
+                if (fu != 1.0) {  // the running max rose (uniform over the group)
+#pragma unroll
+                    for (int v = 0; v < VEC; v++)
+#pragma unroll
+                        for (int w = 0; w < W; w++) acc[v][w] *= fu;
+                    l_run *= fu;
+                }
+                l_run += pu;
+#pragma unroll
+                for (int v = 0; v < VEC; v++)
+#pragma unroll
+                    for (int w = 0; w < W; w++) acc[v][w] = fma(pu, b.y[u][v][w], acc[v][w]);
+            }
+#pragma unroll
+            for (int v = 0; v < VEC; v++)
+#pragma unroll
+                for (int w = 0; w < W; w++) asm volatile("" : "+v"(acc[v][w]));
+        } else {
+            double d[U];
+#pragma unroll
+            for (int u = 0; u < U; u++) {
+                double sd = 0.0;
+#pragma unroll
+                for (int v = 0; v < VEC; v++)
+#pragma unroll
+                    for (int w = 0; w < W; w++) sd = fma(x[v][w], b.y[u][v][w], sd);
+                d[u] = sd;
+            }
+            const double da = group_multi_reduce<LPR, U>(d, lig);  // reduction number lig / SUB
+            const double l = PASS == 1 ? lse_i : q1, dl = PASS == 1 ? delta_i : q2;
+            double wa = exp(ev - l);
+            double wdz = wa * (da - dl) * slope;
+            if (!have) {
+                wa = 0.0;
+                wdz = 0.0;
+            }
+#pragma unroll
+            for (int u = 0; u < U; u++) {
+                dsum += group_bcast<LPR>(wdz, u * SUB);  // in row order
+                if constexpr (PASS == 2) {
+                    const double au = group_bcast<LPR>(wa, u * SUB);
+#pragma unroll
+                    for (int v = 0; v < VEC; v++)
+#pragma unroll
+                        for (int w = 0; w < W; w++) acc[v][w] = fma(au, b.y[u][v][w], acc[v][w]);
+                }
+            }
+            if constexpr (PASS == 2) {
+#pragma unroll
+                for (int v = 0; v < VEC; v++)
+#pragma unroll
+                    for (int w = 0; w < W; w++) asm volatile("" : "+v"(acc[v][w]));
+            }
+            asm volatile("" : "+v"(dsum));
+        }
+    };
+    const BoolTag<true> kFull;
+    const BoolTag<false> kMasked;
+
+    int e = beg;
+    Batch ba, bb;
+    if (e + U <= end) {
+        int c0[U], c1[U];
+        load_idx(kFull, e, c0);
+        gather(kFull, c0, ba);
+        for (;;) {
+            const bool more = e + 2 * U <= end;
+            if (more) {  // the next batch's gathers fly while this one is computed
+                load_idx(kFull, e + U, c1);
+                gather(kFull, c1, bb);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            compute(kFull, e, ba);
+            __builtin_amdgcn_sched_barrier(0);
+            e += U;
+            if (!more) break;
+            const bool more2 = e + 2 * U <= end;
+            if (more2) {
+                load_idx(kFull, e + U, c0);
+                gather(kFull, c0, ba);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            compute(kFull, e, bb);
+            __builtin_amdgcn_sched_barrier(0);
+            e += U;
+            if (!more2) break;
+        }
+    }
+    if (e < end) {  // fewer than U nonzeros left: one masked batch
+        int c0[U];
+        load_idx(kMasked, e, c0);
+        gather(kMasked, c0, ba);
+        compute(kMasked, e, ba);
+    }
+
+    if constexpr (PASS == 0) {
+        // the row's state leaves with every launch, as in process_row
+        if (lig == 0) {
+            a.row_max[row] = m_run;
+            a.row_sum[row] = l_run;
+        }
+        if (flags & kInternalEpilogue) {  // finish: o = acc / l through the ReLU into the head's column block, and lse; Out is scratch
+            const bool live = l_run > 0.0;
+#pragma unroll
+            for (int v = 0; v < VEC; v++) {
+                double o[W];
+#pragma unroll
+                for (int w = 0; w < W; w++) o[w] = live ? fmax(acc[v][w] / l_run, 0.0) : 0.0;
+                if (act[v]) store_w_stream<W>(a.relu_dst + row * a.relu_ld + coff[v], o);
+            }
+            if (lig == 0) a.lse[row] = live ? m_run + log(l_run) : 0.0;
+            return;
+        }
+    }
+    if constexpr (PASS != 1) {
+#pragma unroll
+        for (int v = 0; v < VEC; v++) {
+            if (!act[v]) continue;
+            if (part_row != nullptr) store_w_stream<W>(part_row + coff[v], acc[v]);  // a hub row's segment: added up in order afterwards
+            else store_w_stream<W>(a.Out + row * a.ld_out + coff[v], acc[v]);
+        }
+    }
+    if constexpr (PASS != 0) {
+        if (lig == 0) {
+            if (part_row != nullptr) part_row[PASS == 2 ? a.fp : 0] = dsum;
+            else a.vec[row * a.ld_vec] = dsum;
+        }
+    }
+}
+
+template <int PASS, int LPR, int VEC, int W, bool EXACT>
+__global__ __launch_bounds__(kBlock) void attn_add_row_kernel(int64_t rows, const int32_t* __restrict__ rowptr, const int32_t* __restrict__ beg_ptr,
+                                                              const int32_t* __restrict__ end_ptr, const int32_t* __restrict__ colidx, AaArgs a,
+                                                              unsigned flags) {
+    constexpr int GROUPS = kBlock / LPR;
+    const int tid = threadIdx.x;
+    const int lig = tid % LPR;
+    int64_t row = (int64_t)blockIdx.x * GROUPS + tid / LPR;
+    if constexpr (LPR == 64) row = ((int64_t)blockIdx.x * GROUPS) + __builtin_amdgcn_readfirstlane(tid >> 6);
+    if (row >= rows) return;
+    int beg = beg_ptr[row];
+    int end = end_ptr[row];
+    if constexpr (LPR == 64) {
+        beg = __builtin_amdgcn_readfirstlane(beg);
+        end = __builtin_amdgcn_readfirstlane(end);
+    }
+    if constexpr (PASS != 0) {  // (the forward pass walks hub rows whole and visits every row: the reset and the finish apply to empty pieces too)
+        if (flags & kInternalSplitLong) {  // hub rows go to the segment kernel, whose sums are ADDED to the row (as in row_kernel)
+            int full = rowptr[row + 1] - rowptr[row];
+            if constexpr (LPR == 64) full = __builtin_amdgcn_readfirstlane(full);
+            if (full > long_row_of(flags)) {
+                if (flags & HNH_FUSED_OUT_OVERWRITE) end = beg;  // an overwritten row has to start from zero
+                else return;
+            }
+        }
+        if (beg == end && !(flags & HNH_FUSED_OUT_OVERWRITE)) return;  // nothing to add
+    }
+    attn_add_process<PASS, LPR, VEC, W, EXACT>(row, beg, end, colidx, a, flags, lig, nullptr);
+}
+
+// one work item = kLongSeg consecutive nonzeros of a hub row (the row kernels' work list); every segment writes its partial result
+template <int PASS, int LPR, int VEC, int W, bool EXACT>
+__global__ __launch_bounds__(kBlock) void attn_add_long_kernel(const int2* __restrict__ items, const int* __restrict__ item_count, int capacity,
+                                                               const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colidx, AaArgs a,
+                                                               double* partials, int64_t pitch) {
+    constexpr int GROUPS = kBlock / LPR;
+    const int tid = threadIdx.x;
+    const int lig = tid % LPR;
+    int count = *item_count;
+    if (count > capacity) count = capacity;
+    const int ngroups = (int)gridDim.x * GROUPS;
+    int first = (int)blockIdx.x * GROUPS + tid / LPR;
+    if constexpr (LPR == 64) first = __builtin_amdgcn_readfirstlane(first);
+    for (int it = first; it < count; it += ngroups) {
+        const int2 item = items[it];
+        int rbeg = rowptr[item.x], rend = rowptr[item.x + 1], seg = item.y;
+        int64_t row = item.x;
+        if constexpr (LPR == 64) {
+            rbeg = __builtin_amdgcn_readfirstlane(rbeg);
+            rend = __builtin_amdgcn_readfirstlane(rend);
+            seg = __builtin_amdgcn_readfirstlane(seg);
+            row = __builtin_amdgcn_readfirstlane(item.x);
+        }
+        const int beg = rbeg + seg * kLongSeg;
+        const int end = (beg + kLongSeg < rend) ? beg + kLongSeg : rend;
+        attn_add_process<PASS, LPR, VEC, W, EXACT>(row, beg, end, colidx, a, HNH_FUSED_OUT_OVERWRITE, lig, partials + (int64_t)it * pitch);
+    }
+}
+
+// a block without any nonzero, forward: the state reset of HNH_FUSED_OUT_OVERWRITE and the finish, as attn_add_process does them for a
+// row whose piece is empty (one wave per row)
+__global__ __launch_bounds__(kBlock) void attn_add_empty_rows_kernel(int64_t rows, AaArgs a, unsigned flags) {
+    const int64_t row = ((int64_t)blockIdx.x * kBlock + threadIdx.x) / 64;
+    const int lane = threadIdx.x % 64;
+    if (row >= rows) return;
+    const bool fresh = (flags & HNH_FUSED_OUT_OVERWRITE) != 0, finish = (flags & kInternalEpilogue) != 0;
+    const double m = fresh ? -__builtin_inf() : a.row_max[row];
+    const double l = fresh ? 0.0 : a.row_sum[row];
+    for (int c = lane; c < a.f; c += 64) {
+        const double v = fresh ? 0.0 : a.Out[row * a.ld_out + c];
+        if (finish) a.relu_dst[row * a.relu_ld + c] = l > 0.0 ? fmax(v / l, 0.0) : 0.0;
+        else a.Out[row * a.ld_out + c] = v;
+    }
+    if (lane == 0) {
+        a.row_max[row] = m;
+        a.row_sum[row] = l;
+        if (finish) a.lse[row] = l > 0.0 ? m + log(l) : 0.0;
+    }
+}
+
+// M[r, :] = [A_r (0) | <A_r, a1> <A_r, a2>], one wave per row
+__global__ __launch_bounds__(kBlock) void attn_add_scores_kernel(double* __restrict__ M, int64_t ld_m, const double* __restrict__ A, int64_t ld_a,
+                                                                 const double* __restrict__ a1, const double* __restrict__ a2, int64_t rows, int f, int fp) {
+    const int64_t row = ((int64_t)blockIdx.x * kBlock + threadIdx.x) / 64;
+    const int lane = threadIdx.x % 64;
+    if (row >= rows) return;
+    double s = 0.0, t = 0.0;
+    for (int c = lane; c < f; c += 64) {
+        const double v = A[row * ld_a + c];
+        s = fma(v, a1[c], s);
+        t = fma(v, a2[c], t);
+        M[row * ld_m + c] = v;
+    }
+    s = group_sum<64>(s);
+    t = group_sum<64>(t);
+    if (lane == 0) {
+        if (fp != f) M[row * ld_m + f] = 0.0;
+        M[row * ld_m + fp] = s;
+        M[row * ld_m + fp + 1] = t;
+    }
+}
+
+// Q[r, :] = [dZ_r (0) | s_r lse_r delta_r 0], the layout of include/hnh_attn_additive.h
+__global__ __launch_bounds__(kBlock) void attn_add_pack_kernel(double* __restrict__ Q, int64_t ld_q, const double* __restrict__ dZ, int64_t ld_dz,
+                                                               const double* __restrict__ M, int64_t ld_m, const double* __restrict__ lse,
+                                                               const double* __restrict__ delta, int64_t rows, int f, int fp) {
+    const int pw = fp + 4;
+    const int64_t stride = (int64_t)gridDim.x * kBlock, total = rows * pw;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < total; i += stride) {
+        const int64_t r = i / pw;
+        const int c = (int)(i % pw);
+        double v = 0.0;
+        if (c < f) v = dZ[r * ld_dz + c];
+        else if (c == fp) v = M[r * ld_m + fp];
+        else if (c == fp + 1) v = lse[r];
+        else if (c == fp + 2) v = delta[r];
+        Q[r * ld_q + c] = v;
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void attn_add_update_kernel(double* __restrict__ dA, int64_t ld_da, int64_t col0, const double* __restrict__ dAgg,
+                                                                 int64_t ld_g, const double* __restrict__ D, int64_t ld_d, const double* __restrict__ a1,
+                                                                 const double* __restrict__ a2, int64_t rows, int f) {
+    const int64_t stride = (int64_t)gridDim.x * kBlock, total = rows * f;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < total; i += stride) {
+        const int64_t r = i / f;
+        const int c = (int)(i % f);
+        dA[r * ld_da + col0 + c] = fma(D[r * ld_d + 1], a2[c], fma(D[r * ld_d], a1[c], dAgg[r * ld_g + c]));
+    }
+}
+
+template <int PASS, int LPR, int VEC, int W, bool EXACT>
+int attn_add_launch(hnh_ctx* ctx, hipStream_t st, const LongCtl& lc, int64_t rows, const int32_t* rowptr, const int32_t* beg_ptr,
+                    const int32_t* end_ptr, const int32_t* colidx, const AaArgs& a, unsigned flags, bool run_long) {
+    constexpr int GROUPS = kBlock / LPR;
+    const int64_t blocks = (rows + GROUPS - 1) / GROUPS;
+    if (blocks <= 0) return HNH_OK;
+    if (blocks > 0x7fffffffLL) return hnh::fail(ctx, HNH_ERR_UNSUPPORTED, "too many rows for one launch");
+    if (lc.enabled) flags |= kInternalSplitLong | ((unsigned)(lc.threshold / 64) << kLongRowShift);
+    const size_t lds_pad = lc.lds_pad <= 48 * 1024 ? lc.lds_pad : 0;
+    hipLaunchKernelGGL((attn_add_row_kernel<PASS, LPR, VEC, W, EXACT>), dim3((unsigned)blocks), dim3(kBlock), lds_pad, st, rows, rowptr, beg_ptr, end_ptr,
+                       colidx, a, flags);
+    if (int rc = hnh::check_hip(ctx, hipGetLastError(), "attn_add_row_kernel launch")) return rc;
+    if constexpr (PASS != 0) {
+        if (lc.enabled && run_long) {  // hub rows once per pass, over their whole length: segments, then the ordered sums
+            const int64_t pitch = PASS == 2 ? a.fp + 2 : 2;
+            hipLaunchKernelGGL((attn_add_long_kernel<PASS, LPR, VEC, W, EXACT>), dim3((unsigned)ctx->long_grid), dim3(kBlock), 0, st, lc.items, lc.count,
+                               lc.capacity, rowptr, colidx, a, lc.partials, pitch);
+            if (int rc = hnh::check_hip(ctx, hipGetLastError(), "attn_add_long_kernel launch")) return rc;
+            if (PASS == 2) {
+                hipLaunchKernelGGL(attn_grad_reduce_kernel, dim3(2048), dim3(kBlock), 0, st, lc.hub_rows, lc.count, lc.capacity_rows, lc.partials, pitch,
+                                   a.Out, a.ld_out, a.f);
+                if (int rc = hnh::check_hip(ctx, hipGetLastError(), "attn_grad_reduce_kernel launch")) return rc;
+            }
+            hipLaunchKernelGGL(attn_grad_reduce_kernel, dim3(2048), dim3(kBlock), 0, st, lc.hub_rows, lc.count, lc.capacity_rows,
+                               lc.partials + (PASS == 2 ? a.fp : 0), pitch, a.vec, a.ld_vec, 1);
+            return hnh::check_hip(ctx, hipGetLastError(), "attn_grad_reduce_kernel launch");
+        }
+    }
+    return HNH_OK;
+}
+
+// the instance that fits (f, alignment): exact widths 64 / 128 / 256, every other width bounds-checked (16-byte lanes when even)
+template <int PASS>
+int attn_add_launch_shape(hnh_ctx* ctx, hipStream_t st, const LongCtl& lc, bool w2, int64_t rows, const int32_t* rowptr, const int32_t* beg_ptr,
+                          const int32_t* end_ptr, const int32_t* colidx, const AaArgs& a, unsigned flags, bool run_long) {
+#define HNH_AA(L, V, WW, EX) return attn_add_launch<PASS, L, V, WW, EX>(ctx, st, lc, rows, rowptr, beg_ptr, end_ptr, colidx, a, flags, run_long)
+    const int f = a.f;
+    if (w2) {
+        if (f == 64) HNH_AA(32, 1, 2, true);
+        if (f == 128) HNH_AA(64, 1, 2, true);
+        if (f == 256) HNH_AA(64, 2, 2, true);
+        if (f < 128) HNH_AA(64, 1, 2, false);
+        HNH_AA(64, 2, 2, false);
+    }
+    if (f <= 64) HNH_AA(64, 1, 1, false);
+    if (f <= 128) HNH_AA(64, 2, 1, false);
+    HNH_AA(64, 4, 1, false);
+#undef HNH_AA
+}
+
+template <int PASS>
+int attn_add_dispatch(hnh_ctx* ctx, const hnh_csr_block* b, const hnh_attn_add* g, unsigned flags, const hnh_csr_window* win, int stream,
+                      const char* who) {
+    HNH_ENTER(ctx, stream);
+    if (!b || !g) return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": null block or arguments");
+    if (int rc = check_common(ctx, b->rows, g->f, who)) return rc;
+    if (flags & ~(HNH_FUSED_OUT_OVERWRITE | (PASS == 0 ? HNH_ATTN_FINISH : 0u))) return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": unknown flag");
+    if (g->f > HNH_ATTN_ADD_MAX_F)
+        return hnh::fail(ctx, HNH_ERR_UNSUPPORTED, std::string(who) + ": head width " + std::to_string(g->f) + " beyond the limit of " +
+                                                       std::to_string(HNH_ATTN_ADD_MAX_F) + " (HNH_ATTN_ADD_MAX_F)");
+    const bool finish = PASS == 0 && (flags & HNH_ATTN_FINISH) != 0;
+    if (finish && win != nullptr && !win->last) return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": the finish belongs to the last window");
+    if (b->rows == 0) return HNH_OK;
+    const int f = g->f, fp = f + (f & 1);
+    if (PASS != 1 && (!g->Out || g->ld_out < f)) return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": bad output");
+    if (PASS != 0 && (!g->vec || g->ld_vec < 1)) return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": bad scalar output");
+    if (PASS == 0 && (!g->row_max || !g->row_sum || !g->lse || !g->relu_dst || g->relu_ld < f))
+        return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": bad row state");
+    AaArgs a;
+    a.M = g->M; a.dZ = g->dZ; a.delta = g->delta; a.Y = g->Y; a.lse = g->lse; a.Out = g->Out; a.vec = g->vec;
+    a.row_max = g->row_max; a.row_sum = g->row_sum; a.relu_dst = g->relu_dst;
+    a.ld_m = g->ld_m; a.ld_dz = g->ld_dz; a.ld_y = g->ld_y; a.ld_out = g->ld_out; a.ld_vec = g->ld_vec; a.relu_ld = g->relu_ld;
+    a.f = f; a.fp = fp; a.alpha = g->leaky_alpha;
+    hipStream_t st = ctx->streams[stream];
+    const unsigned kflags = (flags & HNH_FUSED_OUT_OVERWRITE) | (finish ? kInternalEpilogue : 0u);
+    if (b->rowptr == nullptr) {  // a block without nonzeros
+        if (b->nnz > 0) return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": null rowptr");
+        if (PASS == 0) {
+            if (!kflags) return HNH_OK;
+            hipLaunchKernelGGL(attn_add_empty_rows_kernel, dim3((unsigned)((b->rows * 64 + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, b->rows, a, kflags);
+            return hnh::check_hip(ctx, hipGetLastError(), "attn_add_empty_rows_kernel launch");
+        }
+        if (!(flags & HNH_FUSED_OUT_OVERWRITE)) return HNH_OK;
+        if (PASS == 2) {
+            hipLaunchKernelGGL(attn_grad_zero_rows_kernel, dim3(ew_grid(b->rows * f)), dim3(kBlock), 0, st, g->Out, g->ld_out, b->rows, f);
+            if (int rc = hnh::check_hip(ctx, hipGetLastError(), "attn_grad_zero_rows_kernel launch")) return rc;
+        }
+        hipLaunchKernelGGL(attn_grad_zero_rows_kernel, dim3(ew_grid(b->rows)), dim3(kBlock), 0, st, g->vec, g->ld_vec, b->rows, 1);
+        return hnh::check_hip(ctx, hipGetLastError(), "attn_grad_zero_rows_kernel launch");
+    }
+    if (!b->col_idx || !g->M || !g->Y) return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": null pointer");
+    if (g->ld_m < fp + 2) return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": ld_m is narrower than the scored width");
+    // the gathered operand (hnh_attn_additive.h): an even pitch and a 16-byte aligned base, whatever f is
+    const int gather_w = PASS == 2 ? HNH_ATTN_ADD_PACKED_WIDTH(f) : HNH_ATTN_ADD_SCORED_WIDTH(f);
+    if (g->ld_y < gather_w || g->ld_y % 2 != 0 || !aligned16(g->Y))
+        return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": the gathered operand needs an even pitch of at least " + std::to_string(gather_w) +
+                                                   " and a 16-byte aligned base");
+    if (PASS != 1 && ((const double*)g->Out == g->M || (const double*)g->Out == g->Y))
+        return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": Out aliases an input");
+    bool w2 = f % 2 == 0;
+    if (PASS == 0) w2 = w2 && aligned16(g->Out) && g->ld_out % 2 == 0 && aligned16(g->relu_dst) && g->relu_ld % 2 == 0;
+    if (PASS == 1) {
+        if (!g->dZ || g->ld_dz < f || !g->lse || !g->delta) return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": bad dZ, lse or delta");
+        w2 = w2 && aligned16(g->dZ) && g->ld_dz % 2 == 0;
+    }
+    if (PASS == 2) w2 = w2 && aligned16(g->M) && g->ld_m % 2 == 0 && aligned16(g->Out) && g->ld_out % 2 == 0;
+
+    const int64_t rows = b->rows, nnz = b->nnz;
+    const int32_t* rowptr = b->rowptr;
+    const int32_t* colidx = b->col_idx;
+    if (int rc = adopt_plan(ctx, b->plan, rows, nnz, rowptr, colidx)) return rc;
+    LongCtl lc;
+    if (PASS != 0) {  // (the forward pass walks hub rows whole: a row's scores are combined in row order, never by segments)
+        const int64_t pitch = PASS == 2 ? fp + 2 : 2;
+        if (int rc = prepare_long(ctx, st, stream, rows, rowptr, nnz, b->max_row_nnz, pitch, &lc, win == nullptr || win->last != 0, b->plan)) return rc;
+        if (lc.enabled && lc.items != nullptr) {  // this pass has hub rows: every segment needs its partial result (no atomics here)
+            if (lc.partials == nullptr)
+                if (int rc = partial_scratch(ctx, st, stream, (size_t)lc.capacity, pitch, &lc)) return rc;
+            if (lc.partials == nullptr || lc.partial_items < lc.capacity)
+                return hnh::fail(ctx, HNH_ERR_NOMEM, std::string(who) + ": the hub rows' partial rows exceed HNH_HUB_SCRATCH_MB");
+        }
+    }
+    if (!lc.enabled || ctx->row_waves_cap > 0) {
+        Shape s = pick_shape(f, w2);
+        lc.lds_pad = row_occupancy_pad(ctx, s, rows, nnz, b->max_row_nnz);
+    }
+    if (win != nullptr) {
+        const int32_t* beg_ptr = win->beg ? win->beg : rowptr;
+        const int32_t* end_ptr = win->end ? win->end : rowptr + 1;
+        return attn_add_launch_shape<PASS>(ctx, st, lc, w2, rows, rowptr, beg_ptr, end_ptr, colidx, a, kflags, win->last != 0);
+    }
+    const int panels = (!lc.enabled || ctx->panels_with_hubs) ? panel_count(ctx, b->cols, gather_w) : 1;
+    if (panels > 1) {
+        int32_t* split = nullptr;
+        if (int rc = panel_split_rows(ctx, st, stream, b->plan, rows, b->cols, rowptr, colidx, panels, &split)) return rc;
+        for (int q = 0; q < panels; q++) {
+            const int32_t* beg_ptr = (q == 0) ? rowptr : split + (size_t)(q - 1) * rows;
+            const int32_t* end_ptr = (q == panels - 1) ? rowptr + 1 : split + (size_t)q * rows;
+            unsigned fq = kflags;
+            if (q > 0) fq &= ~HNH_FUSED_OUT_OVERWRITE;       // later panels continue the rows the first one started
+            if (q < panels - 1) fq &= ~kInternalEpilogue;    // the last panel finishes them
+            if (int rc = attn_add_launch_shape<PASS>(ctx, st, lc, w2, rows, rowptr, beg_ptr, end_ptr, colidx, a, fq, q == panels - 1)) return rc;
+        }
+        return HNH_OK;
+    }
+    return attn_add_launch_shape<PASS>(ctx, st, lc, w2, rows, rowptr, rowptr, rowptr + 1, colidx, a, kflags, true);
+}
+
+}  // namespace
+
+extern "C" {
+
+int hnh_attn_add_fwd_csr_p(hnh_ctx* ctx, const hnh_csr_block* b, const hnh_attn_add* args, unsigned flags, const hnh_csr_window* window,
+                           int stream) {
+    return attn_add_dispatch<0>(ctx, b, args, flags, window, stream, "hnh_attn_add_fwd_csr_p");
+}
+
+int hnh_attn_add_row_csr_p(hnh_ctx* ctx, const hnh_csr_block* b, const hnh_attn_add* args, unsigned flags, const hnh_csr_window* window,
+                           int stream) {
+    return attn_add_dispatch<1>(ctx, b, args, flags, window, stream, "hnh_attn_add_row_csr_p");
+}
+
+int hnh_attn_add_col_csr_p(hnh_ctx* ctx, const hnh_csr_block* b, const hnh_attn_add* args, unsigned flags, const hnh_csr_window* window,
+                           int stream) {
+    return attn_add_dispatch<2>(ctx, b, args, flags, window, stream, "hnh_attn_add_col_csr_p");
+}
+
+int hnh_attn_add_scores_f64(hnh_ctx* ctx, double* M, int64_t ld_m, const double* A, int64_t ld_a, const double* a1, const double* a2,
+                            int64_t rows, int f, int stream) {
+    HNH_ENTER(ctx, stream);
+    if (int rc = check_common(ctx, rows, f, "hnh_attn_add_scores_f64")) return rc;
+    const int fp = f + (f & 1);
+    if (ld_m < fp + 2 || ld_m % 2 != 0 || ld_a < f) return hnh::fail(ctx, HNH_ERR_INVALID, "hnh_attn_add_scores_f64: bad pitch");
+    if (rows == 0) return HNH_OK;
+    if (!M || !A || !a1 || !a2 || M == A) return hnh::fail(ctx, HNH_ERR_INVALID, "hnh_attn_add_scores_f64: null or aliased pointer");
+    hipLaunchKernelGGL(attn_add_scores_kernel, dim3((unsigned)((rows * 64 + kBlock - 1) / kBlock)), dim3(kBlock), 0, ctx->streams[stream], M, ld_m, A, ld_a,
+                       a1, a2, rows, f, fp);
+    return hnh::check_hip(ctx, hipGetLastError(), "attn_add_scores_kernel launch");
+}
+
+int hnh_attn_add_pack_f64(hnh_ctx* ctx, double* Q, int64_t ld_q, const double* dZ, int64_t ld_dz, const double* M, int64_t ld_m,
+                          const double* lse, const double* delta, int64_t rows, int f, int stream) {
+    HNH_ENTER(ctx, stream);
+    if (int rc = check_common(ctx, rows, f, "hnh_attn_add_pack_f64")) return rc;
+    const int fp = f + (f & 1);
+    if (ld_q < fp + 4 || ld_q % 2 != 0 || ld_dz < f || ld_m < fp + 2) return hnh::fail(ctx, HNH_ERR_INVALID, "hnh_attn_add_pack_f64: bad pitch");
+    if (rows == 0) return HNH_OK;
+    if (!Q || !dZ || !M || !lse || !delta) return hnh::fail(ctx, HNH_ERR_INVALID, "hnh_attn_add_pack_f64: null pointer");
+    hipLaunchKernelGGL(attn_add_pack_kernel, dim3(ew_grid(rows * (fp + 4))), dim3(kBlock), 0, ctx->streams[stream], Q, ld_q, dZ, ld_dz, M, ld_m, lse, delta,
+                       rows, f, fp);
+    return hnh::check_hip(ctx, hipGetLastError(), "attn_add_pack_kernel launch");
+}
+
+int hnh_attn_add_update_f64(hnh_ctx* ctx, double* dA, int64_t ld_da, int64_t col0, const double* dAgg, int64_t ld_g, const double* D,
+                            int64_t ld_d, const double* a1, const double* a2, int64_t rows, int f, int stream) {
+    HNH_ENTER(ctx, stream);
+    if (int rc = check_common(ctx, rows, f, "hnh_attn_add_update_f64")) return rc;
+    if (col0 < 0 || ld_da < col0 + f || ld_g < f || ld_d < 2) return hnh::fail(ctx, HNH_ERR_INVALID, "hnh_attn_add_update_f64: bad pitch");
+    if (rows == 0) return HNH_OK;
+    if (!dA || !dAgg || !D || !a1 || !a2) return hnh::fail(ctx, HNH_ERR_INVALID, "hnh_attn_add_update_f64: null pointer");
+    hipLaunchKernelGGL(attn_add_update_kernel, dim3(ew_grid(rows * f)), dim3(kBlock), 0, ctx->streams[stream], dA, ld_da, col0, dAgg, ld_g, D, ld_d, a1, a2,
+                       rows, f);
+    return hnh::check_hip(ctx, hipGetLastError(), "attn_add_update_kernel launch");
+}
+
+}  // extern "C"

@@ -29,6 +29,7 @@
 #include "hnh_ctx.hpp"
 #include "hnh_attention.h"
 #include "hnh_attn_grad.h"
+#include "hnh_attn_additive.h"
 
 namespace {
 
@@ -2773,3 +2774,6 @@ int hnh_rowdot_cols_f64(hnh_ctx* ctx, double* out, const double* dZ, int64_t ld_
 
 // ---------------------------------------------------------------- fused attention backward (include/hnh_attn_grad.h)
 #include "hnh_attn_grad_kernels.hpp"
+
+// ---------------------------------------------------------------- additive attention scores (include/hnh_attn_additive.h)
+#include "hnh_attn_additive_kernels.hpp"

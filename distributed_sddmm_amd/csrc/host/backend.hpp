@@ -7,6 +7,7 @@
 #include <cstdint>
 #include <string>
 #include "hnh_attention.h"
+#include "hnh_attn_additive.h"
 #include "hnh_attn_grad.h"
 #include "hnh_grad.h"
 #include "hnh_kernels.h"
@@ -49,6 +50,9 @@ struct Backend {
     HNH_FN(hnh_attn_softmax_csr_p) HNH_FN(hnh_softmax_gate_f64) HNH_FN(hnh_rowdot_cols_f64)
     // OPTIONAL group (include/hnh_attn_grad.h), bound the same way: only the GAT's fused backward mode needs it
     HNH_FN(hnh_attn_grad_row_csr_p) HNH_FN(hnh_attn_grad_col_csr_p) HNH_FN(hnh_attn_grad_pack_f64)
+    // OPTIONAL group (include/hnh_attn_additive.h), bound the same way: only the GAT's additive score needs it
+    HNH_FN(hnh_attn_add_fwd_csr_p) HNH_FN(hnh_attn_add_row_csr_p) HNH_FN(hnh_attn_add_col_csr_p)
+    HNH_FN(hnh_attn_add_scores_f64) HNH_FN(hnh_attn_add_pack_f64) HNH_FN(hnh_attn_add_update_f64)
 #ifdef HNH_MEASUREMENT_AIDS
     HNH_FN(hnh_stream_delay_us) HNH_FN(hnh_stream_paced_copy) HNH_FN(hnh_stream_pace_begin) HNH_FN(hnh_stream_pace_end)
 #endif

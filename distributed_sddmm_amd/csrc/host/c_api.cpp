@@ -774,6 +774,31 @@ int hnh_gat_set_attention(hnh_gat* g, int mode) {
 int hnh_gat_set_backward(hnh_gat* g, int mode) {
     return guarded(g->w, [&] { g->g->set_backward(mode); });
 }
+int hnh_gat_set_score(hnh_gat* g, int mode) {
+    return guarded(g->w, [&] { g->g->set_score(mode); });
+}
+int hnh_gat_set_attn_vectors(hnh_gat* g, int layer, int head, const double* a1_host, const double* a2_host) {
+    return guarded(g->w, [&] {
+        if (layer < 0 || layer >= (int)g->g->layers.size()) throw hnh::Error("Error, GAT layer index out of range!");
+        if (!a1_host || !a2_host) throw hnh::Error("Error, hnh_gat_set_attn_vectors: null pointer!");
+        g->g->set_attn_vectors(layer, head, a1_host, a2_host);
+    });
+}
+int hnh_gat_get_attn_grads(hnh_gat* g, int layer, int head, double* da1_host, double* da2_host) {
+    return guarded(g->w, [&] {
+        GAT& gat = *g->g;
+        const GATLayer& l = gat.layers.at(layer);
+        if (head < 0 || head >= l.num_heads) throw hnh::Error("Error, GAT head index out of range!");
+        if (gat.attn_grads.size() != gat.layers.size() || gat.attn_grads[(size_t)layer].size() == 0)
+            throw hnh::Error("Error, no GAT attention-vector gradient yet: call hnh_gat_backward with score additive first!");
+        const std::vector<double> all = gat.attn_grads[(size_t)layer].to_host();  // (heads * f) x 2
+        const int64_t f = l.features_per_head;
+        for (int64_t c = 0; c < f; c++) {
+            da1_host[c] = all[(size_t)(((int64_t)head * f + c) * 2)];
+            da2_host[c] = all[(size_t)(((int64_t)head * f + c) * 2 + 1)];
+        }
+    });
+}
 int hnh_gat_backward(hnh_gat* g, hnh_dense* grad_out) {
     return guarded(g->w, [&] { g->g->backwardPass(grad_out->m); });
 }

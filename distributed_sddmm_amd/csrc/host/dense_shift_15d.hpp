@@ -337,6 +337,47 @@ public:
         return true;
     }
 
+    // One pass of the additive-score attention (include/hnh_attn_additive.h): pass 0 = the forward pass over S (`moving` = the scored
+    // operand M), 1 = the backward row pass over S (M again), 2 = the backward column pass over S^T (`moving` = the packed operand Q).
+    // As for attnGrad_pass the schedule's R must be the MOVING operand's width; everything else is addressed through args.  The forward
+    // pass makes its first call (the state reset) and its closing call (the finish) also for an absent block, like fusedSoftmax_out.
+    // Returns false, having done nothing, where a rank's own launches do not see all of a row's nonzeros (only approach 2 with c = 1).
+    // Not a virtual of Distributed_Sparse, for fusedSoftmax_out's reason.
+    bool attnAdditive_pass(int pass, DenseMatrix& moving, const hnh_attn_add& args, int64_t out_rows, bool overwrite) {
+        if (fusionApproach != 2 || c != 1) return false;
+        if (pass < 0 || pass > 2) hnh::fatal("Error, attnAdditive_pass: unknown pass!");
+        if (moving.cols() != R) hnh::fatal("Error, attnAdditive_pass: the schedule's R must be the moving operand's width!");
+        SpmatLocal* choice = pass == 2 ? ST.get() : S.get();
+        const int n = p / c;
+        bool fresh = overwrite;
+        auto on = [&](int block_id, DenseMatrix& Y, int window, int window_end, bool closing) {
+            CSRLocal* blk = choice->csr_blocks[block_id];
+            const bool finish = pass == 0 && closing;
+            if (blk == nullptr && !fresh && !finish) return;  // nothing to add
+            if (blk != nullptr) {
+                blk->window = window;
+                blk->window_end = window_end;
+            }
+            hnh_attn_add a = args;
+            a.Y = Y.data();
+            a.ld_y = Y.cols();
+            const bool done = kernel->attn_additive_local(*choice, block_id, a, pass, fresh ? HNH_FUSED_OUT_OVERWRITE : 0u, out_rows, finish);
+            if (blk != nullptr) blk->window = blk->window_end = -1;
+            if (!done) throw hnh::Error("Error, the kernel implementation has no additive attention pass (KernelImplementation::attn_additive_local)!");
+            fresh = false;
+        };
+        if (merged) {
+            walk_merged(choice, &moving, [&](int block_id, DenseMatrix& Y, int window, int window_end, bool is_last) { on(block_id, Y, window, window_end, is_last); });
+        } else {
+            ring_readonly(&moving, n, [&](int i, DenseMatrix& cur) {
+                auto t = phase_begin("Computation Time");
+                on(block_at(i), cur, -1, -1, i == n - 1);
+                phase_end(t);
+            });
+        }
+        return true;
+    }
+
 private:
     // ---- merged layout helpers
     // visiting step of global block column b on this rank (block_at(k) == b), or -1 when the rank never visits it

@@ -40,6 +40,17 @@
 // straight into the head's column block of dA_all: no value vectors, no gate launches, no width-1 SDDMMs, no sum3.  15d_fusion2 with
 // c = 1 only (the condition of the fused forward: a rank's own launches see all of a row's nonzeros and no output row is summed
 // across ranks), heads of at most HNH_ATTN_GRAD_MAX_F features.  Switching the mode needs no new forward pass.
+//
+// Score (an addition): HNH_GAT_SCORE_DOT (the default) is everything above, e_ij = LeakyReLU(<A_i, A_j>).  HNH_GAT_SCORE_ADDITIVE scores an
+// edge with the layer's two learned vectors (Velickovic et al.; head h uses the slices [h f, (h + 1) f) of GATLayer::a1 / a2):
+//     s_i = <A_i, a1_h>,  t_j = <A_j, a2_h>,  z_ij = s_i + t_j,  e_ij = LeakyReLU(z_ij),  then the neighbourhood softmax as above.
+// Forward: the product stage of a head also builds the scored operand M = [A (0) | s t] (one read of A), and the attention pass gathers
+// ONE row of M per nonzero (include/hnh_attn_additive.h).  Backward, with dZ and delta as above:
+//     dz_ij = a_ij (<dZ_i, A_j> - delta_i) LeakyReLU'(z_ij),  ds_i = sum_j dz_ij  (row pass over S),
+//     dt_j = sum_i dz_ij,  dAgg_j = sum_i a_ij dZ_i  (column pass over S^T, gathering the packed Q_i = [dZ_i (0) | s_i lse_i delta_i 0]),
+//     dA = dAgg + ds a1_h^T + dt a2_h^T,  da1_h = A^T ds,  da2_h = A^T dt  (attn_grads, summed over the world like dW).
+// Supported where the softmax is (15d_fusion2 with c = 1, attention softmax) with heads of at most HNH_ATTN_ADD_MAX_F features; everything
+// else raises before anything is launched.  With score ADDITIVE there is ONE backward implementation: set_backward is not consulted.
 #pragma once
 #include "dense_shift_15d.hpp"
 #include "distributed_sparse.hpp"
@@ -101,7 +112,37 @@ public:
         attention_ = mode;
     }
 
+    // HNH_GAT_SCORE_DOT | HNH_GAT_SCORE_ADDITIVE (include/hnh_dist.h); a change invalidates the stored forward pass
+    int score() const { return score_; }
+    void set_score(int mode) {
+        if (mode != HNH_GAT_SCORE_DOT && mode != HNH_GAT_SCORE_ADDITIVE)
+            throw hnh::Error("Error, unknown GAT score " + std::to_string(mode) + " (dot = 0, additive = 1)!");
+        if (mode != score_) invalidate_forward();
+        score_ = mode;
+    }
+
+    // The additive score's vectors of a layer (GATLayer::a1 / a2: num_heads * features_per_head entries each, zero until set; head h
+    // uses the slice [h f, (h + 1) f)), allocated on first use.
+    void ensure_attn_vectors(int i) {
+        GATLayer& L = layers.at((size_t)i);
+        const int64_t n = (int64_t)L.num_heads * L.features_per_head;
+        if (L.a1.size() != n) L.a1 = VectorXd::Constant(n, 0.0);
+        if (L.a2.size() != n) L.a2 = VectorXd::Constant(n, 0.0);
+    }
+    void set_attn_vectors(int i, int h, const double* a1_host, const double* a2_host) {
+        ensure_attn_vectors(i);
+        GATLayer& L = layers.at((size_t)i);
+        if (h < 0 || h >= L.num_heads) throw hnh::Error("Error, GAT head index out of range!");
+        const int f = L.features_per_head;
+        hnh::World* w = d_ops->world;
+        w->copy(L.a1.data() + (int64_t)h * f, a1_host, (size_t)f * sizeof(double), HNH_COPY_H2D, HNH_STREAM_COMPUTE);
+        w->copy(L.a2.data() + (int64_t)h * f, a2_host, (size_t)f * sizeof(double), HNH_COPY_H2D, HNH_STREAM_COMPUTE);
+        w->sync(HNH_STREAM_COMPUTE);
+        invalidate_forward();
+    }
+
     // HNH_GAT_BACKWARD_UNFUSED | HNH_GAT_BACKWARD_FUSED (include/hnh_dist.h); the stored forward pass serves either
+    // (not consulted with score ADDITIVE, which has one backward implementation)
     int backward() const { return backward_; }
     void set_backward(int mode) {
         if (mode != HNH_GAT_BACKWARD_UNFUSED && mode != HNH_GAT_BACKWARD_FUSED)
@@ -113,6 +154,12 @@ public:
     void computeSelfAttentionHead(int i, int j) {
         DenseMatrix A;
         head_product(i, j, A, HNH_STREAM_COMPUTE);
+        if (score_ == HNH_GAT_SCORE_ADDITIVE) {
+            shape_scored(i, scored[0]);
+            head_scores(i, j, A, scored[0], HNH_STREAM_COMPUTE);
+            head_attention(i, j, scored[0]);
+            return;
+        }
         head_attention(i, j, A);
     }
 
@@ -121,7 +168,12 @@ public:
     // between two product buffers; the layers' outputs are the reference's, bit for bit (same kernels, same operands).
     // HNH_GAT_SERIAL=1: the reference's order on one stream (A/B measurements).
     void forwardPass() {
-        if (attention_ == HNH_GAT_ATTENTION_SOFTMAX) check_softmax_supported();
+        const bool additive = score_ == HNH_GAT_SCORE_ADDITIVE;
+        if (attention_ == HNH_GAT_ATTENTION_SOFTMAX && !additive) check_softmax_supported();
+        if (additive) {
+            check_additive_supported();
+            for (size_t i = 0; i < layers.size(); i++) ensure_attn_vectors((int)i);  // (on the compute stream, before the marks below)
+        }
         if (std::getenv("HNH_GAT_SERIAL") != nullptr) {
             for (size_t i = 0; i < layers.size(); i++)
                 for (int j = 0; j < layers[i].num_heads; j++) computeSelfAttentionHead((int)i, j);
@@ -134,11 +186,15 @@ public:
             const int H = layers[i].num_heads;
             // (allocated before the mark below: the allocator orders a recycled block behind its last use on the compute and
             // communication streams, and the auxiliary stream inherits that through the mark)
-            for (int b = 0; b < (H > 1 ? 2 : 1); b++) shape_product((int)i, product[b]);
+            for (int b = 0; b < (H > 1 ? 2 : 1); b++) {
+                shape_product((int)i, product[b]);
+                if (additive) shape_scored((int)i, scored[b]);
+            }
             // the layer's input is complete, and both product buffers are free, once the compute stream gets here
             w->event_record(ev_input, HNH_STREAM_COMPUTE);
             w->event_wait(ev_input, HNH_STREAM_AUX);
             head_product((int)i, 0, product[0], HNH_STREAM_AUX);
+            if (additive) head_scores((int)i, 0, product[0], scored[0], HNH_STREAM_AUX);  // (the score kernel belongs to the product stage)
             w->event_record(ev_gemm[0], HNH_STREAM_AUX);
             for (int j = 0; j < H; j++) {
                 w->event_wait(ev_gemm[j % 2], HNH_STREAM_COMPUTE);
@@ -146,9 +202,10 @@ public:
                     // product[(j + 1) % 2] was last read by head j - 1, which the compute stream has been given already
                     if (j >= 1) w->event_wait(ev_head[(j - 1) % 2], HNH_STREAM_AUX);
                     head_product((int)i, j + 1, product[(j + 1) % 2], HNH_STREAM_AUX);
+                    if (additive) head_scores((int)i, j + 1, product[(j + 1) % 2], scored[(j + 1) % 2], HNH_STREAM_AUX);
                     w->event_record(ev_gemm[(j + 1) % 2], HNH_STREAM_AUX);
                 }
-                head_attention((int)i, j, product[j % 2]);
+                head_attention((int)i, j, additive ? scored[j % 2] : product[j % 2]);
                 w->event_record(ev_head[j % 2], HNH_STREAM_COMPUTE);
             }
         }
@@ -167,7 +224,7 @@ public:
         if (!forward_valid_) throw hnh::Error("Error, GAT backwardPass needs a forwardPass first (and a new one after set_weight / set_input)!");
         const DenseMatrix& last = buffers.back();
         if (grad_out.rows() != last.rows() || grad_out.cols() != last.cols()) throw hnh::Error("Error, GAT output gradient has the wrong shape!");
-        const bool fused = backward_ == HNH_GAT_BACKWARD_FUSED;  // (no per-nonzero vectors in that mode)
+        const bool fused = backward_ == HNH_GAT_BACKWARD_FUSED || score_ == HNH_GAT_SCORE_ADDITIVE;  // (no per-nonzero vectors in those modes)
         if (!fused && ones_S_.size() == 0) {
             ones_S_ = d_ops->like_S_values(1.0);
             ones_ST_ = d_ops->like_ST_values(1.0);
@@ -187,6 +244,7 @@ public:
             weight_grads.assign((size_t)L, DenseMatrix());
             input_grads.assign((size_t)L, DenseMatrix());
         }
+        if (score_ == HNH_GAT_SCORE_ADDITIVE && (int)attn_grads.size() != L) attn_grads.assign((size_t)L, DenseMatrix());
         const DenseMatrix* G = &grad_out;
         for (int i = L - 1; i >= 0; i--) {
             backward_layer(i, *G);
@@ -195,12 +253,16 @@ public:
     }
 
     std::vector<DenseMatrix> weight_grads, input_grads;
+    // score ADDITIVE: attn_grads[i] is (num_heads * features_per_head) x 2 of layer i, row h f + c = (da1_h[c], da2_h[c]), the same on every rank
+    std::vector<DenseMatrix> attn_grads;
 
 private:
     hnh::World* world_ = nullptr;
     bool forward_valid_ = false;
     int attention_ = HNH_GAT_ATTENTION_NONE;
     int backward_ = HNH_GAT_BACKWARD_UNFUSED;
+    int score_ = HNH_GAT_SCORE_DOT;
+    DenseMatrix scored[2];  // score ADDITIVE: [A (0) | s t] of the head in flight and of the next one (include/hnh_attn_additive.h)
     // softmax attention: the rows' running max / sum (reused by every head, which run one after the other on the compute stream), the
     // log-sum-exp of every (layer, head), and for the backward pass a column of ones and the broadcasts of lse and delta onto the nonzeros
     DenseMatrix row_max_, row_sum_, ones_col_;
@@ -217,7 +279,8 @@ private:
 
     // Throws hnh::Error (never a wrong number) where the backward pass is not defined or its kernels are missing.
     void check_backward_supported() {
-        if (backward_ == HNH_GAT_BACKWARD_FUSED) check_fused_backward_supported();
+        if (score_ == HNH_GAT_SCORE_ADDITIVE) check_additive_supported();
+        else if (backward_ == HNH_GAT_BACKWARD_FUSED) check_fused_backward_supported();
         auto* ds = dynamic_cast<Sparse15D_Dense_Shift*>(d_ops);
         if (ds == nullptr || ds->r_split)
             throw hnh::Error("Error, GAT backwardPass supports the 1.5D dense-shift schedules only (15d_fusion1, 15d_fusion2 with c = 1), not " +
@@ -266,6 +329,31 @@ private:
                                  std::to_string(L.features_per_head) + " (include/hnh_attn_grad.h)");
     }
 
+    // The additive score's own conditions, checked before anything is launched: the attention mode, the schedule (the softmax's: a
+    // rank's own launches see all of a row's nonzeros), the head widths, then its kernel group.
+    void check_additive_supported() {
+        if (attention_ != HNH_GAT_ATTENTION_SOFTMAX)
+            throw hnh::Error("Error, GAT score additive supports attention mode softmax only, not attention mode none (include/hnh_attn_additive.h)");
+        auto* ds = dynamic_cast<Sparse15D_Dense_Shift*>(d_ops);
+        if (ds == nullptr || ds->r_split || ds->fusionApproach != 2 || ds->c != 1)
+            throw hnh::Error("Error, GAT score additive supports 15d_fusion2 with c = 1 only, not " +
+                             (ds ? "15d_fusion" + std::to_string(ds->fusionApproach) + " (" + d_ops->algorithm_name + ")" : d_ops->algorithm_name) +
+                             " with c = " + std::to_string(d_ops->c) + ": its rows are summed across ranks");
+        for (const GATLayer& L : layers)
+            if (L.features_per_head > HNH_ATTN_ADD_MAX_F)
+                throw hnh::Error("Error, GAT score additive supports heads of at most " + std::to_string(HNH_ATTN_ADD_MAX_F) + " features, not " +
+                                 std::to_string(L.features_per_head) + " (include/hnh_attn_additive.h)");
+        const hnh::Backend* be = d_ops->world->be;
+        const std::pair<const void*, const char*> need[] = {
+            {(const void*)be->hnh_attn_add_fwd_csr_p, "hnh_attn_add_fwd_csr_p"},   {(const void*)be->hnh_attn_add_row_csr_p, "hnh_attn_add_row_csr_p"},
+            {(const void*)be->hnh_attn_add_col_csr_p, "hnh_attn_add_col_csr_p"},   {(const void*)be->hnh_attn_add_scores_f64, "hnh_attn_add_scores_f64"},
+            {(const void*)be->hnh_attn_add_pack_f64, "hnh_attn_add_pack_f64"},     {(const void*)be->hnh_attn_add_update_f64, "hnh_attn_add_update_f64"}};
+        for (const auto& n : need)
+            if (n.first == nullptr)
+                throw hnh::Error(std::string("Error, GAT score additive needs the kernel ") + n.second + ", which the kernel library " + be->path +
+                                 " does not export (include/hnh_attn_additive.h)");
+    }
+
     // Throws hnh::Error (never a wrong number) where softmax attention is not defined or its kernel is missing: a row's softmax needs
     // all of the row's nonzeros summed by this rank's own launches, which only 15d_fusion2 with c = 1 does (15d_fusion1 reduce-scatters
     // over the mesh; c > 1, the 2.5D schedules and the sparse shift reduce across ranks too).
@@ -302,6 +390,10 @@ private:
             throw hnh::Error("Error, GAT backwardPass: layer buffers do not have the layer's shape!");
         DenseMatrix& dA_all = scratch(0, rows, hf);
         DenseMatrix& Wt = scratch(1, hf, k);
+        if (score_ == HNH_GAT_SCORE_ADDITIVE) {
+            DenseMatrix& dav = attn_grads[(size_t)i];
+            if (dav.rows() != hf || dav.cols() != 2) dav = DenseMatrix(hf, 2);
+        }
         d_ops->setRValue(f);
         for (int h = 0; h < H; h++) {
             DenseMatrix& Wh = layers[(size_t)i].wMats[(size_t)h];
@@ -311,6 +403,11 @@ private:
             w->check(be->hnh_relu_grad_cols_f64(w->ctx, dZ.data(), f, G.data(), hf, out.data(), hf, (int64_t)h * f, rows, f, S0),
                      "hnh_relu_grad_cols_f64");
             const bool softmax = attention_ == HNH_GAT_ATTENTION_SOFTMAX;
+            if (score_ == HNH_GAT_SCORE_ADDITIVE) {
+                backward_head_additive(i, h, A, dZ, dA_all);
+                w->check(be->hnh_transpose_into_f64(w->ctx, Wt.data(), k, (int64_t)h * f, Wh.data(), k, f, S0), "hnh_transpose_into_f64");
+                continue;
+            }
             if (backward_ == HNH_GAT_BACKWARD_FUSED) {
                 // two passes straight into the head's column block of dA_all (include/hnh_attn_grad.h)
                 auto* ds = dynamic_cast<Sparse15D_Dense_Shift*>(d_ops);
@@ -403,11 +500,81 @@ private:
                                      need, S0),
                  "hnh_gemm_tn_f64");
         w->allreduce_f64(w->world_comm(), dW.data(), (size_t)dW.size(), S0);
+        if (score_ == HNH_GAT_SCORE_ADDITIVE) {
+            DenseMatrix& dav = attn_grads[(size_t)i];
+            w->allreduce_f64(w->world_comm(), dav.data(), (size_t)dav.size(), S0);
+        }
         // dX = dA_all [W_1^T; ..; W_H^T]
         DenseMatrix& dX = input_grads[(size_t)i];
         if (dX.rows() != rows || dX.cols() != k) dX = DenseMatrix(rows, k);
         w->check(be->hnh_gemm_f64(w->ctx, rows, k, hf, dA_all.data(), Wt.data(), dX.data(), S0), "hnh_gemm_f64");
     }
+    // One head of the backward pass with score ADDITIVE (include/hnh_attn_additive.h): A = X W_h and dZ are the caller's; the head's
+    // column block of dA_all and its rows of attn_grads[i] (this rank's part) are the results.
+    void backward_head_additive(int i, int h, DenseMatrix& A, DenseMatrix& dZ, DenseMatrix& dA_all) {
+        hnh::World* w = d_ops->world;
+        const hnh::Backend* be = w->be;
+        const int S0 = HNH_STREAM_COMPUTE;
+        GATLayer& L = layers[(size_t)i];
+        const int H = L.num_heads, f = L.features_per_head;
+        const int64_t rows = A.rows(), hf = (int64_t)H * f;
+        const DenseMatrix& out = buffers[(size_t)i + 1];
+        auto* ds = dynamic_cast<Sparse15D_Dense_Shift*>(d_ops);
+        ensure_attn_vectors(i);
+        const double* a1 = L.a1.data() + (int64_t)h * f;
+        const double* a2 = L.a2.data() + (int64_t)h * f;
+        const int mw = HNH_ATTN_ADD_SCORED_WIDTH(f), qw = HNH_ATTN_ADD_PACKED_WIDTH(f);
+        DenseMatrix& M = scratch(10, rows, mw);
+        DenseMatrix& Q = scratch(11, rows, qw);
+        DenseMatrix& D = scratch(12, rows, 2);      // [ds dt]
+        DenseMatrix& dAgg = scratch(13, rows, f);
+        DenseMatrix& dl = scratch(8, rows, 1);
+        double* lse = lse_.at((size_t)i).at((size_t)h).data();
+        w->check(be->hnh_attn_add_scores_f64(w->ctx, M.data(), mw, A.data(), f, a1, a2, rows, f, S0), "hnh_attn_add_scores_f64");
+        w->check(be->hnh_rowdot_cols_f64(w->ctx, dl.data(), dZ.data(), f, out.data(), hf, (int64_t)h * f, rows, f, S0), "hnh_rowdot_cols_f64");
+        w->check(be->hnh_attn_add_pack_f64(w->ctx, Q.data(), qw, dZ.data(), f, M.data(), mw, lse, dl.data(), rows, f, S0), "hnh_attn_add_pack_f64");
+        hnh_attn_add g = {};
+        g.M = M.data();
+        g.ld_m = mw;
+        g.dZ = dZ.data();
+        g.ld_dz = f;
+        g.lse = lse;
+        g.delta = dl.data();
+        g.Out = dAgg.data();
+        g.ld_out = f;
+        g.ld_vec = 2;
+        g.f = f;
+        g.leaky_alpha = leaky_relu_alpha;
+        // the moving operand is M, then Q: the schedule runs at ITS width for each pass
+        bool ok = ds != nullptr;
+        try {
+            if (ok) {
+                d_ops->setRValue(mw);
+                g.vec = D.data();
+                ok = ds->attnAdditive_pass(1, M, g, rows, true);  // row side: ds
+            }
+            if (ok) {
+                d_ops->setRValue(qw);
+                g.vec = D.data() + 1;
+                ok = ds->attnAdditive_pass(2, Q, g, rows, true);  // column side: dAgg, dt
+            }
+        } catch (...) {
+            d_ops->setRValue(f);
+            throw;
+        }
+        d_ops->setRValue(f);
+        if (!ok) throw hnh::Error("Error, GAT score additive supports 15d_fusion2 with c = 1 only, not " + d_ops->algorithm_name);
+        w->check(be->hnh_attn_add_update_f64(w->ctx, dA_all.data(), hf, (int64_t)h * f, dAgg.data(), f, D.data(), 2, a1, a2, rows, f, S0),
+                 "hnh_attn_add_update_f64");
+        // [da1_h da2_h] = A^T [ds dt] over the local rows (A = the first f columns of M)
+        DenseMatrix& dav = attn_grads[(size_t)i];
+        const int64_t need = be->hnh_gemm_tn_f64_workspace(f, 2, rows);
+        DenseMatrix* work = need > 0 ? &scratch(14, need, 1) : nullptr;
+        w->check(be->hnh_gemm_tn_f64(w->ctx, f, 2, rows, M.data(), mw, D.data(), 2, dav.data() + (int64_t)h * f * 2, 2, work ? work->data() : nullptr,
+                                     need, S0),
+                 "hnh_gemm_tn_f64");
+    }
+
     DenseMatrix product[2];  // X * W_j of the head in flight and of the next one
     void* ev_input = nullptr;
     void* ev_gemm[2] = {nullptr, nullptr};
@@ -416,6 +583,33 @@ private:
     void shape_product(int i, DenseMatrix& A) {
         const int64_t rows = buffers[i].rows(), cols = layers[i].wMats[0].cols();
         if (A.rows() != rows || A.cols() != cols) A = DenseMatrix(rows, cols);
+    }
+
+    // the softmax passes' row state: the running max / sum of `rows` rows (shared by the heads) and the lse vector of (layer i, head j)
+    DenseMatrix& softmax_row_state(int i, int j, int64_t rows) {
+        if (row_max_.rows() != rows) {
+            row_max_ = DenseMatrix(rows, 1);
+            row_sum_ = DenseMatrix(rows, 1);
+        }
+        if (lse_.size() != layers.size()) lse_.assign(layers.size(), std::vector<DenseMatrix>());
+        std::vector<DenseMatrix>& lse = lse_[(size_t)i];
+        if (lse.size() != (size_t)layers[i].num_heads) lse.assign((size_t)layers[i].num_heads, DenseMatrix());
+        if (lse[(size_t)j].rows() != rows) lse[(size_t)j] = DenseMatrix(rows, 1);
+        return lse[(size_t)j];
+    }
+
+    void shape_scored(int i, DenseMatrix& M) {
+        const int64_t rows = buffers[i].rows(), cols = HNH_ATTN_ADD_SCORED_WIDTH(layers[i].features_per_head);
+        if (M.rows() != rows || M.cols() != cols) M = DenseMatrix(rows, cols);
+    }
+
+    // M = [A (0) | <A, a1_j> <A, a2_j>] on `stream`, from the head's product A (include/hnh_attn_additive.h)
+    void head_scores(int i, int j, DenseMatrix& A, DenseMatrix& M, int stream) {
+        hnh::World* w = d_ops->world;
+        const int f = layers[i].features_per_head;
+        w->check(w->be->hnh_attn_add_scores_f64(w->ctx, M.data(), M.cols(), A.data(), A.cols(), layers[i].a1.data() + (int64_t)j * f,
+                                                layers[i].a2.data() + (int64_t)j * f, A.rows(), f, stream),
+                 "hnh_attn_add_scores_f64");
     }
 
     // A = buffers[i] * W_j (gat.hpp:88) on `stream`
@@ -434,20 +628,46 @@ private:
         d_ops->setRValue(layers[i].features_per_head);
         DenseMatrix& out = buffers[i + 1];
 
+        if (score_ == HNH_GAT_SCORE_ADDITIVE) {
+            // A is the scored operand M = [A (0) | s t]: one pass that gathers one row of M per nonzero (include/hnh_attn_additive.h), with
+            // the softmax pass's row state; the schedule runs at M's width for it
+            const int f = layers[i].features_per_head;
+            const int64_t rows = A.rows();
+            DenseMatrix& lse = softmax_row_state(i, j, rows);
+            DenseMatrix H(rows, f + (f & 1));
+            hnh_attn_add g = {};
+            g.M = A.data();
+            g.ld_m = A.cols();
+            g.lse = lse.data();
+            g.Out = H.data();
+            g.ld_out = H.cols();
+            g.row_max = row_max_.data();
+            g.row_sum = row_sum_.data();
+            g.relu_dst = out.data() + (int64_t)j * f;
+            g.relu_ld = out.cols();
+            g.f = f;
+            g.leaky_alpha = leaky_relu_alpha;
+            auto* ds = dynamic_cast<Sparse15D_Dense_Shift*>(d_ops);
+            bool ok = ds != nullptr;
+            d_ops->setRValue((int)A.cols());
+            try {
+                ok = ok && ds->attnAdditive_pass(0, A, g, rows, true);
+            } catch (...) {
+                d_ops->setRValue(f);
+                throw;
+            }
+            d_ops->setRValue(f);
+            if (!ok) throw hnh::Error("Error, GAT score additive supports 15d_fusion2 with c = 1 only, not " + d_ops->algorithm_name);
+            return;
+        }
+
         if (attention_ == HNH_GAT_ATTENTION_SOFTMAX) {
             // one fused pass with the online softmax (include/hnh_attention.h): the head's ReLU output leaves the finishing launch
             // straight into its column block, lse into this head's vector; H carries the unnormalised rows between the launches
             const int64_t rows = A.rows();
-            if (row_max_.rows() != rows) {
-                row_max_ = DenseMatrix(rows, 1);
-                row_sum_ = DenseMatrix(rows, 1);
-            }
-            if (lse_.size() != layers.size()) lse_.assign(layers.size(), std::vector<DenseMatrix>());
-            std::vector<DenseMatrix>& lse = lse_[(size_t)i];
-            if (lse.size() != (size_t)layers[i].num_heads) lse.assign((size_t)layers[i].num_heads, DenseMatrix());
-            if (lse[(size_t)j].rows() != rows) lse[(size_t)j] = DenseMatrix(rows, 1);
+            DenseMatrix& lse = softmax_row_state(i, j, rows);
             DenseMatrix H(A.rows(), A.cols());
-            const hnh_attn_state st = {row_max_.data(), row_sum_.data(), lse[(size_t)j].data(), leaky_relu_alpha,
+            const hnh_attn_state st = {row_max_.data(), row_sum_.data(), lse.data(), leaky_relu_alpha,
                                        out.data() + (int64_t)j * A.cols(), (int64_t)out.cols()};
             auto* ds = dynamic_cast<Sparse15D_Dense_Shift*>(d_ops);
             if (ds == nullptr || !ds->fusedSoftmax_out(A, A, Amat, H, st))

@@ -186,6 +186,42 @@ bool StandardKernel::attn_grad_block(SpmatLocal& S, int block, const hnh_attn_gr
     return true;
 }
 
+bool KernelImplementation::attn_additive_local(SpmatLocal& S, int block, const hnh_attn_add& args, int pass, unsigned flags, int64_t rows, bool finish) {
+    StandardKernel* k = dynamic_cast<StandardKernel*>(this);
+    return k != nullptr && k->attn_additive_block(S, block, args, pass, flags, rows, finish);
+}
+
+// The three passes of the additive-score attention (include/hnh_attn_additive.h), next to attn_grad_block: same block and window
+// handling; the forward pass's finish belongs to the pass's last call (win.last when windows are selected).
+bool StandardKernel::attn_additive_block(SpmatLocal& S, int block, const hnh_attn_add& args, int pass, unsigned flags, int64_t rows, bool finish) {
+    hnh::World* w = S.world;
+    auto fn = pass == 0 ? w->be->hnh_attn_add_fwd_csr_p : (pass == 1 ? w->be->hnh_attn_add_row_csr_p : w->be->hnh_attn_add_col_csr_p);
+    const char* name = pass == 0 ? "hnh_attn_add_fwd_csr_p" : (pass == 1 ? "hnh_attn_add_row_csr_p" : "hnh_attn_add_col_csr_p");
+    if (fn == nullptr)
+        throw hnh::Error(std::string("Error, the additive attention score needs the kernel ") + name + ", which the kernel library " + w->be->path +
+                         " does not export (include/hnh_attn_additive.h)");
+    const unsigned f = flags | ((pass == 0 && finish) ? HNH_ATTN_FINISH : 0u);
+    CSRLocal* blk = S.csr_blocks[block];
+    if (blk == nullptr || blk->num_coords == 0) {  // no nonzeros; the reset / zeroing of an overwrite and the forward finish still apply
+        hnh_csr_block none = {};
+        none.rows = rows;
+        none.cols = -1;
+        w->check(fn(w->ctx, &none, &args, f, nullptr, HNH_STREAM_COMPUTE), name);
+        return true;
+    }
+    if (blk->transpose) hnh::fatal("Error, local matrix is transposed, can't perform the additive attention pass");
+    begin(w);
+    hnh_csr_window win;
+    const hnh_csr_block desc = blk->block_args();
+    if (desc.rows != rows) hnh::fatal("Error, the additive attention pass needs an output of the block's rows!");
+    const bool windowed = blk->window_args(&win);
+    if (windowed && pass == 0 && finish && !win.last) hnh::fatal("Error, the additive forward finish belongs to the block's last window!");
+    w->check(fn(w->ctx, &desc, &args, f, windowed ? &win : nullptr, HNH_STREAM_COMPUTE), name);
+    end(w, (profile && !windowed) ? w->be->hnh_panel_count(w->ctx, desc.rows, desc.nnz, desc.cols, pass == 2 ? HNH_ATTN_ADD_PACKED_WIDTH(args.f) : HNH_ATTN_ADD_SCORED_WIDTH(args.f), desc.max_row_nnz)
+                                   : 1);
+    return true;
+}
+
 void StandardKernel::begin(hnh::World* w) {
     if (!profile) return;
     if (evw_ != nullptr && evw_ != w) hnh::fatal("Error, a profiled StandardKernel belongs to one world!");

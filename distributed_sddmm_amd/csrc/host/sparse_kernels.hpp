@@ -72,6 +72,14 @@ public:
     // false, having done nothing, when the implementation has no such pass.  NOT virtual, for softmax_local's reason.
     bool attn_grad_local(SpmatLocal& S, int block, const hnh_attn_grad& args, bool column_side, unsigned flags, int64_t rows);
 
+    // One pass of the additive-score attention (include/hnh_attn_additive.h, the GAT's score "additive") on one block, or the selected
+    // window(s) of it: pass 0 = forward over a block of S (continues the rows' running state; `finish` = the pass's last call, which a
+    // schedule makes also when the block is absent), 1 = backward row pass over a block of S, 2 = backward column pass over a block of
+    // S^T.  `args` carries the operands with their leading dimensions (args.Y = the gathered operand the schedule hands in); rows =
+    // the rows of the output (used when the block is absent).  Returns false, having done nothing, when the implementation has no such
+    // pass.  NOT virtual, for softmax_local's reason.
+    bool attn_additive_local(SpmatLocal& S, int block, const hnh_attn_add& args, int pass, unsigned flags, int64_t rows, bool finish);
+
     // Row windows (CSRLocal::window): a schedule may select one column range of a block before calling the kernels, to
     // work on data that arrives piece by piece.  An implementation that honours CSRLocal::window says so here; for the
     // others (plugins written against the reference's two pure virtuals) the schedule waits for the whole block instead.
@@ -150,6 +158,8 @@ public:
                        bool finish);
     // KernelImplementation::attn_grad_local's pass (non-virtual: see there)
     bool attn_grad_block(SpmatLocal& S, int block, const hnh_attn_grad& args, bool column_side, unsigned flags, int64_t rows);
+    // KernelImplementation::attn_additive_local's pass (non-virtual: see there)
+    bool attn_additive_block(SpmatLocal& S, int block, const hnh_attn_add& args, int pass, unsigned flags, int64_t rows, bool finish);
     ~StandardKernel() override;
 
 private:

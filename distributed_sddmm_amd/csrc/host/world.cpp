@@ -120,6 +120,8 @@ Backend* load_backend(const char* path_c) {
     HNH_BIND_OPTIONAL(hnh_relu_grad_cols_f64) HNH_BIND_OPTIONAL(hnh_sum3_cols_f64) HNH_BIND_OPTIONAL(hnh_transpose_into_f64)
     HNH_BIND_OPTIONAL(hnh_attn_softmax_csr_p) HNH_BIND_OPTIONAL(hnh_softmax_gate_f64) HNH_BIND_OPTIONAL(hnh_rowdot_cols_f64)
     HNH_BIND_OPTIONAL(hnh_attn_grad_row_csr_p) HNH_BIND_OPTIONAL(hnh_attn_grad_col_csr_p) HNH_BIND_OPTIONAL(hnh_attn_grad_pack_f64)
+    HNH_BIND_OPTIONAL(hnh_attn_add_fwd_csr_p) HNH_BIND_OPTIONAL(hnh_attn_add_row_csr_p) HNH_BIND_OPTIONAL(hnh_attn_add_col_csr_p)
+    HNH_BIND_OPTIONAL(hnh_attn_add_scores_f64) HNH_BIND_OPTIONAL(hnh_attn_add_pack_f64) HNH_BIND_OPTIONAL(hnh_attn_add_update_f64)
 #undef HNH_BIND_OPTIONAL
 #ifdef HNH_MEASUREMENT_AIDS
     HNH_BIND(hnh_stream_delay_us) HNH_BIND(hnh_stream_paced_copy) HNH_BIND(hnh_stream_pace_begin) HNH_BIND(hnh_stream_pace_end)

@@ -247,6 +247,18 @@ int hnh_gat_set_attention(hnh_gat* g, int mode);
 #define HNH_GAT_BACKWARD_UNFUSED 0
 #define HNH_GAT_BACKWARD_FUSED 1
 int hnh_gat_set_backward(hnh_gat* g, int mode);
+/* Score (an addition).  DOT (the default of hnh_gat_create): e_ij = LeakyReLU(<A_i, A_j>), everything above.  ADDITIVE: the two learned
+ * vectors of a layer score an edge, e_ij = LeakyReLU(<A_i, a1_h> + <A_j, a2_h>) (include/hnh_attn_additive.h), forward and backward;
+ * attention SOFTMAX on 15d_fusion2 with c = 1 and heads of at most 256 features only — hnh_gat_forward / hnh_gat_backward fail elsewhere,
+ * naming the schedule, the mode or the width, or the missing symbol when the kernel library lacks the group.  With ADDITIVE there is one
+ * backward implementation: the backward mode is not consulted.  A change of score invalidates the stored forward pass; an unknown one fails.
+ * a1 / a2 (features_per_head doubles each, per layer and head) are zero until set; setting them invalidates the forward pass like
+ * hnh_gat_set_weight.  Their gradients (summed over all ranks) are available after hnh_gat_backward with score ADDITIVE. */
+#define HNH_GAT_SCORE_DOT 0
+#define HNH_GAT_SCORE_ADDITIVE 1
+int hnh_gat_set_score(hnh_gat* g, int mode);
+int hnh_gat_set_attn_vectors(hnh_gat* g, int layer, int head, const double* a1_host, const double* a2_host);
+int hnh_gat_get_attn_grads(hnh_gat* g, int layer, int head, double* da1_host, double* da2_host);
 
 #ifdef __cplusplus
 }

@@ -190,6 +190,35 @@ class AttnAdd(C.Structure):
                 ("relu_ld", _i64), ("f", _i32), ("leaky_alpha", _dbl)]
 
 
+# include/hnh_attn_dropout.h: attention and feature dropout of the GAT with masks from a keyed counter-based generator; a fifth OPTIONAL
+# group bound only for the product library
+ATTN_DROP_SIGNATURES = {
+    "hnh_attn_drop_fwd_csr_p": (_i32, [_vp, _vp, _vp, _vp, C.c_uint, _vp, _i32]),
+    "hnh_attn_drop_row_csr_p": (_i32, [_vp, _vp, _vp, _vp, C.c_uint, _vp, _i32]),
+    "hnh_attn_drop_col_csr_p": (_i32, [_vp, _vp, _vp, _vp, C.c_uint, _vp, _i32]),
+    "hnh_attn_drop_scores_f64": (_i32, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i32, _i64, _i32]),
+    "hnh_attn_drop_pack_f64": (_i32, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i32, _i64, _i32]),
+    "hnh_feat_drop_f64": (_i32, [_vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, C.c_uint64, C.c_uint32, C.c_uint32, _dbl, _i32]),
+    "hnh_dropout_words_u32": (_i32, [_vp, _vp, _vp, _vp, _i64, C.c_uint64, C.c_uint32, C.c_uint32, _i32]),
+}
+DROPOUT_STREAM_ATTENTION, DROPOUT_STREAM_FEATURE = 0, 1  # HNH_DROPOUT_STREAM_*
+
+
+def attn_drop_scored_width(f: int) -> int:
+    """HNH_ATTN_DROP_SCORED_WIDTH: [A (0) | s t | id 0]"""
+    return f + (f & 1) + 4
+
+
+def dropout_threshold(p: float) -> int:
+    """floor(p * 2^32): an entry is kept iff its word is >= this"""
+    return int(np.floor(p * 4294967296.0))
+
+
+class AttnDrop(C.Structure):
+    """struct hnh_attn_drop"""
+    _fields_ = [("seed", C.c_uint64), ("w2", C.c_uint32), ("threshold", C.c_uint32), ("scale", _dbl), ("row_id0", _i64)]
+
+
 class AttnState(C.Structure):
     """struct hnh_attn_state"""
     _fields_ = [("row_max", _vp), ("row_sum", _vp), ("lse", _vp), ("leaky_alpha", _dbl), ("relu_dst", _vp), ("relu_ld", _i64)]
@@ -252,7 +281,7 @@ def load(path: str | None = None) -> C.CDLL:
         fn.restype, fn.argtypes = res, args
     if path is None or os.path.abspath(p) == os.path.abspath(LIB_PATH):
         for name, (res, args) in list(GRAD_SIGNATURES.items()) + list(ATTN_SIGNATURES.items()) + list(ATTN_GRAD_SIGNATURES.items()) + \
-                list(ATTN_ADD_SIGNATURES.items()):
+                list(ATTN_ADD_SIGNATURES.items()) + list(ATTN_DROP_SIGNATURES.items()):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
     if path is None:

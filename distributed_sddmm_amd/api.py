@@ -136,6 +136,9 @@ SIGNATURES = {
     "hnh_gat_set_score": (_i32, [_vp, _i32]),
     "hnh_gat_set_attn_vectors": (_i32, [_vp, _i32, _i32, _vp, _vp]),
     "hnh_gat_get_attn_grads": (_i32, [_vp, _i32, _i32, _vp, _vp]),
+    "hnh_gat_set_dropout": (_i32, [_vp, _dbl, _dbl, C.c_uint64]),
+    "hnh_gat_set_dropout_seed": (_i32, [_vp, C.c_uint64]),
+    "hnh_dropout_word": (C.c_uint32, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
 }
 
 _lib = None
@@ -654,7 +657,7 @@ class GAT:
     SCORE = {"dot": 0, "additive": 1}  # HNH_GAT_SCORE_DOT / _ADDITIVE
 
     def __init__(self, op: DistributedSparse, layers, leaky_relu_alpha: float = 0.2, attention: str = "none", backward: str = "unfused",
-                 score: str = "dot"):
+                 score: str = "dot", dropout=(0.0, 0.0), seed: int = 0):
         self.op, self.layers = op, [tuple(l) for l in layers]
         spec = (C.c_int * (3 * len(layers)))(*[x for l in self.layers for x in l])
         self.h = _vp()
@@ -665,6 +668,23 @@ class GAT:
             self.set_backward(backward)
         if score != "dot":
             self.set_score(score)
+        if tuple(dropout) != (0.0, 0.0) or seed != 0:
+            self.set_dropout(dropout[0], dropout[1], seed)
+
+    def set_dropout(self, attention_p: float, feature_p: float, seed: int = 0):
+        """Dropout rates in [0, 1) on the normalised attention coefficients (score "additive" only) and on every layer's input, with masks
+        recomputed in every pass from Philox-4x32-10 keyed by (seed, layer, head, global row, global column)
+        (include/hnh_attn_dropout.h): they do not depend on the rank count or the schedule's windows.  (0, 0), the default, runs the
+        kernels without dropout at their widths.  Invalidates the stored forward pass; forwardPass raises HnhError where a rate is not
+        supported."""
+        for p in (attention_p, feature_p):
+            if not (0.0 <= p < 1.0):
+                raise ValueError("dropout rates must lie in [0, 1), not %r" % (p,))
+        _check(lib().hnh_gat_set_dropout(self.h, float(attention_p), float(feature_p), int(seed) & 0xFFFFFFFFFFFFFFFF), "gat_set_dropout")
+
+    def set_dropout_seed(self, seed: int):
+        """New masks at the same rates (one call per training step).  Invalidates the stored forward pass."""
+        _check(lib().hnh_gat_set_dropout_seed(self.h, int(seed) & 0xFFFFFFFFFFFFFFFF), "gat_set_dropout_seed")
 
     def set_attention(self, mode: str):
         """"none" (the default: the LeakyReLU scores are the edge weights) or "softmax" (normalised over each row's neighbourhood;

@@ -31,10 +31,46 @@ struct AaArgs {  // hnh_attn_add as the kernels take it
     double alpha;
 };
 
-template <int PASS, int LPR, int VEC, int W, bool EXACT>
-__device__ __forceinline__ void attn_add_process(int64_t row, int beg, int end, const int32_t* __restrict__ colidx, const AaArgs& a,
-                                                 unsigned flags, int lig, double* part_row) {
-    constexpr int U = AgUnroll<0, LPR, VEC, W>::value;
+// DROP instances (include/hnh_attn_dropout.h): the same arguments plus the mask's key.  A separate type, so that the plain instances'
+// kernel arguments stay as they are.
+struct AaDropArgs : AaArgs {
+    unsigned key0, key1;  // seed, low and high word
+    unsigned w2;          // layer * 65536 + head
+    unsigned threshold;   // keep iff word 0 >= threshold
+    double scale;         // 1 / (1 - p)
+    int64_t row_id0;      // global id of the block's row 0
+};
+template <bool DROP> struct AaKernelArgs { using type = AaArgs; };
+template <> struct AaKernelArgs<true> { using type = AaDropArgs; };
+
+// Philox-4x32-10, word 0 (the contract of include/hnh_attn_dropout.h)
+__device__ __forceinline__ unsigned philox_word0(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1) {
+#pragma unroll
+    for (int r = 0; r < 10; r++) {
+        const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+        const unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+        c0 = hi1 ^ c1 ^ k0;
+        c1 = lo1;
+        c2 = hi0 ^ c3 ^ k1;
+        c3 = lo0;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    return c0;
+}
+
+// The column pass's DROP instances that would unroll by 8 take 4: at 8 the instances of f = 64 (255 VGPRs without the mask), f = 128 and
+// the 8-byte-lane one of f <= 128 do not fit 256 VGPRs (the compiler moves 6 - 10 values to AGPRs and one wave per SIMD is left).
+template <int PASS, int LPR, int VEC, int W, bool DROP>
+struct AaUnroll {
+    static constexpr int full = AgUnroll<0, LPR, VEC, W>::value;
+    static constexpr int value = (DROP && PASS == 2 && full == 8) ? 4 : full;
+};
+
+template <int PASS, int LPR, int VEC, int W, bool EXACT, bool DROP = false>
+__device__ __forceinline__ void attn_add_process(int64_t row, int beg, int end, const int32_t* __restrict__ colidx,
+                                                 const typename AaKernelArgs<DROP>::type& a, unsigned flags, int lig, double* part_row) {
+    constexpr int U = AaUnroll<PASS, LPR, VEC, W, DROP>::value;
     constexpr int SUB = LPR / U;  // lanes that own the same nonzero of a batch
     static_assert(SUB >= 1, "needs U <= LPR");
     bool act[VEC];
@@ -88,7 +124,7 @@ __device__ __forceinline__ void attn_add_process(int64_t row, int beg, int end, 
     struct Batch {
         double y[U][VEC][W];
         double sa[U][2];                    // [s t] of a scored row, [s lse] of a packed one
-        double sb[PASS == 2 ? U : 1][2];    // [delta 0] of a packed row
+        double sb[(PASS == 2 || DROP) ? U : 1][2];  // [delta 0] of a packed row; DROP: [id 0] of a scored row, [delta id] of a packed one
     };
 
     auto load_idx = [&](auto full, int e, int (&c)[U]) {
@@ -127,7 +163,7 @@ __device__ __forceinline__ void attn_add_process(int64_t row, int beg, int end, 
             b.sa[u][0] = 0.0;
             b.sa[u][1] = 0.0;
             if (live) load_w_global<2>(b.sa[u], rowp, sc_bytes);  // (16-byte aligned: an even pitch, fp even)
-            if constexpr (PASS == 2) {
+            if constexpr (PASS == 2 || DROP) {
                 b.sb[u][0] = 0.0;
                 b.sb[u][1] = 0.0;
                 if (live) load_w_global<2>(b.sb[u], rowp, sc_bytes + 16u);
@@ -139,13 +175,23 @@ __device__ __forceinline__ void attn_add_process(int64_t row, int beg, int end, 
         const int umine = lig / SUB;
         const bool have = FULL || e + umine < end;
         double q0 = 0.0, q1 = 0.0, q2 = 0.0;  // the scalars of this lane's nonzero
+        [[maybe_unused]] double qid = 0.0;    // DROP: the gathered row's global id
 #pragma unroll
         for (int u = 0; u < U; u++)
             if (u == umine) {
                 q0 = b.sa[u][0];
                 q1 = b.sa[u][1];
                 if constexpr (PASS == 2) q2 = b.sb[u][0];
+                if constexpr (DROP) qid = b.sb[u][PASS == 2 ? 1 : 0];
             }
+        // DROP: c m_ij of this lane's nonzero, recomputed from (seed, layer, head, global row, global column): the same bits in the
+        // forward pass, the row pass and (with the roles of own and gathered row exchanged) the column pass over S^T
+        [[maybe_unused]] double keep = 1.0;
+        if constexpr (DROP) {
+            const unsigned own_id = (unsigned)(a.row_id0 + row), got_id = (unsigned)(unsigned long long)qid;
+            const unsigned word = philox_word0(PASS == 2 ? got_id : own_id, PASS == 2 ? own_id : got_id, a.w2, 0u, a.key0, a.key1);
+            keep = word >= a.threshold ? a.scale : 0.0;
+        }
         const double z = PASS == 2 ? q0 + own : own + q1;  // s_i + t_j
         const double slope = z > 0.0 ? 1.0 : a.alpha;
         const double ev = z * slope;
@@ -162,11 +208,14 @@ __device__ __forceinline__ void attn_add_process(int64_t row, int beg, int end, 
             }
             const double fac = (mcur == mprev) ? 1.0 : (mprev == -__builtin_inf() ? 0.0 : exp(mprev - mcur));
             const double pw = have ? exp(s - mcur) : 0.0;
+            [[maybe_unused]] const double pwk = pw * keep;
             m_run = run;
 #pragma unroll
             for (int u = 0; u < U; u++) {
                 const double fu = group_bcast<LPR>(fac, u * SUB);
                 const double pu = group_bcast<LPR>(pw, u * SUB);
+                double pa = pu;  // l takes every edge, acc the kept ones times c
+                if constexpr (DROP) pa = group_bcast<LPR>(pwk, u * SUB);
                 if (fu != 1.0) {  // the running max rose (uniform over the group)
 #pragma unroll
                     for (int v = 0; v < VEC; v++)
@@ -178,7 +227,7 @@ __device__ __forceinline__ void attn_add_process(int64_t row, int beg, int end, 
 #pragma unroll
                 for (int v = 0; v < VEC; v++)
 #pragma unroll
-                    for (int w = 0; w < W; w++) acc[v][w] = fma(pu, b.y[u][v][w], acc[v][w]);
+                    for (int w = 0; w < W; w++) acc[v][w] = fma(pa, b.y[u][v][w], acc[v][w]);
             }
 #pragma unroll
             for (int v = 0; v < VEC; v++)
@@ -198,7 +247,8 @@ __device__ __forceinline__ void attn_add_process(int64_t row, int beg, int end, 
             const double da = group_multi_reduce<LPR, U>(d, lig);  // reduction number lig / SUB
             const double l = PASS == 1 ? lse_i : q1, dl = PASS == 1 ? delta_i : q2;
             double wa = exp(ev - l);
-            double wdz = wa * (da - dl) * slope;
+            double wdz = wa * ((DROP ? keep * da : da) - dl) * slope;
+            if constexpr (DROP) wa *= keep;  // (only dAgg reads it from here on)
             if (!have) {
                 wa = 0.0;
                 wdz = 0.0;
@@ -297,10 +347,10 @@ __device__ __forceinline__ void attn_add_process(int64_t row, int beg, int end, 
     }
 }
 
-template <int PASS, int LPR, int VEC, int W, bool EXACT>
+template <int PASS, int LPR, int VEC, int W, bool EXACT, bool DROP = false>
 __global__ __launch_bounds__(kBlock) void attn_add_row_kernel(int64_t rows, const int32_t* __restrict__ rowptr, const int32_t* __restrict__ beg_ptr,
-                                                              const int32_t* __restrict__ end_ptr, const int32_t* __restrict__ colidx, AaArgs a,
-                                                              unsigned flags) {
+                                                              const int32_t* __restrict__ end_ptr, const int32_t* __restrict__ colidx,
+                                                              typename AaKernelArgs<DROP>::type a, unsigned flags) {
     constexpr int GROUPS = kBlock / LPR;
     const int tid = threadIdx.x;
     const int lig = tid % LPR;
@@ -324,14 +374,14 @@ __global__ __launch_bounds__(kBlock) void attn_add_row_kernel(int64_t rows, cons
         }
         if (beg == end && !(flags & HNH_FUSED_OUT_OVERWRITE)) return;  // nothing to add
     }
-    attn_add_process<PASS, LPR, VEC, W, EXACT>(row, beg, end, colidx, a, flags, lig, nullptr);
+    attn_add_process<PASS, LPR, VEC, W, EXACT, DROP>(row, beg, end, colidx, a, flags, lig, nullptr);
 }
 
 // one work item = kLongSeg consecutive nonzeros of a hub row (the row kernels' work list); every segment writes its partial result
-template <int PASS, int LPR, int VEC, int W, bool EXACT>
+template <int PASS, int LPR, int VEC, int W, bool EXACT, bool DROP = false>
 __global__ __launch_bounds__(kBlock) void attn_add_long_kernel(const int2* __restrict__ items, const int* __restrict__ item_count, int capacity,
-                                                               const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colidx, AaArgs a,
-                                                               double* partials, int64_t pitch) {
+                                                               const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colidx,
+                                                               typename AaKernelArgs<DROP>::type a, double* partials, int64_t pitch) {
     constexpr int GROUPS = kBlock / LPR;
     const int tid = threadIdx.x;
     const int lig = tid % LPR;
@@ -352,7 +402,7 @@ __global__ __launch_bounds__(kBlock) void attn_add_long_kernel(const int2* __res
         }
         const int beg = rbeg + seg * kLongSeg;
         const int end = (beg + kLongSeg < rend) ? beg + kLongSeg : rend;
-        attn_add_process<PASS, LPR, VEC, W, EXACT>(row, beg, end, colidx, a, HNH_FUSED_OUT_OVERWRITE, lig, partials + (int64_t)it * pitch);
+        attn_add_process<PASS, LPR, VEC, W, EXACT, DROP>(row, beg, end, colidx, a, HNH_FUSED_OUT_OVERWRITE, lig, partials + (int64_t)it * pitch);
     }
 }
 
@@ -428,22 +478,22 @@ __global__ __launch_bounds__(kBlock) void attn_add_update_kernel(double* __restr
     }
 }
 
-template <int PASS, int LPR, int VEC, int W, bool EXACT>
+template <int PASS, int LPR, int VEC, int W, bool EXACT, bool DROP>
 int attn_add_launch(hnh_ctx* ctx, hipStream_t st, const LongCtl& lc, int64_t rows, const int32_t* rowptr, const int32_t* beg_ptr,
-                    const int32_t* end_ptr, const int32_t* colidx, const AaArgs& a, unsigned flags, bool run_long) {
+                    const int32_t* end_ptr, const int32_t* colidx, const typename AaKernelArgs<DROP>::type& a, unsigned flags, bool run_long) {
     constexpr int GROUPS = kBlock / LPR;
     const int64_t blocks = (rows + GROUPS - 1) / GROUPS;
     if (blocks <= 0) return HNH_OK;
     if (blocks > 0x7fffffffLL) return hnh::fail(ctx, HNH_ERR_UNSUPPORTED, "too many rows for one launch");
     if (lc.enabled) flags |= kInternalSplitLong | ((unsigned)(lc.threshold / 64) << kLongRowShift);
     const size_t lds_pad = lc.lds_pad <= 48 * 1024 ? lc.lds_pad : 0;
-    hipLaunchKernelGGL((attn_add_row_kernel<PASS, LPR, VEC, W, EXACT>), dim3((unsigned)blocks), dim3(kBlock), lds_pad, st, rows, rowptr, beg_ptr, end_ptr,
+    hipLaunchKernelGGL((attn_add_row_kernel<PASS, LPR, VEC, W, EXACT, DROP>), dim3((unsigned)blocks), dim3(kBlock), lds_pad, st, rows, rowptr, beg_ptr, end_ptr,
                        colidx, a, flags);
     if (int rc = hnh::check_hip(ctx, hipGetLastError(), "attn_add_row_kernel launch")) return rc;
     if constexpr (PASS != 0) {
         if (lc.enabled && run_long) {  // hub rows once per pass, over their whole length: segments, then the ordered sums
             const int64_t pitch = PASS == 2 ? a.fp + 2 : 2;
-            hipLaunchKernelGGL((attn_add_long_kernel<PASS, LPR, VEC, W, EXACT>), dim3((unsigned)ctx->long_grid), dim3(kBlock), 0, st, lc.items, lc.count,
+            hipLaunchKernelGGL((attn_add_long_kernel<PASS, LPR, VEC, W, EXACT, DROP>), dim3((unsigned)ctx->long_grid), dim3(kBlock), 0, st, lc.items, lc.count,
                                lc.capacity, rowptr, colidx, a, lc.partials, pitch);
             if (int rc = hnh::check_hip(ctx, hipGetLastError(), "attn_add_long_kernel launch")) return rc;
             if (PASS == 2) {
@@ -460,10 +510,10 @@ int attn_add_launch(hnh_ctx* ctx, hipStream_t st, const LongCtl& lc, int64_t row
 }
 
 // the instance that fits (f, alignment): exact widths 64 / 128 / 256, every other width bounds-checked (16-byte lanes when even)
-template <int PASS>
+template <int PASS, bool DROP>
 int attn_add_launch_shape(hnh_ctx* ctx, hipStream_t st, const LongCtl& lc, bool w2, int64_t rows, const int32_t* rowptr, const int32_t* beg_ptr,
-                          const int32_t* end_ptr, const int32_t* colidx, const AaArgs& a, unsigned flags, bool run_long) {
-#define HNH_AA(L, V, WW, EX) return attn_add_launch<PASS, L, V, WW, EX>(ctx, st, lc, rows, rowptr, beg_ptr, end_ptr, colidx, a, flags, run_long)
+                          const int32_t* end_ptr, const int32_t* colidx, const typename AaKernelArgs<DROP>::type& a, unsigned flags, bool run_long) {
+#define HNH_AA(L, V, WW, EX) return attn_add_launch<PASS, L, V, WW, EX, DROP>(ctx, st, lc, rows, rowptr, beg_ptr, end_ptr, colidx, a, flags, run_long)
     const int f = a.f;
     if (w2) {
         if (f == 64) HNH_AA(32, 1, 2, true);
@@ -478,11 +528,11 @@ int attn_add_launch_shape(hnh_ctx* ctx, hipStream_t st, const LongCtl& lc, bool 
 #undef HNH_AA
 }
 
-template <int PASS>
+template <int PASS, bool DROP = false>
 int attn_add_dispatch(hnh_ctx* ctx, const hnh_csr_block* b, const hnh_attn_add* g, unsigned flags, const hnh_csr_window* win, int stream,
-                      const char* who) {
+                      const char* who, const hnh_attn_drop* drop = nullptr) {
     HNH_ENTER(ctx, stream);
-    if (!b || !g) return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": null block or arguments");
+    if (!b || !g || (DROP && !drop)) return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": null block or arguments");
     if (int rc = check_common(ctx, b->rows, g->f, who)) return rc;
     if (flags & ~(HNH_FUSED_OUT_OVERWRITE | (PASS == 0 ? HNH_ATTN_FINISH : 0u))) return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": unknown flag");
     if (g->f > HNH_ATTN_ADD_MAX_F)
@@ -496,7 +546,18 @@ int attn_add_dispatch(hnh_ctx* ctx, const hnh_csr_block* b, const hnh_attn_add* 
     if (PASS != 0 && (!g->vec || g->ld_vec < 1)) return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": bad scalar output");
     if (PASS == 0 && (!g->row_max || !g->row_sum || !g->lse || !g->relu_dst || g->relu_ld < f))
         return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": bad row state");
-    AaArgs a;
+    typename AaKernelArgs<DROP>::type a;
+    if constexpr (DROP) {
+        // ids travel as 32-bit counter words: the block's own rows and (the operand's ids are the caller's) nothing else is checked here
+        if (drop->row_id0 < 0 || drop->row_id0 + b->rows > 0x100000000LL)
+            return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": the block's global row ids do not fit 32 bits");
+        a.key0 = (unsigned)(drop->seed & 0xffffffffu);
+        a.key1 = (unsigned)(drop->seed >> 32);
+        a.w2 = drop->w2;
+        a.threshold = drop->threshold;
+        a.scale = drop->scale;
+        a.row_id0 = drop->row_id0;
+    }
     a.M = g->M; a.dZ = g->dZ; a.delta = g->delta; a.Y = g->Y; a.lse = g->lse; a.Out = g->Out; a.vec = g->vec;
     a.row_max = g->row_max; a.row_sum = g->row_sum; a.relu_dst = g->relu_dst;
     a.ld_m = g->ld_m; a.ld_dz = g->ld_dz; a.ld_y = g->ld_y; a.ld_out = g->ld_out; a.ld_vec = g->ld_vec; a.relu_ld = g->relu_ld;
@@ -521,7 +582,7 @@ int attn_add_dispatch(hnh_ctx* ctx, const hnh_csr_block* b, const hnh_attn_add* 
     if (!b->col_idx || !g->M || !g->Y) return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": null pointer");
     if (g->ld_m < fp + 2) return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": ld_m is narrower than the scored width");
     // the gathered operand (hnh_attn_additive.h): an even pitch and a 16-byte aligned base, whatever f is
-    const int gather_w = PASS == 2 ? HNH_ATTN_ADD_PACKED_WIDTH(f) : HNH_ATTN_ADD_SCORED_WIDTH(f);
+    const int gather_w = PASS == 2 ? HNH_ATTN_ADD_PACKED_WIDTH(f) : (DROP ? HNH_ATTN_DROP_SCORED_WIDTH(f) : HNH_ATTN_ADD_SCORED_WIDTH(f));
     if (g->ld_y < gather_w || g->ld_y % 2 != 0 || !aligned16(g->Y))
         return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": the gathered operand needs an even pitch of at least " + std::to_string(gather_w) +
                                                    " and a 16-byte aligned base");
@@ -557,7 +618,7 @@ int attn_add_dispatch(hnh_ctx* ctx, const hnh_csr_block* b, const hnh_attn_add* 
     if (win != nullptr) {
         const int32_t* beg_ptr = win->beg ? win->beg : rowptr;
         const int32_t* end_ptr = win->end ? win->end : rowptr + 1;
-        return attn_add_launch_shape<PASS>(ctx, st, lc, w2, rows, rowptr, beg_ptr, end_ptr, colidx, a, kflags, win->last != 0);
+        return attn_add_launch_shape<PASS, DROP>(ctx, st, lc, w2, rows, rowptr, beg_ptr, end_ptr, colidx, a, kflags, win->last != 0);
     }
     const int panels = (!lc.enabled || ctx->panels_with_hubs) ? panel_count(ctx, b->cols, gather_w) : 1;
     if (panels > 1) {
@@ -569,11 +630,11 @@ int attn_add_dispatch(hnh_ctx* ctx, const hnh_csr_block* b, const hnh_attn_add* 
             unsigned fq = kflags;
             if (q > 0) fq &= ~HNH_FUSED_OUT_OVERWRITE;       // later panels continue the rows the first one started
             if (q < panels - 1) fq &= ~kInternalEpilogue;    // the last panel finishes them
-            if (int rc = attn_add_launch_shape<PASS>(ctx, st, lc, w2, rows, rowptr, beg_ptr, end_ptr, colidx, a, fq, q == panels - 1)) return rc;
+            if (int rc = attn_add_launch_shape<PASS, DROP>(ctx, st, lc, w2, rows, rowptr, beg_ptr, end_ptr, colidx, a, fq, q == panels - 1)) return rc;
         }
         return HNH_OK;
     }
-    return attn_add_launch_shape<PASS>(ctx, st, lc, w2, rows, rowptr, rowptr, rowptr + 1, colidx, a, kflags, true);
+    return attn_add_launch_shape<PASS, DROP>(ctx, st, lc, w2, rows, rowptr, rowptr, rowptr + 1, colidx, a, kflags, true);
 }
 
 }  // namespace

@@ -30,6 +30,7 @@
 #include "hnh_attention.h"
 #include "hnh_attn_grad.h"
 #include "hnh_attn_additive.h"
+#include "hnh_attn_dropout.h"
 
 namespace {
 
@@ -2777,3 +2778,6 @@ int hnh_rowdot_cols_f64(hnh_ctx* ctx, double* out, const double* dZ, int64_t ld_
 
 // ---------------------------------------------------------------- additive attention scores (include/hnh_attn_additive.h)
 #include "hnh_attn_additive_kernels.hpp"
+
+// ---------------------------------------------------------------- GAT dropout (include/hnh_attn_dropout.h)
+#include "hnh_attn_dropout_kernels.hpp"

@@ -8,6 +8,7 @@
 #include <string>
 #include "hnh_attention.h"
 #include "hnh_attn_additive.h"
+#include "hnh_attn_dropout.h"
 #include "hnh_attn_grad.h"
 #include "hnh_grad.h"
 #include "hnh_kernels.h"
@@ -53,6 +54,9 @@ struct Backend {
     // OPTIONAL group (include/hnh_attn_additive.h), bound the same way: only the GAT's additive score needs it
     HNH_FN(hnh_attn_add_fwd_csr_p) HNH_FN(hnh_attn_add_row_csr_p) HNH_FN(hnh_attn_add_col_csr_p)
     HNH_FN(hnh_attn_add_scores_f64) HNH_FN(hnh_attn_add_pack_f64) HNH_FN(hnh_attn_add_update_f64)
+    // OPTIONAL group (include/hnh_attn_dropout.h), bound the same way: only the GAT's dropout needs it
+    HNH_FN(hnh_attn_drop_fwd_csr_p) HNH_FN(hnh_attn_drop_row_csr_p) HNH_FN(hnh_attn_drop_col_csr_p)
+    HNH_FN(hnh_attn_drop_scores_f64) HNH_FN(hnh_attn_drop_pack_f64) HNH_FN(hnh_feat_drop_f64) HNH_FN(hnh_dropout_words_u32)
 #ifdef HNH_MEASUREMENT_AIDS
     HNH_FN(hnh_stream_delay_us) HNH_FN(hnh_stream_paced_copy) HNH_FN(hnh_stream_pace_begin) HNH_FN(hnh_stream_pace_end)
 #endif

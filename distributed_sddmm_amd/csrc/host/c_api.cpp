@@ -799,6 +799,27 @@ int hnh_gat_get_attn_grads(hnh_gat* g, int layer, int head, double* da1_host, do
         }
     });
 }
+int hnh_gat_set_dropout(hnh_gat* g, double attention_p, double feature_p, uint64_t seed) {
+    return guarded(g->w, [&] { g->g->set_dropout(attention_p, feature_p, seed); });
+}
+int hnh_gat_set_dropout_seed(hnh_gat* g, uint64_t seed) {
+    return guarded(g->w, [&] { g->g->set_dropout_seed(seed); });
+}
+// the generator of include/hnh_attn_dropout.h restated once on the host: Philox-4x32, 10 rounds, word 0
+uint32_t hnh_dropout_word(uint64_t seed, uint32_t stream, uint32_t w2, uint32_t gi, uint32_t gj) {
+    uint32_t c0 = gi, c1 = gj, c2 = w2, c3 = stream, k0 = (uint32_t)(seed & 0xffffffffu), k1 = (uint32_t)(seed >> 32);
+    for (int r = 0; r < 10; r++) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+        c1 = (uint32_t)p1;
+        c3 = (uint32_t)p0;
+        c0 = n0;
+        c2 = n2;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    return c0;
+}
 int hnh_gat_backward(hnh_gat* g, hnh_dense* grad_out) {
     return guarded(g->w, [&] { g->g->backwardPass(grad_out->m); });
 }

@@ -343,7 +343,10 @@ public:
     // pass makes its first call (the state reset) and its closing call (the finish) also for an absent block, like fusedSoftmax_out.
     // Returns false, having done nothing, where a rank's own launches do not see all of a row's nonzeros (only approach 2 with c = 1).
     // Not a virtual of Distributed_Sparse, for fusedSoftmax_out's reason.
-    bool attnAdditive_pass(int pass, DenseMatrix& moving, const hnh_attn_add& args, int64_t out_rows, bool overwrite) {
+    // `drop` (include/hnh_attn_dropout.h): the passes' DROP instances; `moving` is then M' / Q', whose rows carry their global ids, and
+    // drop->row_id0 is the global id of this rank's row 0 (the same for every block: a block's rows are the rank's rows).
+    bool attnAdditive_pass(int pass, DenseMatrix& moving, const hnh_attn_add& args, int64_t out_rows, bool overwrite,
+                           const hnh_attn_drop* drop = nullptr) {
         if (fusionApproach != 2 || c != 1) return false;
         if (pass < 0 || pass > 2) hnh::fatal("Error, attnAdditive_pass: unknown pass!");
         if (moving.cols() != R) hnh::fatal("Error, attnAdditive_pass: the schedule's R must be the moving operand's width!");
@@ -361,7 +364,7 @@ public:
             hnh_attn_add a = args;
             a.Y = Y.data();
             a.ld_y = Y.cols();
-            const bool done = kernel->attn_additive_local(*choice, block_id, a, pass, fresh ? HNH_FUSED_OUT_OVERWRITE : 0u, out_rows, finish);
+            const bool done = kernel->attn_additive_local(*choice, block_id, a, pass, fresh ? HNH_FUSED_OUT_OVERWRITE : 0u, out_rows, finish, drop);
             if (blk != nullptr) blk->window = blk->window_end = -1;
             if (!done) throw hnh::Error("Error, the kernel implementation has no additive attention pass (KernelImplementation::attn_additive_local)!");
             fresh = false;

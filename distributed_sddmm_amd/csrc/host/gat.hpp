@@ -51,6 +51,19 @@
 //     dA = dAgg + ds a1_h^T + dt a2_h^T,  da1_h = A^T ds,  da2_h = A^T dt  (attn_grads, summed over the world like dW).
 // Supported where the softmax is (15d_fusion2 with c = 1, attention softmax) with heads of at most HNH_ATTN_ADD_MAX_F features; everything
 // else raises before anything is launched.  With score ADDITIVE there is ONE backward implementation: set_backward is not consulted.
+//
+// Dropout (an addition; set_dropout(attention_p, feature_p, seed), both rates 0 by default, which launches exactly the kernels above at
+// their widths).  The masks are never stored: every pass recomputes them from Philox-4x32-10 keyed by (seed, layer, head, global row,
+// global column) (include/hnh_attn_dropout.h), so they do not depend on the rank count, windows, panels or hub-row segments, and the
+// backward column pass over S^T on another rank sees the forward pass's mask.  A change of rates or seed invalidates the stored
+// forward pass, so backwardPass always differentiates the masks of the forward pass it belongs to.
+//     attention_p > 0 (score ADDITIVE only): o_i = sum_j c m_ij a_ij A_j with c = 1 / (1 - p); lse and a_ij are those of ALL edges;
+//         dz_ij = a_ij (c m_ij <dZ_i, A_j> - delta_i) LeakyReLU'(z_ij), dAgg_j = sum_i c m_ij a_ij dZ_i.  The gathered row's global id
+//         travels in the operand: the head pipeline builds M' = [A (0) | s t | id 0] (fp + 4 columns) and the backward Q' = [dZ (0) | s
+//         lse delta id], and the schedule runs at that width.
+//     feature_p > 0 (wherever the passes themselves are supported, one dense block per rank): layer l keeps Xd = c_q mask o X, made on
+//         the compute stream before the product stage starts; Xd replaces X in the head products and in dW = Xd^T dA_all, and
+//         input_grads[l] = c_q mask o (dA_all Wt).
 #pragma once
 #include "dense_shift_15d.hpp"
 #include "distributed_sparse.hpp"
@@ -121,6 +134,25 @@ public:
         score_ = mode;
     }
 
+    // Dropout (include/hnh_attn_dropout.h): rates in [0, 1) on the attention coefficients (score ADDITIVE only; checked by forwardPass)
+    // and on every layer's input, masks keyed by `seed`.  (0, 0) is the default: today's kernels at today's widths.  A change
+    // invalidates the stored forward pass.
+    double attention_dropout() const { return attn_p_; }
+    double feature_dropout() const { return feat_p_; }
+    uint64_t dropout_seed() const { return seed_; }
+    void set_dropout(double attention_p, double feature_p, uint64_t seed) {
+        for (double p : {attention_p, feature_p})
+            if (!(p >= 0.0 && p < 1.0)) throw hnh::Error("Error, GAT dropout rates must lie in [0, 1), not " + std::to_string(p) + "!");
+        attn_p_ = attention_p;
+        feat_p_ = feature_p;
+        seed_ = seed;
+        invalidate_forward();
+    }
+    void set_dropout_seed(uint64_t seed) {
+        seed_ = seed;
+        invalidate_forward();
+    }
+
     // The additive score's vectors of a layer (GATLayer::a1 / a2: num_heads * features_per_head entries each, zero until set; head h
     // uses the slice [h f, (h + 1) f)), allocated on first use.
     void ensure_attn_vectors(int i) {
@@ -153,6 +185,7 @@ public:
     // Computes the j'th self-attention head of the i'th layer (gat.hpp:83-104)
     void computeSelfAttentionHead(int i, int j) {
         DenseMatrix A;
+        if (j == 0) drop_input(i);
         head_product(i, j, A, HNH_STREAM_COMPUTE);
         if (score_ == HNH_GAT_SCORE_ADDITIVE) {
             shape_scored(i, scored[0]);
@@ -169,6 +202,7 @@ public:
     // HNH_GAT_SERIAL=1: the reference's order on one stream (A/B measurements).
     void forwardPass() {
         const bool additive = score_ == HNH_GAT_SCORE_ADDITIVE;
+        check_dropout_supported();
         if (attention_ == HNH_GAT_ATTENTION_SOFTMAX && !additive) check_softmax_supported();
         if (additive) {
             check_additive_supported();
@@ -190,6 +224,7 @@ public:
                 shape_product((int)i, product[b]);
                 if (additive) shape_scored((int)i, scored[b]);
             }
+            drop_input((int)i);  // (Xd: allocated and made on the compute stream, before the mark below)
             // the layer's input is complete, and both product buffers are free, once the compute stream gets here
             w->event_record(ev_input, HNH_STREAM_COMPUTE);
             w->event_wait(ev_input, HNH_STREAM_AUX);
@@ -220,6 +255,7 @@ public:
     // Results: weight_grads[i] (input_features x H f of layer i, column block h = dW_h, the same on every rank) and input_grads[i]
     // (dL/d(buffers[i]); input_grads[0] is the input gradient).  Buffers are allocated on the first call and reused.
     void backwardPass(const DenseMatrix& grad_out) {
+        check_dropout_supported();
         check_backward_supported();
         if (!forward_valid_) throw hnh::Error("Error, GAT backwardPass needs a forwardPass first (and a new one after set_weight / set_input)!");
         const DenseMatrix& last = buffers.back();
@@ -262,6 +298,9 @@ private:
     int attention_ = HNH_GAT_ATTENTION_NONE;
     int backward_ = HNH_GAT_BACKWARD_UNFUSED;
     int score_ = HNH_GAT_SCORE_DOT;
+    double attn_p_ = 0.0, feat_p_ = 0.0;  // dropout rates and the masks' seed (include/hnh_attn_dropout.h)
+    uint64_t seed_ = 0;
+    std::vector<DenseMatrix> xd_;         // feature dropout: Xd of every layer (allocated only then)
     DenseMatrix scored[2];  // score ADDITIVE: [A (0) | s t] of the head in flight and of the next one (include/hnh_attn_additive.h)
     // softmax attention: the rows' running max / sum (reused by every head, which run one after the other on the compute stream), the
     // log-sum-exp of every (layer, head), and for the backward pass a column of ones and the broadcasts of lse and delta onto the nonzeros
@@ -275,6 +314,64 @@ private:
         DenseMatrix& m = scratch_[std::make_tuple(role, rows, cols)];
         if (m.rows() != rows || m.cols() != cols) m = DenseMatrix(rows, cols);
         return m;
+    }
+
+    static uint32_t drop_threshold(double p) { return (uint32_t)std::floor(p * 4294967296.0); }  // keep iff word 0 >= floor(p 2^32)
+    // the key of (layer i, head j)'s attention mask on this rank's rows
+    hnh_attn_drop attn_drop_args(int i, int j) const {
+        hnh_attn_drop d = {};
+        d.seed = seed_;
+        d.w2 = (uint32_t)i * 65536u + (uint32_t)j;
+        d.threshold = drop_threshold(attn_p_);
+        d.scale = 1.0 / (1.0 - attn_p_);
+        d.row_id0 = d_ops->aSubmatrices[0].topRow;
+        return d;
+    }
+    // the input of layer i as the products and the dW GEMM see it: Xd with feature dropout, the buffer itself without
+    DenseMatrix& layer_input(int i) { return feat_p_ > 0.0 ? xd_.at((size_t)i) : buffers[(size_t)i]; }
+    // dst = c_q mask o src with layer i's feature mask (dst == src allowed), on the compute stream
+    void feature_mask(int i, DenseMatrix& dst, const DenseMatrix& src) {
+        hnh::World* w = d_ops->world;
+        const DenseSubmatrix& sub = i == 0 ? d_ops->bSubmatrices[0] : d_ops->aSubmatrices[0];  // (buffers[0] is laid out like B)
+        w->check(w->be->hnh_feat_drop_f64(w->ctx, dst.data(), dst.cols(), src.data(), src.cols(), src.rows(), src.cols(), sub.topRow, seed_, (uint32_t)i,
+                                          drop_threshold(feat_p_), 1.0 / (1.0 - feat_p_), HNH_STREAM_COMPUTE),
+                 "hnh_feat_drop_f64");
+    }
+    void drop_input(int i) {
+        if (!(feat_p_ > 0.0)) return;
+        if (xd_.size() != buffers.size() - 1) xd_.assign(buffers.size() - 1, DenseMatrix());
+        DenseMatrix& X = buffers[(size_t)i];
+        DenseMatrix& Xd = xd_[(size_t)i];
+        if (Xd.rows() != X.rows() || Xd.cols() != X.cols()) Xd = DenseMatrix(X.rows(), X.cols());
+        feature_mask(i, Xd, X);
+    }
+
+    // Dropout's own conditions, checked before anything is launched (and before the additive score's, whose kernel group a library
+    // may lack as well): the score, the counter's field widths, the layout, then its kernel group.
+    void check_dropout_supported() {
+        if (!(attn_p_ > 0.0) && !(feat_p_ > 0.0)) return;
+        if (attn_p_ > 0.0 && score_ != HNH_GAT_SCORE_ADDITIVE)
+            throw hnh::Error("Error, GAT attention dropout supports score additive only, not score dot: the dot-product passes have no mask "
+                             "(include/hnh_attn_dropout.h)");
+        if (d_ops->M > 4294967296LL || d_ops->N > 4294967296LL || layers.size() > 65536)
+            throw hnh::Error("Error, GAT dropout needs row ids below 2^32 and at most 65536 layers (the generator's counter words)!");
+        for (const GATLayer& L : layers)
+            if (L.num_heads > 65536 || (int64_t)L.input_features > 4294967296LL)
+                throw hnh::Error("Error, GAT dropout needs at most 65536 heads per layer (the generator's counter words)!");
+        if (feat_p_ > 0.0 && (d_ops->r_split || d_ops->aSubmatrices.size() != 1 || d_ops->bSubmatrices.size() != 1 ||
+                              d_ops->aSubmatrices[0].leftCol != 0 || d_ops->bSubmatrices[0].leftCol != 0))
+            throw hnh::Error("Error, GAT feature dropout needs one dense block of whole rows per rank, which " + d_ops->algorithm_name + " does not have!");
+        const hnh::Backend* be = d_ops->world->be;
+        std::vector<std::pair<const void*, const char*>> need;
+        if (attn_p_ > 0.0)
+            need = {{(const void*)be->hnh_attn_drop_fwd_csr_p, "hnh_attn_drop_fwd_csr_p"}, {(const void*)be->hnh_attn_drop_row_csr_p, "hnh_attn_drop_row_csr_p"},
+                    {(const void*)be->hnh_attn_drop_col_csr_p, "hnh_attn_drop_col_csr_p"}, {(const void*)be->hnh_attn_drop_scores_f64, "hnh_attn_drop_scores_f64"},
+                    {(const void*)be->hnh_attn_drop_pack_f64, "hnh_attn_drop_pack_f64"}};
+        if (feat_p_ > 0.0) need.push_back({(const void*)be->hnh_feat_drop_f64, "hnh_feat_drop_f64"});
+        for (const auto& n : need)
+            if (n.first == nullptr)
+                throw hnh::Error(std::string("Error, GAT dropout needs the kernel ") + n.second + ", which the kernel library " + be->path +
+                                 " does not export (include/hnh_attn_dropout.h)");
     }
 
     // Throws hnh::Error (never a wrong number) where the backward pass is not defined or its kernels are missing.
@@ -382,7 +479,7 @@ private:
         hnh::World* w = d_ops->world;
         const hnh::Backend* be = w->be;
         const int S0 = HNH_STREAM_COMPUTE;
-        DenseMatrix& X = buffers[(size_t)i];
+        DenseMatrix& X = layer_input(i);  // (Xd with feature dropout: the forward pass's products used it)
         const DenseMatrix& out = buffers[(size_t)i + 1];
         const int H = layers[(size_t)i].num_heads, f = layers[(size_t)i].features_per_head;
         const int64_t rows = X.rows(), k = X.cols(), hf = (int64_t)H * f;
@@ -508,6 +605,7 @@ private:
         DenseMatrix& dX = input_grads[(size_t)i];
         if (dX.rows() != rows || dX.cols() != k) dX = DenseMatrix(rows, k);
         w->check(be->hnh_gemm_f64(w->ctx, rows, k, hf, dA_all.data(), Wt.data(), dX.data(), S0), "hnh_gemm_f64");
+        if (feat_p_ > 0.0) feature_mask(i, dX, dX);  // dL/dX = c_q mask o dL/dXd
     }
     // One head of the backward pass with score ADDITIVE (include/hnh_attn_additive.h): A = X W_h and dZ are the caller's; the head's
     // column block of dA_all and its rows of attn_grads[i] (this rank's part) are the results.
@@ -523,16 +621,22 @@ private:
         ensure_attn_vectors(i);
         const double* a1 = L.a1.data() + (int64_t)h * f;
         const double* a2 = L.a2.data() + (int64_t)h * f;
-        const int mw = HNH_ATTN_ADD_SCORED_WIDTH(f), qw = HNH_ATTN_ADD_PACKED_WIDTH(f);
+        const bool drop = attn_p_ > 0.0;  // M', Q' and the DROP instances (include/hnh_attn_dropout.h)
+        const hnh_attn_drop dr = attn_drop_args(i, h);
+        const int mw = drop ? HNH_ATTN_DROP_SCORED_WIDTH(f) : HNH_ATTN_ADD_SCORED_WIDTH(f), qw = HNH_ATTN_ADD_PACKED_WIDTH(f);
         DenseMatrix& M = scratch(10, rows, mw);
         DenseMatrix& Q = scratch(11, rows, qw);
         DenseMatrix& D = scratch(12, rows, 2);      // [ds dt]
         DenseMatrix& dAgg = scratch(13, rows, f);
         DenseMatrix& dl = scratch(8, rows, 1);
         double* lse = lse_.at((size_t)i).at((size_t)h).data();
-        w->check(be->hnh_attn_add_scores_f64(w->ctx, M.data(), mw, A.data(), f, a1, a2, rows, f, S0), "hnh_attn_add_scores_f64");
+        if (drop) w->check(be->hnh_attn_drop_scores_f64(w->ctx, M.data(), mw, A.data(), f, a1, a2, rows, f, dr.row_id0, S0), "hnh_attn_drop_scores_f64");
+        else w->check(be->hnh_attn_add_scores_f64(w->ctx, M.data(), mw, A.data(), f, a1, a2, rows, f, S0), "hnh_attn_add_scores_f64");
         w->check(be->hnh_rowdot_cols_f64(w->ctx, dl.data(), dZ.data(), f, out.data(), hf, (int64_t)h * f, rows, f, S0), "hnh_rowdot_cols_f64");
-        w->check(be->hnh_attn_add_pack_f64(w->ctx, Q.data(), qw, dZ.data(), f, M.data(), mw, lse, dl.data(), rows, f, S0), "hnh_attn_add_pack_f64");
+        if (drop)
+            w->check(be->hnh_attn_drop_pack_f64(w->ctx, Q.data(), qw, dZ.data(), f, M.data(), mw, lse, dl.data(), rows, f, dr.row_id0, S0),
+                     "hnh_attn_drop_pack_f64");
+        else w->check(be->hnh_attn_add_pack_f64(w->ctx, Q.data(), qw, dZ.data(), f, M.data(), mw, lse, dl.data(), rows, f, S0), "hnh_attn_add_pack_f64");
         hnh_attn_add g = {};
         g.M = M.data();
         g.ld_m = mw;
@@ -551,12 +655,12 @@ private:
             if (ok) {
                 d_ops->setRValue(mw);
                 g.vec = D.data();
-                ok = ds->attnAdditive_pass(1, M, g, rows, true);  // row side: ds
+                ok = ds->attnAdditive_pass(1, M, g, rows, true, drop ? &dr : nullptr);  // row side: ds
             }
             if (ok) {
                 d_ops->setRValue(qw);
                 g.vec = D.data() + 1;
-                ok = ds->attnAdditive_pass(2, Q, g, rows, true);  // column side: dAgg, dt
+                ok = ds->attnAdditive_pass(2, Q, g, rows, true, drop ? &dr : nullptr);  // column side: dAgg, dt
             }
         } catch (...) {
             d_ops->setRValue(f);
@@ -599,7 +703,8 @@ private:
     }
 
     void shape_scored(int i, DenseMatrix& M) {
-        const int64_t rows = buffers[i].rows(), cols = HNH_ATTN_ADD_SCORED_WIDTH(layers[i].features_per_head);
+        const int f = layers[i].features_per_head;
+        const int64_t rows = buffers[i].rows(), cols = attn_p_ > 0.0 ? HNH_ATTN_DROP_SCORED_WIDTH(f) : HNH_ATTN_ADD_SCORED_WIDTH(f);
         if (M.rows() != rows || M.cols() != cols) M = DenseMatrix(rows, cols);
     }
 
@@ -607,6 +712,12 @@ private:
     void head_scores(int i, int j, DenseMatrix& A, DenseMatrix& M, int stream) {
         hnh::World* w = d_ops->world;
         const int f = layers[i].features_per_head;
+        if (attn_p_ > 0.0) {  // M' = [A (0) | s t | id 0]
+            w->check(w->be->hnh_attn_drop_scores_f64(w->ctx, M.data(), M.cols(), A.data(), A.cols(), layers[i].a1.data() + (int64_t)j * f,
+                                                     layers[i].a2.data() + (int64_t)j * f, A.rows(), f, d_ops->aSubmatrices[0].topRow, stream),
+                     "hnh_attn_drop_scores_f64");
+            return;
+        }
         w->check(w->be->hnh_attn_add_scores_f64(w->ctx, M.data(), M.cols(), A.data(), A.cols(), layers[i].a1.data() + (int64_t)j * f,
                                                 layers[i].a2.data() + (int64_t)j * f, A.rows(), f, stream),
                  "hnh_attn_add_scores_f64");
@@ -615,7 +726,7 @@ private:
     // A = buffers[i] * W_j (gat.hpp:88) on `stream`
     void head_product(int i, int j, DenseMatrix& A, int stream) {
         hnh::World* w = d_ops->world;
-        DenseMatrix& X = buffers[i];
+        DenseMatrix& X = layer_input(i);
         DenseMatrix& W = layers[i].wMats[j];
         if (X.cols() != W.rows()) hnh::fatal("Error, GAT weight shape does not match the layer input!");
         shape_product(i, A);
@@ -651,7 +762,8 @@ private:
             bool ok = ds != nullptr;
             d_ops->setRValue((int)A.cols());
             try {
-                ok = ok && ds->attnAdditive_pass(0, A, g, rows, true);
+                const hnh_attn_drop dr = attn_drop_args(i, j);
+                ok = ok && ds->attnAdditive_pass(0, A, g, rows, true, attn_p_ > 0.0 ? &dr : nullptr);
             } catch (...) {
                 d_ops->setRValue(f);
                 throw;

@@ -187,19 +187,35 @@ bool StandardKernel::attn_grad_block(SpmatLocal& S, int block, const hnh_attn_gr
 }
 
 bool KernelImplementation::attn_additive_local(SpmatLocal& S, int block, const hnh_attn_add& args, int pass, unsigned flags, int64_t rows, bool finish) {
+    return attn_additive_local(S, block, args, pass, flags, rows, finish, nullptr);
+}
+
+bool KernelImplementation::attn_additive_local(SpmatLocal& S, int block, const hnh_attn_add& args, int pass, unsigned flags, int64_t rows, bool finish,
+                                               const hnh_attn_drop* drop) {
     StandardKernel* k = dynamic_cast<StandardKernel*>(this);
-    return k != nullptr && k->attn_additive_block(S, block, args, pass, flags, rows, finish);
+    return k != nullptr && k->attn_additive_block(S, block, args, pass, flags, rows, finish, drop);
 }
 
 // The three passes of the additive-score attention (include/hnh_attn_additive.h), next to attn_grad_block: same block and window
 // handling; the forward pass's finish belongs to the pass's last call (win.last when windows are selected).
 bool StandardKernel::attn_additive_block(SpmatLocal& S, int block, const hnh_attn_add& args, int pass, unsigned flags, int64_t rows, bool finish) {
+    return attn_additive_block(S, block, args, pass, flags, rows, finish, nullptr);
+}
+
+// ... and with `drop` their DROP instances (include/hnh_attn_dropout.h): the same calls with one more argument.
+bool StandardKernel::attn_additive_block(SpmatLocal& S, int block, const hnh_attn_add& args, int pass, unsigned flags, int64_t rows, bool finish,
+                                         const hnh_attn_drop* drop) {
     hnh::World* w = S.world;
-    auto fn = pass == 0 ? w->be->hnh_attn_add_fwd_csr_p : (pass == 1 ? w->be->hnh_attn_add_row_csr_p : w->be->hnh_attn_add_col_csr_p);
-    const char* name = pass == 0 ? "hnh_attn_add_fwd_csr_p" : (pass == 1 ? "hnh_attn_add_row_csr_p" : "hnh_attn_add_col_csr_p");
-    if (fn == nullptr)
+    auto plain = pass == 0 ? w->be->hnh_attn_add_fwd_csr_p : (pass == 1 ? w->be->hnh_attn_add_row_csr_p : w->be->hnh_attn_add_col_csr_p);
+    auto masked = pass == 0 ? w->be->hnh_attn_drop_fwd_csr_p : (pass == 1 ? w->be->hnh_attn_drop_row_csr_p : w->be->hnh_attn_drop_col_csr_p);
+    const char* name = drop ? (pass == 0 ? "hnh_attn_drop_fwd_csr_p" : (pass == 1 ? "hnh_attn_drop_row_csr_p" : "hnh_attn_drop_col_csr_p"))
+                            : (pass == 0 ? "hnh_attn_add_fwd_csr_p" : (pass == 1 ? "hnh_attn_add_row_csr_p" : "hnh_attn_add_col_csr_p"));
+    if (drop ? masked == nullptr : plain == nullptr)
         throw hnh::Error(std::string("Error, the additive attention score needs the kernel ") + name + ", which the kernel library " + w->be->path +
-                         " does not export (include/hnh_attn_additive.h)");
+                         " does not export (" + (drop ? "include/hnh_attn_dropout.h" : "include/hnh_attn_additive.h") + ")");
+    auto fn = [&](hnh_ctx* ctx, const hnh_csr_block* b, const hnh_attn_add* a, unsigned fl, const hnh_csr_window* win, int stream) {
+        return drop ? masked(ctx, b, a, drop, fl, win, stream) : plain(ctx, b, a, fl, win, stream);
+    };
     const unsigned f = flags | ((pass == 0 && finish) ? HNH_ATTN_FINISH : 0u);
     CSRLocal* blk = S.csr_blocks[block];
     if (blk == nullptr || blk->num_coords == 0) {  // no nonzeros; the reset / zeroing of an overwrite and the forward finish still apply
@@ -217,7 +233,7 @@ bool StandardKernel::attn_additive_block(SpmatLocal& S, int block, const hnh_att
     const bool windowed = blk->window_args(&win);
     if (windowed && pass == 0 && finish && !win.last) hnh::fatal("Error, the additive forward finish belongs to the block's last window!");
     w->check(fn(w->ctx, &desc, &args, f, windowed ? &win : nullptr, HNH_STREAM_COMPUTE), name);
-    end(w, (profile && !windowed) ? w->be->hnh_panel_count(w->ctx, desc.rows, desc.nnz, desc.cols, pass == 2 ? HNH_ATTN_ADD_PACKED_WIDTH(args.f) : HNH_ATTN_ADD_SCORED_WIDTH(args.f), desc.max_row_nnz)
+    end(w, (profile && !windowed) ? w->be->hnh_panel_count(w->ctx, desc.rows, desc.nnz, desc.cols, (pass == 2 || drop) ? HNH_ATTN_ADD_PACKED_WIDTH(args.f) : HNH_ATTN_ADD_SCORED_WIDTH(args.f), desc.max_row_nnz)
                                    : 1);
     return true;
 }

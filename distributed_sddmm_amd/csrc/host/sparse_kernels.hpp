@@ -79,6 +79,11 @@ public:
     // the rows of the output (used when the block is absent).  Returns false, having done nothing, when the implementation has no such
     // pass.  NOT virtual, for softmax_local's reason.
     bool attn_additive_local(SpmatLocal& S, int block, const hnh_attn_add& args, int pass, unsigned flags, int64_t rows, bool finish);
+    // The same pass with attention dropout (include/hnh_attn_dropout.h) when `drop` is not null: args.Y is then M' / Q', whose rows carry
+    // their global ids, and drop->row_id0 is the global id of the block's row 0.  An overload, not a changed signature and not a virtual:
+    // the symbol above stays, and no vtable changes.
+    bool attn_additive_local(SpmatLocal& S, int block, const hnh_attn_add& args, int pass, unsigned flags, int64_t rows, bool finish,
+                             const hnh_attn_drop* drop);
 
     // Row windows (CSRLocal::window): a schedule may select one column range of a block before calling the kernels, to
     // work on data that arrives piece by piece.  An implementation that honours CSRLocal::window says so here; for the
@@ -160,6 +165,8 @@ public:
     bool attn_grad_block(SpmatLocal& S, int block, const hnh_attn_grad& args, bool column_side, unsigned flags, int64_t rows);
     // KernelImplementation::attn_additive_local's pass (non-virtual: see there)
     bool attn_additive_block(SpmatLocal& S, int block, const hnh_attn_add& args, int pass, unsigned flags, int64_t rows, bool finish);
+    bool attn_additive_block(SpmatLocal& S, int block, const hnh_attn_add& args, int pass, unsigned flags, int64_t rows, bool finish,
+                             const hnh_attn_drop* drop);
     ~StandardKernel() override;
 
 private:

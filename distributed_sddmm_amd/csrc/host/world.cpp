@@ -122,6 +122,9 @@ Backend* load_backend(const char* path_c) {
     HNH_BIND_OPTIONAL(hnh_attn_grad_row_csr_p) HNH_BIND_OPTIONAL(hnh_attn_grad_col_csr_p) HNH_BIND_OPTIONAL(hnh_attn_grad_pack_f64)
     HNH_BIND_OPTIONAL(hnh_attn_add_fwd_csr_p) HNH_BIND_OPTIONAL(hnh_attn_add_row_csr_p) HNH_BIND_OPTIONAL(hnh_attn_add_col_csr_p)
     HNH_BIND_OPTIONAL(hnh_attn_add_scores_f64) HNH_BIND_OPTIONAL(hnh_attn_add_pack_f64) HNH_BIND_OPTIONAL(hnh_attn_add_update_f64)
+    HNH_BIND_OPTIONAL(hnh_attn_drop_fwd_csr_p) HNH_BIND_OPTIONAL(hnh_attn_drop_row_csr_p) HNH_BIND_OPTIONAL(hnh_attn_drop_col_csr_p)
+    HNH_BIND_OPTIONAL(hnh_attn_drop_scores_f64) HNH_BIND_OPTIONAL(hnh_attn_drop_pack_f64) HNH_BIND_OPTIONAL(hnh_feat_drop_f64)
+    HNH_BIND_OPTIONAL(hnh_dropout_words_u32)
 #undef HNH_BIND_OPTIONAL
 #ifdef HNH_MEASUREMENT_AIDS
     HNH_BIND(hnh_stream_delay_us) HNH_BIND(hnh_stream_paced_copy) HNH_BIND(hnh_stream_pace_begin) HNH_BIND(hnh_stream_pace_end)

@@ -260,6 +260,18 @@ int hnh_gat_set_score(hnh_gat* g, int mode);
 int hnh_gat_set_attn_vectors(hnh_gat* g, int layer, int head, const double* a1_host, const double* a2_host);
 int hnh_gat_get_attn_grads(hnh_gat* g, int layer, int head, double* da1_host, double* da2_host);
 
+/* Dropout (include/hnh_attn_dropout.h): rate attention_p on the normalised attention coefficients (score ADDITIVE only: requesting it
+ * with score DOT makes hnh_gat_forward fail with an error naming score dot) and feature_p on every layer's input, both in [0, 1)
+ * (anything else fails here), with masks recomputed in every pass from Philox-4x32-10 keyed by (seed, layer, head, global row, global
+ * column): results do not depend on the rank count or on how a schedule splits a pass.  Rates (0, 0) are the default and launch the
+ * kernels without dropout.  Both calls invalidate the stored forward pass, so hnh_gat_backward always differentiates the masks of the
+ * forward pass it follows.  A kernel library without the group makes hnh_gat_forward fail with an error naming the missing symbol. */
+int hnh_gat_set_dropout(hnh_gat* g, double attention_p, double feature_p, uint64_t seed);
+int hnh_gat_set_dropout_seed(hnh_gat* g, uint64_t seed);
+/* Word 0 of Philox-4x32-10 with counter (gi, gj, w2, stream) and key (seed & 0xffffffff, seed >> 32): the masks' generator, on the host
+ * (stream 0: attention, w2 = layer * 65536 + head; stream 1: features, w2 = layer).  An entry is kept iff the word is >= floor(p 2^32). */
+uint32_t hnh_dropout_word(uint64_t seed, uint32_t stream, uint32_t w2, uint32_t gi, uint32_t gj);
+
 #ifdef __cplusplus
 }
 #endif

@@ -219,6 +219,28 @@ class AttnDrop(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("w2", C.c_uint32), ("threshold", C.c_uint32), ("scale", _dbl), ("row_id0", _i64)]
 
 
+# include/hnh_train.h: the training step's cross-entropy head and table-driven optimizer; a sixth OPTIONAL group bound only for the
+# product library
+TRAIN_SIGNATURES = {
+    "hnh_xent_rows_f64_workspace": (_i64, [_i64]),
+    "hnh_xent_rows_f64": (_i32, [_vp, _vp, _i64, _vp, _i64, _i32, _i32, _dbl, _vp, _i64, _vp, _vp, _i64, _i32]),
+    "hnh_optim_step_f64": (_i32, [_vp, _vp, _i32, _vp, _i32]),
+}
+XENT_MAX_WIDTH = 4096  # HNH_XENT_MAX_WIDTH
+OPTIM_ADAM, OPTIM_SGD, OPTIM_MAX_TENSORS = 0, 1, 32  # HNH_OPTIM_*
+
+
+class OptimTensor(C.Structure):
+    """struct hnh_optim_tensor"""
+    _fields_ = [("p", _vp), ("ld_p", _i64), ("g", _vp), ("ld_g", _i64), ("m", _vp), ("v", _vp), ("rows", _i64), ("cols", _i64)]
+
+
+class Optim(C.Structure):
+    """struct hnh_optim"""
+    _fields_ = [("kind", _i32), ("reserved", _i32), ("lr", _dbl), ("beta1", _dbl), ("beta2", _dbl), ("eps", _dbl), ("momentum", _dbl),
+                ("weight_decay", _dbl), ("bias1", _dbl), ("bias2", _dbl)]
+
+
 class AttnState(C.Structure):
     """struct hnh_attn_state"""
     _fields_ = [("row_max", _vp), ("row_sum", _vp), ("lse", _vp), ("leaky_alpha", _dbl), ("relu_dst", _vp), ("relu_ld", _i64)]
@@ -281,7 +303,7 @@ def load(path: str | None = None) -> C.CDLL:
         fn.restype, fn.argtypes = res, args
     if path is None or os.path.abspath(p) == os.path.abspath(LIB_PATH):
         for name, (res, args) in list(GRAD_SIGNATURES.items()) + list(ATTN_SIGNATURES.items()) + list(ATTN_GRAD_SIGNATURES.items()) + \
-                list(ATTN_ADD_SIGNATURES.items()) + list(ATTN_DROP_SIGNATURES.items()):
+                list(ATTN_ADD_SIGNATURES.items()) + list(ATTN_DROP_SIGNATURES.items()) + list(TRAIN_SIGNATURES.items()):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
     if path is None:

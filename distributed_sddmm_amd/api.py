@@ -138,6 +138,14 @@ SIGNATURES = {
     "hnh_gat_get_attn_grads": (_i32, [_vp, _i32, _i32, _vp, _vp]),
     "hnh_gat_set_dropout": (_i32, [_vp, _dbl, _dbl, C.c_uint64]),
     "hnh_gat_set_dropout_seed": (_i32, [_vp, C.c_uint64]),
+    "hnh_gat_get_weight": (_i32, [_vp, _i32, _i32, _vp]),
+    "hnh_gat_get_attn_vectors": (_i32, [_vp, _i32, _i32, _vp, _vp]),
+    "hnh_gat_set_labels": (_i32, [_vp, _vp, _vp, _i64, _i32]),
+    "hnh_gat_loss": (_i32, [_vp, _vp, _i64, _vp, _pdbl, _pdbl]),
+    "hnh_gat_set_optimizer": (_i32, [_vp, _i32, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl]),
+    "hnh_gat_optimizer_step": (_i32, [_vp]),
+    "hnh_gat_train_step": (_i32, [_vp, _pdbl, _pdbl]),
+    "hnh_gat_evaluate": (_i32, [_vp, _vp, _i64, _pdbl, _pdbl]),
     "hnh_dropout_word": (C.c_uint32, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
 }
 
@@ -656,6 +664,10 @@ class GAT:
 
     SCORE = {"dot": 0, "additive": 1}  # HNH_GAT_SCORE_DOT / _ADDITIVE
 
+    HEADS = {"mean": 0, "concat": 1}  # HNH_GAT_HEADS_MEAN / _CONCAT
+
+    OPTIMIZER = {"adam": 0, "sgd": 1}  # HNH_GAT_OPTIMIZER_ADAM / _SGD
+
     def __init__(self, op: DistributedSparse, layers, leaky_relu_alpha: float = 0.2, attention: str = "none", backward: str = "unfused",
                  score: str = "dot", dropout=(0.0, 0.0), seed: int = 0):
         self.op, self.layers = op, [tuple(l) for l in layers]
@@ -763,6 +775,81 @@ class GAT:
     def get_input_grad(self, dx: Dense):
         """dL/d(input) after backwardPass, in the layout of buffer 0 (set_input's)."""
         _check(lib().hnh_gat_get_input_grad(self.h, dx.h), "gat_get_input_grad")
+
+    # ---- training (include/hnh_train.h)
+    def get_weight(self, layer: int, head: int) -> np.ndarray:
+        out = np.empty(self.weight_shape(layer, head))
+        _check(lib().hnh_gat_get_weight(self.h, layer, head, out.ctypes.data), "gat_get_weight")
+        return out
+
+    def get_attention_vectors(self, layer: int, head: int):
+        """(a1, a2) of (layer, head): zero until set or trained."""
+        f = self.layers[layer][1]
+        a1, a2 = np.empty(f), np.empty(f)
+        _check(lib().hnh_gat_get_attn_vectors(self.h, layer, head, a1.ctypes.data, a2.ctypes.data), "gat_get_attn_vectors")
+        return a1, a2
+
+    def _mask(self, mask):
+        if mask is None:
+            return None, 0
+        m = np.ascontiguousarray(np.asarray(mask).astype(bool), dtype=np.uint8)
+        if m.ndim != 1:
+            raise ValueError("a mask is a one-dimensional array with one entry per global row")
+        return m, len(m)
+
+    def set_labels(self, labels, train_mask=None, heads: str = "mean"):
+        """Class labels and the training mask: host arrays with one entry per global row of the operator (the numbering of get_output's
+        rows); a negative label or a row outside the mask is not in the loss.  heads "mean": the logits are the mean over the last
+        layer's heads (features_per_head classes); "concat": the row as it is (num_heads * features_per_head classes).  Each rank keeps
+        its slice on the device; collective.  A label out of range, a mask without a labelled row or a wrong length raises."""
+        if heads not in self.HEADS:
+            raise ValueError("heads must be one of %s, not %r" % (sorted(self.HEADS), heads))
+        lab = np.ascontiguousarray(labels, dtype=np.int32)
+        if lab.ndim != 1:
+            raise ValueError("labels is a one-dimensional array with one entry per global row")
+        m, n = self._mask(train_mask)
+        if m is not None and n != len(lab):
+            raise ValueError("labels and train_mask differ in length: %d and %d" % (len(lab), n))
+        _check(lib().hnh_gat_set_labels(self.h, lab.ctypes.data, None if m is None else m.ctypes.data, len(lab), self.HEADS[heads]), "gat_set_labels")
+
+    def loss(self, mask=None, grad_out: Dense | None = None):
+        """(loss, accuracy) of the stored forward pass over the labelled rows of `mask` (None: the training rows): the mean softmax
+        cross-entropy and the share of rows whose argmax is the label, over the whole world.  grad_out receives dL/d(output), which
+        backwardPass takes."""
+        m, n = self._mask(mask)
+        lo, acc = C.c_double(), C.c_double()
+        _check(lib().hnh_gat_loss(self.h, None if m is None else m.ctypes.data, n, grad_out.h if grad_out is not None else None, C.byref(lo), C.byref(acc)),
+               "gat_loss")
+        return lo.value, acc.value
+
+    def set_optimizer(self, kind: str, lr: float, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8, momentum: float = 0.0,
+                      weight_decay: float = 0.0):
+        """"adam" or "sgd" (with momentum) over every W, and a1, a2 with score "additive"; weight decay is added to the gradient.
+        (Re)allocates zeroed moments and resets the step count."""
+        if kind not in self.OPTIMIZER:
+            raise ValueError("optimizer must be one of %s, not %r" % (sorted(self.OPTIMIZER), kind))
+        _check(lib().hnh_gat_set_optimizer(self.h, self.OPTIMIZER[kind], float(lr), float(beta1), float(beta2), float(eps), float(momentum),
+                                           float(weight_decay)), "gat_set_optimizer")
+
+    def optimizer_step(self):
+        """One optimizer step from the gradients of the last backwardPass, on the device.  Invalidates the stored forward pass."""
+        _check(lib().hnh_gat_optimizer_step(self.h), "gat_optimizer_step")
+
+    def train_step(self):
+        """Forward pass, loss over the training rows, backward pass and optimizer step on the device; returns (loss, accuracy) of the
+        parameters before the update, the call's only host synchronisation.  With a nonzero dropout rate the seed advances by one
+        first: step t of a run uses the masks of seed + t."""
+        lo, acc = C.c_double(), C.c_double()
+        _check(lib().hnh_gat_train_step(self.h, C.byref(lo), C.byref(acc)), "gat_train_step")
+        return lo.value, acc.value
+
+    def evaluate(self, mask=None):
+        """(loss, accuracy) over the labelled rows of `mask` from a forward pass without dropout and without a gradient; rates and seed
+        are as before afterwards."""
+        m, n = self._mask(mask)
+        lo, acc = C.c_double(), C.c_double()
+        _check(lib().hnh_gat_evaluate(self.h, None if m is None else m.ctypes.data, n, C.byref(lo), C.byref(acc)), "gat_evaluate")
+        return lo.value, acc.value
 
     def free(self):
         if self.h:

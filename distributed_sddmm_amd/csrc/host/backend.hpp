@@ -12,6 +12,7 @@
 #include "hnh_attn_grad.h"
 #include "hnh_grad.h"
 #include "hnh_kernels.h"
+#include "hnh_train.h"
 #ifdef HNH_MEASUREMENT_AIDS
 #include "hnh_measurement_aids.h"
 #endif
@@ -57,6 +58,8 @@ struct Backend {
     // OPTIONAL group (include/hnh_attn_dropout.h), bound the same way: only the GAT's dropout needs it
     HNH_FN(hnh_attn_drop_fwd_csr_p) HNH_FN(hnh_attn_drop_row_csr_p) HNH_FN(hnh_attn_drop_col_csr_p)
     HNH_FN(hnh_attn_drop_scores_f64) HNH_FN(hnh_attn_drop_pack_f64) HNH_FN(hnh_feat_drop_f64) HNH_FN(hnh_dropout_words_u32)
+    // OPTIONAL group (include/hnh_train.h), bound the same way: only the GAT's loss, optimizer and training step need it
+    HNH_FN(hnh_xent_rows_f64_workspace) HNH_FN(hnh_xent_rows_f64) HNH_FN(hnh_optim_step_f64)
 #ifdef HNH_MEASUREMENT_AIDS
     HNH_FN(hnh_stream_delay_us) HNH_FN(hnh_stream_paced_copy) HNH_FN(hnh_stream_pace_begin) HNH_FN(hnh_stream_pace_end)
 #endif

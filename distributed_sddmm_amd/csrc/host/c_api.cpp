@@ -820,6 +820,48 @@ uint32_t hnh_dropout_word(uint64_t seed, uint32_t stream, uint32_t w2, uint32_t 
     }
     return c0;
 }
+int hnh_gat_get_weight(hnh_gat* g, int layer, int head, double* host) {
+    return guarded(g->w, [&] {
+        if (!host) throw hnh::Error("Error, hnh_gat_get_weight: null pointer!");
+        g->g->get_weight(layer, head, host);
+    });
+}
+int hnh_gat_get_attn_vectors(hnh_gat* g, int layer, int head, double* a1_host, double* a2_host) {
+    return guarded(g->w, [&] {
+        if (!a1_host || !a2_host) throw hnh::Error("Error, hnh_gat_get_attn_vectors: null pointer!");
+        g->g->get_attn_vectors(layer, head, a1_host, a2_host);
+    });
+}
+int hnh_gat_set_labels(hnh_gat* g, const int32_t* labels, const uint8_t* mask_or_null, int64_t n, int heads_mode) {
+    return guarded(g->w, [&] { g->g->set_labels(labels, mask_or_null, n, heads_mode); });
+}
+int hnh_gat_loss(hnh_gat* g, const uint8_t* mask_or_null, int64_t n, hnh_dense* grad_out_or_null, double* loss, double* accuracy) {
+    return guarded(g->w, [&] {
+        const std::pair<double, double> r = g->g->loss(mask_or_null, n, grad_out_or_null ? &grad_out_or_null->m : nullptr);
+        if (loss) *loss = r.first;
+        if (accuracy) *accuracy = r.second;
+    });
+}
+int hnh_gat_set_optimizer(hnh_gat* g, int kind, double lr, double beta1, double beta2, double eps, double momentum, double weight_decay) {
+    return guarded(g->w, [&] { g->g->set_optimizer(kind, lr, beta1, beta2, eps, momentum, weight_decay); });
+}
+int hnh_gat_optimizer_step(hnh_gat* g) {
+    return guarded(g->w, [&] { g->g->optimizer_step(); });
+}
+int hnh_gat_train_step(hnh_gat* g, double* loss, double* accuracy) {
+    return guarded(g->w, [&] {
+        const std::pair<double, double> r = g->g->train_step();
+        if (loss) *loss = r.first;
+        if (accuracy) *accuracy = r.second;
+    });
+}
+int hnh_gat_evaluate(hnh_gat* g, const uint8_t* mask_or_null, int64_t n, double* loss, double* accuracy) {
+    return guarded(g->w, [&] {
+        const std::pair<double, double> r = g->g->evaluate(mask_or_null, n);
+        if (loss) *loss = r.first;
+        if (accuracy) *accuracy = r.second;
+    });
+}
 int hnh_gat_backward(hnh_gat* g, hnh_dense* grad_out) {
     return guarded(g->w, [&] { g->g->backwardPass(grad_out->m); });
 }

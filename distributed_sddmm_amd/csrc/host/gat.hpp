@@ -64,9 +64,20 @@
 //     feature_p > 0 (wherever the passes themselves are supported, one dense block per rank): layer l keeps Xd = c_q mask o X, made on
 //         the compute stream before the product stage starts; Xd replaces X in the head products and in dW = Xd^T dA_all, and
 //         input_grads[l] = c_q mask o (dA_all Wt).
+//
+// Training (an addition; include/hnh_train.h).  set_labels keeps this rank's slice of the labels on the device (local row r is global row
+// aSubmatrices[0].topRow + r, the numbering of the output's rows; a negative label or a row outside the mask is not in the loss) and sums the
+// labelled count over the world once.  loss() is ONE pass over the last buffer: masked softmax cross-entropy of z = the mean over the last
+// layer's heads (HNH_GAT_HEADS_MEAN) or of the whole row (HNH_GAT_HEADS_CONCAT), with loss_sum, correct and G = dL/d(output) from the same
+// read; the two sums are all-reduced like dW.  optimizer_step() is one table-driven launch over every W (and a1, a2 with score ADDITIVE):
+// weight_grads / attn_grads are identical on every rank, so every rank applies the same update and the parameters stay equal bit for bit
+// without a broadcast.  train_step() = [seed + 1 when a dropout rate is nonzero] forwardPass, loss into an internal G, backwardPass,
+// optimizer_step, all on the compute stream; the host waits once, for the two scalars (of the parameters BEFORE the update).
+// Known deviation from the published output layer: the heads pass through the ReLU epilogue before they are averaged.
 #pragma once
 #include "dense_shift_15d.hpp"
 #include "distributed_sparse.hpp"
+#include <cmath>
 #include <cstdlib>
 #include <map>
 #include <tuple>
@@ -286,6 +297,190 @@ public:
             backward_layer(i, *G);
             G = &input_grads[(size_t)i];
         }
+        grads_fresh_ = true;  // (optimizer_step takes them once)
+    }
+
+    // ---- training (include/hnh_train.h)
+    // Labels and training mask as HOST arrays of d_ops->M entries in the operator's global row numbering (mask == nullptr: every row with
+    // a label >= 0).  heads_mode: HNH_GAT_HEADS_MEAN (classes = the last layer's features_per_head) | HNH_GAT_HEADS_CONCAT (classes =
+    // num_heads * features_per_head).  Collective: the labelled count is summed over the world.
+    void set_labels(const int32_t* labels, const uint8_t* mask, int64_t n, int heads_mode) {
+        if (heads_mode != HNH_GAT_HEADS_MEAN && heads_mode != HNH_GAT_HEADS_CONCAT)
+            throw hnh::Error("Error, unknown GAT label heads mode " + std::to_string(heads_mode) + " (mean = 0, concat = 1)!");
+        if (labels == nullptr) throw hnh::Error("Error, GAT set_labels: null labels!");
+        if (n != d_ops->M)
+            throw hnh::Error("Error, GAT set_labels needs one label per global row: " + std::to_string(d_ops->M) + " entries, not " + std::to_string(n) + "!");
+        check_whole_rows("set_labels");
+        std::vector<int32_t> keep_labels(labels, labels + n);
+        std::vector<uint8_t> keep_mask;
+        if (mask) keep_mask.assign(mask, mask + n);
+        const int old_mode = label_heads_;
+        label_heads_ = heads_mode;
+        try {
+            labels_host_.swap(keep_labels);
+            train_set_ = make_label_set(keep_mask.empty() ? nullptr : keep_mask.data());
+        } catch (...) {
+            labels_host_.swap(keep_labels);  // a refused call leaves the object as it was
+            label_heads_ = old_mode;
+            throw;
+        }
+        train_mask_.swap(keep_mask);
+        labels_set_ = true;
+    }
+
+    // (loss, accuracy) of the stored forward pass over the rows of `mask` (HOST, global numbering; nullptr: the training rows of set_labels);
+    // grad_out != nullptr also receives dL/d(output) in the last buffer's layout, which backwardPass takes.  Collective.
+    std::pair<double, double> loss(const uint8_t* mask, int64_t n, DenseMatrix* grad_out) {
+        check_train_supported(false);
+        if (!forward_valid_) throw hnh::Error("Error, GAT loss needs a forwardPass first (and a new one after set_weight / set_input / optimizer_step)!");
+        if (mask != nullptr && n != d_ops->M) throw hnh::Error("Error, GAT loss: the mask needs " + std::to_string(d_ops->M) + " entries, not " + std::to_string(n) + "!");
+        const DenseMatrix& last = buffers.back();
+        if (grad_out != nullptr && (grad_out->rows() != last.rows() || grad_out->cols() != last.cols()))
+            throw hnh::Error("Error, GAT loss: the output gradient has the wrong shape!");
+        LabelSet other;
+        if (mask != nullptr) other = make_label_set(mask);
+        const LabelSet& ls = mask != nullptr ? other : train_set_;
+        loss_enqueue(ls, grad_out);
+        return loss_read(ls);
+    }
+
+    // (Re)allocates zeroed moments and resets the step count.  kind: HNH_OPTIM_ADAM | HNH_OPTIM_SGD (include/hnh_train.h).
+    void set_optimizer(int kind, double lr, double beta1, double beta2, double eps, double momentum, double weight_decay) {
+        if (kind != HNH_OPTIM_ADAM && kind != HNH_OPTIM_SGD) throw hnh::Error("Error, unknown GAT optimizer " + std::to_string(kind) + " (adam = 0, sgd = 1)!");
+        if (!(lr >= 0.0) || !std::isfinite(lr) || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0) || !(eps >= 0.0) || !(momentum >= 0.0 && momentum < 1.0) ||
+            !(weight_decay >= 0.0) || !std::isfinite(weight_decay) || !std::isfinite(eps))
+            throw hnh::Error("Error, GAT set_optimizer needs lr, eps, weight_decay >= 0 and beta1, beta2, momentum in [0, 1)!");
+        optim_ = {};
+        optim_.kind = kind;
+        optim_.lr = lr;
+        optim_.beta1 = beta1;
+        optim_.beta2 = beta2;
+        optim_.eps = eps;
+        optim_.momentum = momentum;
+        optim_.weight_decay = weight_decay;
+        const size_t L = layers.size();
+        mom_w_.assign(L, std::vector<DenseMatrix>());
+        var_w_.assign(L, std::vector<DenseMatrix>());
+        mom_a_.assign(L * 2, DenseMatrix());
+        var_a_.assign(L * 2, DenseMatrix());
+        for (size_t i = 0; i < L; i++) {
+            const int64_t hf = (int64_t)layers[i].num_heads * layers[i].features_per_head;
+            for (const DenseMatrix& W : layers[i].wMats) {
+                mom_w_[i].push_back(kind == HNH_OPTIM_ADAM ? DenseMatrix::Constant(W.rows(), W.cols(), 0.0) : DenseMatrix());
+                var_w_[i].push_back(DenseMatrix::Constant(W.rows(), W.cols(), 0.0));
+            }
+            for (int q = 0; q < 2; q++) {
+                if (kind == HNH_OPTIM_ADAM) mom_a_[i * 2 + q] = DenseMatrix::Constant(hf, 1, 0.0);
+                var_a_[i * 2 + q] = DenseMatrix::Constant(hf, 1, 0.0);
+            }
+        }
+        optim_steps_ = 0;
+        optimizer_set_ = true;
+    }
+    int64_t optimizer_steps() const { return optim_steps_; }
+
+    // One optimizer step from the gradients of the last backwardPass: every W, and a1, a2 with score ADDITIVE, in one table.  Invalidates
+    // the stored forward pass.  No host synchronisation.
+    void optimizer_step() {
+        const hnh::Backend* be = d_ops->world->be;
+        if (!optimizer_set_) throw hnh::Error("Error, GAT optimizer_step needs set_optimizer first!");
+        if (be->hnh_optim_step_f64 == nullptr) throw_missing_train_kernel("hnh_optim_step_f64");
+        const bool additive = score_ == HNH_GAT_SCORE_ADDITIVE;
+        if (!grads_fresh_ || weight_grads.size() != layers.size() || (additive && attn_grads.size() != layers.size()))
+            throw hnh::Error("Error, GAT optimizer_step needs the gradients of a backwardPass since the last step!");
+        std::vector<hnh_optim_tensor> table;
+        for (size_t i = 0; i < layers.size(); i++) {
+            GATLayer& L = layers[i];
+            const int64_t f = L.features_per_head, hf = (int64_t)L.num_heads * f;
+            const DenseMatrix& dW = weight_grads[i];
+            for (int h = 0; h < L.num_heads; h++) {
+                DenseMatrix& W = L.wMats[(size_t)h];
+                if (dW.rows() != W.rows() || dW.cols() != hf || W.cols() != f) throw hnh::Error("Error, GAT optimizer_step: a weight gradient has the wrong shape!");
+                table.push_back({W.data(), f, dW.data() + (int64_t)h * f, hf, mom_w_[i][(size_t)h].data(), var_w_[i][(size_t)h].data(), W.rows(), f});
+            }
+            if (additive) {
+                ensure_attn_vectors((int)i);
+                const DenseMatrix& da = attn_grads[i];  // (hf x 2: da1 and da2 interleaved)
+                if (da.rows() != hf || da.cols() != 2) throw hnh::Error("Error, GAT optimizer_step: an attention-vector gradient has the wrong shape!");
+                table.push_back({L.a1.data(), 1, da.data(), 2, mom_a_[i * 2].data(), var_a_[i * 2].data(), hf, 1});
+                table.push_back({L.a2.data(), 1, da.data() + 1, 2, mom_a_[i * 2 + 1].data(), var_a_[i * 2 + 1].data(), hf, 1});
+            }
+        }
+        optim_steps_++;
+        hnh_optim hy = optim_;
+        hy.bias1 = 1.0 - std::pow(hy.beta1, (double)optim_steps_);
+        hy.bias2 = 1.0 - std::pow(hy.beta2, (double)optim_steps_);
+        hnh::World* w = d_ops->world;
+        w->check(be->hnh_optim_step_f64(w->ctx, table.data(), (int)table.size(), &hy, HNH_STREAM_COMPUTE), "hnh_optim_step_f64");
+        grads_fresh_ = false;
+        invalidate_forward();
+    }
+
+    // One training step; returns (loss, accuracy) over the training rows, of the parameters before the update.  With a nonzero dropout
+    // rate the seed advances by one first, so step t of a run uses the masks of seed0 + t.
+    std::pair<double, double> train_step() {
+        check_train_supported(true);
+        check_dropout_supported();
+        check_backward_supported();
+        const uint64_t seed0 = seed_;
+        const int64_t steps0 = optim_steps_;
+        if (attn_p_ > 0.0 || feat_p_ > 0.0) seed_ += 1;  // (mod 2^64)
+        try {
+            forwardPass();
+            const DenseMatrix& last = buffers.back();
+            if (train_grad_.rows() != last.rows() || train_grad_.cols() != last.cols()) train_grad_ = DenseMatrix(last.rows(), last.cols());
+            loss_enqueue(train_set_, &train_grad_);
+            backwardPass(train_grad_);
+            optimizer_step();
+        } catch (...) {  // (a step that did not update leaves seed and step count as they were: step t keeps seed0 + t)
+            if (optim_steps_ == steps0) seed_ = seed0;
+            throw;
+        }
+        return loss_read(train_set_);
+    }
+
+    // (loss, accuracy) over the rows of `mask` (nullptr: the training rows) from a forward pass without dropout and without a gradient.
+    // Rates and seed are as before afterwards; the stored forward pass is valid only if both rates were 0.
+    std::pair<double, double> evaluate(const uint8_t* mask, int64_t n) {
+        check_train_supported(false);
+        check_dropout_supported();  // (an object that forwardPass and train_step refuse is not evaluated either)
+        if (mask != nullptr && n != d_ops->M) throw hnh::Error("Error, GAT evaluate: the mask needs " + std::to_string(d_ops->M) + " entries, not " + std::to_string(n) + "!");
+        LabelSet other;
+        if (mask != nullptr) other = make_label_set(mask);
+        const LabelSet& ls = mask != nullptr ? other : train_set_;
+        const double ap = attn_p_, fp = feat_p_;
+        attn_p_ = feat_p_ = 0.0;
+        std::pair<double, double> res;
+        try {
+            forwardPass();
+            loss_enqueue(ls, nullptr);
+            res = loss_read(ls);
+        } catch (...) {
+            attn_p_ = ap;
+            feat_p_ = fp;
+            invalidate_forward();
+            throw;
+        }
+        attn_p_ = ap;
+        feat_p_ = fp;
+        if (ap > 0.0 || fp > 0.0) invalidate_forward();
+        return res;
+    }
+
+    void get_weight(int i, int h, double* host) {
+        check_layer_head(i, h);
+        layers[(size_t)i].wMats[(size_t)h].copy_to_host(host);
+    }
+    void get_attn_vectors(int i, int h, double* a1_host, double* a2_host) {
+        check_layer_head(i, h);
+        ensure_attn_vectors(i);
+        GATLayer& L = layers[(size_t)i];
+        const int f = L.features_per_head;
+        hnh::World* w = d_ops->world;
+        w->sync_all();
+        w->copy(a1_host, L.a1.data() + (int64_t)h * f, (size_t)f * sizeof(double), HNH_COPY_D2H, HNH_STREAM_COMPUTE);
+        w->copy(a2_host, L.a2.data() + (int64_t)h * f, (size_t)f * sizeof(double), HNH_COPY_D2H, HNH_STREAM_COMPUTE);
+        w->sync(HNH_STREAM_COMPUTE);
     }
 
     std::vector<DenseMatrix> weight_grads, input_grads;
@@ -301,6 +496,117 @@ private:
     double attn_p_ = 0.0, feat_p_ = 0.0;  // dropout rates and the masks' seed (include/hnh_attn_dropout.h)
     uint64_t seed_ = 0;
     std::vector<DenseMatrix> xd_;         // feature dropout: Xd of every layer (allocated only then)
+    // training (include/hnh_train.h): this rank's labels on the device (-1: not in the loss) with the world's labelled count; the host's
+    // copy of all labels and of the training mask (loss / evaluate build other sets from them); the optimizer and its moments
+    struct LabelSet {
+        hnh::DeviceArray labels;
+        double count = 0.0;
+    };
+    bool labels_set_ = false, optimizer_set_ = false, grads_fresh_ = false;
+    int label_heads_ = HNH_GAT_HEADS_MEAN;
+    std::vector<int32_t> labels_host_;
+    std::vector<uint8_t> train_mask_;
+    LabelSet train_set_;
+    DenseMatrix train_grad_, loss_result_;
+    hnh_optim optim_ = {};
+    int64_t optim_steps_ = 0;
+    std::vector<std::vector<DenseMatrix>> mom_w_, var_w_;
+    std::vector<DenseMatrix> mom_a_, var_a_;  // [2 layer + (0: a1, 1: a2)]
+
+    void check_layer_head(int i, int h) const {
+        if (i < 0 || i >= (int)layers.size()) throw hnh::Error("Error, GAT layer index " + std::to_string(i) + " out of range: " + std::to_string(layers.size()) + " layers!");
+        if (h < 0 || h >= layers[(size_t)i].num_heads)
+            throw hnh::Error("Error, GAT head index " + std::to_string(h) + " out of range: layer " + std::to_string(i) + " has " + std::to_string(layers[(size_t)i].num_heads) + " heads!");
+    }
+    int label_classes() const {
+        const GATLayer& L = layers.back();
+        return label_heads_ == HNH_GAT_HEADS_MEAN ? L.features_per_head : L.num_heads * L.features_per_head;
+    }
+    // the labels live with the output's rows: one dense block of whole rows per rank
+    void check_whole_rows(const char* what) const {
+        if (d_ops->r_split || d_ops->aSubmatrices.size() != 1 || d_ops->aSubmatrices[0].leftCol != 0)
+            throw hnh::Error(std::string("Error, GAT ") + what + " needs one dense block of whole rows per rank, which " + d_ops->algorithm_name + " does not have!");
+    }
+    [[noreturn]] void throw_missing_train_kernel(const char* name) const {
+        throw hnh::Error(std::string("Error, GAT training needs the kernel ") + name + ", which the kernel library " + d_ops->world->be->path +
+                         " does not export (include/hnh_train.h)");
+    }
+    // Refuses before anything is launched: labels (and the optimizer) not set, then the kernel group, then the row width.
+    void check_train_supported(bool need_optimizer) {
+        if (!labels_set_) throw hnh::Error("Error, GAT loss / train_step / evaluate need set_labels first!");
+        if (need_optimizer && !optimizer_set_) throw hnh::Error("Error, GAT train_step needs set_optimizer first!");
+        const hnh::Backend* be = d_ops->world->be;
+        if (be->hnh_xent_rows_f64_workspace == nullptr) throw_missing_train_kernel("hnh_xent_rows_f64_workspace");
+        if (be->hnh_xent_rows_f64 == nullptr) throw_missing_train_kernel("hnh_xent_rows_f64");
+        if (need_optimizer && be->hnh_optim_step_f64 == nullptr) throw_missing_train_kernel("hnh_optim_step_f64");
+        const int64_t width = (int64_t)layers.back().num_heads * layers.back().features_per_head;
+        if (width > HNH_XENT_MAX_WIDTH)
+            throw hnh::Error("Error, GAT loss supports output rows of at most " + std::to_string(HNH_XENT_MAX_WIDTH) + " values, not " + std::to_string(width) +
+                             " (include/hnh_train.h)");
+        check_whole_rows("loss");
+    }
+    // This rank's slice of labels_host_ under `mask` (nullptr: every label >= 0), and the labelled count of the world.  Every rank sees
+    // the same host arrays, so a refusal is the same on all of them and happens before the collective.
+    LabelSet make_label_set(const uint8_t* mask) {
+        const int64_t M = d_ops->M;
+        const int classes = label_classes();
+        int64_t global = 0;
+        for (int64_t r = 0; r < M; r++) {
+            if (mask != nullptr && !mask[r]) continue;
+            const int32_t l = labels_host_[(size_t)r];
+            if (l >= classes)
+                throw hnh::Error("Error, GAT label " + std::to_string(l) + " of row " + std::to_string(r) + " is out of range: " + std::to_string(classes) + " classes!");
+            if (l >= 0) global++;
+        }
+        if (global == 0) throw hnh::Error("Error, the GAT label mask selects no labelled row!");
+        hnh::World* w = d_ops->world;
+        const int64_t rows = buffers.back().rows(), top = d_ops->aSubmatrices[0].topRow;
+        std::vector<int32_t> local((size_t)rows, -1);
+        double mine = 0.0;
+        for (int64_t r = 0; r < rows; r++) {
+            const int64_t gr = top + r;
+            if (gr >= M || (mask != nullptr && !mask[gr]) || labels_host_[(size_t)gr] < 0) continue;
+            local[(size_t)r] = labels_host_[(size_t)gr];
+            mine += 1.0;
+        }
+        LabelSet ls;
+        ls.labels = hnh::DeviceArray(w, (size_t)rows * sizeof(int32_t));
+        if (rows > 0) w->copy(ls.labels.ptr(), local.data(), (size_t)rows * sizeof(int32_t), HNH_COPY_H2D, HNH_STREAM_COMPUTE);
+        DenseMatrix cnt(1, 1);
+        w->copy(cnt.data(), &mine, sizeof(double), HNH_COPY_H2D, HNH_STREAM_COMPUTE);
+        w->allreduce_f64(w->world_comm(), cnt.data(), 1, HNH_STREAM_COMPUTE);
+        w->copy(&ls.count, cnt.data(), sizeof(double), HNH_COPY_D2H, HNH_STREAM_COMPUTE);
+        w->sync(HNH_STREAM_COMPUTE);  // (also: `local` and `mine` have been read)
+        if (ls.count != (double)global)
+            throw hnh::Error("Error, GAT labels: the ranks' rows hold " + std::to_string((int64_t)ls.count) + " labelled rows, the global arrays " + std::to_string(global) + "!");
+        return ls;
+    }
+    // the loss pass and the all-reduce of its two sums on the compute stream; G == nullptr: no gradient
+    void loss_enqueue(const LabelSet& ls, DenseMatrix* G) {
+        hnh::World* w = d_ops->world;
+        const hnh::Backend* be = w->be;
+        const DenseMatrix& out = buffers.back();
+        const GATLayer& L = layers.back();
+        const int heads = label_heads_ == HNH_GAT_HEADS_MEAN ? L.num_heads : 1;
+        if (loss_result_.size() != 2) loss_result_ = DenseMatrix(2, 1);
+        const int64_t need = be->hnh_xent_rows_f64_workspace(out.rows());
+        DenseMatrix& work = scratch(15, need, 1);
+        w->check(be->hnh_xent_rows_f64(w->ctx, out.data(), out.cols(), (const int32_t*)ls.labels.ptr(), out.rows(), heads, label_classes(), 1.0 / ls.count,
+                                       G ? G->data() : nullptr, out.cols(), loss_result_.data(), work.data(), need, HNH_STREAM_COMPUTE),
+                 "hnh_xent_rows_f64");
+        w->allreduce_f64(w->world_comm(), loss_result_.data(), 2, HNH_STREAM_COMPUTE);
+    }
+    std::pair<double, double> loss_read(const LabelSet& ls) {
+        hnh::World* w = d_ops->world;
+        double r[2] = {0.0, 0.0};
+        w->copy(r, loss_result_.data(), sizeof(r), HNH_COPY_D2H, HNH_STREAM_COMPUTE);
+        w->sync(HNH_STREAM_COMPUTE);
+        // a rank that met a bad label reports (NaN, -count); the sum over the world keeps the NaN, while other ranks' `correct` can lift
+        // the second word above 0
+        if (!(r[1] >= 0.0) || std::isnan(r[0]))
+            throw hnh::Error("Error, GAT loss is not a number: the device met a label outside its classes, or the output holds NaN!");
+        return {r[0] / ls.count, r[1] / ls.count};
+    }
     DenseMatrix scored[2];  // score ADDITIVE: [A (0) | s t] of the head in flight and of the next one (include/hnh_attn_additive.h)
     // softmax attention: the rows' running max / sum (reused by every head, which run one after the other on the compute stream), the
     // log-sum-exp of every (layer, head), and for the backward pass a column of ones and the broadcasts of lse and delta onto the nonzeros

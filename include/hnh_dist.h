@@ -272,6 +272,40 @@ int hnh_gat_set_dropout_seed(hnh_gat* g, uint64_t seed);
  * (stream 0: attention, w2 = layer * 65536 + head; stream 1: features, w2 = layer).  An entry is kept iff the word is >= floor(p 2^32). */
 uint32_t hnh_dropout_word(uint64_t seed, uint32_t stream, uint32_t w2, uint32_t gi, uint32_t gj);
 
+/* Training (an addition; kernels: include/hnh_train.h, an optional group — a kernel library without it makes hnh_gat_loss, hnh_gat_train_step,
+ * hnh_gat_evaluate and hnh_gat_optimizer_step fail with an error naming the missing symbol).  Supported wherever hnh_gat_backward is.
+ * Parameters can be read back: */
+int hnh_gat_get_weight(hnh_gat* g, int layer, int head, double* host);                            /* row-major, hnh_gat_weight_shape */
+int hnh_gat_get_attn_vectors(hnh_gat* g, int layer, int head, double* a1_host, double* a2_host); /* features_per_head doubles each */
+/* Labels: n = M host entries in the operator's global row numbering (the rows of hnh_gat_get_output: block row + local row); a negative
+ * label, or a row whose mask byte is 0 (mask_or_null == NULL: no mask), is not in the loss.  heads_mode MEAN: the classes are the last
+ * layer's features_per_head and the logits the mean over its heads; CONCAT: num_heads * features_per_head classes, the row as it is.
+ * (Known deviation: the heads pass through the forward pass's ReLU before they are averaged; the published output layer averages raw
+ * head outputs.)  Each rank keeps its slice on the device; the labelled count is summed over the world once (collective).  A label
+ * >= the class count, a mask without a labelled row or a wrong n fails and leaves the object as it was. */
+#define HNH_GAT_HEADS_MEAN 0
+#define HNH_GAT_HEADS_CONCAT 1
+int hnh_gat_set_labels(hnh_gat* g, const int32_t* labels, const uint8_t* mask_or_null, int64_t n, int heads_mode);
+/* Masked softmax cross-entropy of the stored forward pass (needs a valid one): *loss = the mean of -log p(label) and *accuracy = the share
+ * of rows whose argmax is the label, over the labelled rows of the mask (NULL: the training rows of hnh_gat_set_labels), both summed over
+ * the world.  grad_out_or_null receives dL/d(output) in the layout hnh_gat_backward takes. */
+int hnh_gat_loss(hnh_gat* g, const uint8_t* mask_or_null, int64_t n, hnh_dense* grad_out_or_null, double* loss, double* accuracy);
+/* kind ADAM: m = beta1 m + (1 - beta1) g', v = beta2 v + (1 - beta2) g'^2, p -= lr (m / (1 - beta1^t)) / (sqrt(v / (1 - beta2^t)) + eps);
+ * SGD: v = momentum v + g', p -= lr v; g' = g + weight_decay p.  (Re)allocates zeroed moments and resets the step count t. */
+#define HNH_GAT_OPTIMIZER_ADAM 0
+#define HNH_GAT_OPTIMIZER_SGD 1
+int hnh_gat_set_optimizer(hnh_gat* g, int kind, double lr, double beta1, double beta2, double eps, double momentum, double weight_decay);
+/* Applies the optimizer to the gradients of the last hnh_gat_backward — every W, and a1, a2 with score ADDITIVE — in one table-driven
+ * launch, and invalidates the stored forward pass.  The gradients are the same on every rank, so the parameters stay equal bit for bit. */
+int hnh_gat_optimizer_step(hnh_gat* g);
+/* One training step on the compute stream: [seed + 1 (mod 2^64) when a dropout rate is nonzero,] forward pass, loss over the training
+ * rows into an internal gradient, backward pass, optimizer step.  *loss and *accuracy are those of the parameters BEFORE the update; reading
+ * them is the call's only host synchronisation.  Fails before anything is launched when labels or optimizer are not set. */
+int hnh_gat_train_step(hnh_gat* g, double* loss, double* accuracy);
+/* Loss and accuracy over the mask's rows (NULL: the training rows) from a forward pass with both dropout rates 0 and no gradient.  Rates
+ * and seed are restored; the stored forward pass stays invalid whenever a rate was nonzero. */
+int hnh_gat_evaluate(hnh_gat* g, const uint8_t* mask_or_null, int64_t n, double* loss, double* accuracy);
+
 #ifdef __cplusplus
 }
 #endif

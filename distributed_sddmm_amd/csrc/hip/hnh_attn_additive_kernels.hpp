@@ -509,25 +509,6 @@ int attn_add_launch(hnh_ctx* ctx, hipStream_t st, const LongCtl& lc, int64_t row
     return HNH_OK;
 }
 
-// the instance that fits (f, alignment): exact widths 64 / 128 / 256, every other width bounds-checked (16-byte lanes when even)
-template <int PASS, bool DROP>
-int attn_add_launch_shape(hnh_ctx* ctx, hipStream_t st, const LongCtl& lc, bool w2, int64_t rows, const int32_t* rowptr, const int32_t* beg_ptr,
-                          const int32_t* end_ptr, const int32_t* colidx, const typename AaKernelArgs<DROP>::type& a, unsigned flags, bool run_long) {
-#define HNH_AA(L, V, WW, EX) return attn_add_launch<PASS, L, V, WW, EX, DROP>(ctx, st, lc, rows, rowptr, beg_ptr, end_ptr, colidx, a, flags, run_long)
-    const int f = a.f;
-    if (w2) {
-        if (f == 64) HNH_AA(32, 1, 2, true);
-        if (f == 128) HNH_AA(64, 1, 2, true);
-        if (f == 256) HNH_AA(64, 2, 2, true);
-        if (f < 128) HNH_AA(64, 1, 2, false);
-        HNH_AA(64, 2, 2, false);
-    }
-    if (f <= 64) HNH_AA(64, 1, 1, false);
-    if (f <= 128) HNH_AA(64, 2, 1, false);
-    HNH_AA(64, 4, 1, false);
-#undef HNH_AA
-}
-
 template <int PASS, bool DROP = false>
 int attn_add_dispatch(hnh_ctx* ctx, const hnh_csr_block* b, const hnh_attn_add* g, unsigned flags, const hnh_csr_window* win, int stream,
                       const char* who, const hnh_attn_drop* drop = nullptr) {
@@ -596,45 +577,14 @@ int attn_add_dispatch(hnh_ctx* ctx, const hnh_csr_block* b, const hnh_attn_add* 
     }
     if (PASS == 2) w2 = w2 && aligned16(g->M) && g->ld_m % 2 == 0 && aligned16(g->Out) && g->ld_out % 2 == 0;
 
-    const int64_t rows = b->rows, nnz = b->nnz;
-    const int32_t* rowptr = b->rowptr;
-    const int32_t* colidx = b->col_idx;
-    if (int rc = adopt_plan(ctx, b->plan, rows, nnz, rowptr, colidx)) return rc;
-    LongCtl lc;
-    if (PASS != 0) {  // (the forward pass walks hub rows whole: a row's scores are combined in row order, never by segments)
-        const int64_t pitch = PASS == 2 ? fp + 2 : 2;
-        if (int rc = prepare_long(ctx, st, stream, rows, rowptr, nnz, b->max_row_nnz, pitch, &lc, win == nullptr || win->last != 0, b->plan)) return rc;
-        if (lc.enabled && lc.items != nullptr) {  // this pass has hub rows: every segment needs its partial result (no atomics here)
-            if (lc.partials == nullptr)
-                if (int rc = partial_scratch(ctx, st, stream, (size_t)lc.capacity, pitch, &lc)) return rc;
-            if (lc.partials == nullptr || lc.partial_items < lc.capacity)
-                return hnh::fail(ctx, HNH_ERR_NOMEM, std::string(who) + ": the hub rows' partial rows exceed HNH_HUB_SCRATCH_MB");
-        }
-    }
-    if (!lc.enabled || ctx->row_waves_cap > 0) {
-        Shape s = pick_shape(f, w2);
-        lc.lds_pad = row_occupancy_pad(ctx, s, rows, nnz, b->max_row_nnz);
-    }
-    if (win != nullptr) {
-        const int32_t* beg_ptr = win->beg ? win->beg : rowptr;
-        const int32_t* end_ptr = win->end ? win->end : rowptr + 1;
-        return attn_add_launch_shape<PASS, DROP>(ctx, st, lc, w2, rows, rowptr, beg_ptr, end_ptr, colidx, a, kflags, win->last != 0);
-    }
-    const int panels = (!lc.enabled || ctx->panels_with_hubs) ? panel_count(ctx, b->cols, gather_w) : 1;
-    if (panels > 1) {
-        int32_t* split = nullptr;
-        if (int rc = panel_split_rows(ctx, st, stream, b->plan, rows, b->cols, rowptr, colidx, panels, &split)) return rc;
-        for (int q = 0; q < panels; q++) {
-            const int32_t* beg_ptr = (q == 0) ? rowptr : split + (size_t)(q - 1) * rows;
-            const int32_t* end_ptr = (q == panels - 1) ? rowptr + 1 : split + (size_t)q * rows;
-            unsigned fq = kflags;
-            if (q > 0) fq &= ~HNH_FUSED_OUT_OVERWRITE;       // later panels continue the rows the first one started
-            if (q < panels - 1) fq &= ~kInternalEpilogue;    // the last panel finishes them
-            if (int rc = attn_add_launch_shape<PASS, DROP>(ctx, st, lc, w2, rows, rowptr, beg_ptr, end_ptr, colidx, a, fq, q == panels - 1)) return rc;
-        }
-        return HNH_OK;
-    }
-    return attn_add_launch_shape<PASS, DROP>(ctx, st, lc, w2, rows, rowptr, rowptr, rowptr + 1, colidx, a, kflags, true);
+    auto launch = [&](const LongCtl& lc, const int32_t* beg_ptr, const int32_t* end_ptr, unsigned fl, bool run_long) {
+        return attn_launch_shape(f, w2, [&](auto l, auto v, auto w, auto ex) {
+            return attn_add_launch<PASS, decltype(l)::value, decltype(v)::value, decltype(w)::value, decltype(ex)::value, DROP>(
+                ctx, st, lc, b->rows, b->rowptr, beg_ptr, end_ptr, b->col_idx, a, fl, run_long);
+        });
+    };
+    // a segment's partial result: [dAgg (0) | dt] (column pass) or ds alone; none for the forward pass, which walks hub rows whole
+    return attn_dispatch_tail(ctx, st, stream, b, win, f, w2, PASS == 0 ? 0 : (PASS == 2 ? fp + 2 : 2), gather_w, kflags, who, launch);
 }
 
 }  // namespace

@@ -14,6 +14,7 @@
 // The gate is evaluated per lane (softmax: one exp per nonzero), the weights are handed round with group broadcasts as in kFused.
 // U is chosen so that a batch is at most 16 gathered doubles per lane: 32 doubles (64 VGPRs) of gather buffers in every instance.
 #pragma once
+#include "hnh_attn_dispatch.hpp"
 
 namespace {
 
@@ -372,25 +373,6 @@ int attn_grad_launch(hnh_ctx* ctx, hipStream_t st, const LongCtl& lc, int64_t ro
     return HNH_OK;
 }
 
-// the instance that fits (f, alignment): exact widths 64 / 128 / 256, every other width bounds-checked (16-byte lanes when even)
-template <int PASS>
-int attn_grad_launch_shape(hnh_ctx* ctx, hipStream_t st, const LongCtl& lc, bool w2, int64_t rows, const int32_t* rowptr, const int32_t* beg_ptr,
-                           const int32_t* end_ptr, const int32_t* colidx, const AgArgs& a, unsigned flags, bool run_long) {
-#define HNH_AG(L, V, WW, EX) return attn_grad_launch<PASS, L, V, WW, EX>(ctx, st, lc, rows, rowptr, beg_ptr, end_ptr, colidx, a, flags, run_long)
-    const int f = a.f;
-    if (w2) {
-        if (f == 64) HNH_AG(32, 1, 2, true);
-        if (f == 128) HNH_AG(64, 1, 2, true);
-        if (f == 256) HNH_AG(64, 2, 2, true);
-        if (f < 128) HNH_AG(64, 1, 2, false);
-        HNH_AG(64, 2, 2, false);
-    }
-    if (f <= 64) HNH_AG(64, 1, 1, false);
-    if (f <= 128) HNH_AG(64, 2, 1, false);
-    HNH_AG(64, 4, 1, false);
-#undef HNH_AG
-}
-
 template <int PASS>
 int attn_grad_dispatch(hnh_ctx* ctx, const hnh_csr_block* b, const hnh_attn_grad* g, unsigned flags, const hnh_csr_window* win, int stream,
                        const char* who) {
@@ -432,41 +414,14 @@ int attn_grad_dispatch(hnh_ctx* ctx, const hnh_csr_block* b, const hnh_attn_grad
     a.ld_x = g->ld_x; a.ld_dz = g->ld_dz; a.ld_y = g->ld_y; a.ld_out = g->ld_out;
     a.f = f; a.fp = fp; a.softmax = softmax ? 1 : 0; a.alpha = g->leaky_alpha;
 
-    const int64_t rows = b->rows, nnz = b->nnz;
-    const int32_t* rowptr = b->rowptr;
-    const int32_t* colidx = b->col_idx;
-    if (int rc = adopt_plan(ctx, b->plan, rows, nnz, rowptr, colidx)) return rc;
-    LongCtl lc;
-    if (int rc = prepare_long(ctx, st, stream, rows, rowptr, nnz, b->max_row_nnz, (int64_t)f, &lc, win == nullptr || win->last != 0, b->plan)) return rc;
-    if (lc.enabled && lc.items != nullptr) {  // this pass has hub rows: every segment needs its partial row (no atomics here)
-        if (lc.partials == nullptr)
-            if (int rc = partial_scratch(ctx, st, stream, (size_t)lc.capacity, (int64_t)f, &lc)) return rc;
-        if (lc.partials == nullptr || lc.partial_items < lc.capacity)
-            return hnh::fail(ctx, HNH_ERR_NOMEM, std::string(who) + ": the hub rows' partial rows exceed HNH_HUB_SCRATCH_MB");
-    }
     const int gather_w = PASS == 1 ? HNH_ATTN_GRAD_PACKED_WIDTH(f, softmax) : f;
-    if (!lc.enabled || ctx->row_waves_cap > 0) {
-        Shape s = pick_shape(f, w2);
-        lc.lds_pad = row_occupancy_pad(ctx, s, rows, nnz, b->max_row_nnz);
-    }
-    if (win != nullptr) {
-        const int32_t* beg_ptr = win->beg ? win->beg : rowptr;
-        const int32_t* end_ptr = win->end ? win->end : rowptr + 1;
-        return attn_grad_launch_shape<PASS>(ctx, st, lc, w2, rows, rowptr, beg_ptr, end_ptr, colidx, a, flags, win->last != 0);
-    }
-    const int panels = (!lc.enabled || ctx->panels_with_hubs) ? panel_count(ctx, b->cols, gather_w) : 1;
-    if (panels > 1) {
-        int32_t* split = nullptr;
-        if (int rc = panel_split_rows(ctx, st, stream, b->plan, rows, b->cols, rowptr, colidx, panels, &split)) return rc;
-        for (int q = 0; q < panels; q++) {
-            const int32_t* beg_ptr = (q == 0) ? rowptr : split + (size_t)(q - 1) * rows;
-            const int32_t* end_ptr = (q == panels - 1) ? rowptr + 1 : split + (size_t)q * rows;
-            const unsigned fq = (q > 0) ? (flags & ~HNH_FUSED_OUT_OVERWRITE) : flags;  // later panels add to the rows the first one wrote
-            if (int rc = attn_grad_launch_shape<PASS>(ctx, st, lc, w2, rows, rowptr, beg_ptr, end_ptr, colidx, a, fq, q == panels - 1)) return rc;
-        }
-        return HNH_OK;
-    }
-    return attn_grad_launch_shape<PASS>(ctx, st, lc, w2, rows, rowptr, rowptr, rowptr + 1, colidx, a, flags, true);
+    auto launch = [&](const LongCtl& lc, const int32_t* beg_ptr, const int32_t* end_ptr, unsigned fl, bool run_long) {
+        return attn_launch_shape(f, w2, [&](auto l, auto v, auto w, auto ex) {
+            return attn_grad_launch<PASS, decltype(l)::value, decltype(v)::value, decltype(w)::value, decltype(ex)::value>(
+                ctx, st, lc, b->rows, b->rowptr, beg_ptr, end_ptr, b->col_idx, a, fl, run_long);
+        });
+    };
+    return attn_dispatch_tail(ctx, st, stream, b, win, f, w2, (int64_t)f, gather_w, flags, who, launch);  // (a segment's partial result: its row)
 }
 
 }  // namespace

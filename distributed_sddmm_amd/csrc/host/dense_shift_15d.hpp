@@ -307,33 +307,11 @@ public:
     bool attnGrad_pass(bool column_side, DenseMatrix& moving, const hnh_attn_grad& args, int64_t out_rows, bool overwrite) {
         if (fusionApproach != 2 || c != 1) return false;
         if (moving.cols() != R) hnh::fatal("Error, attnGrad_pass: the schedule's R must be the moving operand's width!");
-        SpmatLocal* choice = column_side ? ST.get() : S.get();
-        const int n = p / c;
-        bool fresh = overwrite;
-        auto on = [&](int block_id, DenseMatrix& Y, int window, int window_end) {
-            CSRLocal* blk = choice->csr_blocks[block_id];
-            if (blk == nullptr && !fresh) return;  // nothing to add
-            if (blk != nullptr) {
-                blk->window = window;
-                blk->window_end = window_end;
-            }
-            hnh_attn_grad a = args;
-            a.Y = Y.data();
-            a.ld_y = Y.cols();
-            const bool done = kernel->attn_grad_local(*choice, block_id, a, column_side, fresh ? HNH_FUSED_OUT_OVERWRITE : 0u, out_rows);
-            if (blk != nullptr) blk->window = blk->window_end = -1;
-            if (!done) throw hnh::Error("Error, the kernel implementation has no fused attention backward pass (KernelImplementation::attn_grad_local)!");
-            fresh = false;
-        };
-        if (merged) {
-            walk_merged(choice, &moving, [&](int block_id, DenseMatrix& Y, int window, int window_end, bool) { on(block_id, Y, window, window_end); });
-        } else {
-            ring_readonly(&moving, n, [&](int i, DenseMatrix& cur) {
-                auto t = phase_begin("Computation Time");
-                on(block_at(i), cur, -1, -1);
-                phase_end(t);
-            });
-        }
+        attn_walk(column_side ? ST.get() : S.get(), moving, args, overwrite, false,
+                  "Error, the kernel implementation has no fused attention backward pass (KernelImplementation::attn_grad_local)!",
+                  [&](SpmatLocal& choice, int block_id, const hnh_attn_grad& a, unsigned flags, bool) {
+                      return kernel->attn_grad_local(choice, block_id, a, column_side, flags, out_rows);
+                  });
         return true;
     }
 
@@ -350,34 +328,11 @@ public:
         if (fusionApproach != 2 || c != 1) return false;
         if (pass < 0 || pass > 2) hnh::fatal("Error, attnAdditive_pass: unknown pass!");
         if (moving.cols() != R) hnh::fatal("Error, attnAdditive_pass: the schedule's R must be the moving operand's width!");
-        SpmatLocal* choice = pass == 2 ? ST.get() : S.get();
-        const int n = p / c;
-        bool fresh = overwrite;
-        auto on = [&](int block_id, DenseMatrix& Y, int window, int window_end, bool closing) {
-            CSRLocal* blk = choice->csr_blocks[block_id];
-            const bool finish = pass == 0 && closing;
-            if (blk == nullptr && !fresh && !finish) return;  // nothing to add
-            if (blk != nullptr) {
-                blk->window = window;
-                blk->window_end = window_end;
-            }
-            hnh_attn_add a = args;
-            a.Y = Y.data();
-            a.ld_y = Y.cols();
-            const bool done = kernel->attn_additive_local(*choice, block_id, a, pass, fresh ? HNH_FUSED_OUT_OVERWRITE : 0u, out_rows, finish, drop);
-            if (blk != nullptr) blk->window = blk->window_end = -1;
-            if (!done) throw hnh::Error("Error, the kernel implementation has no additive attention pass (KernelImplementation::attn_additive_local)!");
-            fresh = false;
-        };
-        if (merged) {
-            walk_merged(choice, &moving, [&](int block_id, DenseMatrix& Y, int window, int window_end, bool is_last) { on(block_id, Y, window, window_end, is_last); });
-        } else {
-            ring_readonly(&moving, n, [&](int i, DenseMatrix& cur) {
-                auto t = phase_begin("Computation Time");
-                on(block_at(i), cur, -1, -1, i == n - 1);
-                phase_end(t);
-            });
-        }
+        attn_walk(pass == 2 ? ST.get() : S.get(), moving, args, overwrite, pass == 0,
+                  "Error, the kernel implementation has no additive attention pass (KernelImplementation::attn_additive_local)!",
+                  [&](SpmatLocal& choice, int block_id, const hnh_attn_add& a, unsigned flags, bool finish) {
+                      return kernel->attn_additive_local(choice, block_id, a, pass, flags, out_rows, finish, drop);
+                  });
         return true;
     }
 
@@ -539,6 +494,49 @@ private:
         phase_end(t);
     }
 
+    // `call()` on a block with the windows [window, window_end) selected (-1: all of it; an absent block has nothing to select)
+    template <typename Call>
+    static bool in_window(CSRLocal* blk, int window, int window_end, Call&& call) {
+        if (blk != nullptr) {
+            blk->window = window;
+            blk->window_end = window_end;
+        }
+        const bool done = call();
+        if (blk != nullptr) blk->window = blk->window_end = -1;
+        return done;
+    }
+
+    // The walk of attnGrad_pass and attnAdditive_pass: the own block, then the fetched blocks window by window or in adaptive groups as
+    // their chunks land (merged layout), or the blocks of the ring.  call(choice, block, args with Y / ld_y = the block's gathered operand,
+    // flags, finish) is the pass on one block; it returns false when the kernel implementation has no such pass (`missing`).  The first
+    // call of an `overwrite` pass carries HNH_FUSED_OUT_OVERWRITE; an absent block is skipped unless its call is that one or, with
+    // `finishes`, the closing one (the forward pass's finish).
+    template <typename Args, typename Call>
+    void attn_walk(SpmatLocal* choice, DenseMatrix& moving, const Args& args, bool overwrite, bool finishes, const char* missing, Call&& call) {
+        const int n = p / c;
+        bool fresh = overwrite;
+        auto on = [&](int block_id, DenseMatrix& Y, int window, int window_end, bool closing) {
+            CSRLocal* blk = choice->csr_blocks[block_id];
+            const bool finish = finishes && closing;
+            if (blk == nullptr && !fresh && !finish) return;  // nothing to add
+            Args a = args;
+            a.Y = Y.data();
+            a.ld_y = Y.cols();
+            if (!in_window(blk, window, window_end, [&] { return call(*choice, block_id, a, fresh ? HNH_FUSED_OUT_OVERWRITE : 0u, finish); }))
+                throw hnh::Error(missing);
+            fresh = false;
+        };
+        if (merged) {
+            walk_merged(choice, &moving, on);
+        } else {
+            ring_readonly(&moving, n, [&](int i, DenseMatrix& cur) {
+                auto t = phase_begin("Computation Time");
+                on(block_at(i), cur, -1, -1, i == n - 1);
+                phase_end(t);
+            });
+        }
+    }
+
     // One pass of shifts with the fused kernel on every visiting block.  target == nullptr: the result replaces
     // Xin (the reference's in-place fusedSpMM); otherwise it is written to *target and Xin survives.
     // softmax != nullptr: the neighbourhood-softmax instance (KernelImplementation::softmax_local) instead of the fused pair, c == 1 only.
@@ -576,14 +574,11 @@ private:
             const hnh_fused_extras* ex = closing ? last : act;
             CSRLocal* blk = choice->csr_blocks[block_id];
             if (blk == nullptr && ex == act && !(softmax && (closing || out_fresh))) return;  // nothing to multiply and no epilogue to run
-            if (blk != nullptr) {
-                blk->window = window;
-                blk->window_end = window_end;
-            }
             const unsigned flags = base | (out_fresh ? HNH_FUSED_OUT_OVERWRITE : 0u);
-            const bool done = softmax ? kernel->softmax_local(*choice, *rowOperand, Y, *accum, block_id, flags, *softmax, closing)
-                                      : (kernel->fused_local(*choice, *rowOperand, Y, *accum, block_id, flags, ex), true);
-            if (blk != nullptr) blk->window = blk->window_end = -1;
+            const bool done = in_window(blk, window, window_end, [&] {
+                return softmax ? kernel->softmax_local(*choice, *rowOperand, Y, *accum, block_id, flags, *softmax, closing)
+                               : (kernel->fused_local(*choice, *rowOperand, Y, *accum, block_id, flags, ex), true);
+            });
             if (!done) throw hnh::Error("Error, the kernel implementation has no softmax attention pass (KernelImplementation::softmax_local)!");
             out_fresh = false;
         };

@@ -82,6 +82,7 @@
 #include <map>
 #include <tuple>
 #include "hnh_dist.h"
+#define HNH_GAT_KERNEL(name) {(const void*)be->name, #name}  // (require_kernels; `be` = the backend in scope)
 
 class GATLayer {
 public:
@@ -271,21 +272,6 @@ public:
         if (!forward_valid_) throw hnh::Error("Error, GAT backwardPass needs a forwardPass first (and a new one after set_weight / set_input)!");
         const DenseMatrix& last = buffers.back();
         if (grad_out.rows() != last.rows() || grad_out.cols() != last.cols()) throw hnh::Error("Error, GAT output gradient has the wrong shape!");
-        const bool fused = backward_ == HNH_GAT_BACKWARD_FUSED || score_ == HNH_GAT_SCORE_ADDITIVE;  // (no per-nonzero vectors in those modes)
-        if (!fused && ones_S_.size() == 0) {
-            ones_S_ = d_ops->like_S_values(1.0);
-            ones_ST_ = d_ops->like_ST_values(1.0);
-            e_S_ = VectorXd(ones_S_.size());
-            d_S_ = VectorXd(ones_S_.size());
-            e_ST_ = VectorXd(ones_ST_.size());
-            d_ST_ = VectorXd(ones_ST_.size());
-        }
-        if (!fused && attention_ == HNH_GAT_ATTENTION_SOFTMAX && lse_S_.size() != ones_S_.size()) {
-            lse_S_ = VectorXd(ones_S_.size());
-            delta_S_ = VectorXd(ones_S_.size());
-            lse_ST_ = VectorXd(ones_ST_.size());
-            delta_ST_ = VectorXd(ones_ST_.size());
-        }
         const int L = (int)layers.size();
         if ((int)weight_grads.size() != L) {
             weight_grads.assign((size_t)L, DenseMatrix());
@@ -384,7 +370,7 @@ public:
     void optimizer_step() {
         const hnh::Backend* be = d_ops->world->be;
         if (!optimizer_set_) throw hnh::Error("Error, GAT optimizer_step needs set_optimizer first!");
-        if (be->hnh_optim_step_f64 == nullptr) throw_missing_train_kernel("hnh_optim_step_f64");
+        require_kernels("training", "include/hnh_train.h", {HNH_GAT_KERNEL(hnh_optim_step_f64)});
         const bool additive = score_ == HNH_GAT_SCORE_ADDITIVE;
         if (!grads_fresh_ || weight_grads.size() != layers.size() || (additive && attn_grads.size() != layers.size()))
             throw hnh::Error("Error, GAT optimizer_step needs the gradients of a backwardPass since the last step!");
@@ -522,23 +508,53 @@ private:
         const GATLayer& L = layers.back();
         return label_heads_ == HNH_GAT_HEADS_MEAN ? L.features_per_head : L.num_heads * L.features_per_head;
     }
-    // the labels live with the output's rows: one dense block of whole rows per rank
+    // one dense block of whole rows per rank: the output's side, and with `input_too` the side of buffers[0], which is laid out like B
+    bool whole_rows(bool input_too) const {
+        return !d_ops->r_split && d_ops->aSubmatrices.size() == 1 && d_ops->aSubmatrices[0].leftCol == 0 &&
+               (!input_too || (d_ops->bSubmatrices.size() == 1 && d_ops->bSubmatrices[0].leftCol == 0));
+    }
+    // the labels live with the output's rows
     void check_whole_rows(const char* what) const {
-        if (d_ops->r_split || d_ops->aSubmatrices.size() != 1 || d_ops->aSubmatrices[0].leftCol != 0)
+        if (!whole_rows(false))
             throw hnh::Error(std::string("Error, GAT ") + what + " needs one dense block of whole rows per rank, which " + d_ops->algorithm_name + " does not have!");
     }
-    [[noreturn]] void throw_missing_train_kernel(const char* name) const {
-        throw hnh::Error(std::string("Error, GAT training needs the kernel ") + name + ", which the kernel library " + d_ops->world->be->path +
-                         " does not export (include/hnh_train.h)");
+    // Refuses with the first kernel of an optional group that the library lacks: `what` are the words after "GAT", `header` the group's;
+    // HNH_GAT_KERNEL(name) is an entry of the list.
+    void require_kernels(const std::string& what, const char* header, std::initializer_list<std::pair<const void*, const char*>> need) const {
+        for (const auto& n : need)
+            if (n.first == nullptr)
+                throw hnh::Error("Error, GAT " + what + " needs the kernel " + n.second + ", which the kernel library " + d_ops->world->be->path +
+                                 " does not export (" + header + ")");
     }
+    // Refuses a schedule on which a rank's own launches do not see all of a row's nonzeros, or an output row is summed across ranks: all
+    // but 15d_fusion2 with c = 1 (15d_fusion1 reduce-scatters over the mesh; c > 1, the 2.5D schedules and the sparse shift reduce across
+    // ranks too).  `declined`: after a pass, when the schedule itself returned false, having done nothing.
+    void require_own_rows(const std::string& what, bool declined = false) const {
+        auto* ds = dynamic_cast<Sparse15D_Dense_Shift*>(d_ops);
+        if (!declined && ds != nullptr && !ds->r_split && ds->fusionApproach == 2 && ds->c == 1) return;
+        std::string found = d_ops->algorithm_name;
+        if (!declined)
+            found = (ds ? "15d_fusion" + std::to_string(ds->fusionApproach) + " (" + found + ")" : found) + " with c = " + std::to_string(d_ops->c) +
+                    ": its rows are summed across ranks";
+        throw hnh::Error("Error, GAT " + what + " supports 15d_fusion2 with c = 1 only, not " + found);
+    }
+    // The schedule runs a pass at the MOVING operand's width (what its landing buffers and fetches are sized by), and at the head's f
+    // again on every exit.
+    struct ScheduleWidth {
+        Distributed_Sparse* ops;
+        int f;
+        ScheduleWidth(Distributed_Sparse* ops, int width, int f) : ops(ops), f(f) { ops->setRValue(width); }
+        ~ScheduleWidth() { ops->setRValue(f); }
+        ScheduleWidth(const ScheduleWidth&) = delete;
+        ScheduleWidth& operator=(const ScheduleWidth&) = delete;
+    };
     // Refuses before anything is launched: labels (and the optimizer) not set, then the kernel group, then the row width.
     void check_train_supported(bool need_optimizer) {
         if (!labels_set_) throw hnh::Error("Error, GAT loss / train_step / evaluate need set_labels first!");
         if (need_optimizer && !optimizer_set_) throw hnh::Error("Error, GAT train_step needs set_optimizer first!");
         const hnh::Backend* be = d_ops->world->be;
-        if (be->hnh_xent_rows_f64_workspace == nullptr) throw_missing_train_kernel("hnh_xent_rows_f64_workspace");
-        if (be->hnh_xent_rows_f64 == nullptr) throw_missing_train_kernel("hnh_xent_rows_f64");
-        if (need_optimizer && be->hnh_optim_step_f64 == nullptr) throw_missing_train_kernel("hnh_optim_step_f64");
+        require_kernels("training", "include/hnh_train.h", {HNH_GAT_KERNEL(hnh_xent_rows_f64_workspace), HNH_GAT_KERNEL(hnh_xent_rows_f64)});
+        if (need_optimizer) require_kernels("training", "include/hnh_train.h", {HNH_GAT_KERNEL(hnh_optim_step_f64)});
         const int64_t width = (int64_t)layers.back().num_heads * layers.back().features_per_head;
         if (width > HNH_XENT_MAX_WIDTH)
             throw hnh::Error("Error, GAT loss supports output rows of at most " + std::to_string(HNH_XENT_MAX_WIDTH) + " values, not " + std::to_string(width) +
@@ -664,20 +680,14 @@ private:
         for (const GATLayer& L : layers)
             if (L.num_heads > 65536 || (int64_t)L.input_features > 4294967296LL)
                 throw hnh::Error("Error, GAT dropout needs at most 65536 heads per layer (the generator's counter words)!");
-        if (feat_p_ > 0.0 && (d_ops->r_split || d_ops->aSubmatrices.size() != 1 || d_ops->bSubmatrices.size() != 1 ||
-                              d_ops->aSubmatrices[0].leftCol != 0 || d_ops->bSubmatrices[0].leftCol != 0))
+        if (feat_p_ > 0.0 && !whole_rows(true))
             throw hnh::Error("Error, GAT feature dropout needs one dense block of whole rows per rank, which " + d_ops->algorithm_name + " does not have!");
         const hnh::Backend* be = d_ops->world->be;
-        std::vector<std::pair<const void*, const char*>> need;
         if (attn_p_ > 0.0)
-            need = {{(const void*)be->hnh_attn_drop_fwd_csr_p, "hnh_attn_drop_fwd_csr_p"}, {(const void*)be->hnh_attn_drop_row_csr_p, "hnh_attn_drop_row_csr_p"},
-                    {(const void*)be->hnh_attn_drop_col_csr_p, "hnh_attn_drop_col_csr_p"}, {(const void*)be->hnh_attn_drop_scores_f64, "hnh_attn_drop_scores_f64"},
-                    {(const void*)be->hnh_attn_drop_pack_f64, "hnh_attn_drop_pack_f64"}};
-        if (feat_p_ > 0.0) need.push_back({(const void*)be->hnh_feat_drop_f64, "hnh_feat_drop_f64"});
-        for (const auto& n : need)
-            if (n.first == nullptr)
-                throw hnh::Error(std::string("Error, GAT dropout needs the kernel ") + n.second + ", which the kernel library " + be->path +
-                                 " does not export (include/hnh_attn_dropout.h)");
+            require_kernels("dropout", "include/hnh_attn_dropout.h",
+                            {HNH_GAT_KERNEL(hnh_attn_drop_fwd_csr_p), HNH_GAT_KERNEL(hnh_attn_drop_row_csr_p), HNH_GAT_KERNEL(hnh_attn_drop_col_csr_p),
+                             HNH_GAT_KERNEL(hnh_attn_drop_scores_f64), HNH_GAT_KERNEL(hnh_attn_drop_pack_f64)});
+        if (feat_p_ > 0.0) require_kernels("dropout", "include/hnh_attn_dropout.h", {HNH_GAT_KERNEL(hnh_feat_drop_f64)});
     }
 
     // Throws hnh::Error (never a wrong number) where the backward pass is not defined or its kernels are missing.
@@ -691,22 +701,12 @@ private:
         if (ds->fusionApproach == 2 && ds->c != 1)
             throw hnh::Error("Error, GAT backwardPass does not support 15d_fusion2 with c > 1 (its forward pass reproduces a quirk of the reference)");
         const hnh::Backend* be = d_ops->world->be;
-        const std::pair<const void*, const char*> need[] = {
-            {(const void*)be->hnh_gemm_tn_f64_workspace, "hnh_gemm_tn_f64_workspace"}, {(const void*)be->hnh_gemm_tn_f64, "hnh_gemm_tn_f64"},
-            {(const void*)be->hnh_leaky_relu_grad_f64, "hnh_leaky_relu_grad_f64"}, {(const void*)be->hnh_relu_grad_cols_f64, "hnh_relu_grad_cols_f64"},
-            {(const void*)be->hnh_sum3_cols_f64, "hnh_sum3_cols_f64"}, {(const void*)be->hnh_transpose_into_f64, "hnh_transpose_into_f64"}};
-        for (const auto& n : need)
-            if (n.first == nullptr)
-                throw hnh::Error(std::string("Error, GAT backwardPass needs the kernel ") + n.second + ", which the kernel library " + be->path +
-                                 " does not export (include/hnh_grad.h)");
-        if (attention_ == HNH_GAT_ATTENTION_SOFTMAX) {
-            const std::pair<const void*, const char*> need_attn[] = {
-                {(const void*)be->hnh_softmax_gate_f64, "hnh_softmax_gate_f64"}, {(const void*)be->hnh_rowdot_cols_f64, "hnh_rowdot_cols_f64"}};
-            for (const auto& n : need_attn)
-                if (n.first == nullptr)
-                    throw hnh::Error(std::string("Error, GAT backwardPass with softmax attention needs the kernel ") + n.second +
-                                     ", which the kernel library " + be->path + " does not export (include/hnh_attention.h)");
-        }
+        require_kernels("backwardPass", "include/hnh_grad.h",
+                        {HNH_GAT_KERNEL(hnh_gemm_tn_f64_workspace), HNH_GAT_KERNEL(hnh_gemm_tn_f64), HNH_GAT_KERNEL(hnh_leaky_relu_grad_f64),
+                         HNH_GAT_KERNEL(hnh_relu_grad_cols_f64), HNH_GAT_KERNEL(hnh_sum3_cols_f64), HNH_GAT_KERNEL(hnh_transpose_into_f64)});
+        if (attention_ == HNH_GAT_ATTENTION_SOFTMAX)
+            require_kernels("backwardPass with softmax attention", "include/hnh_attention.h",
+                            {HNH_GAT_KERNEL(hnh_softmax_gate_f64), HNH_GAT_KERNEL(hnh_rowdot_cols_f64)});
     }
 
     // The fused backward mode's own conditions, checked before anything is launched: its kernel group first, then the schedule (a rank's
@@ -714,18 +714,9 @@ private:
     // of the fused forward), then the head widths.
     void check_fused_backward_supported() {
         const hnh::Backend* be = d_ops->world->be;
-        const std::pair<const void*, const char*> need[] = {{(const void*)be->hnh_attn_grad_row_csr_p, "hnh_attn_grad_row_csr_p"},
-                                                            {(const void*)be->hnh_attn_grad_col_csr_p, "hnh_attn_grad_col_csr_p"},
-                                                            {(const void*)be->hnh_attn_grad_pack_f64, "hnh_attn_grad_pack_f64"}};
-        for (const auto& n : need)
-            if (n.first == nullptr)
-                throw hnh::Error(std::string("Error, GAT backwardPass in fused mode needs the kernel ") + n.second + ", which the kernel library " +
-                                 be->path + " does not export (include/hnh_attn_grad.h)");
-        auto* ds = dynamic_cast<Sparse15D_Dense_Shift*>(d_ops);
-        if (ds == nullptr || ds->r_split || ds->fusionApproach != 2 || ds->c != 1)
-            throw hnh::Error("Error, GAT fused backward supports 15d_fusion2 with c = 1 only, not " +
-                             (ds ? "15d_fusion" + std::to_string(ds->fusionApproach) + " (" + d_ops->algorithm_name + ")" : d_ops->algorithm_name) +
-                             " with c = " + std::to_string(d_ops->c) + ": its rows are summed across ranks");
+        require_kernels("backwardPass in fused mode", "include/hnh_attn_grad.h",
+                        {HNH_GAT_KERNEL(hnh_attn_grad_row_csr_p), HNH_GAT_KERNEL(hnh_attn_grad_col_csr_p), HNH_GAT_KERNEL(hnh_attn_grad_pack_f64)});
+        require_own_rows("fused backward");
         for (const GATLayer& L : layers)
             if (L.features_per_head > HNH_ATTN_GRAD_MAX_F)
                 throw hnh::Error("Error, GAT fused backward supports heads of at most " + std::to_string(HNH_ATTN_GRAD_MAX_F) + " features, not " +
@@ -737,35 +728,21 @@ private:
     void check_additive_supported() {
         if (attention_ != HNH_GAT_ATTENTION_SOFTMAX)
             throw hnh::Error("Error, GAT score additive supports attention mode softmax only, not attention mode none (include/hnh_attn_additive.h)");
-        auto* ds = dynamic_cast<Sparse15D_Dense_Shift*>(d_ops);
-        if (ds == nullptr || ds->r_split || ds->fusionApproach != 2 || ds->c != 1)
-            throw hnh::Error("Error, GAT score additive supports 15d_fusion2 with c = 1 only, not " +
-                             (ds ? "15d_fusion" + std::to_string(ds->fusionApproach) + " (" + d_ops->algorithm_name + ")" : d_ops->algorithm_name) +
-                             " with c = " + std::to_string(d_ops->c) + ": its rows are summed across ranks");
+        require_own_rows("score additive");
         for (const GATLayer& L : layers)
             if (L.features_per_head > HNH_ATTN_ADD_MAX_F)
                 throw hnh::Error("Error, GAT score additive supports heads of at most " + std::to_string(HNH_ATTN_ADD_MAX_F) + " features, not " +
                                  std::to_string(L.features_per_head) + " (include/hnh_attn_additive.h)");
         const hnh::Backend* be = d_ops->world->be;
-        const std::pair<const void*, const char*> need[] = {
-            {(const void*)be->hnh_attn_add_fwd_csr_p, "hnh_attn_add_fwd_csr_p"},   {(const void*)be->hnh_attn_add_row_csr_p, "hnh_attn_add_row_csr_p"},
-            {(const void*)be->hnh_attn_add_col_csr_p, "hnh_attn_add_col_csr_p"},   {(const void*)be->hnh_attn_add_scores_f64, "hnh_attn_add_scores_f64"},
-            {(const void*)be->hnh_attn_add_pack_f64, "hnh_attn_add_pack_f64"},     {(const void*)be->hnh_attn_add_update_f64, "hnh_attn_add_update_f64"}};
-        for (const auto& n : need)
-            if (n.first == nullptr)
-                throw hnh::Error(std::string("Error, GAT score additive needs the kernel ") + n.second + ", which the kernel library " + be->path +
-                                 " does not export (include/hnh_attn_additive.h)");
+        require_kernels("score additive", "include/hnh_attn_additive.h",
+                        {HNH_GAT_KERNEL(hnh_attn_add_fwd_csr_p), HNH_GAT_KERNEL(hnh_attn_add_row_csr_p), HNH_GAT_KERNEL(hnh_attn_add_col_csr_p),
+                         HNH_GAT_KERNEL(hnh_attn_add_scores_f64), HNH_GAT_KERNEL(hnh_attn_add_pack_f64), HNH_GAT_KERNEL(hnh_attn_add_update_f64)});
     }
 
     // Throws hnh::Error (never a wrong number) where softmax attention is not defined or its kernel is missing: a row's softmax needs
-    // all of the row's nonzeros summed by this rank's own launches, which only 15d_fusion2 with c = 1 does (15d_fusion1 reduce-scatters
-    // over the mesh; c > 1, the 2.5D schedules and the sparse shift reduce across ranks too).
+    // all of the row's nonzeros summed by this rank's own launches (require_own_rows).
     void check_softmax_supported() {
-        auto* ds = dynamic_cast<Sparse15D_Dense_Shift*>(d_ops);
-        if (ds == nullptr || ds->r_split || ds->fusionApproach != 2 || ds->c != 1)
-            throw hnh::Error("Error, GAT softmax attention supports 15d_fusion2 with c = 1 only, not " +
-                             (ds ? "15d_fusion" + std::to_string(ds->fusionApproach) + " (" + d_ops->algorithm_name + ")" : d_ops->algorithm_name) +
-                             " with c = " + std::to_string(d_ops->c) + ": its rows are summed across ranks");
+        require_own_rows("softmax attention");
         // a head is one pass over its columns (include/hnh_attention.h); its operands are whole allocations and column blocks at an even
         // offset of an even pitch when f is even, so the 16-byte condition of the 512 limit holds for every even f
         for (const GATLayer& L : layers) {
@@ -775,9 +752,7 @@ private:
                                  ": a row's softmax is one pass over its columns (include/hnh_attention.h)");
         }
         const hnh::Backend* be = d_ops->world->be;
-        if (be->hnh_attn_softmax_csr_p == nullptr)
-            throw hnh::Error(std::string("Error, GAT softmax attention needs the kernel hnh_attn_softmax_csr_p, which the kernel library ") + be->path +
-                             " does not export (include/hnh_attention.h)");
+        require_kernels("softmax attention", "include/hnh_attention.h", {HNH_GAT_KERNEL(hnh_attn_softmax_csr_p)});
     }
 
     // one layer of the backward pass: G = dL/d(buffers[i + 1]) -> weight_grads[i], input_grads[i]
@@ -805,93 +780,9 @@ private:
             w->check(be->hnh_gemm_f64(w->ctx, rows, f, k, X.data(), Wh.data(), A.data(), S0), "hnh_gemm_f64");
             w->check(be->hnh_relu_grad_cols_f64(w->ctx, dZ.data(), f, G.data(), hf, out.data(), hf, (int64_t)h * f, rows, f, S0),
                      "hnh_relu_grad_cols_f64");
-            const bool softmax = attention_ == HNH_GAT_ATTENTION_SOFTMAX;
-            if (score_ == HNH_GAT_SCORE_ADDITIVE) {
-                backward_head_additive(i, h, A, dZ, dA_all);
-                w->check(be->hnh_transpose_into_f64(w->ctx, Wt.data(), k, (int64_t)h * f, Wh.data(), k, f, S0), "hnh_transpose_into_f64");
-                continue;
-            }
-            if (backward_ == HNH_GAT_BACKWARD_FUSED) {
-                // two passes straight into the head's column block of dA_all (include/hnh_attn_grad.h)
-                auto* ds = dynamic_cast<Sparse15D_Dense_Shift*>(d_ops);
-                const double* lse = nullptr;
-                const double* delta = nullptr;
-                if (softmax) {
-                    DenseMatrix& dl = scratch(8, rows, 1);
-                    w->check(be->hnh_rowdot_cols_f64(w->ctx, dl.data(), dZ.data(), f, out.data(), hf, (int64_t)h * f, rows, f, S0), "hnh_rowdot_cols_f64");
-                    delta = dl.data();
-                    lse = lse_.at((size_t)i).at((size_t)h).data();
-                }
-                const int pw = HNH_ATTN_GRAD_PACKED_WIDTH(f, softmax);
-                DenseMatrix& P = scratch(9, rows, pw);
-                w->check(be->hnh_attn_grad_pack_f64(w->ctx, P.data(), pw, A.data(), f, dZ.data(), f, lse, delta, rows, f, S0), "hnh_attn_grad_pack_f64");
-                hnh_attn_grad g = {};
-                g.X = A.data();
-                g.ld_x = f;
-                g.dZ = dZ.data();
-                g.ld_dz = f;
-                g.lse = lse;
-                g.delta = delta;
-                g.Out = dA_all.data() + (int64_t)h * f;
-                g.ld_out = hf;
-                g.f = f;
-                g.softmax = softmax ? 1 : 0;
-                g.leaky_alpha = leaky_relu_alpha;
-                bool ok = ds != nullptr && ds->attnGrad_pass(false, A, g, rows, true);  // row side: dA_i = sum_j de_ij A_j
-                if (ok) {
-                    // column side onto the same rows; the moving operand is the packed one, so the schedule runs at ITS width for this pass
-                    d_ops->setRValue(pw);
-                    try {
-                        ok = ds->attnGrad_pass(true, P, g, rows, false);
-                    } catch (...) {
-                        d_ops->setRValue(f);
-                        throw;
-                    }
-                    d_ops->setRValue(f);
-                }
-                if (!ok) throw hnh::Error("Error, GAT fused backward supports 15d_fusion2 with c = 1 only, not " + d_ops->algorithm_name);
-                w->check(be->hnh_transpose_into_f64(w->ctx, Wt.data(), k, (int64_t)h * f, Wh.data(), k, f, S0), "hnh_transpose_into_f64");
-                continue;
-            }
-            DenseMatrix& dArow = scratch(4, rows, f);
-            DenseMatrix& T1 = scratch(5, rows, f);
-            DenseMatrix& T2 = scratch(6, rows, f);
-            if (softmax) {
-                // delta_i = <dZ_i, out_i> (= <dZ_i, o_i>: dZ is 0 where out is), then lse_i and delta_i onto the nonzeros of both layouts:
-                // width-1 SDDMMs whose first operand is the S-row side in both, so S^T gets the per-row scalars from the rank that owns them
-                DenseMatrix& delta = scratch(8, rows, 1);
-                w->check(be->hnh_rowdot_cols_f64(w->ctx, delta.data(), dZ.data(), f, out.data(), hf, (int64_t)h * f, rows, f, S0),
-                         "hnh_rowdot_cols_f64");
-                DenseMatrix& lse = lse_.at((size_t)i).at((size_t)h);
-                if (ones_col_.rows() != rows) ones_col_ = DenseMatrix::Constant(rows, 1, 1.0);
-                d_ops->setRValue(1);
-                d_ops->sddmmA(lse, ones_col_, ones_S_, lse_S_);
-                d_ops->sddmmA(delta, ones_col_, ones_S_, delta_S_);
-                d_ops->sddmmB(lse, ones_col_, ones_ST_, lse_ST_);
-                d_ops->sddmmB(delta, ones_col_, ones_ST_, delta_ST_);
-                d_ops->setRValue(f);
-            }
-            // the gate: e -> a (LeakyReLU(e), or its softmax weight), da -> de
-            auto gate = [&](VectorXd& e, VectorXd& d, VectorXd& lse_nz, VectorXd& delta_nz) {
-                if (softmax)
-                    w->check(be->hnh_softmax_gate_f64(w->ctx, e.data(), d.data(), lse_nz.data(), delta_nz.data(), leaky_relu_alpha, e.size(), S0),
-                             "hnh_softmax_gate_f64");
-                else
-                    w->check(be->hnh_leaky_relu_grad_f64(w->ctx, e.data(), d.data(), leaky_relu_alpha, e.size(), S0), "hnh_leaky_relu_grad_f64");
-            };
-            // S layout: e_ij = <A_i, A_j>, da_ij = <dZ_i, A_j>, gate, row side dA_i = sum_j de_ij A_j
-            d_ops->sddmmA(A, A, ones_S_, e_S_);
-            d_ops->sddmmA(dZ, A, ones_S_, d_S_);
-            gate(e_S_, d_S_, lse_S_, delta_S_);
-            d_ops->spmmA(dArow, A, d_S_);
-            // ST layout: the same values on the transpose's nonzeros, column sides sum_i a_ij dZ_i and sum_i de_ij A_i
-            d_ops->sddmmB(A, A, ones_ST_, e_ST_);
-            d_ops->sddmmB(dZ, A, ones_ST_, d_ST_);
-            gate(e_ST_, d_ST_, lse_ST_, delta_ST_);
-            d_ops->spmmB(dZ, T1, e_ST_);
-            d_ops->spmmB(A, T2, d_ST_);
-            w->check(be->hnh_sum3_cols_f64(w->ctx, dA_all.data(), hf, (int64_t)h * f, dArow.data(), T1.data(), T2.data(), rows, f, S0),
-                     "hnh_sum3_cols_f64");
+            if (score_ == HNH_GAT_SCORE_ADDITIVE) backward_head_additive(i, h, A, dZ, dA_all);
+            else if (backward_ == HNH_GAT_BACKWARD_FUSED) backward_head_fused(i, h, A, dZ, dA_all);
+            else backward_head_unfused(i, h, A, dZ, dA_all);
             w->check(be->hnh_transpose_into_f64(w->ctx, Wt.data(), k, (int64_t)h * f, Wh.data(), k, f, S0), "hnh_transpose_into_f64");
         }
         // dW_all = X^T dA_all over the local rows, then over every rank (the dense rows of the 1.5D layout are not replicated)
@@ -913,8 +804,114 @@ private:
         w->check(be->hnh_gemm_f64(w->ctx, rows, k, hf, dA_all.data(), Wt.data(), dX.data(), S0), "hnh_gemm_f64");
         if (feat_p_ > 0.0) feature_mask(i, dX, dX);  // dL/dX = c_q mask o dL/dXd
     }
-    // One head of the backward pass with score ADDITIVE (include/hnh_attn_additive.h): A = X W_h and dZ are the caller's; the head's
-    // column block of dA_all and its rows of attn_grads[i] (this rank's part) are the results.
+    // The three implementations of one head of the backward pass.  A = X W_h and dZ are backward_layer's; the head's column block of dA_all
+    // is the result.
+    // delta_i = <dZ_i, out_i> of head h (= <dZ_i, o_i>: dZ is 0 where out is), the softmax's row scalar, on the compute stream
+    DenseMatrix& head_delta(int i, int h, const DenseMatrix& dZ) {
+        hnh::World* w = d_ops->world;
+        const DenseMatrix& out = buffers[(size_t)i + 1];
+        const int64_t f = dZ.cols();
+        DenseMatrix& delta = scratch(8, dZ.rows(), 1);
+        w->check(w->be->hnh_rowdot_cols_f64(w->ctx, delta.data(), dZ.data(), f, out.data(), out.cols(), (int64_t)h * f, dZ.rows(), f, HNH_STREAM_COMPUTE),
+                 "hnh_rowdot_cols_f64");
+        return delta;
+    }
+    // HNH_GAT_BACKWARD_UNFUSED: seven operator calls through value vectors on the nonzeros of both layouts (allocated on first use)
+    void backward_head_unfused(int i, int h, DenseMatrix& A, DenseMatrix& dZ, DenseMatrix& dA_all) {
+        hnh::World* w = d_ops->world;
+        const hnh::Backend* be = w->be;
+        const int S0 = HNH_STREAM_COMPUTE;
+        const bool softmax = attention_ == HNH_GAT_ATTENTION_SOFTMAX;
+        const int64_t rows = A.rows(), f = A.cols();
+        if (ones_S_.size() == 0) {
+            ones_S_ = d_ops->like_S_values(1.0);
+            ones_ST_ = d_ops->like_ST_values(1.0);
+            e_S_ = VectorXd(ones_S_.size());
+            d_S_ = VectorXd(ones_S_.size());
+            e_ST_ = VectorXd(ones_ST_.size());
+            d_ST_ = VectorXd(ones_ST_.size());
+        }
+        if (softmax && lse_S_.size() != ones_S_.size()) {
+            lse_S_ = VectorXd(ones_S_.size());
+            delta_S_ = VectorXd(ones_S_.size());
+            lse_ST_ = VectorXd(ones_ST_.size());
+            delta_ST_ = VectorXd(ones_ST_.size());
+        }
+        DenseMatrix& dArow = scratch(4, rows, f);
+        DenseMatrix& T1 = scratch(5, rows, f);
+        DenseMatrix& T2 = scratch(6, rows, f);
+        if (softmax) {
+            // lse_i and delta_i onto the nonzeros of both layouts: width-1 SDDMMs whose first operand is the S-row side in both, so S^T gets
+            // the per-row scalars from the rank that owns them
+            DenseMatrix& delta = head_delta(i, h, dZ);
+            DenseMatrix& lse = lse_.at((size_t)i).at((size_t)h);
+            if (ones_col_.rows() != rows) ones_col_ = DenseMatrix::Constant(rows, 1, 1.0);
+            d_ops->setRValue(1);
+            d_ops->sddmmA(lse, ones_col_, ones_S_, lse_S_);
+            d_ops->sddmmA(delta, ones_col_, ones_S_, delta_S_);
+            d_ops->sddmmB(lse, ones_col_, ones_ST_, lse_ST_);
+            d_ops->sddmmB(delta, ones_col_, ones_ST_, delta_ST_);
+            d_ops->setRValue((int)f);
+        }
+        // the gate: e -> a (LeakyReLU(e), or its softmax weight), da -> de
+        auto gate = [&](VectorXd& e, VectorXd& d, VectorXd& lse_nz, VectorXd& delta_nz) {
+            if (softmax)
+                w->check(be->hnh_softmax_gate_f64(w->ctx, e.data(), d.data(), lse_nz.data(), delta_nz.data(), leaky_relu_alpha, e.size(), S0),
+                         "hnh_softmax_gate_f64");
+            else
+                w->check(be->hnh_leaky_relu_grad_f64(w->ctx, e.data(), d.data(), leaky_relu_alpha, e.size(), S0), "hnh_leaky_relu_grad_f64");
+        };
+        // S layout: e_ij = <A_i, A_j>, da_ij = <dZ_i, A_j>, gate, row side dA_i = sum_j de_ij A_j
+        d_ops->sddmmA(A, A, ones_S_, e_S_);
+        d_ops->sddmmA(dZ, A, ones_S_, d_S_);
+        gate(e_S_, d_S_, lse_S_, delta_S_);
+        d_ops->spmmA(dArow, A, d_S_);
+        // ST layout: the same values on the transpose's nonzeros, column sides sum_i a_ij dZ_i and sum_i de_ij A_i
+        d_ops->sddmmB(A, A, ones_ST_, e_ST_);
+        d_ops->sddmmB(dZ, A, ones_ST_, d_ST_);
+        gate(e_ST_, d_ST_, lse_ST_, delta_ST_);
+        d_ops->spmmB(dZ, T1, e_ST_);
+        d_ops->spmmB(A, T2, d_ST_);
+        w->check(be->hnh_sum3_cols_f64(w->ctx, dA_all.data(), dA_all.cols(), (int64_t)h * f, dArow.data(), T1.data(), T2.data(), rows, f, S0),
+                 "hnh_sum3_cols_f64");
+    }
+    // HNH_GAT_BACKWARD_FUSED: two passes straight into the head's column block of dA_all (include/hnh_attn_grad.h)
+    void backward_head_fused(int i, int h, DenseMatrix& A, DenseMatrix& dZ, DenseMatrix& dA_all) {
+        hnh::World* w = d_ops->world;
+        const bool softmax = attention_ == HNH_GAT_ATTENTION_SOFTMAX;
+        const int f = (int)A.cols();
+        const int64_t rows = A.rows();
+        auto* ds = dynamic_cast<Sparse15D_Dense_Shift*>(d_ops);
+        const double* lse = nullptr;
+        const double* delta = nullptr;
+        if (softmax) {
+            delta = head_delta(i, h, dZ).data();
+            lse = lse_.at((size_t)i).at((size_t)h).data();
+        }
+        const int pw = HNH_ATTN_GRAD_PACKED_WIDTH(f, softmax);
+        DenseMatrix& P = scratch(9, rows, pw);
+        w->check(w->be->hnh_attn_grad_pack_f64(w->ctx, P.data(), pw, A.data(), f, dZ.data(), f, lse, delta, rows, f, HNH_STREAM_COMPUTE), "hnh_attn_grad_pack_f64");
+        hnh_attn_grad g = {};
+        g.X = A.data();
+        g.ld_x = f;
+        g.dZ = dZ.data();
+        g.ld_dz = f;
+        g.lse = lse;
+        g.delta = delta;
+        g.Out = dA_all.data() + (int64_t)h * f;
+        g.ld_out = dA_all.cols();
+        g.f = f;
+        g.softmax = softmax ? 1 : 0;
+        g.leaky_alpha = leaky_relu_alpha;
+        bool ok = ds != nullptr && ds->attnGrad_pass(false, A, g, rows, true);  // row side: dA_i = sum_j de_ij A_j
+        if (ok) {
+            // column side onto the same rows; the moving operand is the packed one
+            ScheduleWidth width(d_ops, pw, f);
+            ok = ds->attnGrad_pass(true, P, g, rows, false);
+        }
+        require_own_rows("fused backward", !ok);
+    }
+    // score ADDITIVE (include/hnh_attn_additive.h): also the head's rows of attn_grads[i] (this rank's part)
     void backward_head_additive(int i, int h, DenseMatrix& A, DenseMatrix& dZ, DenseMatrix& dA_all) {
         hnh::World* w = d_ops->world;
         const hnh::Backend* be = w->be;
@@ -922,7 +919,6 @@ private:
         GATLayer& L = layers[(size_t)i];
         const int H = L.num_heads, f = L.features_per_head;
         const int64_t rows = A.rows(), hf = (int64_t)H * f;
-        const DenseMatrix& out = buffers[(size_t)i + 1];
         auto* ds = dynamic_cast<Sparse15D_Dense_Shift*>(d_ops);
         ensure_attn_vectors(i);
         const double* a1 = L.a1.data() + (int64_t)h * f;
@@ -934,11 +930,9 @@ private:
         DenseMatrix& Q = scratch(11, rows, qw);
         DenseMatrix& D = scratch(12, rows, 2);      // [ds dt]
         DenseMatrix& dAgg = scratch(13, rows, f);
-        DenseMatrix& dl = scratch(8, rows, 1);
         double* lse = lse_.at((size_t)i).at((size_t)h).data();
-        if (drop) w->check(be->hnh_attn_drop_scores_f64(w->ctx, M.data(), mw, A.data(), f, a1, a2, rows, f, dr.row_id0, S0), "hnh_attn_drop_scores_f64");
-        else w->check(be->hnh_attn_add_scores_f64(w->ctx, M.data(), mw, A.data(), f, a1, a2, rows, f, S0), "hnh_attn_add_scores_f64");
-        w->check(be->hnh_rowdot_cols_f64(w->ctx, dl.data(), dZ.data(), f, out.data(), hf, (int64_t)h * f, rows, f, S0), "hnh_rowdot_cols_f64");
+        head_scores(i, h, A, M, S0);
+        DenseMatrix& dl = head_delta(i, h, dZ);
         if (drop)
             w->check(be->hnh_attn_drop_pack_f64(w->ctx, Q.data(), qw, dZ.data(), f, M.data(), mw, lse, dl.data(), rows, f, dr.row_id0, S0),
                      "hnh_attn_drop_pack_f64");
@@ -955,25 +949,18 @@ private:
         g.ld_vec = 2;
         g.f = f;
         g.leaky_alpha = leaky_relu_alpha;
-        // the moving operand is M, then Q: the schedule runs at ITS width for each pass
-        bool ok = ds != nullptr;
-        try {
-            if (ok) {
-                d_ops->setRValue(mw);
-                g.vec = D.data();
-                ok = ds->attnAdditive_pass(1, M, g, rows, true, drop ? &dr : nullptr);  // row side: ds
-            }
+        bool ok = false;
+        if (ds != nullptr) {  // the moving operand is M, then Q
+            ScheduleWidth width(d_ops, mw, f);
+            g.vec = D.data();
+            ok = ds->attnAdditive_pass(1, M, g, rows, true, drop ? &dr : nullptr);  // row side: ds
             if (ok) {
                 d_ops->setRValue(qw);
                 g.vec = D.data() + 1;
                 ok = ds->attnAdditive_pass(2, Q, g, rows, true, drop ? &dr : nullptr);  // column side: dAgg, dt
             }
-        } catch (...) {
-            d_ops->setRValue(f);
-            throw;
         }
-        d_ops->setRValue(f);
-        if (!ok) throw hnh::Error("Error, GAT score additive supports 15d_fusion2 with c = 1 only, not " + d_ops->algorithm_name);
+        require_own_rows("score additive", !ok);
         w->check(be->hnh_attn_add_update_f64(w->ctx, dA_all.data(), hf, (int64_t)h * f, dAgg.data(), f, D.data(), 2, a1, a2, rows, f, S0),
                  "hnh_attn_add_update_f64");
         // [da1_h da2_h] = A^T [ds dt] over the local rows (A = the first f columns of M)
@@ -1014,19 +1001,17 @@ private:
         if (M.rows() != rows || M.cols() != cols) M = DenseMatrix(rows, cols);
     }
 
-    // M = [A (0) | <A, a1_j> <A, a2_j>] on `stream`, from the head's product A (include/hnh_attn_additive.h)
+    // The scored operand of (layer i, head j) from the head's product A, on `stream`: M = [A (0) | <A, a1_j> <A, a2_j>]
+    // (include/hnh_attn_additive.h) or, with attention dropout, M' = [A (0) | s t | id 0] at M's own width
     void head_scores(int i, int j, DenseMatrix& A, DenseMatrix& M, int stream) {
         hnh::World* w = d_ops->world;
         const int f = layers[i].features_per_head;
-        if (attn_p_ > 0.0) {  // M' = [A (0) | s t | id 0]
-            w->check(w->be->hnh_attn_drop_scores_f64(w->ctx, M.data(), M.cols(), A.data(), A.cols(), layers[i].a1.data() + (int64_t)j * f,
-                                                     layers[i].a2.data() + (int64_t)j * f, A.rows(), f, d_ops->aSubmatrices[0].topRow, stream),
+        const double* a1 = layers[i].a1.data() + (int64_t)j * f;
+        const double* a2 = layers[i].a2.data() + (int64_t)j * f;
+        if (attn_p_ > 0.0)
+            w->check(w->be->hnh_attn_drop_scores_f64(w->ctx, M.data(), M.cols(), A.data(), A.cols(), a1, a2, A.rows(), f, d_ops->aSubmatrices[0].topRow, stream),
                      "hnh_attn_drop_scores_f64");
-            return;
-        }
-        w->check(w->be->hnh_attn_add_scores_f64(w->ctx, M.data(), M.cols(), A.data(), A.cols(), layers[i].a1.data() + (int64_t)j * f,
-                                                layers[i].a2.data() + (int64_t)j * f, A.rows(), f, stream),
-                 "hnh_attn_add_scores_f64");
+        else w->check(w->be->hnh_attn_add_scores_f64(w->ctx, M.data(), M.cols(), A.data(), A.cols(), a1, a2, A.rows(), f, stream), "hnh_attn_add_scores_f64");
     }
 
     // A = buffers[i] * W_j (gat.hpp:88) on `stream`
@@ -1065,17 +1050,13 @@ private:
             g.f = f;
             g.leaky_alpha = leaky_relu_alpha;
             auto* ds = dynamic_cast<Sparse15D_Dense_Shift*>(d_ops);
-            bool ok = ds != nullptr;
-            d_ops->setRValue((int)A.cols());
-            try {
+            bool ok = false;
+            if (ds != nullptr) {
+                ScheduleWidth width(d_ops, (int)A.cols(), f);
                 const hnh_attn_drop dr = attn_drop_args(i, j);
-                ok = ok && ds->attnAdditive_pass(0, A, g, rows, true, attn_p_ > 0.0 ? &dr : nullptr);
-            } catch (...) {
-                d_ops->setRValue(f);
-                throw;
+                ok = ds->attnAdditive_pass(0, A, g, rows, true, attn_p_ > 0.0 ? &dr : nullptr);
             }
-            d_ops->setRValue(f);
-            if (!ok) throw hnh::Error("Error, GAT score additive supports 15d_fusion2 with c = 1 only, not " + d_ops->algorithm_name);
+            require_own_rows("score additive", !ok);
             return;
         }
 
@@ -1088,8 +1069,7 @@ private:
             const hnh_attn_state st = {row_max_.data(), row_sum_.data(), lse.data(), leaky_relu_alpha,
                                        out.data() + (int64_t)j * A.cols(), (int64_t)out.cols()};
             auto* ds = dynamic_cast<Sparse15D_Dense_Shift*>(d_ops);
-            if (ds == nullptr || !ds->fusedSoftmax_out(A, A, Amat, H, st))
-                throw hnh::Error("Error, GAT softmax attention supports 15d_fusion2 with c = 1 only, not " + d_ops->algorithm_name);
+            require_own_rows("softmax attention", ds == nullptr || !ds->fusedSoftmax_out(A, A, Amat, H, st));
             return;
         }
 
@@ -1118,3 +1098,4 @@ private:
                  "hnh_relu_store_cols_f64");
     }
 };
+#undef HNH_GAT_KERNEL

@@ -154,6 +154,33 @@ bool StandardKernel::softmax_block(SpmatLocal& S, DenseMatrix& A, DenseMatrix& B
     return true;
 }
 
+// The block and window handling that the attention passes share around their backend call `call(descriptor, window)`, `pass` in the complaints.
+// An absent or empty block still gets the call, with the output's rows alone: an overwrite's zeroing, the state reset and the forward finish
+// apply to it too.  Otherwise the call runs between begin() and end(launches), the profile's event pair, with the panel count of a `width`
+// wide operand when no window is selected.  finish_text != nullptr: the call finishes a forward pass, which belongs to the block's last window.
+template <typename Call, typename Begin, typename End>
+static void attn_block_call(SpmatLocal& S, int block, int64_t rows, const std::string& pass, const char* finish_text, int width, bool profile,
+                            Call&& call, Begin&& begin, End&& end) {
+    hnh::World* w = S.world;
+    CSRLocal* blk = S.csr_blocks[block];
+    if (blk == nullptr || blk->num_coords == 0) {
+        hnh_csr_block none = {};
+        none.rows = rows;
+        none.cols = -1;
+        call(none, nullptr);
+        return;
+    }
+    if (blk->transpose) hnh::fatal("Error, local matrix is transposed, can't perform " + pass);
+    begin();
+    hnh_csr_window win;
+    const hnh_csr_block desc = blk->block_args();
+    if (desc.rows != rows) hnh::fatal("Error, " + pass + " needs an output of the block's rows!");
+    const bool windowed = blk->window_args(&win);
+    if (windowed && finish_text != nullptr && !win.last) hnh::fatal(finish_text);
+    call(desc, windowed ? &win : nullptr);
+    end((profile && !windowed) ? w->be->hnh_panel_count(w->ctx, desc.rows, desc.nnz, desc.cols, width, desc.max_row_nnz) : 1);
+}
+
 bool KernelImplementation::attn_grad_local(SpmatLocal& S, int block, const hnh_attn_grad& args, bool column_side, unsigned flags, int64_t rows) {
     StandardKernel* k = dynamic_cast<StandardKernel*>(this);
     return k != nullptr && k->attn_grad_block(S, block, args, column_side, flags, rows);
@@ -167,22 +194,9 @@ bool StandardKernel::attn_grad_block(SpmatLocal& S, int block, const hnh_attn_gr
     if (fn == nullptr)
         throw hnh::Error(std::string("Error, the fused attention backward needs the kernel ") + name + ", which the kernel library " + w->be->path +
                          " does not export (include/hnh_attn_grad.h)");
-    CSRLocal* blk = S.csr_blocks[block];
-    if (blk == nullptr || blk->num_coords == 0) {  // nothing to add; overwritten output rows still have to hold zeros afterwards
-        hnh_csr_block none = {};
-        none.rows = rows;
-        none.cols = -1;
-        w->check(fn(w->ctx, &none, &args, flags, nullptr, HNH_STREAM_COMPUTE), name);
-        return true;
-    }
-    if (blk->transpose) hnh::fatal("Error, local matrix is transposed, can't perform the fused attention backward");
-    begin(w);
-    hnh_csr_window win;
-    const hnh_csr_block desc = blk->block_args();
-    if (desc.rows != rows) hnh::fatal("Error, the fused attention backward needs an output of the block's rows!");
-    const bool windowed = blk->window_args(&win);
-    w->check(fn(w->ctx, &desc, &args, flags, windowed ? &win : nullptr, HNH_STREAM_COMPUTE), name);
-    end(w, (profile && !windowed) ? w->be->hnh_panel_count(w->ctx, desc.rows, desc.nnz, desc.cols, column_side ? 2 * args.f : args.f, desc.max_row_nnz) : 1);
+    attn_block_call(S, block, rows, "the fused attention backward", nullptr, column_side ? 2 * args.f : args.f, profile,
+                    [&](const hnh_csr_block& d, const hnh_csr_window* win) { w->check(fn(w->ctx, &d, &args, flags, win, HNH_STREAM_COMPUTE), name); },
+                    [&] { begin(w); }, [&](long launches) { end(w, launches); });
     return true;
 }
 
@@ -196,8 +210,7 @@ bool KernelImplementation::attn_additive_local(SpmatLocal& S, int block, const h
     return k != nullptr && k->attn_additive_block(S, block, args, pass, flags, rows, finish, drop);
 }
 
-// The three passes of the additive-score attention (include/hnh_attn_additive.h), next to attn_grad_block: same block and window
-// handling; the forward pass's finish belongs to the pass's last call (win.last when windows are selected).
+// The three passes of the additive-score attention (include/hnh_attn_additive.h), next to attn_grad_block: same block and window handling.
 bool StandardKernel::attn_additive_block(SpmatLocal& S, int block, const hnh_attn_add& args, int pass, unsigned flags, int64_t rows, bool finish) {
     return attn_additive_block(S, block, args, pass, flags, rows, finish, nullptr);
 }
@@ -217,24 +230,10 @@ bool StandardKernel::attn_additive_block(SpmatLocal& S, int block, const hnh_att
         return drop ? masked(ctx, b, a, drop, fl, win, stream) : plain(ctx, b, a, fl, win, stream);
     };
     const unsigned f = flags | ((pass == 0 && finish) ? HNH_ATTN_FINISH : 0u);
-    CSRLocal* blk = S.csr_blocks[block];
-    if (blk == nullptr || blk->num_coords == 0) {  // no nonzeros; the reset / zeroing of an overwrite and the forward finish still apply
-        hnh_csr_block none = {};
-        none.rows = rows;
-        none.cols = -1;
-        w->check(fn(w->ctx, &none, &args, f, nullptr, HNH_STREAM_COMPUTE), name);
-        return true;
-    }
-    if (blk->transpose) hnh::fatal("Error, local matrix is transposed, can't perform the additive attention pass");
-    begin(w);
-    hnh_csr_window win;
-    const hnh_csr_block desc = blk->block_args();
-    if (desc.rows != rows) hnh::fatal("Error, the additive attention pass needs an output of the block's rows!");
-    const bool windowed = blk->window_args(&win);
-    if (windowed && pass == 0 && finish && !win.last) hnh::fatal("Error, the additive forward finish belongs to the block's last window!");
-    w->check(fn(w->ctx, &desc, &args, f, windowed ? &win : nullptr, HNH_STREAM_COMPUTE), name);
-    end(w, (profile && !windowed) ? w->be->hnh_panel_count(w->ctx, desc.rows, desc.nnz, desc.cols, (pass == 2 || drop) ? HNH_ATTN_ADD_PACKED_WIDTH(args.f) : HNH_ATTN_ADD_SCORED_WIDTH(args.f), desc.max_row_nnz)
-                                   : 1);
+    const char* finish_text = (pass == 0 && finish) ? "Error, the additive forward finish belongs to the block's last window!" : nullptr;
+    attn_block_call(S, block, rows, "the additive attention pass", finish_text, (pass == 2 || drop) ? HNH_ATTN_ADD_PACKED_WIDTH(args.f) : HNH_ATTN_ADD_SCORED_WIDTH(args.f),
+                    profile, [&](const hnh_csr_block& d, const hnh_csr_window* win) { w->check(fn(w->ctx, &d, &args, f, win, HNH_STREAM_COMPUTE), name); },
+                    [&] { begin(w); }, [&](long launches) { end(w, launches); });
     return true;
 }
 

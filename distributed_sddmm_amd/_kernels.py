@@ -124,6 +124,7 @@ GRAD_SIGNATURES = {
     "hnh_gemm_tn_f64": (_i32, [_vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i32]),
     "hnh_leaky_relu_grad_f64": (_i32, [_vp, _vp, _vp, _dbl, _i64, _i32]),
     "hnh_relu_grad_cols_f64": (_i32, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _i32]),
+    "hnh_act_grad_cols_f64": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _i32, _i32]),
     "hnh_sum3_cols_f64": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _i64, _i32]),
     "hnh_transpose_into_f64": (_i32, [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _i32]),
 }
@@ -137,6 +138,8 @@ ATTN_SIGNATURES = {
     "hnh_rowdot_cols_f64": (_i32, [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _i32]),
 }
 ATTN_FINISH = 8  # HNH_ATTN_FINISH
+ATTN_ACT_ELU, ATTN_ACT_IDENTITY = 0x10, 0x20  # HNH_ATTN_ACT_*: the finishing call's output activation (neither: ReLU)
+ACT_RELU, ACT_ELU, ACT_IDENTITY = 0, 1, 2     # HNH_ACT_* of hnh_act_grad_cols_f64
 
 
 # include/hnh_attn_grad.h: the fused backward pass of the GAT's attention, a third OPTIONAL group bound only for the product library

@@ -134,6 +134,7 @@ SIGNATURES = {
     "hnh_gat_set_attention": (_i32, [_vp, _i32]),
     "hnh_gat_set_backward": (_i32, [_vp, _i32]),
     "hnh_gat_set_score": (_i32, [_vp, _i32]),
+    "hnh_gat_set_activation": (_i32, [_vp, _i32, _i32]),
     "hnh_gat_set_attn_vectors": (_i32, [_vp, _i32, _i32, _vp, _vp]),
     "hnh_gat_get_attn_grads": (_i32, [_vp, _i32, _i32, _vp, _vp]),
     "hnh_gat_set_dropout": (_i32, [_vp, _dbl, _dbl, C.c_uint64]),
@@ -664,13 +665,21 @@ class GAT:
 
     SCORE = {"dot": 0, "additive": 1}  # HNH_GAT_SCORE_DOT / _ADDITIVE
 
+    ACTIVATION = {"relu": 0, "elu": 1, "identity": 2}  # HNH_GAT_ACT_RELU / _ELU / _IDENTITY
+
     HEADS = {"mean": 0, "concat": 1}  # HNH_GAT_HEADS_MEAN / _CONCAT
 
     OPTIMIZER = {"adam": 0, "sgd": 1}  # HNH_GAT_OPTIMIZER_ADAM / _SGD
 
     def __init__(self, op: DistributedSparse, layers, leaky_relu_alpha: float = 0.2, attention: str = "none", backward: str = "unfused",
-                 score: str = "dot", dropout=(0.0, 0.0), seed: int = 0):
+                 score: str = "dot", dropout=(0.0, 0.0), seed: int = 0, activation="relu"):
         self.op, self.layers = op, [tuple(l) for l in layers]
+        acts = [activation] * len(self.layers) if isinstance(activation, str) else list(activation)
+        if len(acts) != len(self.layers):
+            raise ValueError("activation is one name or one name per layer: %d layers, not %d names" % (len(self.layers), len(acts)))
+        for a in acts:
+            if a not in self.ACTIVATION:
+                raise ValueError("activation must be one of %s, not %r" % (sorted(self.ACTIVATION), a))
         spec = (C.c_int * (3 * len(layers)))(*[x for l in self.layers for x in l])
         self.h = _vp()
         _check(lib().hnh_gat_create(op.h, len(layers), spec, leaky_relu_alpha, C.byref(self.h)), "gat_create")
@@ -682,6 +691,9 @@ class GAT:
             self.set_score(score)
         if tuple(dropout) != (0.0, 0.0) or seed != 0:
             self.set_dropout(dropout[0], dropout[1], seed)
+        for i, a in enumerate(acts):
+            if a != "relu":
+                self.set_activation(i, a)
 
     def set_dropout(self, attention_p: float, feature_p: float, seed: int = 0):
         """Dropout rates in [0, 1) on the normalised attention coefficients (score "additive" only) and on every layer's input, with masks
@@ -720,6 +732,18 @@ class GAT:
         if mode not in self.SCORE:
             raise ValueError("score must be one of %s, not %r" % (sorted(self.SCORE), mode))
         _check(lib().hnh_gat_set_score(self.h, self.SCORE[mode]), "gat_set_score")
+
+    def set_activation(self, layer: int, mode: str):
+        """"relu" (the default on every layer: out = max(o, 0)), "elu" (out = o for o > 0, expm1(o) otherwise) or "identity" (out = o) on the
+        layer's output; the backward pass works from the stored output (include/hnh_grad.h, hnh_act_grad_cols_f64).  A non-ReLU layer needs
+        attention "softmax" (score "dot" or "additive", any dropout rates) on 15d_fusion2 with c = 1: forwardPass / backwardPass /
+        train_step / evaluate raise HnhError elsewhere, before anything is launched.  The published network is "elu" on the hidden layers
+        and "identity" on the last with set_labels(heads="mean").  A change invalidates the stored forward pass."""
+        if mode not in self.ACTIVATION:
+            raise ValueError("activation must be one of %s, not %r" % (sorted(self.ACTIVATION), mode))
+        if not (0 <= int(layer) < len(self.layers)):
+            raise ValueError("layer %r out of range: %d layers" % (layer, len(self.layers)))
+        _check(lib().hnh_gat_set_activation(self.h, int(layer), self.ACTIVATION[mode]), "gat_set_activation")
 
     def set_attention_vectors(self, layer: int, head: int, a1: np.ndarray, a2: np.ndarray):
         """The additive score's vectors of (layer, head): features_per_head entries each, zero until set.  Invalidates the stored

@@ -320,12 +320,22 @@ __device__ __forceinline__ void attn_add_process(int64_t row, int beg, int end, 
         }
         if (flags & kInternalEpilogue) {  // finish: o = acc / l through the ReLU into the head's column block, and lse; Out is scratch
             const bool live = l_run > 0.0;
+            if (flags & kAttnActMask) {  // ELU / identity in the ReLU's place (wave-uniform)
 #pragma unroll
-            for (int v = 0; v < VEC; v++) {
-                double o[W];
+                for (int v = 0; v < VEC; v++) {
+                    double o[W];
 #pragma unroll
-                for (int w = 0; w < W; w++) o[w] = live ? fmax(acc[v][w] / l_run, 0.0) : 0.0;
-                if (act[v]) store_w_stream<W>(a.relu_dst + row * a.relu_ld + coff[v], o);
+                    for (int w = 0; w < W; w++) o[w] = live ? attn_out_act(acc[v][w] / l_run, flags) : 0.0;
+                    if (act[v]) store_w_stream<W>(a.relu_dst + row * a.relu_ld + coff[v], o);
+                }
+            } else {
+#pragma unroll
+                for (int v = 0; v < VEC; v++) {
+                    double o[W];
+#pragma unroll
+                    for (int w = 0; w < W; w++) o[w] = live ? fmax(acc[v][w] / l_run, 0.0) : 0.0;
+                    if (act[v]) store_w_stream<W>(a.relu_dst + row * a.relu_ld + coff[v], o);
+                }
             }
             if (lig == 0) a.lse[row] = live ? m_run + log(l_run) : 0.0;
             return;
@@ -407,7 +417,8 @@ __global__ __launch_bounds__(kBlock) void attn_add_long_kernel(const int2* __res
 }
 
 // a block without any nonzero, forward: the state reset of HNH_FUSED_OUT_OVERWRITE and the finish, as attn_add_process does them for a
-// row whose piece is empty (one wave per row)
+// row whose piece is empty (one wave per row).  ACT: the finish applies ELU / the identity (flags) instead of the ReLU, its own instance
+template <bool ACT>
 __global__ __launch_bounds__(kBlock) void attn_add_empty_rows_kernel(int64_t rows, AaArgs a, unsigned flags) {
     const int64_t row = ((int64_t)blockIdx.x * kBlock + threadIdx.x) / 64;
     const int lane = threadIdx.x % 64;
@@ -417,7 +428,7 @@ __global__ __launch_bounds__(kBlock) void attn_add_empty_rows_kernel(int64_t row
     const double l = fresh ? 0.0 : a.row_sum[row];
     for (int c = lane; c < a.f; c += 64) {
         const double v = fresh ? 0.0 : a.Out[row * a.ld_out + c];
-        if (finish) a.relu_dst[row * a.relu_ld + c] = l > 0.0 ? fmax(v / l, 0.0) : 0.0;
+        if (finish) a.relu_dst[row * a.relu_ld + c] = l > 0.0 ? (ACT ? attn_out_act(v / l, flags) : fmax(v / l, 0.0)) : 0.0;
         else a.Out[row * a.ld_out + c] = v;
     }
     if (lane == 0) {
@@ -515,7 +526,9 @@ int attn_add_dispatch(hnh_ctx* ctx, const hnh_csr_block* b, const hnh_attn_add* 
     HNH_ENTER(ctx, stream);
     if (!b || !g || (DROP && !drop)) return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": null block or arguments");
     if (int rc = check_common(ctx, b->rows, g->f, who)) return rc;
-    if (flags & ~(HNH_FUSED_OUT_OVERWRITE | (PASS == 0 ? HNH_ATTN_FINISH : 0u))) return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": unknown flag");
+    if (flags & ~(HNH_FUSED_OUT_OVERWRITE | (PASS == 0 ? (HNH_ATTN_FINISH | kAttnActMask) : 0u)))
+        return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": unknown flag");
+    if (int rc = check_attn_act_flags(ctx, flags, who)) return rc;
     if (g->f > HNH_ATTN_ADD_MAX_F)
         return hnh::fail(ctx, HNH_ERR_UNSUPPORTED, std::string(who) + ": head width " + std::to_string(g->f) + " beyond the limit of " +
                                                        std::to_string(HNH_ATTN_ADD_MAX_F) + " (HNH_ATTN_ADD_MAX_F)");
@@ -544,12 +557,14 @@ int attn_add_dispatch(hnh_ctx* ctx, const hnh_csr_block* b, const hnh_attn_add* 
     a.ld_m = g->ld_m; a.ld_dz = g->ld_dz; a.ld_y = g->ld_y; a.ld_out = g->ld_out; a.ld_vec = g->ld_vec; a.relu_ld = g->relu_ld;
     a.f = f; a.fp = fp; a.alpha = g->leaky_alpha;
     hipStream_t st = ctx->streams[stream];
-    const unsigned kflags = (flags & HNH_FUSED_OUT_OVERWRITE) | (finish ? kInternalEpilogue : 0u);
+    const unsigned kflags = (flags & (HNH_FUSED_OUT_OVERWRITE | kAttnActMask)) | (finish ? kInternalEpilogue : 0u);
     if (b->rowptr == nullptr) {  // a block without nonzeros
         if (b->nnz > 0) return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": null rowptr");
         if (PASS == 0) {
             if (!kflags) return HNH_OK;
-            hipLaunchKernelGGL(attn_add_empty_rows_kernel, dim3((unsigned)((b->rows * 64 + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, b->rows, a, kflags);
+            const dim3 grid((unsigned)((b->rows * 64 + kBlock - 1) / kBlock));
+            if (kflags & kAttnActMask) hipLaunchKernelGGL(attn_add_empty_rows_kernel<true>, grid, dim3(kBlock), 0, st, b->rows, a, kflags);
+            else hipLaunchKernelGGL(attn_add_empty_rows_kernel<false>, grid, dim3(kBlock), 0, st, b->rows, a, kflags);
             return hnh::check_hip(ctx, hipGetLastError(), "attn_add_empty_rows_kernel launch");
         }
         if (!(flags & HNH_FUSED_OUT_OVERWRITE)) return HNH_OK;

@@ -188,6 +188,58 @@ __global__ __launch_bounds__(kBlock) void relu_grad_cols_kernel(double* __restri
     }
 }
 
+// dZ and delta of one head from G and the STORED output in one pass (hnh_act_grad_cols_f64).  A group of 2^lpr_log2 lanes owns a row and
+// walks its columns W doubles per lane (W = 2: 16-byte lanes): 256 >> lpr_log2 short rows per workgroup, one wave per wide row.  delta is
+// the lanes' partial sums (each in column order) added by an xor butterfly inside the group, a fixed order: no atomics, no LDS.
+//   relu:     dz = out > 0 ? g : 0,                 term = dz * out
+//   identity: dz = g,                               term = g * out
+//   elu:      out >= 0: dz = g, term = g * out;     out < 0: u = 1 + out, dz = g * u, term = dz * log1p(out), 0 where u == 0 (a unit
+//             saturated at -1 has dz = 0, and 0 * -inf must not become a NaN)
+template <int W>
+__global__ __launch_bounds__(kBlock) void act_grad_cols_kernel(double* __restrict__ dz, int64_t ld_dz, double* __restrict__ delta,
+                                                               const double* __restrict__ g, int64_t ld_g, const double* __restrict__ out,
+                                                               int64_t ld_out, int64_t col0, int64_t rows, int cols, int act, int lpr_log2) {
+    const int lpr = 1 << lpr_log2;
+    const int tid = threadIdx.x, lig = tid & (lpr - 1);
+    const int64_t row = (int64_t)blockIdx.x * (kBlock >> lpr_log2) + (tid >> lpr_log2);
+    if (row >= rows) return;  // (whole groups leave: the butterfly below stays inside a group)
+    const double* __restrict__ gr = g + row * ld_g + col0;
+    const double* __restrict__ orow = out + row * ld_out + col0;
+    double* __restrict__ zr = dz + row * ld_dz;
+    double s = 0.0;
+    for (int c = lig * W; c < cols; c += lpr * W) {
+        double gv[W], ov[W], zv[W];
+        if constexpr (W == 2) {
+            const double2 a = *reinterpret_cast<const double2*>(gr + c);
+            const double2 b = *reinterpret_cast<const double2*>(orow + c);
+            gv[0] = a.x; gv[1] = a.y;
+            ov[0] = b.x; ov[1] = b.y;
+        } else {
+            gv[0] = gr[c];
+            ov[0] = orow[c];
+        }
+#pragma unroll
+        for (int w = 0; w < W; w++) {
+            const double o = ov[w];
+            if (act == HNH_ACT_RELU) {
+                zv[w] = o > 0.0 ? gv[w] : 0.0;
+                s = fma(zv[w], o, s);
+            } else if (act == HNH_ACT_IDENTITY || o >= 0.0) {
+                zv[w] = gv[w];
+                s = fma(gv[w], o, s);
+            } else {
+                const double u = 1.0 + o;
+                zv[w] = gv[w] * u;
+                if (u > 0.0) s = fma(zv[w], log1p(o), s);
+            }
+        }
+        if constexpr (W == 2) *reinterpret_cast<double2*>(zr + c) = make_double2(zv[0], zv[1]);
+        else zr[c] = zv[0];
+    }
+    for (int m = lpr >> 1; m >= 1; m >>= 1) s += __shfl_xor(s, m, 64);
+    if (lig == 0) delta[row] = s;
+}
+
 __global__ __launch_bounds__(kBlock) void sum3_cols_kernel(double* __restrict__ dst, int64_t ld, int64_t col0, const double* __restrict__ x,
                                                            const double* __restrict__ y, const double* __restrict__ z, int64_t rows,
                                                            int64_t cols) {
@@ -271,6 +323,31 @@ int hnh_relu_grad_cols_f64(hnh_ctx* ctx, double* dZ, int64_t ld_dz, const double
     hipLaunchKernelGGL(relu_grad_cols_kernel, dim3(ew_grid(rows * cols)), dim3(kBlock), 0, ctx->streams[stream], dZ, ld_dz, G, ld_g, out,
                        ld_out, col0, rows, cols);
     return hnh::check_hip(ctx, hipGetLastError(), "relu_grad_cols_kernel launch");
+}
+
+int hnh_act_grad_cols_f64(hnh_ctx* ctx, double* dZ, int64_t ld_dz, double* delta, const double* G, int64_t ld_g, const double* out,
+                          int64_t ld_out, int64_t col0, int64_t rows, int64_t cols, int act, int stream) {
+    HNH_ENTER(ctx, stream);
+    if (rows < 0 || cols < 0 || col0 < 0 || ld_dz < cols || col0 + cols > ld_g || col0 + cols > ld_out || cols > 0x7fffffffLL)
+        return hnh::fail(ctx, HNH_ERR_INVALID, "hnh_act_grad_cols_f64: bad shape");
+    if (act != HNH_ACT_RELU && act != HNH_ACT_ELU && act != HNH_ACT_IDENTITY)
+        return hnh::fail(ctx, HNH_ERR_INVALID, "hnh_act_grad_cols_f64: unknown activation " + std::to_string(act) + " (relu = 0, elu = 1, identity = 2)");
+    if (rows == 0) return HNH_OK;
+    if (!delta || (cols > 0 && (!dZ || !G || !out))) return hnh::fail(ctx, HNH_ERR_INVALID, "hnh_act_grad_cols_f64: null pointer");
+    // 16-byte lanes where every row's column block starts on a 16-byte boundary in all three matrices
+    const bool vec = cols % 2 == 0 && col0 % 2 == 0 && ld_dz % 2 == 0 && ld_g % 2 == 0 && ld_out % 2 == 0 && aligned16(dZ) && aligned16(G) && aligned16(out);
+    const int w = vec ? 2 : 1;
+    int lpr_log2 = 0;  // the smallest power-of-two group that covers the row in one trip, at most one wave
+    while (lpr_log2 < 6 && ((int64_t)w << lpr_log2) < cols) lpr_log2++;
+    const int64_t groups = kBlock >> lpr_log2, blocks = (rows + groups - 1) / groups;
+    if (blocks > 0x7fffffffLL) return hnh::fail(ctx, HNH_ERR_UNSUPPORTED, "hnh_act_grad_cols_f64: too many rows for one launch");
+    if (vec)
+        hipLaunchKernelGGL(act_grad_cols_kernel<2>, dim3((unsigned)blocks), dim3(kBlock), 0, ctx->streams[stream], dZ, ld_dz, delta, G, ld_g, out, ld_out,
+                           col0, rows, (int)cols, act, lpr_log2);
+    else
+        hipLaunchKernelGGL(act_grad_cols_kernel<1>, dim3((unsigned)blocks), dim3(kBlock), 0, ctx->streams[stream], dZ, ld_dz, delta, G, ld_g, out, ld_out,
+                           col0, rows, (int)cols, act, lpr_log2);
+    return hnh::check_hip(ctx, hipGetLastError(), "act_grad_cols_kernel launch");
 }
 
 int hnh_sum3_cols_f64(hnh_ctx* ctx, double* dst, int64_t ld_dst, int64_t col0, const double* x, const double* y, const double* z,

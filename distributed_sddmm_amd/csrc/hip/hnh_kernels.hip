@@ -216,6 +216,23 @@ __host__ __device__ constexpr int long_row_of(unsigned flags) { return (int)((fl
 constexpr unsigned kInternalSplitLong = 0x100u;  // flag bit, never set by callers
 constexpr unsigned kInternalEpilogue = 0x200u;   // flag bit: apply Extras::x_scale / rowdot when the output row is stored
 
+// the public activation bits of a finishing attention call (hnh_attention.h) travel to the kernels in their flags word as they are
+constexpr unsigned kAttnActMask = HNH_ATTN_ACT_ELU | HNH_ATTN_ACT_IDENTITY;
+static_assert((kAttnActMask & (kInternalSplitLong | kInternalEpilogue | (0x1fu << kLongRowShift) | HNH_FUSED_VALUES_OVERWRITE | HNH_FUSED_OUT_OVERWRITE |
+                               HNH_FUSED_LEAKY_RELU | HNH_ATTN_FINISH)) == 0,
+              "the activation bits must not meet another flag");
+// ELU or the identity on a finished attention row's value (a wave-uniform choice; the ReLU default stays where it was)
+__device__ __forceinline__ double attn_out_act(double o, unsigned flags) {
+    return (flags & HNH_ATTN_ACT_IDENTITY) ? o : (o > 0.0 ? o : expm1(o));
+}
+// the flag checks the three finishing entry points share: 0, or the status of the complaint
+inline int check_attn_act_flags(hnh_ctx* ctx, unsigned flags, const char* who) {
+    const unsigned act = flags & kAttnActMask;
+    if (act == kAttnActMask) return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": HNH_ATTN_ACT_ELU and HNH_ATTN_ACT_IDENTITY exclude each other");
+    if (act != 0 && !(flags & HNH_ATTN_FINISH)) return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": an activation flag needs HNH_ATTN_FINISH");
+    return HNH_OK;
+}
+
 // Optional extras of the fused pass (hnh_fused_extras): an activation between the two halves and a row epilogue.
 struct Extras {
     double leaky_alpha = 0.0;  // HNH_FUSED_LEAKY_RELU: weight = dot > 0 ? dot : leaky_alpha * dot
@@ -730,12 +747,22 @@ __device__ __forceinline__ void process_row(int64_t row, int beg, int end, bool 
         }
         if (flags & kInternalEpilogue) {  // finish: o = Out / l through the ReLU into the head's column block, and lse; Out is scratch
             const bool live = l_run > 0.0;
+            if (flags & kAttnActMask) {  // ELU / identity in the ReLU's place (wave-uniform)
 #pragma unroll
-            for (int v = 0; v < VEC; v++) {
-                double o[W];
+                for (int v = 0; v < VEC; v++) {
+                    double o[W];
 #pragma unroll
-                for (int w = 0; w < W; w++) o[w] = live ? fmax(acc[v][w] / l_run, 0.0) : 0.0;
-                if (act[v]) store_w_stream<W>(ex.relu_dst + row * ex.relu_ld + coff[v], o);
+                    for (int w = 0; w < W; w++) o[w] = live ? attn_out_act(acc[v][w] / l_run, flags) : 0.0;
+                    if (act[v]) store_w_stream<W>(ex.relu_dst + row * ex.relu_ld + coff[v], o);
+                }
+            } else {
+#pragma unroll
+                for (int v = 0; v < VEC; v++) {
+                    double o[W];
+#pragma unroll
+                    for (int w = 0; w < W; w++) o[w] = live ? fmax(acc[v][w] / l_run, 0.0) : 0.0;
+                    if (act[v]) store_w_stream<W>(ex.relu_dst + row * ex.relu_ld + coff[v], o);
+                }
             }
             if (lig == 0) ex.lse[row] = live ? m_run + log(l_run) : 0.0;
             return;
@@ -2658,7 +2685,8 @@ int hnh_expand_rowptr(hnh_ctx* ctx, int64_t rows, const int32_t* rowptr, int32_t
 // ---------------------------------------------------------------- neighbourhood-softmax attention (include/hnh_attention.h)
 namespace {
 // a block without any nonzero: the state reset of HNH_FUSED_OUT_OVERWRITE and the finish of HNH_ATTN_FINISH, as process_row does them
-// for a row whose piece is empty (one wave per row)
+// for a row whose piece is empty (one wave per row).  ACT: the finish applies ELU / the identity (flags) instead of the ReLU, its own instance
+template <bool ACT>
 __global__ __launch_bounds__(kBlock) void attn_empty_rows_kernel(int64_t rows, double* __restrict__ Out, int R, unsigned flags, Extras ex) {
     const int64_t row = ((int64_t)blockIdx.x * kBlock + threadIdx.x) / 64;
     const int lane = threadIdx.x % 64;
@@ -2668,7 +2696,7 @@ __global__ __launch_bounds__(kBlock) void attn_empty_rows_kernel(int64_t rows, d
     const double l = fresh ? 0.0 : ex.row_sum[row];
     for (int c = lane; c < R; c += 64) {
         const double a = fresh ? 0.0 : Out[row * R + c];
-        if (finish) ex.relu_dst[row * ex.relu_ld + c] = l > 0.0 ? fmax(a / l, 0.0) : 0.0;
+        if (finish) ex.relu_dst[row * ex.relu_ld + c] = l > 0.0 ? (ACT ? attn_out_act(a / l, flags) : fmax(a / l, 0.0)) : 0.0;
         else Out[row * R + c] = a;
     }
     if (lane == 0) {
@@ -2711,7 +2739,9 @@ int hnh_attn_softmax_csr_p(hnh_ctx* ctx, const hnh_csr_block* b, double* values,
     const char* who = "hnh_attn_softmax_csr_p";
     if (!b || !state) return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": null block or state");
     if (int rc = check_common(ctx, b->rows, R, who)) return rc;
-    if (flags & ~(HNH_FUSED_VALUES_OVERWRITE | HNH_FUSED_OUT_OVERWRITE | HNH_ATTN_FINISH)) return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": unknown flag");
+    if (flags & ~(HNH_FUSED_VALUES_OVERWRITE | HNH_FUSED_OUT_OVERWRITE | HNH_ATTN_FINISH | kAttnActMask))
+        return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": unknown flag");
+    if (int rc = check_attn_act_flags(ctx, flags, who)) return rc;
     const bool finish = (flags & HNH_ATTN_FINISH) != 0;
     if (finish && window != nullptr && !window->last) return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": the finish belongs to the last window");
     if (!state->row_max || !state->row_sum || !state->lse || !state->relu_dst) return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": null state pointer");
@@ -2728,8 +2758,10 @@ int hnh_attn_softmax_csr_p(hnh_ctx* ctx, const hnh_csr_block* b, double* values,
     hipStream_t st = ctx->streams[stream];
     if (b->rowptr == nullptr) {  // a block without nonzeros
         if (b->nnz > 0) return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": null rowptr");
-        const unsigned f = (flags & HNH_FUSED_OUT_OVERWRITE) | (finish ? kInternalEpilogue : 0u);
-        hipLaunchKernelGGL(attn_empty_rows_kernel, dim3((unsigned)((b->rows * 64 + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, b->rows, Out, R, f, ex);
+        const unsigned f = (flags & (HNH_FUSED_OUT_OVERWRITE | kAttnActMask)) | (finish ? kInternalEpilogue : 0u);
+        const dim3 grid((unsigned)((b->rows * 64 + kBlock - 1) / kBlock));
+        if (f & kAttnActMask) hipLaunchKernelGGL(attn_empty_rows_kernel<true>, grid, dim3(kBlock), 0, st, b->rows, Out, R, f, ex);
+        else hipLaunchKernelGGL(attn_empty_rows_kernel<false>, grid, dim3(kBlock), 0, st, b->rows, Out, R, f, ex);
         return hnh::check_hip(ctx, hipGetLastError(), "attn_empty_rows_kernel launch");
     }
     if (!b->col_idx || !values || !X || !Y) return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": null pointer");
@@ -2742,7 +2774,7 @@ int hnh_attn_softmax_csr_p(hnh_ctx* ctx, const hnh_csr_block* b, double* values,
                                                        " beyond the one-pass instances (R <= 512 even with X, Y, Out and relu_dst 16-byte aligned and relu_ld "
                                                        "even, R <= 256 otherwise; a softmax cannot be composed of two passes)");
     bool done = false;
-    const unsigned f = (flags & (HNH_FUSED_VALUES_OVERWRITE | HNH_FUSED_OUT_OVERWRITE)) | HNH_FUSED_LEAKY_RELU;
+    const unsigned f = (flags & (HNH_FUSED_VALUES_OVERWRITE | HNH_FUSED_OUT_OVERWRITE | kAttnActMask)) | HNH_FUSED_LEAKY_RELU;
     if (int rc = dispatch_row<Op::kFusedSoftmax>(ctx, st, stream, s, b->rows, b->nnz, b->max_row_nnz, window ? -1 : b->cols, b->rowptr, b->col_idx, values,
                                                  nullptr, X, Y, Out, R, f, ex, finish ? &done : nullptr, window, b->plan))
         return rc;

@@ -48,6 +48,8 @@ struct Backend {
     // only GAT::backwardPass needs it, and it fails with an error naming the missing symbol
     HNH_FN(hnh_gemm_tn_f64_workspace) HNH_FN(hnh_gemm_tn_f64) HNH_FN(hnh_leaky_relu_grad_f64) HNH_FN(hnh_relu_grad_cols_f64)
     HNH_FN(hnh_sum3_cols_f64) HNH_FN(hnh_transpose_into_f64)
+    // (its presence also says that the library knows the HNH_ATTN_ACT_* flags: only a GAT layer with a non-ReLU activation needs it)
+    HNH_FN(hnh_act_grad_cols_f64)
     // OPTIONAL group (include/hnh_attention.h), bound the same way: only the GAT's softmax attention needs it
     HNH_FN(hnh_attn_softmax_csr_p) HNH_FN(hnh_softmax_gate_f64) HNH_FN(hnh_rowdot_cols_f64)
     // OPTIONAL group (include/hnh_attn_grad.h), bound the same way: only the GAT's fused backward mode needs it

@@ -777,6 +777,9 @@ int hnh_gat_set_backward(hnh_gat* g, int mode) {
 int hnh_gat_set_score(hnh_gat* g, int mode) {
     return guarded(g->w, [&] { g->g->set_score(mode); });
 }
+int hnh_gat_set_activation(hnh_gat* g, int layer, int mode) {
+    return guarded(g->w, [&] { g->g->set_activation(layer, mode); });
+}
 int hnh_gat_set_attn_vectors(hnh_gat* g, int layer, int head, const double* a1_host, const double* a2_host) {
     return guarded(g->w, [&] {
         if (layer < 0 || layer >= (int)g->g->layers.size()) throw hnh::Error("Error, GAT layer index out of range!");

@@ -288,12 +288,14 @@ public:
     // holds the rows' running max / sum, the log-sum-exp and the ReLU destination.  Returns false, having done nothing, where a row's
     // nonzeros are not all summed by this rank's own launches (only approach 2 with c = 1 has such a pass).  Not a virtual of
     // Distributed_Sparse: that would change the vtable of every schedule, which drivers compiled against the previous headers embed.
-    bool fusedSoftmax_out(DenseMatrix& localA, DenseMatrix& localB, MatMode mode, DenseMatrix& Out, const hnh_attn_state& state) {
+    // `finish_flags`: HNH_ATTN_ACT_ELU / HNH_ATTN_ACT_IDENTITY (or 0: ReLU) for the pass's finishing call alone.
+    bool fusedSoftmax_out(DenseMatrix& localA, DenseMatrix& localB, MatMode mode, DenseMatrix& Out, const hnh_attn_state& state,
+                          unsigned finish_flags = 0u) {
         if (fusionApproach != 2 || c != 1) return false;  // (c > 1 reduce-scatters partial rows: a softmax cannot be summed that way)
         DenseMatrix& Xin = (mode == Amat) ? localA : localB;
         if (Out.rows() != Xin.rows() || Out.cols() != Xin.cols() || Out.data() == Xin.data())
             hnh::fatal("Error, fusedSoftmax_out needs a separate output of the input's shape!");
-        fused_pass(Xin, mode == Amat ? localB : localA, mode == Amat ? S.get() : ST.get(), &Out, 0u, nullptr, &state);
+        fused_pass(Xin, mode == Amat ? localB : localA, mode == Amat ? S.get() : ST.get(), &Out, 0u, nullptr, &state, finish_flags);
         return true;
     }
 
@@ -323,15 +325,16 @@ public:
     // Not a virtual of Distributed_Sparse, for fusedSoftmax_out's reason.
     // `drop` (include/hnh_attn_dropout.h): the passes' DROP instances; `moving` is then M' / Q', whose rows carry their global ids, and
     // drop->row_id0 is the global id of this rank's row 0 (the same for every block: a block's rows are the rank's rows).
+    // `finish_flags`: HNH_ATTN_ACT_ELU / HNH_ATTN_ACT_IDENTITY (or 0: ReLU) for the forward pass's finishing call alone.
     bool attnAdditive_pass(int pass, DenseMatrix& moving, const hnh_attn_add& args, int64_t out_rows, bool overwrite,
-                           const hnh_attn_drop* drop = nullptr) {
+                           const hnh_attn_drop* drop = nullptr, unsigned finish_flags = 0u) {
         if (fusionApproach != 2 || c != 1) return false;
         if (pass < 0 || pass > 2) hnh::fatal("Error, attnAdditive_pass: unknown pass!");
         if (moving.cols() != R) hnh::fatal("Error, attnAdditive_pass: the schedule's R must be the moving operand's width!");
         attn_walk(pass == 2 ? ST.get() : S.get(), moving, args, overwrite, pass == 0,
                   "Error, the kernel implementation has no additive attention pass (KernelImplementation::attn_additive_local)!",
                   [&](SpmatLocal& choice, int block_id, const hnh_attn_add& a, unsigned flags, bool finish) {
-                      return kernel->attn_additive_local(choice, block_id, a, pass, flags, out_rows, finish, drop);
+                      return kernel->attn_additive_local(choice, block_id, a, pass, flags | (finish ? finish_flags : 0u), out_rows, finish, drop);
                   });
         return true;
     }
@@ -540,8 +543,9 @@ private:
     // One pass of shifts with the fused kernel on every visiting block.  target == nullptr: the result replaces
     // Xin (the reference's in-place fusedSpMM); otherwise it is written to *target and Xin survives.
     // softmax != nullptr: the neighbourhood-softmax instance (KernelImplementation::softmax_local) instead of the fused pair, c == 1 only.
+    // softmax_finish_flags: the output activation bits of the softmax pass's closing call (include/hnh_attention.h).
     void fused_pass(DenseMatrix& Xin, DenseMatrix& moving, SpmatLocal* choice, DenseMatrix* target, unsigned act_flag,
-                    const hnh_fused_extras* extras, const hnh_attn_state* softmax = nullptr) {
+                    const hnh_fused_extras* extras, const hnh_attn_state* softmax = nullptr, unsigned softmax_finish_flags = 0u) {
         DenseMatrix* Arole = &Xin;
         DenseMatrix* Brole = &moving;
         const int n = p / c;
@@ -574,7 +578,7 @@ private:
             const hnh_fused_extras* ex = closing ? last : act;
             CSRLocal* blk = choice->csr_blocks[block_id];
             if (blk == nullptr && ex == act && !(softmax && (closing || out_fresh))) return;  // nothing to multiply and no epilogue to run
-            const unsigned flags = base | (out_fresh ? HNH_FUSED_OUT_OVERWRITE : 0u);
+            const unsigned flags = base | (out_fresh ? HNH_FUSED_OUT_OVERWRITE : 0u) | ((softmax && closing) ? softmax_finish_flags : 0u);
             const bool done = in_window(blk, window, window_end, [&] {
                 return softmax ? kernel->softmax_local(*choice, *rowOperand, Y, *accum, block_id, flags, *softmax, closing)
                                : (kernel->fused_local(*choice, *rowOperand, Y, *accum, block_id, flags, ex), true);

@@ -73,7 +73,16 @@
 // weight_grads / attn_grads are identical on every rank, so every rank applies the same update and the parameters stay equal bit for bit
 // without a broadcast.  train_step() = [seed + 1 when a dropout rate is nonzero] forwardPass, loss into an internal G, backwardPass,
 // optimizer_step, all on the compute stream; the host waits once, for the two scalars (of the parameters BEFORE the update).
-// Known deviation from the published output layer: the heads pass through the ReLU epilogue before they are averaged.
+//
+// Output activation (an addition; set_activation(layer, mode), HNH_GAT_ACT_RELU on every layer by default, which launches exactly the kernels
+// above).  out[:, h f ..] = phi_l(o) with phi in {relu, elu, identity} leaves the finishing launch of the softmax and additive forward passes
+// (the HNH_ATTN_ACT_* flags of include/hnh_attention.h).  The backward pass keeps no pre-activation: for a non-ReLU layer ONE pass
+// (hnh_act_grad_cols_f64, include/hnh_grad.h) makes dZ and delta of a head from G and the stored output, in place of hnh_relu_grad_cols_f64 and
+// hnh_rowdot_cols_f64:  identity  dZ = G, delta_i = <G_i, out_i>;  elu  dZ = G where out >= 0 and G (1 + out) below, delta_i = sum_c dZ_ic o_ic
+// with o = log1p(out) below 0 (the term is 0 where 1 + out == 0).  Supported with attention softmax (score dot or additive, any dropout rates)
+// on 15d_fusion2 with c = 1; attention none keeps ReLU only, and everything else raises before anything is launched.
+// The published network is activation elu on the hidden layers and identity on the last with HNH_GAT_HEADS_MEAN: the loss then averages the raw
+// head aggregates.  With the default relu on the last layer the heads pass through the ReLU epilogue before they are averaged.
 #pragma once
 #include "dense_shift_15d.hpp"
 #include "distributed_sparse.hpp"
@@ -105,6 +114,7 @@ public:
         this->d_ops = d_ops;
         world_ = d_ops->world;  // not owned by the operator: benchmark_dist.cpp:166 deletes d_ops while its GAT is still alive
         layers = l_input;
+        act_.assign(layers.size(), HNH_GAT_ACT_RELU);
         d_ops->setRValue(layers[0].input_features);
         buffers.push_back(d_ops->like_B_matrix(0.0));
         for (size_t i = 0; i < layers.size(); i++) {
@@ -144,6 +154,20 @@ public:
             throw hnh::Error("Error, unknown GAT score " + std::to_string(mode) + " (dot = 0, additive = 1)!");
         if (mode != score_) invalidate_forward();
         score_ = mode;
+    }
+
+    // HNH_GAT_ACT_RELU | HNH_GAT_ACT_ELU | HNH_GAT_ACT_IDENTITY of layer i's output (include/hnh_dist.h); a change invalidates the stored
+    // forward pass.  Kept here, not in GATLayer, whose size drivers compiled against the previous headers embed.
+    int activation(int i) const {
+        check_layer(i);
+        return act_[(size_t)i];
+    }
+    void set_activation(int i, int mode) {
+        check_layer(i);
+        if (mode != HNH_GAT_ACT_RELU && mode != HNH_GAT_ACT_ELU && mode != HNH_GAT_ACT_IDENTITY)
+            throw hnh::Error("Error, unknown GAT activation " + std::to_string(mode) + " (relu = 0, elu = 1, identity = 2)!");
+        if (mode != act_[(size_t)i]) invalidate_forward();
+        act_[(size_t)i] = mode;
     }
 
     // Dropout (include/hnh_attn_dropout.h): rates in [0, 1) on the attention coefficients (score ADDITIVE only; checked by forwardPass)
@@ -215,6 +239,7 @@ public:
     void forwardPass() {
         const bool additive = score_ == HNH_GAT_SCORE_ADDITIVE;
         check_dropout_supported();
+        check_activation_supported();
         if (attention_ == HNH_GAT_ATTENTION_SOFTMAX && !additive) check_softmax_supported();
         if (additive) {
             check_additive_supported();
@@ -268,6 +293,7 @@ public:
     // (dL/d(buffers[i]); input_grads[0] is the input gradient).  Buffers are allocated on the first call and reused.
     void backwardPass(const DenseMatrix& grad_out) {
         check_dropout_supported();
+        check_activation_supported();
         check_backward_supported();
         if (!forward_valid_) throw hnh::Error("Error, GAT backwardPass needs a forwardPass first (and a new one after set_weight / set_input)!");
         const DenseMatrix& last = buffers.back();
@@ -407,6 +433,7 @@ public:
     std::pair<double, double> train_step() {
         check_train_supported(true);
         check_dropout_supported();
+        check_activation_supported();
         check_backward_supported();
         const uint64_t seed0 = seed_;
         const int64_t steps0 = optim_steps_;
@@ -430,6 +457,7 @@ public:
     std::pair<double, double> evaluate(const uint8_t* mask, int64_t n) {
         check_train_supported(false);
         check_dropout_supported();  // (an object that forwardPass and train_step refuse is not evaluated either)
+        check_activation_supported();
         if (mask != nullptr && n != d_ops->M) throw hnh::Error("Error, GAT evaluate: the mask needs " + std::to_string(d_ops->M) + " entries, not " + std::to_string(n) + "!");
         LabelSet other;
         if (mask != nullptr) other = make_label_set(mask);
@@ -481,6 +509,8 @@ private:
     int score_ = HNH_GAT_SCORE_DOT;
     double attn_p_ = 0.0, feat_p_ = 0.0;  // dropout rates and the masks' seed (include/hnh_attn_dropout.h)
     uint64_t seed_ = 0;
+    std::vector<int> act_;                // HNH_GAT_ACT_* of every layer's output
+    DenseMatrix act_delta_;               // a non-ReLU layer's delta of the head in hand: backward_layer writes it, head_delta hands it out
     std::vector<DenseMatrix> xd_;         // feature dropout: Xd of every layer (allocated only then)
     // training (include/hnh_train.h): this rank's labels on the device (-1: not in the loss) with the world's labelled count; the host's
     // copy of all labels and of the training mask (loss / evaluate build other sets from them); the optimizer and its moments
@@ -499,8 +529,11 @@ private:
     std::vector<std::vector<DenseMatrix>> mom_w_, var_w_;
     std::vector<DenseMatrix> mom_a_, var_a_;  // [2 layer + (0: a1, 1: a2)]
 
-    void check_layer_head(int i, int h) const {
+    void check_layer(int i) const {
         if (i < 0 || i >= (int)layers.size()) throw hnh::Error("Error, GAT layer index " + std::to_string(i) + " out of range: " + std::to_string(layers.size()) + " layers!");
+    }
+    void check_layer_head(int i, int h) const {
+        check_layer(i);
         if (h < 0 || h >= layers[(size_t)i].num_heads)
             throw hnh::Error("Error, GAT head index " + std::to_string(h) + " out of range: layer " + std::to_string(i) + " has " + std::to_string(layers[(size_t)i].num_heads) + " heads!");
     }
@@ -690,6 +723,28 @@ private:
         if (feat_p_ > 0.0) require_kernels("dropout", "include/hnh_attn_dropout.h", {HNH_GAT_KERNEL(hnh_feat_drop_f64)});
     }
 
+    static const char* activation_name(int mode) { return mode == HNH_GAT_ACT_ELU ? "elu" : (mode == HNH_GAT_ACT_IDENTITY ? "identity" : "relu"); }
+    // the finishing call's flag of layer i's activation (include/hnh_attention.h); 0 for relu
+    unsigned activation_flag(int i) const {
+        const int m = act_[(size_t)i];
+        return m == HNH_GAT_ACT_ELU ? HNH_ATTN_ACT_ELU : (m == HNH_GAT_ACT_IDENTITY ? HNH_ATTN_ACT_IDENTITY : 0u);
+    }
+    // A non-ReLU layer's own conditions, checked before anything is launched: the attention mode (attention none ends in the fused pair's
+    // or the un-fused route's ReLU), the schedule (the softmax's), then a kernel library that knows the activation flags, which is one
+    // that exports hnh_act_grad_cols_f64.  Every layer at relu: nothing to check, today's launches.
+    void check_activation_supported() {
+        for (size_t i = 0; i < layers.size(); i++) {
+            if (act_[i] == HNH_GAT_ACT_RELU) continue;
+            const std::string what = std::string("activation ") + activation_name(act_[i]) + " of layer " + std::to_string(i);
+            if (attention_ != HNH_GAT_ATTENTION_SOFTMAX)
+                throw hnh::Error("Error, GAT " + what + " supports attention mode softmax only, not attention mode none: its passes end in a ReLU "
+                                 "(include/hnh_attention.h)");
+            require_own_rows(what);
+            const hnh::Backend* be = d_ops->world->be;
+            require_kernels(what, "include/hnh_grad.h", {HNH_GAT_KERNEL(hnh_act_grad_cols_f64)});
+        }
+    }
+
     // Throws hnh::Error (never a wrong number) where the backward pass is not defined or its kernels are missing.
     void check_backward_supported() {
         if (score_ == HNH_GAT_SCORE_ADDITIVE) check_additive_supported();
@@ -778,8 +833,15 @@ private:
             DenseMatrix& A = scratch(2, rows, f);
             DenseMatrix& dZ = scratch(3, rows, f);
             w->check(be->hnh_gemm_f64(w->ctx, rows, f, k, X.data(), Wh.data(), A.data(), S0), "hnh_gemm_f64");
-            w->check(be->hnh_relu_grad_cols_f64(w->ctx, dZ.data(), f, G.data(), hf, out.data(), hf, (int64_t)h * f, rows, f, S0),
-                     "hnh_relu_grad_cols_f64");
+            if (act_[(size_t)i] == HNH_GAT_ACT_RELU)
+                w->check(be->hnh_relu_grad_cols_f64(w->ctx, dZ.data(), f, G.data(), hf, out.data(), hf, (int64_t)h * f, rows, f, S0),
+                         "hnh_relu_grad_cols_f64");
+            else {  // dZ and delta from one read of G and the stored output; the delta waits in act_delta_ for head_delta
+                if (act_delta_.rows() != rows || act_delta_.cols() != 1) act_delta_ = DenseMatrix(rows, 1);
+                w->check(be->hnh_act_grad_cols_f64(w->ctx, dZ.data(), f, act_delta_.data(), G.data(), hf, out.data(), hf, (int64_t)h * f, rows, f,
+                                                   act_[(size_t)i] == HNH_GAT_ACT_ELU ? HNH_ACT_ELU : HNH_ACT_IDENTITY, S0),
+                         "hnh_act_grad_cols_f64");
+            }
             if (score_ == HNH_GAT_SCORE_ADDITIVE) backward_head_additive(i, h, A, dZ, dA_all);
             else if (backward_ == HNH_GAT_BACKWARD_FUSED) backward_head_fused(i, h, A, dZ, dA_all);
             else backward_head_unfused(i, h, A, dZ, dA_all);
@@ -806,9 +868,16 @@ private:
     }
     // The three implementations of one head of the backward pass.  A = X W_h and dZ are backward_layer's; the head's column block of dA_all
     // is the result.
-    // delta_i = <dZ_i, out_i> of head h (= <dZ_i, o_i>: dZ is 0 where out is), the softmax's row scalar, on the compute stream
+    // delta_i = <dZ_i, out_i> of head h (= <dZ_i, o_i>: dZ is 0 where out is), the softmax's row scalar, on the compute stream; for a
+    // non-ReLU layer delta_i = <dZ_i, o_i> is what backward_layer's hnh_act_grad_cols_f64 call of this head left in act_delta_ (a buffer of
+    // its own, which nothing else writes)
     DenseMatrix& head_delta(int i, int h, const DenseMatrix& dZ) {
         hnh::World* w = d_ops->world;
+        if (act_[(size_t)i] != HNH_GAT_ACT_RELU) {
+            if (act_delta_.rows() != dZ.rows() || act_delta_.cols() != 1)
+                throw hnh::Error("Error, GAT backwardPass: the activation's delta does not have the head's rows!");
+            return act_delta_;
+        }
         const DenseMatrix& out = buffers[(size_t)i + 1];
         const int64_t f = dZ.cols();
         DenseMatrix& delta = scratch(8, dZ.rows(), 1);
@@ -1054,14 +1123,14 @@ private:
             if (ds != nullptr) {
                 ScheduleWidth width(d_ops, (int)A.cols(), f);
                 const hnh_attn_drop dr = attn_drop_args(i, j);
-                ok = ds->attnAdditive_pass(0, A, g, rows, true, attn_p_ > 0.0 ? &dr : nullptr);
+                ok = ds->attnAdditive_pass(0, A, g, rows, true, attn_p_ > 0.0 ? &dr : nullptr, activation_flag(i));
             }
             require_own_rows("score additive", !ok);
             return;
         }
 
         if (attention_ == HNH_GAT_ATTENTION_SOFTMAX) {
-            // one fused pass with the online softmax (include/hnh_attention.h): the head's ReLU output leaves the finishing launch
+            // one fused pass with the online softmax (include/hnh_attention.h): the head's activated output leaves the finishing launch
             // straight into its column block, lse into this head's vector; H carries the unnormalised rows between the launches
             const int64_t rows = A.rows();
             DenseMatrix& lse = softmax_row_state(i, j, rows);
@@ -1069,7 +1138,7 @@ private:
             const hnh_attn_state st = {row_max_.data(), row_sum_.data(), lse.data(), leaky_relu_alpha,
                                        out.data() + (int64_t)j * A.cols(), (int64_t)out.cols()};
             auto* ds = dynamic_cast<Sparse15D_Dense_Shift*>(d_ops);
-            require_own_rows("softmax attention", ds == nullptr || !ds->fusedSoftmax_out(A, A, Amat, H, st));
+            require_own_rows("softmax attention", ds == nullptr || !ds->fusedSoftmax_out(A, A, Amat, H, st, activation_flag(i)));
             return;
         }
 

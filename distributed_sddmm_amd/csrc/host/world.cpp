@@ -118,6 +118,7 @@ Backend* load_backend(const char* path_c) {
 #define HNH_BIND_OPTIONAL(sym) b->sym = (decltype(b->sym))dlsym(dl, #sym);
     HNH_BIND_OPTIONAL(hnh_gemm_tn_f64_workspace) HNH_BIND_OPTIONAL(hnh_gemm_tn_f64) HNH_BIND_OPTIONAL(hnh_leaky_relu_grad_f64)
     HNH_BIND_OPTIONAL(hnh_relu_grad_cols_f64) HNH_BIND_OPTIONAL(hnh_sum3_cols_f64) HNH_BIND_OPTIONAL(hnh_transpose_into_f64)
+    HNH_BIND_OPTIONAL(hnh_act_grad_cols_f64)
     HNH_BIND_OPTIONAL(hnh_attn_softmax_csr_p) HNH_BIND_OPTIONAL(hnh_softmax_gate_f64) HNH_BIND_OPTIONAL(hnh_rowdot_cols_f64)
     HNH_BIND_OPTIONAL(hnh_attn_grad_row_csr_p) HNH_BIND_OPTIONAL(hnh_attn_grad_col_csr_p) HNH_BIND_OPTIONAL(hnh_attn_grad_pack_f64)
     HNH_BIND_OPTIONAL(hnh_attn_add_fwd_csr_p) HNH_BIND_OPTIONAL(hnh_attn_add_row_csr_p) HNH_BIND_OPTIONAL(hnh_attn_add_col_csr_p)

@@ -27,13 +27,20 @@ extern "C" {
  * whole pass, or the window with `last` set).  HNH_FUSED_OUT_OVERWRITE starts every row of the call from the empty state
  * (M = -inf, l = 0, Out row = 0), whether the row has nonzeros in the call or not. */
 #define HNH_ATTN_FINISH 8u
+/* Output activation of the finishing call, with o_i the finished row (o_i = 0 without nonzeros): neither bit writes max(o_i, 0) (ReLU),
+ * HNH_ATTN_ACT_ELU writes o for o > 0 and expm1(o) otherwise, HNH_ATTN_ACT_IDENTITY writes o_i itself.  Meaningful only together with
+ * HNH_ATTN_FINISH: both bits at once, or one without HNH_ATTN_FINISH, return HNH_ERR_INVALID and write nothing.  The same bits serve
+ * hnh_attn_add_fwd_csr_p (hnh_attn_additive.h) and hnh_attn_drop_fwd_csr_p (hnh_attn_dropout.h).  A library that exports
+ * hnh_act_grad_cols_f64 (hnh_grad.h) knows them. */
+#define HNH_ATTN_ACT_ELU 0x10u
+#define HNH_ATTN_ACT_IDENTITY 0x20u
 
 typedef struct hnh_attn_state {
     double* row_max;    /* rows: running max M */
     double* row_sum;    /* rows: running sum l */
     double* lse;        /* rows: M + log l, written by the finishing call (0 for a row without nonzeros) */
     double leaky_alpha; /* slope of the LeakyReLU applied to the scores */
-    double* relu_dst;   /* the finishing call writes max(o_i, 0) to relu_dst[i * relu_ld + c], c < R (o_i = 0 without nonzeros) */
+    double* relu_dst;   /* the finishing call writes act(o_i) to relu_dst[i * relu_ld + c], c < R: max(o_i, 0) unless an HNH_ATTN_ACT_* flag is set */
     int64_t relu_ld;
 } hnh_attn_state;
 

@@ -257,6 +257,17 @@ int hnh_gat_set_backward(hnh_gat* g, int mode);
 #define HNH_GAT_SCORE_DOT 0
 #define HNH_GAT_SCORE_ADDITIVE 1
 int hnh_gat_set_score(hnh_gat* g, int mode);
+/* Output activation of a layer (an addition).  RELU (the default of hnh_gat_create on every layer): out = max(o, 0), everything above.  ELU:
+ * out = o for o > 0 and expm1(o) otherwise.  IDENTITY: out = o.  The backward pass works from the stored output alone (include/hnh_grad.h,
+ * hnh_act_grad_cols_f64).  A non-ReLU layer is supported with attention SOFTMAX, score DOT or ADDITIVE, any dropout rates, on 15d_fusion2
+ * with c = 1; hnh_gat_forward / hnh_gat_backward / hnh_gat_train_step / hnh_gat_evaluate fail elsewhere before anything is launched, naming the
+ * layer, the activation and the mode or the schedule, or hnh_act_grad_cols_f64 when the kernel library lacks it.  The published network is
+ * ELU on the hidden layers and IDENTITY on the last one with HNH_GAT_HEADS_MEAN.  A change invalidates the stored forward pass; an unknown
+ * mode or a layer out of range fails. */
+#define HNH_GAT_ACT_RELU 0
+#define HNH_GAT_ACT_ELU 1
+#define HNH_GAT_ACT_IDENTITY 2
+int hnh_gat_set_activation(hnh_gat* g, int layer, int mode);
 int hnh_gat_set_attn_vectors(hnh_gat* g, int layer, int head, const double* a1_host, const double* a2_host);
 int hnh_gat_get_attn_grads(hnh_gat* g, int layer, int head, double* da1_host, double* da2_host);
 
@@ -280,8 +291,8 @@ int hnh_gat_get_attn_vectors(hnh_gat* g, int layer, int head, double* a1_host, d
 /* Labels: n = M host entries in the operator's global row numbering (the rows of hnh_gat_get_output: block row + local row); a negative
  * label, or a row whose mask byte is 0 (mask_or_null == NULL: no mask), is not in the loss.  heads_mode MEAN: the classes are the last
  * layer's features_per_head and the logits the mean over its heads; CONCAT: num_heads * features_per_head classes, the row as it is.
- * (Known deviation: the heads pass through the forward pass's ReLU before they are averaged; the published output layer averages raw
- * head outputs.)  Each rank keeps its slice on the device; the labelled count is summed over the world once (collective).  A label
+ * (The published output layer averages raw head outputs: that is HNH_GAT_ACT_IDENTITY on the last layer.  With the default RELU there the
+ * heads pass through the forward pass's ReLU before they are averaged.)  Each rank keeps its slice on the device; the labelled count is summed over the world once (collective).  A label
  * >= the class count, a mask without a labelled row or a wrong n fails and leaves the object as it was. */
 #define HNH_GAT_HEADS_MEAN 0
 #define HNH_GAT_HEADS_CONCAT 1

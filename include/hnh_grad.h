@@ -29,6 +29,22 @@ int hnh_leaky_relu_grad_f64(hnh_ctx* ctx, double* e_to_a, double* da_to_de, doub
 int hnh_relu_grad_cols_f64(hnh_ctx* ctx, double* dZ, int64_t ld_dz, const double* G, int64_t ld_g, const double* out, int64_t ld_out,
                            int64_t col0, int64_t rows, int64_t cols, int stream);
 
+/* dZ and delta of one head from G and the STORED output of the head's activation, in one pass over the column block [col0, col0 + cols)
+ * of G and out (each read once): dZ (rows x cols, pitch ld_dz) and delta (rows).  With o the activation's input recovered from out:
+ *     HNH_ACT_RELU      dZ = out > 0 ? G : 0                      delta_r = sum_c dZ[r, c] out[r, c]   (hnh_relu_grad_cols_f64's dZ, bit for bit)
+ *     HNH_ACT_IDENTITY  dZ = G                                    delta_r = sum_c G[r, c] out[r, c]
+ *     HNH_ACT_ELU       dZ = G where out >= 0, G (1 + out) below  delta_r = sum_c dZ[r, c] o[r, c], o = out where out >= 0 and log1p(out) below;
+ *                       the term is 0 where 1 + out == 0 (a unit saturated at -1 has dZ = 0)
+ * A power-of-two group of lanes owns a row; delta is summed in a fixed order (no atomics): bit-identical run to run.  16-byte accesses
+ * when cols, col0 and the three pitches are even and the three bases 16-byte aligned.  Replaces hnh_relu_grad_cols_f64 followed by
+ * hnh_rowdot_cols_f64 (hnh_attention.h).  A kernel library that exports this symbol also knows the HNH_ATTN_ACT_* flags of the forward
+ * passes (hnh_attention.h). */
+#define HNH_ACT_RELU 0
+#define HNH_ACT_ELU 1
+#define HNH_ACT_IDENTITY 2
+int hnh_act_grad_cols_f64(hnh_ctx* ctx, double* dZ, int64_t ld_dz, double* delta, const double* G, int64_t ld_g, const double* out,
+                          int64_t ld_out, int64_t col0, int64_t rows, int64_t cols, int act, int stream);
+
 /* dst[r, col0 + c] = (x[r, c] + y[r, c]) + z[r, c]; x, y, z are rows x cols with leading dimension cols. */
 int hnh_sum3_cols_f64(hnh_ctx* ctx, double* dst, int64_t ld_dst, int64_t col0, const double* x, const double* y, const double* z,
                       int64_t rows, int64_t cols, int stream);

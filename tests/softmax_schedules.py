@@ -4,7 +4,7 @@ their CPU check.
 Every row belongs to one schedule g (row i: g = i % len(SCHEDULES)).  Its row operand is X_i = scale_g * e_g, and column g of the
 gathered operand holds a map t_g(j) of the column index, so s_ij = LeakyReLU(scale_g * t_g(j)): the score of a nonzero is set by its
 column, and a row's sequence of scores is designed by choosing its (sorted) columns.  The other columns of Y are random, so the
-output is not trivial.  `build` returns the designed rise positions of every row (rises = max_rises of gat_softmax_ref):
+output is not trivial.  `build` returns the designed rise positions of every row (rises = max_rises of gat_pass_ref):
 
     monotone      t increasing in j, distinct columns                      every nonzero raises the max
     spike         t decreasing in j, one spike column at position k        rises at 0 and k, k = 0 .. 18; a hub row with its spike last

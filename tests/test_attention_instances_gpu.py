@@ -4,7 +4,7 @@ launch_shape<Op::kFusedSoftmax> picks one of nine row-kernel instances (LPR, VEC
 allows 16-byte accesses (W = 2): exact (32,1,2) R = 64, (64,1,2) 128, (64,2,2) 256; bounds-checked NX(V, W) with LPR = 64 for the other
 widths: NX(1,2) even <= 128, NX(2,2) even 130 .. 256, NX(4,2) even 258 .. 512, NX(1,1) <= 64, NX(2,1) 65 .. 128, NX(4,1) 129 .. 256 when
 W = 1 (odd widths, or a relu_dst that is 8-byte aligned only).  Every width below is checked against the extended-precision reference
-(gat_softmax_ref.attention_ld), for untouched columns outside the head's block and for bit-identical repeats.
+(gat_pass_ref.attention_ld), for untouched columns outside the head's block and for bit-identical repeats.
 
 The rescale of the running state (process_row: `if (fu != 1.0)`) runs only where a row's running max rises, which uniform random
 scores do mostly in a row's first nonzeros.  tests/softmax_schedules.py designs the score sequences instead (monotone rows, a spike at
@@ -14,17 +14,17 @@ column panels and as 6 windows grouped into 1, 2, 5 and 6 launches must give the
 (nothing written) and the block without nonzeros (attn_empty_rows_kernel).
 
 Every test passed on an MI355X (45 tests, 13 s wall under a kernel trace, all nine row-kernel instances launched); the bounds
-asserted are those of test_gat_softmax_gpu.check_against_numpy (1e-12 output and lse, 1e-13 scores)."""
+asserted are those of gat_gpu_harness.check_against_numpy (1e-12 output and lse, 1e-13 scores)."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
-import gat_softmax_ref as R
+import gat_pass_ref as R
 import hnh_testlib as T
 import softmax_schedules as S
 from distributed_sddmm_amd import _kernels as K
-from test_gat_softmax_gpu import ALPHA, check_against_numpy, graph, mixed_degrees, softmax_pass
+from gat_gpu_harness import ALPHA, check_against_numpy, ctx, hip_backend, mixed_degrees, softmax_pass, square_graph  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 ERR_UNSUPPORTED = 4
@@ -37,19 +37,6 @@ SCHEDULE_WIDTHS = [(64, 2), (128, 2), (256, 2), (100, 2), (200, 2), (300, 2), (7
 GROUPINGS = ([(0, 6)], [(0, 3), (3, 6)], [(0, 1), (1, 2), (2, 4), (4, 5), (5, 6)], [(q, q + 1) for q in range(6)])
 
 
-@pytest.fixture(autouse=True, scope="module")
-def hip_backend():
-    assert K.load().hnh_backend_name() == b"hip-gfx950"
-    yield
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    c = K.Ctx(0)
-    yield c
-    c.close()
-
-
 def wid(p):
     return "R%d%s" % (p[0], "_w1" if p[1] % 2 else "")
 
@@ -57,7 +44,7 @@ def wid(p):
 @pytest.mark.parametrize("width,off", WIDTHS, ids=[wid(p) for p in WIDTHS])
 def test_every_width_vs_extended_reference(ctx, width, off):
     m = 4096
-    rowptr, colidx, rows = graph(m, mixed_degrees(m, width + off), width)
+    rowptr, colidx, rows = square_graph(m, mixed_degrees(m, width + off, empty=()), width)
     rng = np.random.default_rng(width * 10 + off)
     x, y = rng.uniform(-1, 1, (m, width)) * 2.0, rng.uniform(-1, 1, (m, width)) * 2.0
     got = softmax_pass(ctx, rowptr, colidx, x, y, ALPHA, off=off)  # (asserts the columns outside the head's block)
@@ -105,7 +92,7 @@ class Call:
     def __init__(self, ctx, m, width, off=2, ld=None, deg=3):
         self.ctx, self.m, self.width, self.off = ctx, m, width, off
         self.ld = ld or width + 4
-        self.rowptr, self.colidx, self.rows = graph(m, np.full(m, deg), width)
+        self.rowptr, self.colidx, self.rows = square_graph(m, np.full(m, deg), width)
         rng = np.random.default_rng(width)
         self.x = rng.uniform(-1, 1, (m, width))
         self.d = dict(rp=ctx.upload(self.rowptr), ci=ctx.upload(self.colidx), x=ctx.upload(self.x), vals=ctx.upload(np.full(m * deg, 3.0)),

@@ -10,7 +10,7 @@ import time
 import numpy as np
 import pytest
 
-from test_gloo_world import ROOT, free_port
+from world_launch import ROOT, can_read_peer_memory, free_port
 
 from bench_line import LINE_LIMIT, read_line  # noqa: E402,F401
 
@@ -115,7 +115,6 @@ def test_the_multi_gpu_product_path_with_every_transport_usable(nranks):
     """What the first run on a node with several GPUs will do, for the first time anywhere (on a one-GPU box RCCL never passes its
     trial): both transports pass their child-process trials, all three variants are created in the benchmark process and run the
     preflight, the default route is measured on each of them, the search continues on the fastest, the winner is measured in full."""
-    from test_ipc_world_cpu import can_read_peer_memory
     if not can_read_peer_memory():
         pytest.skip("process_vm_readv between own processes is not permitted here")
     res, out = product_launch(nranks)
@@ -135,7 +134,6 @@ def test_the_time_budget_ends_the_search_with_a_complete_line():
     """Candidates that take seconds each (here: 2 s of sleep per candidate) on a run with --budget-s 45: the search stops taking
     candidates while the budget still has room for the winner's full measurement, says so in config.budget_stops, and the line is a
     COMPLETE one (no "incomplete" mark, check ok, phases_s) printed well inside the budget — the launcher's limit is budget + 120."""
-    from test_ipc_world_cpu import can_read_peer_memory
     if not can_read_peer_memory():
         pytest.skip("process_vm_readv between own processes is not permitted here")
     t0 = time.time()
@@ -157,7 +155,6 @@ def test_sigterm_to_the_launcher_prints_the_line_in_hand():
     rank 0 first, which prints the complete measurement it already holds, marked "incomplete"; the launcher forwards that ONE line
     and exits 0."""
     import signal
-    from test_ipc_world_cpu import can_read_peer_memory
     if not can_read_peer_memory():
         pytest.skip("process_vm_readv between own processes is not permitted here")
     env = dict(os.environ, OMP_NUM_THREADS="2", GLOO_SOCKET_IFNAME="lo", HNH_ORACLE_COMM_WAIT_S="120", HNH_IPC_WAIT_S="120",
@@ -187,7 +184,6 @@ def test_a_multi_gpu_line_carries_the_whole_step_roofline_and_the_cpu_baseline(t
     record the N = 1 run left on this host is quoted (here: a seeded record), without one the bounded sample leg runs after the line
     is in hand."""
     import socket
-    from test_ipc_world_cpu import can_read_peer_memory
     if not can_read_peer_memory():
         pytest.skip("process_vm_readv between own processes is not permitted here")
     key = "er10_ef8_r16_s10_t1"
@@ -226,7 +222,6 @@ def test_a_multi_gpu_line_carries_the_whole_step_roofline_and_the_cpu_baseline(t
 def test_the_multi_gpu_product_path_when_rccl_cannot_be_created():
     """RCCL fails in its child-process trial (here: the transport constructor raises): the verdict says so, the benchmark process never
     tries it, and the run completes over the ipc-pull transport."""
-    from test_ipc_world_cpu import can_read_peer_memory
     if not can_read_peer_memory():
         pytest.skip("process_vm_readv between own processes is not permitted here")
     res, out = product_launch(2, {"BENCH_PRODUCT_BREAK": "rccl"})
@@ -240,7 +235,6 @@ def test_the_multi_gpu_product_path_when_rccl_cannot_be_created():
 def test_the_multi_gpu_product_path_when_a_transport_trial_hangs():
     """A transport whose child-process trial never answers (an RCCL bootstrap stuck on this node, say) is ended at --probe-timeout, recorded
     as a hang, and left alone; the hang never reaches the benchmark process."""
-    from test_ipc_world_cpu import can_read_peer_memory
     if not can_read_peer_memory():
         pytest.skip("process_vm_readv between own processes is not permitted here")
     res, out = product_launch(2, {"BENCH_PRODUCT_BREAK": "rccl-hang"}, probe_timeout="6")
@@ -253,7 +247,6 @@ def test_the_multi_gpu_product_path_when_a_transport_trial_hangs():
 def test_the_multi_gpu_product_path_when_a_transport_fails_its_preflight_on_one_rank():
     """RCCL passes its trial, is created in the benchmark process, and then fails the preflight ON ONE RANK ONLY: the ranks agree (a
     transport that failed anywhere failed), it is marked dead, the other rank does not wait for it, and the run completes over ipc-pull."""
-    from test_ipc_world_cpu import can_read_peer_memory
     if not can_read_peer_memory():
         pytest.skip("process_vm_readv between own processes is not permitted here")
     res, out = product_launch(2, {"BENCH_PRODUCT_BREAK": "rccl-preflight", "HNH_ORACLE_COMM_WAIT_S": "5"})  # (the stuck rank's transport gives up after 5 s)
@@ -267,7 +260,6 @@ def test_the_multi_gpu_product_path_when_a_transport_fails_its_preflight_on_one_
 def test_the_multi_gpu_product_path_when_a_later_transport_hangs():
     """Only one transport is brought up before the first complete measurement.  The second one hangs while it is created (one rank never
     arrives): the watchdog ends the run — with the line measured on the first transport, marked incomplete, not with an error."""
-    from test_ipc_world_cpu import can_read_peer_memory
     if not can_read_peer_memory():
         pytest.skip("process_vm_readv between own processes is not permitted here")
     res, out = product_launch(2, {"BENCH_PRODUCT_BREAK": "ipc-hang-late"}, extra_args=("--watchdog", "8"))
@@ -278,7 +270,6 @@ def test_the_multi_gpu_product_path_when_a_later_transport_hangs():
 def test_the_multi_gpu_product_path_when_every_trial_fails():
     """No transport passes its child-process trial — the trial machinery itself may be what is broken: the transports are tried in the
     benchmark process after all rather than giving up without a number."""
-    from test_ipc_world_cpu import can_read_peer_memory
     if not can_read_peer_memory():
         pytest.skip("process_vm_readv between own processes is not permitted here")
     res, out = product_launch(2, {"BENCH_PRODUCT_BREAK": "all-trials"})
@@ -291,7 +282,6 @@ def test_the_multi_gpu_product_path_when_a_transport_dies_in_the_search():
     """The fastest transport measures the default route, then one of its candidates raises on ONE rank while the other waits inside the
     transport (which gives up after its own time limit here): the candidate is recorded with its reason, that transport is not used
     again, and the line that was measured stays."""
-    from test_ipc_world_cpu import can_read_peer_memory
     if not can_read_peer_memory():
         pytest.skip("process_vm_readv between own processes is not permitted here")
     res, out = product_launch(2, {"BENCH_PRODUCT_BREAK": "rccl-dies-in-search", "HNH_ORACLE_COMM_WAIT_S": "5", "HNH_IPC_WAIT_S": "5"})
@@ -307,7 +297,6 @@ def test_the_multi_gpu_product_path_under_torch_distributed_run():
     """The driver's launch line — python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P
     <script> --gpus N ... — around the product branch: the transport trials scrub the elastic agent's environment (their children host
     their own store), one JSON line comes out."""
-    from test_ipc_world_cpu import can_read_peer_memory
     if not can_read_peer_memory():
         pytest.skip("process_vm_readv between own processes is not permitted here")
     env = dict(os.environ, OMP_NUM_THREADS="2", GLOO_SOCKET_IFNAME="lo", HNH_ORACLE_COMM_WAIT_S="120", HNH_IPC_WAIT_S="120")

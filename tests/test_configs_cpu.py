@@ -7,7 +7,7 @@ import pytest
 import hnh_testlib as T
 from distributed_sddmm_amd import api as H
 from oracle import oracle as O
-from test_gloo_world import launch
+from world_launch import launch
 
 
 @pytest.fixture(autouse=True, scope="module")

@@ -1,6 +1,7 @@
-"""The GAT's per-layer output activation without a GPU (GAT.set_activation; tests/gat_activation_ref.py is the definition).
+"""The GAT's per-layer output activation without a GPU (GAT.set_activation; tests/gat_ref.py with `activations` is the definition).
 
-* With "relu" on every layer the reference is gat_dropout_ref's forward and backward bit for bit, with and without dropout.
+* With "relu" on every layer, spelled out or left out, the reference computes the recorded results of the dropout reference it replaced
+  (tests/golden/gat_ref_pinned.npz), with and without dropout.
 * The reference backward against central finite differences on a two-layer model ("elu", then "identity"), rates (0, 0), for every dW, da1,
   da2 and dX at the sibling tests' step and bound (1e-6); the inputs are signed and at least a quarter of the hidden aggregates are negative.
   ELU is differentiable at 0 and the identity everywhere, so only the LeakyReLU inputs need the siblings' margin from 0.
@@ -12,52 +13,48 @@
   non-ReLU layer on it is refused by forwardPass with that name before anything runs, bad names and layers raise, and the all-relu object
   behaves as before."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 
-import gat_activation_ref as R
-import gat_dropout_ref as RD
-import gat_train_ref as RT
+import gat_ref as R
 import hnh_testlib as T
 from distributed_sddmm_amd import _kernels as K
 from distributed_sddmm_amd import api as H
-from test_gat_additive_cpu import declared, fd_problem, make_gat
-from test_gat_dropout_cpu import plain_output
+from gat_cpu_harness import ROOT, declared, fd_problem, make_gat, pinned_error, plain_output
 
 ACTS = ("elu", "identity")  # the finite-difference model: hidden ELU, raw output
+MODE = dict(attention="softmax", score="additive")
+DOT = dict(attention="softmax", score="dot")
 
 
 def test_all_relu_is_the_dropout_reference_bit_for_bit():
     rows, cols, m, x, w, av, g = fd_problem()
     layers, alpha = T.GAT_LAYERS, T.GAT_ALPHA
-    for rates, seed in (((0.0, 0.0), 0), ((0.6, 0.3), 2)):
+    for rates, seed, config in (((0.0, 0.0), 0, "softmax_additive"), ((0.6, 0.3), 2, "softmax_additive_dropout")):
         for acts in (None, "relu", ("relu", "relu")):
-            assert np.array_equal(R.forward(rows, cols, m, x, layers, alpha, w, av, rates, seed, acts), RD.forward(rows, cols, m, x, layers, alpha, w, av, rates, seed))
-            a = R.backward(rows, cols, m, x, layers, alpha, g, w, av, rates, seed, acts)
-            b = RD.backward(rows, cols, m, x, layers, alpha, g, w, av, rates, seed)
-            assert np.array_equal(a[2], b[2]) and all(np.array_equal(a[0][k], b[0][k]) for k in b[0])
-            assert all(np.array_equal(a[1][k][i], b[1][k][i]) for k in b[1] for i in (0, 1))
-    other = R.forward(rows, cols, m, x, layers, alpha, w, av, activations=ACTS)
-    assert not np.array_equal(other, RD.forward(rows, cols, m, x, layers, alpha, w, av)) and other.min() < 0
+            kw = dict(MODE, rates=rates, seed=seed, activations=acts)
+            out = R.forward(rows, cols, m, x, layers, alpha, w, av, **kw)
+            assert pinned_error(config, out, *R.backward(rows, cols, m, x, layers, alpha, g, w, av, **kw)) <= 1e-13
+    other = R.forward(rows, cols, m, x, layers, alpha, w, av, activations=ACTS, **MODE)
+    assert not np.array_equal(other, R.forward(rows, cols, m, x, layers, alpha, w, av, **MODE)) and other.min() < 0
+    assert pinned_error("softmax_additive_elu_identity", other, *R.backward(rows, cols, m, x, layers, alpha, g, w, av, activations=ACTS, **MODE)) <= 1e-13
 
 
 def test_reference_backward_matches_finite_differences():
     rows, cols, m, x, w, av, g = fd_problem()  # (x uniform in [-1, 1], W normal: signed)
     layers, alpha, step = T.GAT_LAYERS, T.GAT_ALPHA, 1e-6
-    hidden = np.concatenate([o.reshape(-1) for o in R.pre_activations(rows, cols, m, x, layers, alpha, w, av, activations=ACTS)[0]])
+    hidden = np.concatenate([o.reshape(-1) for _, o in R.pre_activations(rows, cols, m, x, layers, alpha, w, av, activations=ACTS, **MODE)[0]])
     share = np.count_nonzero(hidden < 0) / hidden.size
     print("negative share of the hidden aggregates: %.3f" % share)
     assert share >= 0.25
-    dws, das, dx = R.backward(rows, cols, m, x, layers, alpha, g, w, av, activations=ACTS)
+    dws, das, dx = R.backward(rows, cols, m, x, layers, alpha, g, w, av, activations=ACTS, **MODE)
 
     def loss(ww, aa, xx):
-        return float(np.sum(g * R.forward(rows, cols, m, xx, layers, alpha, ww, aa, activations=ACTS)))
+        return float(np.sum(g * R.forward(rows, cols, m, xx, layers, alpha, ww, aa, activations=ACTS, **MODE)))
 
     def margin_ok(ww, aa, xx, steps=100):  # the LeakyReLU inputs stay on their side of 0 (the activations here are smooth)
-        _, trace = R.forward(rows, cols, m, xx, layers, alpha, ww, aa, activations=ACTS, keep_trace=True)
-        z = np.concatenate([ht[1] for _, _, _, heads_t in trace for ht in heads_t])
+        z = np.concatenate([z for layer in R.pre_activations(rows, cols, m, xx, layers, alpha, ww, aa, activations=ACTS, **MODE) for z, _ in layer])
         return np.abs(z).min() >= steps * step
 
     assert margin_ok(w, av, x)
@@ -114,19 +111,16 @@ def test_reference_backward_matches_finite_differences():
 
 
 def test_score_dot_reference_matches_the_softmax_reference_and_finite_differences():
-    """score "dot": all-relu equals gat_softmax_ref (1e-13: the softmax reference sums dA in another order); elu / identity against
-    central differences on two weights and two inputs."""
-    import gat_softmax_ref as RS
+    """score "dot": all-relu equals the recorded results of the softmax reference that tests/gat_ref.py replaced (1e-13: same maths, the
+    matrix products' summation order may differ); elu / identity against central differences on two weights and two inputs."""
     rows, cols, m, x, w, _, g = fd_problem()
     layers, alpha, step = T.GAT_LAYERS, T.GAT_ALPHA, 1e-6
-    assert np.array_equal(R.forward(rows, cols, m, x, layers, alpha, w, score="dot"), RS.forward(rows, cols, m, x, layers, alpha, w))
-    dws, _, dx = R.backward(rows, cols, m, x, layers, alpha, g, w, score="dot")
-    dws0, dx0 = RS.backward(rows, cols, m, x, layers, alpha, g, w)
-    assert T.rel(dx, dx0) <= 1e-13 and all(T.rel(dws[k], dws0[k]) <= 1e-13 for k in dws0)
-    dws, _, dx = R.backward(rows, cols, m, x, layers, alpha, g, w, activations=ACTS, score="dot")
+    assert pinned_error("softmax_dot", R.forward(rows, cols, m, x, layers, alpha, w, **DOT), *R.backward(rows, cols, m, x, layers, alpha, g, w, **DOT)) <= 1e-13
+    dws, _, dx = R.backward(rows, cols, m, x, layers, alpha, g, w, activations=ACTS, **DOT)
+    assert pinned_error("softmax_dot_elu_identity", R.forward(rows, cols, m, x, layers, alpha, w, activations=ACTS, **DOT), dws, {}, dx) <= 1e-13
 
     def loss(ww, xx):
-        return float(np.sum(g * R.forward(rows, cols, m, xx, layers, alpha, ww, activations=ACTS, score="dot")))
+        return float(np.sum(g * R.forward(rows, cols, m, xx, layers, alpha, ww, activations=ACTS, **DOT)))
 
     for key in ((0, 1), (1, 2)):
         for idx in ((0, 0), (3, 2)):
@@ -145,17 +139,17 @@ def test_score_dot_reference_matches_the_softmax_reference_and_finite_difference
 
 def test_identity_output_with_mean_heads_is_the_published_output_layer():
     layers = T.GAT_LAYERS
-    pp = RT.planted_partition(layers)
+    pp = R.planted_partition(layers)
     args = (pp["rows"], pp["cols"], pp["m"], pp["x"], layers, T.GAT_ALPHA, pp["w"], pp["av"])
-    out = R.forward(*args, activations=ACTS)
-    raw = R.pre_activations(*args, activations=ACTS)[-1]
+    out = R.forward(*args, activations=ACTS, **MODE)
+    raw = [o for _, o in R.pre_activations(*args, activations=ACTS, **MODE)[-1]]
     nh = layers[-1][2]
     assert len(raw) == nh and min(o.min() for o in raw) < 0, "the raw class logits are signed"
     mean_raw = sum(raw) / nh
-    loss, acc, _ = RT.xent(out, pp["labels"], pp["mask"], nh)
-    want, want_acc, _ = RT.xent(mean_raw, pp["labels"], pp["mask"], 1)
+    loss, acc, _ = R.xent(out, pp["labels"], pp["mask"], nh)
+    want, want_acc, _ = R.xent(mean_raw, pp["labels"], pp["mask"], 1)
     assert abs(loss - want) <= 1e-14 * abs(want) and acc == want_acc
-    relu_loss, _, _ = RT.xent(R.forward(*args, activations=("elu", "relu")), pp["labels"], pp["mask"], nh)
+    relu_loss, _, _ = R.xent(R.forward(*args, activations=("elu", "relu"), **MODE), pp["labels"], pp["mask"], nh)
     assert abs(relu_loss - want) > 1e-3, "a ReLU on the output layer computes another loss"
 
 
@@ -195,7 +189,7 @@ def test_recovery_from_the_stored_output():
 
 def test_stored_grad_equals_true_grad_on_the_model():
     rows, cols, m, x, w, av, g = fd_problem()
-    _, trace = R.forward(rows, cols, m, x, T.GAT_LAYERS, T.GAT_ALPHA, w, av, activations=("elu", "elu"), keep_trace=True)
+    _, trace = R.forward(rows, cols, m, x, T.GAT_LAYERS, T.GAT_ALPHA, w, av, activations=("elu", "elu"), keep_trace=True, **MODE)
     for li, (_, fph, heads) in enumerate(T.GAT_LAYERS):
         out = trace[li][2]
         gg = np.random.default_rng(li).uniform(-1, 1, out.shape)
@@ -212,7 +206,7 @@ def test_new_symbols_are_declared_bound_and_exported():
     assert lib.hnh_act_grad_cols_f64.argtypes == K.GRAD_SIGNATURES["hnh_act_grad_cols_f64"][1]
     assert "hnh_gat_set_activation" in declared("hnh_dist.h") and "hnh_gat_set_activation" in H.SIGNATURES and hasattr(H.lib(), "hnh_gat_set_activation")
     assert not hasattr(C.CDLL(T.ORACLE_BACKEND), "hnh_act_grad_cols_f64"), "the CPU test double does not export it"
-    txt = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "hnh_attention.h")).read()
+    txt = open(ROOT + "/include/hnh_attention.h").read()
     assert "#define HNH_ATTN_ACT_ELU 0x%xu" % K.ATTN_ACT_ELU in txt and "#define HNH_ATTN_ACT_IDENTITY 0x%xu" % K.ATTN_ACT_IDENTITY in txt
     used = K.FUSED_VALUES_OVERWRITE | K.FUSED_OUT_OVERWRITE | K.FUSED_LEAKY_RELU | K.ATTN_FINISH | 0x100 | 0x200 | (0x1f << 16)
     assert K.ATTN_ACT_ELU & K.ATTN_ACT_IDENTITY == 0 and (K.ATTN_ACT_ELU | K.ATTN_ACT_IDENTITY) & used == 0 and max(K.ATTN_ACT_ELU, K.ATTN_ACT_IDENTITY) < 0x100

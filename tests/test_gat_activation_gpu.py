@@ -1,9 +1,9 @@
 """The GAT's per-layer output activation on the GPU (the HNH_ATTN_ACT_* flags of include/hnh_attention.h, hnh_act_grad_cols_f64 of
-include/hnh_grad.h, GAT.set_activation); tests/gat_activation_ref.py is the definition.
+include/hnh_grad.h, GAT.set_activation); tests/gat_ref.py with `activations` is the definition.
 
 Kernel level, through ctypes: the finish of the three forward entry points (hnh_attn_softmax_csr_p, hnh_attn_add_fwd_csr_p,
 hnh_attn_drop_fwd_csr_p) with ELU and the identity against the extended-precision references at 1e-12 ABSOLUTE (the forward tolerance of
-test_gat_additive_gpu.py; the activation amplifies nothing: |elu'| <= 1), on 300 rows of at most 16 nonzeros with gathered values in
+the additive kernel tests; the activation amplifies nothing: |elu'| <= 1), on 300 rows of at most 16 nonzeros with gathered values in
 [-50, 5], widths 1, 7, 64, 100, 128, 256 (and 384 for the dot-product softmax), aligned and at an odd offset; the six-window groupings bit
 for bit; blocks without nonzeros; the refused flag combinations; the ReLU default against the same call's identity output.  The dense
 backward helper at rows {1, 5, 257} x f {1, 3, 7, 64, 100, 256} inside a three-head matrix with guards, against np.longdouble at
@@ -23,41 +23,23 @@ import ctypes as C
 import numpy as np
 import pytest
 
-import gat_activation_ref as R
-import gat_additive_ref as RA
-import gat_dropout_ref as RD
-import gat_softmax_ref as RS
-import gat_train_ref as RT
+import gat_gpu_harness as G
+import gat_pass_ref as P
+import gat_ref as R
 import hnh_testlib as T
 from distributed_sddmm_amd import _kernels as K
 from distributed_sddmm_amd import api as H
+from gat_gpu_harness import (ALPHA, FWD, GROUPINGS, DropProblem, Problem, assembled, ctx, er8, hip_backend, one_round, same, setup,  # noqa: F401
+                             softmax_pass, square_graph, teardown)
 from oracle import oracle as O
-from test_gat_additive_gpu import ALPHA, FWD, GROUPINGS, Problem, er8, same, setup, teardown
-from test_gat_dropout_gpu import DropProblem
-from test_gat_softmax_gpu import graph as square_graph
-from test_gat_softmax_gpu import softmax_pass
 
 pytestmark = pytest.mark.gpu
 FTOL = 1e-12   # forward finish and the dense helper, absolute
-TOL = 1e-10    # the operator
+MODE = dict(attention="softmax", score="additive")
 BITS = {"relu": 0, "elu": K.ATTN_ACT_ELU, "identity": K.ATTN_ACT_IDENTITY}
 ERR_INVALID = 1
 M_ROWS, N_COLS = 300, 800
 WIDTHS = [1, 7, 64, 100, 128, 256]
-
-
-@pytest.fixture(autouse=True, scope="module")
-def hip_backend():
-    assert H.load_backend(None) == "hip-gfx950"
-    yield
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    c = K.Ctx(0)
-    assert K.load().hnh_backend_name() == b"hip-gfx950"
-    yield c
-    c.close()
 
 
 def short_degrees(seed, m=M_ROWS):
@@ -83,13 +65,6 @@ class ActMixin:
     def fn(self):
         real = super().fn()
         return lambda h, blk, a, flags, win, stream: real(h, blk, a, flags | (BITS[self.act] if flags & K.ATTN_FINISH else 0), win, stream)
-
-    def raw(self):
-        """(o, lse) in np.longdouble"""
-        cols = self.colidx.astype(np.int64)
-        if isinstance(self, DropProblem):
-            return RD.fwd_pass_ld(self.rows, cols, self.m, self.m_rows, self.y, self.f, ALPHA, self.ref_drop)
-        return RA.fwd_pass_ld(self.rows, cols, self.m, self.m_rows, self.y, self.f, ALPHA)
 
 
 class AddAct(ActMixin, Problem):
@@ -247,7 +222,7 @@ SOFTMAX_CASES = [(f, off) for f in WIDTHS for off in (2, 3)] + [(384, 2)]
 @pytest.mark.parametrize("f,off", SOFTMAX_CASES, ids=["f%d%s" % (f, "_odd-offset" if off % 2 else "") for f, off in SOFTMAX_CASES])
 def test_softmax_finish_vs_extended_reference(ctx, f, off):
     rowptr, colidx, rows, x, y = softmax_problem(f)
-    o, lse, _ = RS.attention_ld(rows, colidx.astype(np.int64), M_ROWS, x, y, ALPHA)
+    o, lse, _ = P.attention_ld(rows, colidx.astype(np.int64), M_ROWS, x, y, ALPHA)
     assert o.min() < -30 and o.max() > 1
     res = {}
     for act in ("relu", "elu", "identity"):
@@ -466,60 +441,19 @@ def signed_parameters(layers, seed=13, scale=2.0):
     """W of scale / sqrt(fan-in), a1 and a2 of order one: aggregates of order one on both sides of 0"""
     rng = np.random.default_rng(seed)
     w = {(li, h): rng.standard_normal((fin, fph)) * scale / np.sqrt(fin) for li, (fin, fph, heads) in enumerate(layers) for h in range(heads)}
-    return w, RA.vectors_of(layers, seed=seed + 1)
-
-
-def one_round(s, weights, additive):
-    gnn = s["gnn"]
-    gnn.forwardPass()
-    gnn.get_output(s["out"])
-    out = s["out"].download()
-    gnn.backwardPass(s["g"])
-    gnn.get_input_grad(s["dx"])
-    r = dict(out=out, dx=s["dx"].download(), dw={k: gnn.weight_grad(*k) for k in weights}, subA=s["subA"], subB=s["subB"])
-    if additive:
-        r["da"] = {k: gnn.attention_grad(*k) for k in weights}
-    return r
+    return w, R.vectors_of(layers, seed=seed + 1)
 
 
 def run_case(world, rows, cols, m, x, layers, w, av, g, additive=True, **kw):
-    s = setup(world, rows, cols, m, x, layers, w, av if additive else None, g, attention="softmax", score="additive" if additive else "dot", **kw)
-    r = one_round(s, w, additive)
-    teardown(s)
-    return r
+    return G.run_rounds(world, rows, cols, m, x, layers, w, av if additive else None, g, attention="softmax", score="additive" if additive else "dot", **kw)
 
 
-def assemble(per_rank, m, layers):
-    r0 = per_rank[0]
-    for pr in per_rank:
-        assert all(np.array_equal(pr["dw"][k], r0["dw"][k]) for k in r0["dw"]), "dW must be equal on every rank"
-        if "da" in r0:
-            assert all(np.array_equal(pr["da"][k][i], r0["da"][k][i]) for k in r0["da"] for i in (0, 1))
-    hf = layers[-1][1] * layers[-1][2]
-    res = dict(out=T.assemble_dense(per_rank, "out", "subA", m, hf), dx=T.assemble_dense(per_rank, "dx", "subB", m, layers[0][0]), dw=r0["dw"])
-    if "da" in r0:
-        res["da"] = r0["da"]
-    return res
-
-
-def compare(got, want_out, want_dw, want_da, want_dx, label, ranks):
-    errs = {"out": T.rel(got["out"], want_out), "dx": T.rel(got["dx"], want_dx)}
-    for key in want_dw:
-        assert np.abs(want_dw[key]).max() > 0
-        errs[("dw",) + key] = T.rel(got["dw"][key], want_dw[key])
-        if want_da:
-            errs[("da1",) + key] = T.rel(got["da"][key][0], want_da[key][0])
-            errs[("da2",) + key] = T.rel(got["da"][key][1], want_da[key][1])
-    worst = max(errs.values())
-    T.record_observed("gat_activation", case=label, ranks=ranks, worst=worst)
-    print("observed", label, ranks, "worst %.2e" % worst, "out %.2e dx %.2e" % (errs["out"], errs["dx"]))
-    assert worst <= TOL, errs
+def compare(got, want, label, ranks):
+    G.compare(got, want, "gat_activation", label, ranks)
 
 
 def reference(rows, cols, m, x, layers, w, av, g, acts=ACTS, rates=(0.0, 0.0), seed=0, score="additive"):
-    out = R.forward(rows, cols, m, x, layers, ALPHA, w, av, rates, seed, acts, score)
-    dw, da, dx = R.backward(rows, cols, m, x, layers, ALPHA, g, w, av, rates, seed, acts, score)
-    return out, dw, da, dx
+    return G.reference(rows, cols, m, x, layers, w, av, g, attention="softmax", score=score, rates=rates, seed=seed, activations=acts)
 
 
 def er8_problem():
@@ -533,9 +467,9 @@ def er8_problem():
 def assert_hidden_is_signed(rows, cols, m, x, layers, w, av, acts):
     """the inputs' own check: every hidden layer's aggregates are negative for a quarter of the units at least and reach below -0.5, so
     that ELU differs from the identity and from ReLU where the comparison looks"""
-    pre = R.pre_activations(rows, cols, m, x, layers, ALPHA, w, av, activations=acts)
+    pre = R.pre_activations(rows, cols, m, x, layers, ALPHA, w, av, activations=acts, **MODE)
     for li in range(len(layers) - 1):
-        hidden = np.concatenate([o.reshape(-1) for o in pre[li]])
+        hidden = np.concatenate([o.reshape(-1) for _, o in pre[li]])
         assert np.count_nonzero(hidden < 0) >= hidden.size // 4 and hidden.min() < -0.5, "the hidden ELU of layer %d sees its negative side" % li
 
 
@@ -548,18 +482,17 @@ def test_operator_er8(p):
     if "ref" not in ER8:
         ER8["ref"] = reference(rows, cols, m, x, LAYERS, w, av, g)
         assert_hidden_is_signed(rows, cols, m, x, LAYERS, w, av, ACTS)
-        assert ER8["ref"][0].min() < 0, "the identity output is signed"
+        assert ER8["ref"]["out"].min() < 0, "the identity output is signed"
     per_rank = H.run_spmd(p, lambda wd: run_case(wd, rows, cols, m, x, LAYERS, w, av, g, activation=ACTS))
-    got = assemble(per_rank, m, LAYERS)
-    compare(got, *ER8["ref"], "er8 elu/identity p%d" % p, p)
+    got = assembled(per_rank, 0, m, LAYERS)
+    compare(got, ER8["ref"], "er8 elu/identity p%d" % p, p)
     ER8[p] = got
 
 
 def test_one_rank_and_eight_ranks_agree():
     rows, cols, m, x, w, av, g = er8_problem()
-    res = {p: ER8.get(p) or assemble(H.run_spmd(p, lambda wd: run_case(wd, rows, cols, m, x, LAYERS, w, av, g, activation=ACTS)), m, LAYERS) for p in (1, 8)}
-    a = res[1]
-    compare(res[8], a["out"], a["dw"], a["da"], a["dx"], "er8 elu/identity p8 against p1", 8)
+    res = {p: ER8.get(p) or assembled(H.run_spmd(p, lambda wd: run_case(wd, rows, cols, m, x, LAYERS, w, av, g, activation=ACTS)), 0, m, LAYERS) for p in (1, 8)}
+    compare(res[8], res[1], "er8 elu/identity p8 against p1", 8)
 
 
 @pytest.mark.parametrize("p", [1, 4])
@@ -567,7 +500,7 @@ def test_operator_with_dropout(p):
     rows, cols, m, x, w, av, g = er8_problem()
     rates, seed = (0.6, 0.6), 11
     per_rank = H.run_spmd(p, lambda wd: run_case(wd, rows, cols, m, x, LAYERS, w, av, g, activation=ACTS, dropout=rates, seed=seed))
-    compare(assemble(per_rank, m, LAYERS), *reference(rows, cols, m, x, LAYERS, w, av, g, rates=rates, seed=seed), "er8 dropout p%d" % p, p)
+    compare(assembled(per_rank, 0, m, LAYERS), reference(rows, cols, m, x, LAYERS, w, av, g, rates=rates, seed=seed), "er8 dropout p%d" % p, p)
 
 
 @pytest.mark.parametrize("backward", ["unfused", "fused"])
@@ -576,9 +509,9 @@ def test_operator_score_dot(p, backward):
     rows, cols, m, x, w, av, g = er8_problem()
     w = {k: v * 0.5 for k, v in w.items()}  # (dot-product scores are quadratic in W)
     per_rank = H.run_spmd(p, lambda wd: run_case(wd, rows, cols, m, x, LAYERS, w, None, g, additive=False, activation=ACTS, backward=backward))
-    out, dw, _, dx = reference(rows, cols, m, x, LAYERS, w, None, g, score="dot")
-    assert out.min() < 0
-    compare(assemble(per_rank, m, LAYERS), out, dw, None, dx, "er8 dot %s p%d" % (backward, p), p)
+    want = reference(rows, cols, m, x, LAYERS, w, None, g, score="dot")
+    assert want["out"].min() < 0
+    compare(assembled(per_rank, 0, m, LAYERS), want, "er8 dot %s p%d" % (backward, p), p)
 
 
 def test_operator_benchmark_widths():
@@ -591,8 +524,8 @@ def test_operator_benchmark_widths():
     assert_hidden_is_signed(rows, cols, m, x, layers, w, av, acts)
     per_rank = H.run_spmd(1, lambda wd: run_case(wd, rows, cols, m, x, layers, w, av, g, activation=acts))
     ref = reference(rows, cols, m, x, layers, w, av, g, acts=acts)
-    assert ref[0].min() < 0
-    compare(assemble(per_rank, m, layers), *ref, "benchmark widths", 1)
+    assert ref["out"].min() < 0
+    compare(assembled(per_rank, 0, m, layers), ref, "benchmark widths", 1)
 
 
 def test_operator_rmat_hub_rows():
@@ -604,7 +537,7 @@ def test_operator_rmat_hub_rows():
     g = O.dense_fill(m, 64, 4) * 32.0
     assert_hidden_is_signed(rows, cols, m, x, layers, w, av, ACTS)
     per_rank = H.run_spmd(1, lambda wd: run_case(wd, rows, cols, m, x, layers, w, av, g, activation=ACTS))
-    compare(assemble(per_rank, m, layers), *reference(rows, cols, m, x, layers, w, av, g), "rmat hubs", 1)
+    compare(assembled(per_rank, 0, m, layers), reference(rows, cols, m, x, layers, w, av, g), "rmat hubs", 1)
 
 
 @pytest.mark.parametrize("alg,attention,words", [("15d_fusion2", "none", "attention mode softmax only"), ("15d_fusion1", "softmax", "15d_fusion1.*c = 1")])
@@ -659,14 +592,14 @@ def test_default_is_untouched(p):
     rows, cols, m, x = er8()
     layers = T.GAT_LAYERS
     w = {(li, h): O.gat_weight(li, h, fin, fph) for li, (fin, fph, heads) in enumerate(layers) for h in range(heads)}
-    av = RA.vectors_of(layers)
+    av = R.vectors_of(layers)
     g = O.dense_fill(m, 12, 9) * 16.0
 
     def plain(world):
-        return run_case(world, rows, cols, m, x, layers, w, av, g)
+        return run_case(world, rows, cols, m, x, layers, w, av, g)["rounds"][0]
 
     def spelled(world):
-        return run_case(world, rows, cols, m, x, layers, w, av, g, activation="relu")
+        return run_case(world, rows, cols, m, x, layers, w, av, g, activation="relu")["rounds"][0]
 
     def trip(world):
         s = setup(world, rows, cols, m, x, layers, w, av, g, attention="softmax", score="additive")
@@ -709,16 +642,16 @@ def device_train(world, pp, layers, optimizer, steps):
 
 @pytest.mark.parametrize("p", [1, 4])
 def test_training_the_published_layers(p):
-    """Hidden ELU, identity output, heads "mean" on gat_train_ref.planted_partition: the 10-step Adam trajectory within 10 x the divergence
+    """Hidden ELU, identity output, heads "mean" on gat_ref.planted_partition: the 10-step Adam trajectory within 10 x the divergence
     of a reference run whose gradients are perturbed by 1e-10 (the criterion of test_gat_train_gpu.py); after LEARN_STEPS the training loss
     is below its starting value; the parameters are bit-equal across the ranks."""
     layers = T.GAT_LAYERS
-    pp = RT.planted_partition(layers)
+    pp = R.planted_partition(layers)
     opt = dict(kind="adam", lr=0.01, weight_decay=5e-4)
     args = (pp["rows"], pp["cols"], pp["m"], pp["x"], layers, ALPHA, pp["labels"], pp["mask"], "mean", pp["w"], pp["av"])
-    ref = R.train(*args, opt, 10, ACTS)
-    per = R.train(*args, opt, 10, ACTS, perturb=(1e-10, np.random.default_rng(7)))
-    bound_p = 10.0 * RT.parameter_divergence(per[2], per[3], ref[2], ref[3])
+    ref = R.train(*args, opt, 10, activations=ACTS)
+    per = R.train(*args, opt, 10, activations=ACTS, perturb=(1e-10, np.random.default_rng(7)))
+    bound_p = 10.0 * R.parameter_divergence(per[2], per[3], ref[2], ref[3])
     bound_l = 10.0 * float(np.max(np.abs(np.array(per[0]) - np.array(ref[0]))) / np.max(np.abs(ref[0])))
     assert bound_p > 0 and bound_l > 0
     per_rank = H.run_spmd(p, lambda wd: device_train(wd, pp, layers, opt, 10))
@@ -728,12 +661,12 @@ def test_training_the_published_layers(p):
         for k in r0["w"]:
             assert np.array_equal(pr["w"][k], r0["w"][k]), "parameters are bit-equal across ranks"
             assert np.array_equal(pr["av"][k][0], r0["av"][k][0]) and np.array_equal(pr["av"][k][1], r0["av"][k][1])
-    got_p = RT.parameter_divergence(r0["w"], r0["av"], ref[2], ref[3])
+    got_p = R.parameter_divergence(r0["w"], r0["av"], ref[2], ref[3])
     got_l = float(np.max(np.abs(np.array(r0["losses"]) - np.array(ref[0]))) / np.max(np.abs(ref[0])))
     T.record_observed("gat_activation_trajectory", ranks=p, parameters=got_p, parameters_bound=bound_p, loss=got_l, loss_bound=bound_l)
     print("observed trajectory", p, "parameters %.2e (bound %.2e) loss %.2e (bound %.2e)" % (got_p, bound_p, got_l, bound_l))
     assert got_p <= bound_p and got_l <= bound_l and r0["accs"] == ref[1]
-    long_run = H.run_spmd(p, lambda wd: device_train(wd, pp, layers, RT.LEARN_OPTIMIZER, RT.LEARN_STEPS))
+    long_run = H.run_spmd(p, lambda wd: device_train(wd, pp, layers, R.LEARN_OPTIMIZER, R.LEARN_STEPS))
     lr0 = long_run[0]
     print("observed learning: loss %.3f -> %.3f, held-out accuracy %.3f" % (lr0["losses"][0], lr0["losses"][-1], lr0["held"][1]))
     assert lr0["losses"][-1] < lr0["losses"][0]

@@ -1,58 +1,39 @@
-"""The GAT's additive (a1, a2) attention score without a GPU: the numpy definition (tests/gat_additive_ref.py: forward, backward, the
-packed layouts and the passes as the kernels take them) against central finite differences, the optional kernel group of
-include/hnh_attn_additive.h (declared == bound == exported by the HIP library, disjoint from the four existing tables, absent from the
+"""The GAT's additive (a1, a2) attention score without a GPU: the numpy definition (tests/gat_ref.py with score "additive"; the
+packed layouts and the passes as the kernels take them: tests/gat_pass_ref.py) against central finite differences, the optional kernel
+group of include/hnh_attn_additive.h (declared == bound == exported by the HIP library, disjoint from the four existing tables, absent from the
 CPU test double), the host calls, and on the test double: score "additive" names a kernel of the new group and its header, every
 unsupported shape is refused by name, and score "dot" on the same object runs as before."""
 import ctypes as C
-import os
 import re
 
 import numpy as np
 import pytest
 
-import gat_additive_ref as R
+import gat_pass_ref as P
+import gat_ref as R
 import hnh_testlib as T
 from distributed_sddmm_amd import _kernels as K
 from distributed_sddmm_amd import api as H
+from gat_cpu_harness import ROOT, declared, fd_problem, make_gat
 from oracle import oracle as O
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+MODE = dict(attention="softmax", score="additive")
 GROUP = {"hnh_attn_add_fwd_csr_p", "hnh_attn_add_row_csr_p", "hnh_attn_add_col_csr_p", "hnh_attn_add_scores_f64", "hnh_attn_add_pack_f64",
          "hnh_attn_add_update_f64"}
-
-
-def declared(header):
-    txt = open(os.path.join(ROOT, "include", header)).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return set(re.findall(r"\b(hnh_[a-z0-9_]+)\s*\(", txt))
-
-
-def fd_problem():
-    """The small ER graph of the existing CPU tests (32 vertices, 123 nonzeros) plus one repeated pair, T.GAT_LAYERS, weights of the usual
-    1 / sqrt(fan-in) scale and a1, a2 of order one.  Seed 5: every pre-activation of the reference is more than 1000 steps from 0."""
-    rows, cols = O.erdos_renyi(5, 4)
-    rows, cols = np.concatenate([rows, rows[:1]]), np.concatenate([cols, cols[:1]])
-    m = 32
-    rng = np.random.default_rng(5)
-    x = rng.uniform(-1, 1, (m, T.GAT_LAYERS[0][0]))
-    w = {(li, h): rng.standard_normal((fin, fph)) / np.sqrt(fin) for li, (fin, fph, heads) in enumerate(T.GAT_LAYERS) for h in range(heads)}
-    av = {(li, h): (rng.standard_normal(fph), rng.standard_normal(fph)) for li, (fin, fph, heads) in enumerate(T.GAT_LAYERS) for h in range(heads)}
-    g = O.dense_fill(m, T.GAT_LAYERS[-1][1] * T.GAT_LAYERS[-1][2], 9) * 16.0  # dL/d(out) of L = <g, out>
-    return rows, cols, m, x, w, av, g
 
 
 def test_reference_backward_matches_finite_differences():
     rows, cols, m, x, w, av, g = fd_problem()
     layers, alpha, step = T.GAT_LAYERS, T.GAT_ALPHA, 1e-6
-    dws, das, dx = R.backward(rows, cols, m, x, layers, alpha, g, w, av)
+    dws, das, dx = R.backward(rows, cols, m, x, layers, alpha, g, w, av, **MODE)
 
     def loss(ww, aa, xx):
-        return float(np.sum(g * R.forward(rows, cols, m, xx, layers, alpha, ww, aa)))
+        return float(np.sum(g * R.forward(rows, cols, m, xx, layers, alpha, ww, aa, **MODE)))
 
     # LeakyReLU and ReLU are not differentiable at 0: every LeakyReLU input z and every ReLU input o of a non-empty row is at least
     # 100 steps away from it (exact zeros are rows that are zero whatever the perturbation: a vertex without nonzeros)
     def margin_ok(ww, aa, xx, steps=100):
-        pre = R.pre_activations(rows, cols, m, xx, layers, alpha, ww, aa)
+        pre = R.kinks(rows, m, R.pre_activations(rows, cols, m, xx, layers, alpha, ww, aa, **MODE))
         return np.abs(pre[pre != 0]).min() >= steps * step
 
     assert margin_ok(w, av, x)
@@ -107,8 +88,8 @@ def test_reference_backward_matches_finite_differences():
 
 def test_two_passes_with_the_packed_operands_equal_the_definition():
     rows, cols, m, x, w, av, g = fd_problem()
-    want = R.backward(rows, cols, m, x, T.GAT_LAYERS, T.GAT_ALPHA, g, w, av)
-    got = R.backward(rows, cols, m, x, T.GAT_LAYERS, T.GAT_ALPHA, g, w, av, by_passes=True)
+    want = R.backward(rows, cols, m, x, T.GAT_LAYERS, T.GAT_ALPHA, g, w, av, **MODE)
+    got = R.backward(rows, cols, m, x, T.GAT_LAYERS, T.GAT_ALPHA, g, w, av, by_passes=True, **MODE)
     for k in want[0]:
         assert T.rel(got[0][k], want[0][k]) <= T.TOL
         assert T.rel(got[1][k][0], want[1][k][0]) <= T.TOL and T.rel(got[1][k][1], want[1][k][1]) <= T.TOL
@@ -116,11 +97,11 @@ def test_two_passes_with_the_packed_operands_equal_the_definition():
     # the forward pass as the kernel takes it, and its extended-precision twin
     fin, f, _ = T.GAT_LAYERS[0]
     a_mat = x @ w[(0, 0)]
-    mm = R.scored(a_mat, *av[(0, 0)])
-    o, lse, z = R.fwd_pass(rows, cols, m, mm, mm, f, T.GAT_ALPHA)
-    _, trace = R.forward(rows, cols, m, x, T.GAT_LAYERS, T.GAT_ALPHA, w, av, keep=True)
-    assert T.rel(o, trace[0][2][0][3]) <= T.TOL and T.rel(lse, trace[0][2][0][4]) <= T.TOL
-    o_ld, lse_ld = R.fwd_pass_ld(rows, cols, m, mm, mm, f, T.GAT_ALPHA)
+    mm = P.scored(a_mat, *av[(0, 0)])
+    o, lse, z, _ = P.fwd_pass(rows, cols, m, mm, mm, f, T.GAT_ALPHA)
+    _, trace = R.forward(rows, cols, m, x, T.GAT_LAYERS, T.GAT_ALPHA, w, av, keep_trace=True, **MODE)
+    assert T.rel(o, trace[0][3][0][3]) <= T.TOL and T.rel(lse, trace[0][3][0][4]) <= T.TOL
+    o_ld, lse_ld = P.fwd_pass_ld(rows, cols, m, mm, mm, f, T.GAT_ALPHA)
     assert o_ld.dtype == np.longdouble and T.rel(np.float64(o_ld), o) <= 1e-13 and T.rel(np.float64(lse_ld), lse) <= 1e-13
 
 
@@ -129,8 +110,8 @@ def test_forward_is_finite_far_outside_exps_range():
     m, f = 64, 6
     rng = np.random.default_rng(1)
     a_mat = rng.uniform(-1, 1, (m, f))
-    mm = R.scored(a_mat, rng.uniform(-1, 1, f) * 400, rng.uniform(-1, 1, f) * 400)
-    o, lse, z = R.fwd_pass(rows, cols, m, mm, mm, f, T.GAT_ALPHA)
+    mm = P.scored(a_mat, rng.uniform(-1, 1, f) * 400, rng.uniform(-1, 1, f) * 400)
+    o, lse, z, _ = P.fwd_pass(rows, cols, m, mm, mm, f, T.GAT_ALPHA)
     assert np.abs(z).max() > 800 and np.all(np.isfinite(o)) and np.all(np.isfinite(lse))
 
 
@@ -142,16 +123,16 @@ def test_packed_layouts(f):
     a1, a2 = rng.uniform(-1, 1, f), rng.uniform(-1, 1, f)
     lse, delta = rng.uniform(0, 1, 5), rng.uniform(-1, 1, 5)
     fp = f + (f & 1)
-    assert R.scored_width(f) == K.attn_add_scored_width(f) == fp + 2 and R.packed_width(f) == K.attn_add_packed_width(f) == fp + 4
-    mm = R.scored(a, a1, a2, ld=fp + 4)
+    assert P.scored_width(f) == K.attn_add_scored_width(f) == fp + 2 and P.packed_width(f) == K.attn_add_packed_width(f) == fp + 4
+    mm = P.scored(a, a1, a2, ld=fp + 4)
     assert np.array_equal(mm[:, :f], a) and np.array_equal(mm[:, fp], a @ a1) and np.array_equal(mm[:, fp + 1], a @ a2)
     assert np.all(np.isnan(mm[:, fp + 2:]))
-    q = R.pack(dz, mm[:, fp], lse, delta, ld=fp + 6)
+    q = P.pack(dz, mm[:, fp], lse, delta, ld=fp + 6)
     assert np.array_equal(q[:, :f], dz) and np.array_equal(q[:, fp], mm[:, fp]) and np.array_equal(q[:, fp + 1], lse)
     assert np.array_equal(q[:, fp + 2], delta) and np.all(q[:, fp + 3] == 0.0) and np.all(np.isnan(q[:, fp + 4:]))
     if f & 1:
         assert np.all(mm[:, f] == 0.0) and np.all(q[:, f] == 0.0)
-    txt = open(os.path.join(ROOT, "include", "hnh_attn_additive.h")).read()
+    txt = open(ROOT + "/include/hnh_attn_additive.h").read()
     assert re.search(r"#define HNH_ATTN_ADD_MAX_F %d\b" % K.ATTN_ADD_MAX_F, txt)
 
 
@@ -176,15 +157,9 @@ def test_additive_kernels_are_an_optional_group():
 def test_host_calls_declared_and_exported():
     for n in ("hnh_gat_set_score", "hnh_gat_set_attn_vectors", "hnh_gat_get_attn_grads"):
         assert n in declared("hnh_dist.h") and n in H.SIGNATURES and hasattr(H.lib(), n), n
-    txt = open(os.path.join(ROOT, "include", "hnh_dist.h")).read()
+    txt = open(ROOT + "/include/hnh_dist.h").read()
     assert re.search(r"#define HNH_GAT_SCORE_DOT 0\b", txt) and re.search(r"#define HNH_GAT_SCORE_ADDITIVE 1\b", txt)
     assert H.GAT.SCORE == {"dot": 0, "additive": 1}
-
-
-def make_gat(world, case, alg, c, layers=None, **kw):
-    sp = H.SpmatLocal.from_global(world, case["M"], case["N"], case["rows"], case["cols"], np.ones(len(case["rows"])))
-    d = H.DistributedSparse(world, alg, sp, case["R"], c)
-    return sp, d, H.GAT(d, layers or T.GAT_LAYERS, T.GAT_ALPHA, **kw)
 
 
 def test_additive_on_the_test_double_names_the_missing_kernel():
@@ -298,6 +273,6 @@ def test_the_reference_trains():
     target = O.dense_fill(m, layers[-1][1] * layers[-1][2], 21) * R.SGD_TARGET_SCALE
     w = {(li, h): O.gat_weight(li, h, fin, fph) for li, (fin, fph, heads) in enumerate(layers) for h in range(heads)}
     av = R.vectors_of(layers)
-    losses, av_end = R.sgd(rows, cols, m, x, layers, T.GAT_ALPHA, target, w, av)
+    losses, av_end = R.descend(rows, cols, m, x, layers, T.GAT_ALPHA, target, w, av, **MODE)
     assert len(losses) == R.SGD_STEPS + 1 and all(losses[i + 1] < losses[i] for i in range(R.SGD_STEPS)), losses
     assert all(np.abs(av_end[k][i] - av[k][i]).max() > 0 for k in av for i in (0, 1))

@@ -1,27 +1,16 @@
-"""GAT backward pass without a GPU: the numpy definition (tests/gat_backward_ref.py) against finite differences of the forward pass,
+"""GAT backward pass without a GPU: the numpy definition (tests/gat_ref.py, attention none) against finite differences of the forward pass,
 the optional kernel group of include/hnh_grad.h (declared == bound == exported by the HIP library, absent from the mandatory table),
 and the host calls, which on the CPU test double (no such kernels) fail with an error naming the missing one."""
 import ctypes as C
-import os
-import re
-
 import numpy as np
 import pytest
 
-import gat_backward_ref as R
+import gat_cpu_harness as CH
+import gat_ref as R
 import hnh_testlib as T
 from distributed_sddmm_amd import _kernels as K
 from distributed_sddmm_amd import api as H
 from oracle import oracle as O
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def declared(header):
-    txt = open(os.path.join(ROOT, "include", header)).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return set(re.findall(r"\b(hnh_[a-z0-9_]+)\s*\(", txt))
-
 
 def fd_problem():
     """A small ER graph (32 vertices, 123 nonzeros) with T.GAT_LAYERS; the second layer's weights are scaled up so that its
@@ -38,7 +27,7 @@ def fd_problem():
 def test_reference_backward_matches_finite_differences():
     rows, cols, m, x, w, g = fd_problem()
     layers, alpha, step = T.GAT_LAYERS, T.GAT_ALPHA, 1e-6
-    dws, dx = R.backward(rows, cols, m, x, layers, alpha, g, w)
+    dws, _, dx = R.backward(rows, cols, m, x, layers, alpha, g, w)
 
     def loss(ww, xx):
         return float(np.sum(g * R.forward(rows, cols, m, xx, layers, alpha, ww)))
@@ -46,7 +35,7 @@ def test_reference_backward_matches_finite_differences():
     # LeakyReLU and ReLU are not differentiable at 0: no pre-activation may lie within +-10 steps of it (exact zeros are rows that
     # are zero whatever the perturbation: a vertex without nonzeros, or an output row that ReLU cleared)
     def margin_ok(ww, xx):
-        pre = R.pre_activations(rows, cols, m, xx, layers, alpha, ww)
+        pre = R.kinks(rows, m, R.pre_activations(rows, cols, m, xx, layers, alpha, ww))
         return np.abs(pre[pre != 0]).min() > 10 * step
 
     assert margin_ok(w, x)
@@ -75,12 +64,15 @@ def test_reference_backward_matches_finite_differences():
     err = np.max(np.abs(np.subtract(fd, an))) / np.max(np.abs(an))
     assert err <= 1e-6, err
     assert np.count_nonzero(dx) > dx.size // 2 and all(np.abs(d).max() > 0 for d in dws.values()), "the gradients must not be vacuous"
+    # ... and the definition is the recorded one, on the problem the recorded results were computed for
+    rows, cols, m, x, w, _, g = CH.fd_problem()
+    assert CH.pinned_error("none_dot", R.forward(rows, cols, m, x, layers, alpha, w), *R.backward(rows, cols, m, x, layers, alpha, g, w)) <= 1e-13
 
 
 def test_grad_kernels_are_an_optional_group():
-    names = declared("hnh_grad.h")
+    names = CH.declared("hnh_grad.h")
     assert names and names == set(K.GRAD_SIGNATURES), names ^ set(K.GRAD_SIGNATURES)
-    assert not names & declared("hnh_kernels.h") and not names & set(K.SIGNATURES), "never part of the mandatory table"
+    assert not names & CH.declared("hnh_kernels.h") and not names & set(K.SIGNATURES), "never part of the mandatory table"
     lib = K.load()  # the HIP library: dlopen needs no GPU
     for n in names:
         assert getattr(lib, n).argtypes == K.GRAD_SIGNATURES[n][1]
@@ -93,7 +85,7 @@ def test_grad_kernels_are_an_optional_group():
 
 
 def test_host_calls_declared():
-    names = declared("hnh_dist.h")
+    names = CH.declared("hnh_dist.h")
     for n in ("hnh_gat_backward", "hnh_gat_get_weight_grad", "hnh_gat_get_input_grad"):
         assert n in names and n in H.SIGNATURES
 

@@ -1,5 +1,5 @@
 """GAT backward pass on the GPU (GAT::backwardPass, include/hnh_grad.h): the split-K weight-gradient GEMM and the gate kernels
-against numpy, then dW of every (layer, head) and the input gradient against the numpy definition (tests/gat_backward_ref.py)
+against numpy, then dW of every (layer, head) and the input gradient against the numpy definition (tests/gat_ref.py, attention none)
 over loopback ranks, determinism, side effects, a few SGD steps, and the schedules that must refuse.
 
 Observed on an MI355X (max |x - ref| / max |ref| per matrix, worst of dW of every (layer, head) and dX): er8_r16 over every
@@ -8,28 +8,14 @@ The bound asserted is 1e-10."""
 import numpy as np
 import pytest
 
-import gat_backward_ref as R
+import gat_gpu_harness as G
 import hnh_testlib as T
 from distributed_sddmm_amd import _kernels as K
 from distributed_sddmm_amd import api as H
+from gat_gpu_harness import ctx, hashed_weights, hip_backend  # noqa: F401
 from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
-TOL = 1e-10
-
-
-@pytest.fixture(autouse=True, scope="module")
-def hip_backend():
-    assert H.load_backend(None) == "hip-gfx950"
-    yield
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    c = K.Ctx(0)
-    assert K.load().hnh_backend_name() == b"hip-gfx950"
-    yield c
-    c.close()
 
 
 # ------------------------------------------------------------------------------------------------ kernels
@@ -109,58 +95,14 @@ def test_gate_kernels_exact(ctx):
 
 
 # ------------------------------------------------------------------------------------------------ the operator
-def hashed_weights(layers, scale_later=1.0):
-    return {(li, h): O.gat_weight(li, h, fin, fph) * (1.0 if li == 0 else scale_later)
-            for li, (fin, fph, heads) in enumerate(layers) for h in range(heads)}
-
-
-def run_backward(world, alg, c, rows, cols, m, x, layers, weights, g_glob, rounds=1, alpha=T.GAT_ALPHA):
-    """Forward + backward on one rank; returns this rank's blocks and the gradients of every round."""
-    sp = H.SpmatLocal.from_global(world, m, m, rows, cols, np.ones(len(rows)))
-    d = H.DistributedSparse(world, alg, sp, layers[0][0], c)
-    gnn = H.GAT(d, layers, alpha)
-    for (li, h), w in weights.items():
-        gnn.set_weight(li, h, w)
-    d.setRValue(layers[0][0])
-    subB = d.submatrices(H.BMAT)
-    d.setRValue(layers[-1][1] * layers[-1][2])
-    subA = d.submatrices(H.AMAT)
-    x_d = H.Dense.create(world, *gnn.buffer_shape(0))
-    x_d.upload(T.fill_local(subB, x_d.shape, x))
-    g = H.Dense.create(world, *gnn.buffer_shape(len(layers)))
-    g.upload(T.fill_local(subA, g.shape, g_glob))
-    out = H.Dense.create(world, *gnn.buffer_shape(len(layers)))
-    dx = H.Dense.create(world, *gnn.buffer_shape(0))
-    gnn.set_input(x_d)
-    res = dict(subA=subA, subB=subB, rounds=[])
-    for _ in range(rounds):
-        gnn.forwardPass()
-        gnn.get_output(out)
-        before = out.download()
-        gnn.backwardPass(g)
-        gnn.get_output(out)
-        gnn.get_input_grad(dx)
-        res["rounds"].append(dict(out=before, out_after=out.download(), dx=dx.download(),
-                                  dw={k: gnn.weight_grad(*k) for k in weights}))
-    for h in (x_d, g, out, dx, gnn, d, sp):
-        h.free()
-    return res
+def run_backward(world, alg, c, rows, cols, m, x, layers, weights, g_glob, rounds=1):
+    """Forward + backward on one rank; returns this rank's blocks and the results of every round."""
+    return G.run_rounds(world, rows, cols, m, x, layers, weights, None, g_glob, rounds, out_after=True, alg=alg, c=c)
 
 
 def check_against_reference(per_rank, rows, cols, m, x, layers, weights, g_glob, label):
-    want_dw, want_dx = R.backward(rows, cols, m, x, layers, T.GAT_ALPHA, g_glob, weights)
-    r0 = per_rank[0]["rounds"][0]
-    errs = {}
-    for k, want in want_dw.items():
-        assert np.abs(want).max() > 0
-        for pr in per_rank:  # replicated: every rank holds the summed gradient
-            assert np.array_equal(pr["rounds"][0]["dw"][k], r0["dw"][k])
-        errs[k] = T.rel(r0["dw"][k], want)
-    per = [dict(dx=pr["rounds"][0]["dx"], subB=pr["subB"]) for pr in per_rank]
-    dx = T.assemble_dense(per, "dx", "subB", m, layers[0][0])
-    errs["dx"] = T.rel(dx, want_dx)
-    T.record_observed("gat_backward", case=label, ranks=len(per_rank), worst=max(errs.values()))
-    assert max(errs.values()) <= TOL, errs
+    G.compare(G.assembled(per_rank, 0, m, layers), G.reference(rows, cols, m, x, layers, weights, None, g_glob), "gat_backward", label, len(per_rank),
+              check=("dw", "dx"))
 
 
 GRIDS = [("15d_fusion1", 1, 1), ("15d_fusion1", 4, 1), ("15d_fusion1", 4, 2), ("15d_fusion1", 8, 2), ("15d_fusion1", 6, 2),
@@ -222,51 +164,15 @@ def test_backward_is_deterministic_and_leaves_the_forward_alone():
             assert np.array_equal(a["dw"][k], b["dw"][k])
 
 
-def sgd(world, alg, c, rows, cols, m, x, layers, target, steps, lr_scale):
-    """steps of W -= lr dW on L = 1/2 |out - target|^2; returns this rank's share of L before every step and after the last."""
-    sp = H.SpmatLocal.from_global(world, m, m, rows, cols, np.ones(len(rows)))
-    d = H.DistributedSparse(world, alg, sp, layers[0][0], c)
-    gnn = H.GAT(d, layers, T.GAT_ALPHA)
-    w = hashed_weights(layers, 40.0)
-    for k, wk in w.items():
-        gnn.set_weight(*k, wk)
-    d.setRValue(layers[0][0])
-    x_d = H.Dense.create(world, *gnn.buffer_shape(0))
-    x_d.upload(T.fill_local(d.submatrices(H.BMAT), x_d.shape, x))
-    d.setRValue(layers[-1][1] * layers[-1][2])
-    tgt = T.fill_local(d.submatrices(H.AMAT), gnn.buffer_shape(len(layers)), target)
-    out = H.Dense.create(world, *gnn.buffer_shape(len(layers)))
-    g = H.Dense.create(world, *gnn.buffer_shape(len(layers)))
-    gnn.set_input(x_d)
-    losses, lr = [], None
-    for step in range(steps + 1):
-        gnn.forwardPass()
-        gnn.get_output(out)
-        diff = out.download() - tgt
-        losses.append(0.5 * float(np.sum(diff * diff)))
-        if step == steps:
-            break
-        g.upload(diff)
-        gnn.backwardPass(g)
-        dw = {k: gnn.weight_grad(*k) for k in w}
-        if lr is None:  # the same on every rank: the gradients are replicated
-            lr = lr_scale * np.sqrt(sum(np.sum(v * v) for v in w.values()) / sum(np.sum(v * v) for v in dw.values()))
-        for k in w:
-            w[k] = w[k] - lr * dw[k]
-            gnn.set_weight(*k, w[k])
-    for h in (x_d, out, g, gnn, d, sp):
-        h.free()
-    return losses
-
-
 @pytest.mark.parametrize("alg,p,c", [("15d_fusion2", 1, 1), ("15d_fusion1", 4, 2)])
 def test_sgd_lowers_the_loss(alg, p, c):
     case = T.case_inputs("er8_r16")
     rows, cols, m = case["rows"], case["cols"], case["M"]
     x = case["A"] * T.GAT_INPUT_SCALE
     target = O.dense_fill(m, 12, 21) * 4.0
-    per_rank = H.run_spmd(p, lambda wd: sgd(wd, alg, c, rows, cols, m, x, T.GAT_LAYERS, target, 5, 0.02))
-    loss = np.sum(np.array(per_rank), axis=0)
+    w = hashed_weights(T.GAT_LAYERS, 40.0)
+    per_rank = H.run_spmd(p, lambda wd: G.sgd(wd, rows, cols, m, x, T.GAT_LAYERS, target, 5, 0.02, w, alg=alg, c=c))
+    loss = np.sum(np.array([pr[0] for pr in per_rank]), axis=0)
     assert all(loss[i + 1] < loss[i] for i in range(5)), loss
 
 

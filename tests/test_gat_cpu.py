@@ -56,14 +56,14 @@ def test_pipelined_forward_is_the_serial_forward(monkeypatch):
     x = O.dense_fill(m, 16, 2) * 4.0
     case = dict(name="gatpipe", M=m, N=m, R=16, rows=rows, cols=cols, vals=np.ones(len(rows)), A=x / T.GAT_INPUT_SCALE, B=x / T.GAT_INPUT_SCALE)
 
-    def forward(p, c, alg):
+    def device_forward(p, c, alg):
         per_rank = H.run_spmd(p, lambda w: T.run_gat(w, alg, c, case, layers=layers))
         return T.assemble_dense(per_rank, "gat", "subA", m, layers[-1][1] * layers[-1][2])
 
     for alg, p, c in [("15d_fusion2", 1, 1), ("15d_fusion1", 2, 2)]:
         monkeypatch.setenv("HNH_GAT_SERIAL", "1")
-        serial = forward(p, c, alg)
+        serial = device_forward(p, c, alg)
         monkeypatch.delenv("HNH_GAT_SERIAL")
         assert np.count_nonzero(serial) > serial.size // 10
-        assert np.array_equal(forward(p, c, alg), serial)
+        assert np.array_equal(device_forward(p, c, alg), serial)
         assert T.rel(serial, O.gat_forward(rows, cols, m, x, layers, T.GAT_ALPHA)) <= T.TOL

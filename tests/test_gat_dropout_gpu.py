@@ -1,47 +1,33 @@
 """The GAT's dropout on the GPU (include/hnh_attn_dropout.h, GAT.set_dropout).
 
 Kernel level, through ctypes: the device generator against numpy bit for bit; the three masked passes against the numpy reference
-(tests/gat_dropout_ref.py; the forward pass against its extended-precision twin) at widths 1, 7, 33, 64, 100, 128, 255, 256 on the
-blocks of test_gat_additive_gpu.py (empty rows, hub rows of 600 and 1500, repeated pairs, guards round every output) and on a block with
+(tests/gat_pass_ref.py with `drop`; the forward pass against its extended-precision twin) at widths 1, 7, 33, 64, 100, 128, 255, 256 on the
+blocks of gat_gpu_harness.Problem (empty rows, hub rows of 600 and 1500, repeated pairs, guards round every output) and on a block with
 an R-MAT graph's degrees, with own-row ids that cross 2^31 and gathered-row ids that are a scattered relabelling; independence of
 windows, groups of windows and forced Infinity-Cache panels, bit for bit; the helper kernels exactly.
 Operator level: GAT(..., score="additive", dropout=(p, q), seed=s) on 15d_fusion2, c = 1 over 1, 2, 4, 8 loopback ranks against the numpy
-definition — output, every dW, da1, da2 and dX — at T.GAT_LAYERS, the benchmark widths and on an R-MAT graph with hub rows; 8 ranks
+definition (tests/gat_ref.py with rates) — output, every dW, da1, da2 and dX — at T.GAT_LAYERS, the benchmark widths and on an R-MAT graph with hub rows; 8 ranks
 against 1; seeds; the refusal of a backward pass after a new seed; rates (0, 0) bit-identical to an object without dropout.
 
 Bounds: those of test_gat_additive_gpu.py — 1e-12 for the forward kernel against the extended-precision reference, 1e-10 for the backward
 kernels and the operator.  The observed worst cases are recorded with T.record_observed."""
-import ctypes as C
 
 import numpy as np
 import pytest
 
-import gat_additive_ref as RA
-import gat_dropout_ref as R
+import gat_gpu_harness as G
+import gat_pass_ref as P
+import gat_ref as R
 import hnh_testlib as T
 from distributed_sddmm_amd import _kernels as K
 from distributed_sddmm_amd import api as H
+from gat_gpu_harness import (COL, FTOL, FWD, GROUPINGS, PASS_NAMES, ROW, TOL, DropProblem, assembled, ctx, er8, errors, hashed_weights,  # noqa: F401
+                             hip_backend, one_round, same, setup, teardown)
 from oracle import oracle as O
-from test_gat_additive_gpu import (ALPHA, COL, FTOL, FWD, GROUPINGS, PASS_NAMES, ROW, TOL, Problem, assembled, check_against, er8, errors,
-                                   hashed_weights, one_round, same, setup, teardown)
 
 pytestmark = pytest.mark.gpu
 WIDTHS = [1, 7, 33, 64, 100, 128, 255, 256]
-P_ATT = 0.6
-
-
-@pytest.fixture(autouse=True, scope="module")
-def hip_backend():
-    assert H.load_backend(None) == "hip-gfx950"
-    yield
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    c = K.Ctx(0)
-    assert K.load().hnh_backend_name() == b"hip-gfx950"
-    yield c
-    c.close()
+MODE = dict(attention="softmax", score="additive")
 
 
 # ------------------------------------------------------------------------------------------------ the generator
@@ -54,61 +40,12 @@ def test_device_words_match_numpy(ctx):
     d_gi, d_gj, d_out = ctx.upload(gi), ctx.upload(gj), K.DevArray(ctx, n, np.uint32)
     for seed, w2, tag in ((0, 0, 0), (0xFFFFFFFFFFFFFFFF, 0xFFFFFFFF, 1), (0x0123456789ABCDEF, 3 * 65536 + 2, 0), (0x0123456789ABCDEF, 3, 1)):
         ctx.check(ctx.lib.hnh_dropout_words_u32(ctx.h, d_out.ptr, d_gi.ptr, d_gj.ptr, n, seed, w2, tag, K.STREAM_COMPUTE), "words")
-        assert np.array_equal(d_out.get(), R.word(seed, tag, w2, gi, gj)), (seed, w2, tag)
+        assert np.array_equal(d_out.get(), P.word(seed, tag, w2, gi, gj)), (seed, w2, tag)
     for d in (d_gi, d_gj, d_out):
         d.free()
 
 
 # ------------------------------------------------------------------------------------------------ kernels
-class DropProblem(Problem):
-    """test_gat_additive_gpu.py's Problem with the ids in the gathered operand (M' for the forward and the row pass, Q' for the column
-    pass) and the DROP entry points.  Own rows are row_id0 + r with row_id0 just below 2^31, so they cross it; gathered rows carry a
-    scattered relabelling that reaches beyond 2^31 as well."""
-
-    def __init__(self, ctx, pas, f, seed=0, drop_seed=0xC0FFEE1234567890, p=P_ATT, **kw):
-        super().__init__(ctx, pas, f, seed=seed, **kw)
-        fp = self.fp
-        self.row_id0 = (1 << 31) - self.m // 2
-        rng = np.random.default_rng(99 + f + seed)
-        self.ids = rng.permutation(np.arange(self.ncols, dtype=np.int64) * 2700001 + 17)  # distinct, scattered over [17, 4.2e9)
-        assert self.ids.max() < 1 << 32 and self.ids.max() >= 1 << 31
-        if pas == COL:
-            self.y[:, fp + 3] = self.ids
-        else:
-            assert self.ld_y >= fp + 4
-            self.y[:, fp + 2], self.y[:, fp + 3] = self.ids, 0.0
-        self.d["y"].set(self.y)
-        self.drop = K.AttnDrop(drop_seed, 2 * 65536 + 5, K.dropout_threshold(p), 1.0 / (1.0 - p), self.row_id0)
-        self.ref_drop = (drop_seed, 2 * 65536 + 5, p, self.row_id0)
-
-    def fn(self):
-        lib = self.ctx.lib
-        f = (lib.hnh_attn_drop_fwd_csr_p, lib.hnh_attn_drop_row_csr_p, lib.hnh_attn_drop_col_csr_p)[self.pas]
-        return lambda h, blk, a, flags, win, stream: f(h, blk, a, C.byref(self.drop), flags, win, stream)
-
-    def factor(self):
-        """c m per nonzero"""
-        cols = self.colidx.astype(np.int64)
-        own = self.rows.astype(np.uint64) + np.uint64(self.row_id0)
-        got = self.ids[cols].astype(np.uint64)
-        seed, w2, p, _ = self.ref_drop
-        gi, gj = (got, own) if self.pas == COL else (own, got)
-        return R.keep(seed, 0, w2, gi, gj, p) / (1.0 - p)
-
-    def want(self, overwrite=True):
-        f, m, cols = self.f, self.m, self.colidx.astype(np.int64)
-        if self.pas == FWD:
-            o, lse = R.fwd_pass_ld(self.rows, cols, m, self.m_rows, self.y, f, ALPHA, self.ref_drop)
-            return dict(out=np.maximum(o, 0), lse=lse)
-        if self.pas == ROW:
-            ds = R.row_pass(self.rows, cols, m, self.dz[:, :f], self.m_rows, self.lse_in, self.delta, self.y, f, ALPHA, self.ref_drop)
-            return dict(vec=ds + (0 if overwrite else self.vec0[:m, 0]))
-        dagg, dt = R.col_pass(self.rows, cols, m, self.m_rows, self.y, f, ALPHA, self.ref_drop)
-        if not overwrite:
-            dagg, dt = dagg + self.out0[:m, self.col0:self.col0 + f], dt + self.vec0[:m, 1]
-        return dict(out=dagg, vec=dt)
-
-
 def check_pass(p, label):
     pas = p.pas
     deg = np.diff(p.rowptr)
@@ -184,7 +121,7 @@ def test_forced_panels_are_bit_identical(monkeypatch, pas, f):
     one, want = p1.run(True), p1.want(True)
     p1.free()
     c1.close()
-    gather_w = R.scored_width(f)  # (= the packed width)
+    gather_w = P.scored_width(f, ids=True)  # (= the packed width)
     monkeypatch.setenv("HNH_PANEL_BYTES", str(ncols * gather_w * 8 / 5))
     monkeypatch.setenv("HNH_MAX_PANELS", "8")
     monkeypatch.setenv("HNH_PANELS_WITH_HUBS", "1")
@@ -216,10 +153,10 @@ def test_helper_kernels(ctx):
                                              row_id0, K.STREAM_COMPUTE), "pack")
         gm, gq = dev["m"].get(), dev["q"].get()
         ids = row_id0 + np.arange(rows)
-        wm = R.scored(a[:, :f], a1, a2, ids)
+        wm = P.scored(a[:, :f], a1, a2, ids)
         assert np.array_equal(gm[:rows, :fp], wm[:, :fp]) and T.rel(gm[:rows, fp:fp + 2], wm[:, fp:fp + 2]) <= T.TOL, f
         assert np.array_equal(gm[:rows, fp + 2:fp + 4], wm[:, fp + 2:]) and np.all(gm[:rows, fp + 4:] == 7.0) and np.all(gm[rows] == 7.0), "ids exact, slot 3 zero"
-        wq = R.pack(dz[:, :f], gm[:rows, fp], lse, delta, ids)
+        wq = P.pack(dz[:, :f], gm[:rows, fp], lse, delta, ids)
         assert np.array_equal(gq[:rows, :fp + 4], wq) and np.all(gq[:rows, fp + 4:] == 7.0) and np.all(gq[rows] == 7.0), f
         assert lib.hnh_attn_drop_scores_f64(ctx.h, dev["m"].ptr, fp + 2, dev["a"].ptr, ld_a, dev["a1"].ptr, dev["a2"].ptr, rows, f, row_id0, K.STREAM_COMPUTE) == 1
         assert lib.hnh_attn_drop_scores_f64(ctx.h, dev["m"].ptr, ld_m, dev["a"].ptr, ld_a, dev["a1"].ptr, dev["a2"].ptr, rows, f, row_id0 + 1, K.STREAM_COMPUTE) == 1, \
@@ -231,8 +168,8 @@ def test_helper_kernels(ctx):
         src = rng.uniform(-1, 1, (rows + 1, cols + 3))
         d_src, d_dst = ctx.upload(src), ctx.upload(np.full((rows + 1, cols + 5), 7.0))
         seed, scale = 0xFEEDFACE12345678, 1.0 / (1.0 - q)
-        want = R.feature_factor(seed, layer, (rows, cols), q, row_id0) * src[:rows, :cols]
-        assert np.array_equal(R.feature_factor(seed, layer, (rows, cols), q, row_id0) > 0, R.keep(seed, 1, layer, (row_id0 + np.arange(rows))[:, None],
+        want = P.feature_factor(seed, layer, (rows, cols), q, row_id0) * src[:rows, :cols]
+        assert np.array_equal(P.feature_factor(seed, layer, (rows, cols), q, row_id0) > 0, P.keep(seed, 1, layer, (row_id0 + np.arange(rows))[:, None],
                                                                                              np.arange(cols)[None, :], q))
         ctx.check(lib.hnh_feat_drop_f64(ctx.h, d_dst.ptr, cols + 5, d_src.ptr, cols + 3, rows, cols, row_id0, seed, layer, K.dropout_threshold(q), scale,
                                         K.STREAM_COMPUTE), "feat")
@@ -249,7 +186,7 @@ def test_helper_kernels(ctx):
 # ------------------------------------------------------------------------------------------------ the operator
 def run_dropout(world, rows, cols, m, x, layers, weights, vectors, g_glob, configs, **kw):
     """One object, one round per (rates, seed) of configs."""
-    s = setup(world, rows, cols, m, x, layers, weights, vectors, g_glob, attention="softmax", score="additive", **kw)
+    s = setup(world, rows, cols, m, x, layers, weights, vectors, g_glob, **MODE, **kw)
     rounds = []
     for rates, seed in configs:
         if rates is not None:
@@ -261,9 +198,11 @@ def run_dropout(world, rows, cols, m, x, layers, weights, vectors, g_glob, confi
 
 
 def reference(rows, cols, m, x, layers, w, av, g, rates, seed):
-    out = R.forward(rows, cols, m, x, layers, ALPHA, w, av, rates, seed)
-    dw, da, dx = R.backward(rows, cols, m, x, layers, ALPHA, g, w, av, rates, seed)
-    return out, dw, da, dx
+    return G.reference(rows, cols, m, x, layers, w, av, g, rates=rates, seed=seed, **MODE)
+
+
+def check_against(got, want, label, ranks):
+    G.compare(got, want, "gat_additive", label, ranks)
 
 
 CONFIGS = [((0.6, 0.6), 1), ((0.6, 0.0), 1), ((0.6, 0.6), 0xDEADBEEF00000002), ((0.6, 0.0), 0xDEADBEEF00000002), ((0.6, 0.6), 1)]
@@ -274,12 +213,12 @@ ER8_RESULTS = {}
 def test_dropout_er8(p):
     rows, cols, m, x = er8()
     layers = T.GAT_LAYERS
-    w, av = hashed_weights(layers), RA.vectors_of(layers)
+    w, av = hashed_weights(layers), R.vectors_of(layers)
     g = O.dense_fill(m, layers[-1][1] * layers[-1][2], 9) * 16.0
     per_rank = H.run_spmd(p, lambda wd: run_dropout(wd, rows, cols, m, x, layers, w, av, g, CONFIGS))
     got = [assembled(per_rank, k, m, layers) for k in range(len(CONFIGS))]
     for k, (rates, seed) in enumerate(CONFIGS[:4]):
-        check_against(got[k], *reference(rows, cols, m, x, layers, w, av, g, rates, seed), "er8_r16 p%d rates %s seed %x" % (p, rates, seed), p)
+        check_against(got[k], reference(rows, cols, m, x, layers, w, av, g, rates, seed), "er8_r16 p%d rates %s seed %x" % (p, rates, seed), p)
     assert np.array_equal(got[0]["out"], got[4]["out"]) and np.array_equal(got[0]["dx"], got[4]["dx"]), "the same seed gives the same bits"
     assert all(np.array_equal(got[0]["dw"][k], got[4]["dw"][k]) and np.array_equal(got[0]["da"][k][0], got[4]["da"][k][0]) for k in w)
     assert not np.array_equal(got[0]["out"], got[2]["out"]) and not np.array_equal(got[1]["out"], got[3]["out"]), "another seed gives another output"
@@ -290,7 +229,7 @@ def test_dropout_er8(p):
 def test_one_rank_and_eight_ranks_agree():
     rows, cols, m, x = er8()
     layers = T.GAT_LAYERS
-    w, av = hashed_weights(layers), RA.vectors_of(layers)
+    w, av = hashed_weights(layers), R.vectors_of(layers)
     g = O.dense_fill(m, layers[-1][1] * layers[-1][2], 9) * 16.0
     res = {}
     for p in (1, 8):
@@ -298,7 +237,7 @@ def test_one_rank_and_eight_ranks_agree():
                                         for k in range(2)]
     for k in range(2):
         a, b = res[1][k], res[8][k]
-        check_against(b, a["out"], a["dw"], a["da"], a["dx"], "er8_r16 p8 against p1 rates %s" % (CONFIGS[k][0],), 8)
+        check_against(b, a, "er8_r16 p8 against p1 rates %s" % (CONFIGS[k][0],), 8)
 
 
 BENCH_WIDTHS = (1 << 12, [(256, 256, 1), (256, 128, 2), (256, 64, 3)])
@@ -309,12 +248,12 @@ def test_dropout_benchmark_widths(p):
     m, layers = BENCH_WIDTHS
     rows, cols = H.generate_er(m, m, m * 16, 77)
     x = O.dense_fill(m, layers[0][0], 41) * 16.0
-    w, av = hashed_weights(layers), RA.vectors_of(layers, seed=5)
+    w, av = hashed_weights(layers), R.vectors_of(layers, seed=5)
     g = O.dense_fill(m, layers[-1][1] * layers[-1][2], 3) * 64.0
     configs = [((0.6, 0.6), 5), ((0.6, 0.0), 5), ((0.6, 0.6), 6), ((0.6, 0.0), 6)] if p in (1, 8) else [((0.6, 0.6), 5), ((0.6, 0.0), 6)]
     per_rank = H.run_spmd(p, lambda wd: run_dropout(wd, rows, cols, m, x, layers, w, av, g, configs))
     for k, (rates, seed) in enumerate(configs):
-        check_against(assembled(per_rank, k, m, layers), *reference(rows, cols, m, x, layers, w, av, g, rates, seed),
+        check_against(assembled(per_rank, k, m, layers), reference(rows, cols, m, x, layers, w, av, g, rates, seed),
                       "benchmark widths p%d rates %s seed %d" % (p, rates, seed), p)
 
 
@@ -324,13 +263,13 @@ def test_dropout_rmat_hub_rows(p):
     rows, cols = H.generate_rmat(13, m * 16)
     assert np.bincount(rows, minlength=m).max() >= 512 and np.bincount(cols, minlength=m).max() >= 512
     x = O.dense_fill(m, 64, 8) * 8.0
-    w, av = hashed_weights(layers), RA.vectors_of(layers, seed=6)
+    w, av = hashed_weights(layers), R.vectors_of(layers, seed=6)
     g = O.dense_fill(m, 64, 4) * 32.0
     configs = [((0.6, 0.6), 9), ((0.6, 0.0), 9), ((0.6, 0.6), 9)]
     per_rank = H.run_spmd(p, lambda wd: run_dropout(wd, rows, cols, m, x, layers, w, av, g, configs))
     got = [assembled(per_rank, k, m, layers) for k in range(3)]
     for k in range(2):
-        check_against(got[k], *reference(rows, cols, m, x, layers, w, av, g, *configs[k]), "rmat hubs p%d rates %s" % (p, configs[k][0]), p)
+        check_against(got[k], reference(rows, cols, m, x, layers, w, av, g, *configs[k]), "rmat hubs p%d rates %s" % (p, configs[k][0]), p)
     assert np.array_equal(got[0]["dx"], got[2]["dx"]) and all(np.array_equal(got[0]["da"][k][1], got[2]["da"][k][1]) for k in w), "a repeat must be bit-identical"
 
 
@@ -338,7 +277,7 @@ def test_dropout_rmat_hub_rows(p):
 def test_a_new_seed_needs_a_new_forward_pass(p):
     rows, cols, m, x = er8()
     layers = T.GAT_LAYERS
-    w, av = hashed_weights(layers), RA.vectors_of(layers)
+    w, av = hashed_weights(layers), R.vectors_of(layers)
     g = O.dense_fill(m, 12, 9) * 16.0
 
     def rank(world):
@@ -366,7 +305,7 @@ def test_rates_zero_are_bit_identical_to_no_dropout(p):
     """dropout=(0, 0) with any seed, and (0, 0) after a round with dropout on the same object, against an object that never heard of it."""
     rows, cols, m, x = er8()
     layers = T.GAT_LAYERS
-    w, av = hashed_weights(layers), RA.vectors_of(layers)
+    w, av = hashed_weights(layers), R.vectors_of(layers)
     g = O.dense_fill(m, 12, 9) * 16.0
     with_arg = H.run_spmd(p, lambda wd: run_dropout(wd, rows, cols, m, x, layers, w, av, g, [(None, 0), ((0.6, 0.6), 3), ((0.0, 0.0), 3)],
                                                     dropout=(0.0, 0.0), seed=77))
@@ -400,5 +339,5 @@ def test_score_dot_refuses_attention_dropout_and_takes_feature_dropout():
 
     per_rank = H.run_spmd(2, rank)
     dx = T.assemble_dense([dict(dx=pr["rounds"][0]["dx"], subB=pr["subB"]) for pr in per_rank], "dx", "subB", m, layers[0][0])
-    mask = R.feature_factor(2, 0, x.shape, 0.5) > 0
+    mask = P.feature_factor(2, 0, x.shape, 0.5) > 0
     assert np.all(dx[~mask] == 0.0) and np.count_nonzero(dx[mask]) > 0.9 * np.count_nonzero(mask), "the input gradient carries layer 0's feature mask"

@@ -1,30 +1,20 @@
-"""The GAT's fused backward mode without a GPU: the numpy restatement of its two passes (tests/gat_fused_backward_ref.py, over S and S^T
-with the packed operand) against the two reference definitions, the optional kernel group of include/hnh_attn_grad.h (declared == bound
+"""The GAT's fused backward mode without a GPU: the numpy restatement of its two passes (tests/gat_pass_ref.py, over S and S^T
+with the packed operand) against the definition (tests/gat_ref.py) in both attention modes, the optional kernel group of include/hnh_attn_grad.h (declared == bound
 == exported by the HIP library, absent from the mandatory table and from the CPU test double), the host call, and the modes on the
 test double: "fused" fails naming a kernel of the new group, an explicit "unfused" is the old pass."""
 import ctypes as C
-import os
 import re
 
 import numpy as np
 import pytest
 
-import gat_backward_ref as RN
-import gat_fused_backward_ref as RF
-import gat_softmax_ref as RS
+import gat_pass_ref as P
+import gat_ref as R
 import hnh_testlib as T
 from distributed_sddmm_amd import _kernels as K
 from distributed_sddmm_amd import api as H
+from gat_cpu_harness import ROOT, declared, make_gat
 from oracle import oracle as O
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def declared(header):
-    txt = open(os.path.join(ROOT, "include", header)).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return set(re.findall(r"\b(hnh_[a-z0-9_]+)\s*\(", txt))
-
 
 def small_problem(softmax):
     """The small ER graph of the reference's own CPU tests (32 vertices, 123 nonzeros) with T.GAT_LAYERS, plus one repeated pair."""
@@ -42,9 +32,8 @@ def small_problem(softmax):
 def test_two_passes_equal_the_reference(attention):
     softmax = attention == "softmax"
     rows, cols, m, x, w, g = small_problem(softmax)
-    ref = RS if softmax else RN
-    want_dw, want_dx = ref.backward(rows, cols, m, x, T.GAT_LAYERS, T.GAT_ALPHA, g, w)
-    got_dw, got_dx = RF.backward(rows, cols, m, x, T.GAT_LAYERS, T.GAT_ALPHA, g, w, attention)
+    want_dw, _, want_dx = R.backward(rows, cols, m, x, T.GAT_LAYERS, T.GAT_ALPHA, g, w, attention=attention)
+    got_dw, _, got_dx = R.backward(rows, cols, m, x, T.GAT_LAYERS, T.GAT_ALPHA, g, w, attention=attention, by_passes=True)
     assert set(got_dw) == set(want_dw) and all(np.abs(v).max() > 0 for v in want_dw.values()) and np.count_nonzero(want_dx) > want_dx.size // 2
     for k in want_dw:
         assert T.rel(got_dw[k], want_dw[k]) <= T.TOL, (k, T.rel(got_dw[k], want_dw[k]))
@@ -58,9 +47,9 @@ def test_packed_layout(f, softmax):
     a, dz = rng.uniform(-1, 1, (5, f)), rng.uniform(-1, 1, (5, f))
     lse, delta = (rng.uniform(0, 1, 5), rng.uniform(-1, 1, 5)) if softmax else (None, None)
     fp = f + (f & 1)
-    pw = RF.packed_width(f, softmax)
+    pw = P.fused_packed_width(f, softmax)
     assert pw == K.attn_grad_packed_width(f, softmax) == 2 * fp + (2 if softmax else 0) and pw % 2 == 0 and fp % 2 == 0
-    p = RF.pack(a, dz, lse, delta, ld=pw + 2)
+    p = P.fused_pack(a, dz, lse, delta, ld=pw + 2)
     assert np.array_equal(p[:, :f], a) and np.array_equal(p[:, fp:fp + f], dz) and np.all(np.isnan(p[:, pw:]))
     if f & 1:
         assert np.all(p[:, f] == 0.0) and np.all(p[:, fp + f] == 0.0)
@@ -81,23 +70,17 @@ def test_attn_grad_kernels_are_an_optional_group():
     for n in names:
         assert not hasattr(dbl, n), "the CPU test double does not export %s" % n
     K.load(T.ORACLE_BACKEND)  # ... and binding it still works
-    txt = open(os.path.join(ROOT, "include", "hnh_attn_grad.h")).read()
+    txt = open(ROOT + "/include/hnh_attn_grad.h").read()
     assert re.search(r"#define HNH_ATTN_GRAD_MAX_F %d\b" % K.ATTN_GRAD_MAX_F, txt)
     assert C.sizeof(K.AttnGrad) == 96  # struct hnh_attn_grad: ten pointers and pitches, two ints, one double
 
 
 def test_host_call_declared_and_exported():
     assert "hnh_gat_set_backward" in declared("hnh_dist.h") and "hnh_gat_set_backward" in H.SIGNATURES
-    txt = open(os.path.join(ROOT, "include", "hnh_dist.h")).read()
+    txt = open(ROOT + "/include/hnh_dist.h").read()
     assert re.search(r"#define HNH_GAT_BACKWARD_UNFUSED 0\b", txt) and re.search(r"#define HNH_GAT_BACKWARD_FUSED 1\b", txt)
     assert hasattr(H.lib(), "hnh_gat_set_backward")
     assert H.GAT.BACKWARD == {"unfused": 0, "fused": 1}
-
-
-def make_gat(world, case, alg, c, layers=None, **kw):
-    sp = H.SpmatLocal.from_global(world, case["M"], case["N"], case["rows"], case["cols"], np.ones(len(case["rows"])))
-    d = H.DistributedSparse(world, alg, sp, case["R"], c)
-    return sp, d, H.GAT(d, layers or T.GAT_LAYERS, T.GAT_ALPHA, **kw)
 
 
 def test_fused_on_the_test_double_names_the_missing_kernel():

@@ -1,11 +1,11 @@
 """The GAT's fused backward mode on the GPU (include/hnh_attn_grad.h, GAT backward mode "fused").
 
-Kernel level, through ctypes: the row pass, the column pass and the pack kernel against numpy (tests/gat_fused_backward_ref.py) at
+Kernel level, through ctypes: the row pass, the column pass and the pack kernel against numpy (tests/gat_pass_ref.py) at
 every kind of width, on blocks with empty rows, hub rows and repeated pairs, with leading dimensions wider than the widths and guard
 values around the output; their independence of how a row's nonzeros are split into launches (forced panels, every grouping of six
 windows); overwrite against accumulate; the width limit; empty blocks.
-Operator level: GAT(..., backward="fused") on 15d_fusion2, c = 1 over loopback ranks against the numpy definitions
-(tests/gat_backward_ref.py, tests/gat_softmax_ref.py) and against the un-fused pass of the same object, determinism, mode switches,
+Operator level: GAT(..., backward="fused") on 15d_fusion2, c = 1 over loopback ranks against the numpy definition
+(tests/gat_ref.py) and against the un-fused pass of the same object, determinism, mode switches,
 SGD, and the refusals.
 
 Bounds: T.TOL = 1e-11 for the kernels with attention none (summation order only), 1e-10 with softmax (the bound of the softmax tests)
@@ -20,65 +20,21 @@ import itertools
 import numpy as np
 import pytest
 
-import gat_backward_ref as RN
-import gat_fused_backward_ref as RF
-import gat_softmax_ref as RS
+import gat_gpu_harness as G
+import gat_pass_ref as P
+import gat_ref as R
 import hnh_testlib as T
 from distributed_sddmm_amd import _kernels as K
 from distributed_sddmm_amd import api as H
+from gat_gpu_harness import ALPHA, NWIN, TOL, ctx, er8, graph, hashed_weights, hip_backend, mixed_degrees  # noqa: F401
 from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
-TOL = 1e-10
 KTOL = {False: T.TOL, True: 1e-10}  # kernel level, by softmax
-ALPHA = T.GAT_ALPHA
 WIDTHS = [1, 7, 8, 16, 33, 64, 100, 128, 200, 255, 256]
-NWIN = 6
-
-
-@pytest.fixture(autouse=True, scope="module")
-def hip_backend():
-    assert H.load_backend(None) == "hip-gfx950"
-    yield
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    c = K.Ctx(0)
-    assert K.load().hnh_backend_name() == b"hip-gfx950"
-    yield c
-    c.close()
 
 
 # ------------------------------------------------------------------------------------------------ kernels
-def graph(m, ncols, degrees, seed):
-    """CSR (sorted columns, repeated pairs kept) with the given row lengths over ncols columns."""
-    rng = np.random.default_rng(seed)
-    rows = np.repeat(np.arange(m), degrees)
-    cols = rng.integers(0, ncols, len(rows))
-    first = int(np.nonzero(degrees >= 2)[0][0])  # a repeated (i, j) pair for certain
-    beg = int(np.cumsum(degrees)[first] - degrees[first])
-    cols[beg + 1] = cols[beg]
-    order = np.lexsort((cols, rows))
-    rows, cols = rows[order], cols[order]
-    rowptr = np.concatenate([[0], np.cumsum(degrees)]).astype(np.int32)
-    pairs = rows.astype(np.int64) * ncols + cols
-    assert len(np.unique(pairs)) < len(pairs)
-    return rowptr, cols.astype(np.int32), rows
-
-
-def mixed_degrees(m, seed):
-    """Rows of length 0 .. 40 (a fifth of them empty), a few of 200 .. 300 and hub rows past every long-row threshold (600, 1500)."""
-    rng = np.random.default_rng(seed)
-    d = rng.integers(0, 41, m)
-    d[rng.random(m) < 0.2] = 0
-    d[5::97] = rng.integers(200, 301, len(d[5::97]))
-    d[7] = 600
-    d[m // 2] = 1500
-    d[3] = 0
-    return d
-
-
 class Problem:
     """One pass's operands on the device, with pitches wider than the widths and guards round the output: run() launches the pass
     (whole block, or one call per window group) and returns the output rows."""
@@ -97,15 +53,15 @@ class Problem:
         self.a_cols = rng.uniform(-1, 1, (ncols, f)) * scale   # the gathered rows' A
         self.dz_cols = rng.uniform(-1, 1, (ncols, f))           # ... and dZ (column pass)
         e = np.einsum("ij,ij->i", self.x[self.rows, :f], self.a_cols[cols])
-        s = RS.leaky(e, ALPHA)
+        s = R.leaky(e, ALPHA)
         self.lse = self.delta = None
         if softmax:  # a real log-sum-exp over the nonzeros that share the scalar (rows of S: the pass's rows / the gathered rows)
             owner, n_own = (cols, ncols) if column_side else (self.rows, m)
-            _, self.lse = RS.row_softmax(owner, n_own, s)
+            _, self.lse = R.row_softmax(owner, n_own, s)
             self.delta = rng.uniform(-1, 1, n_own)
         if column_side:
-            self.ld_y = RF.packed_width(f, softmax) + 4
-            self.y = RF.pack(self.a_cols, self.dz_cols, self.lse, self.delta, ld=self.ld_y)
+            self.ld_y = P.fused_packed_width(f, softmax) + 4
+            self.y = P.fused_pack(self.a_cols, self.dz_cols, self.lse, self.delta, ld=self.ld_y)
             self.y[np.isnan(self.y)] = 1e300  # beyond the packed width: never read
         else:
             self.ld_y = f + (4 if f % 2 == 0 else 5)
@@ -158,8 +114,8 @@ class Problem:
         f, cols = self.f, self.colidx.astype(np.int64)
         out = np.zeros((self.m, f)) if overwrite else self.out0[:self.m, :f].copy()
         if self.column_side:
-            return RF.col_pass(self.rows, cols, self.m, self.x[:, :f], self.y, f, self.softmax, ALPHA, out)
-        return RF.row_pass(self.rows, cols, self.m, self.x[:, :f], self.dz[:, :f], self.y, ALPHA, self.lse, self.delta, out)
+            return P.fused_col_pass(self.rows, cols, self.m, self.x[:, :f], self.y, f, self.softmax, ALPHA, out)
+        return P.fused_row_pass(self.rows, cols, self.m, self.x[:, :f], self.dz[:, :f], self.y, ALPHA, self.lse, self.delta, out)
 
     def free(self):
         for v in self.d.values():
@@ -228,7 +184,7 @@ def test_forced_panels_are_bit_identical(monkeypatch, column_side, softmax, f):
     one, want = p1.run(True), p1.want(True)
     p1.free()
     c1.close()
-    gather_w = RF.packed_width(f, softmax) if column_side else f
+    gather_w = P.fused_packed_width(f, softmax) if column_side else f
     monkeypatch.setenv("HNH_PANEL_BYTES", str(ncols * gather_w * 8 / 5))
     monkeypatch.setenv("HNH_MAX_PANELS", "8")
     monkeypatch.setenv("HNH_PANELS_WITH_HUBS", "1")
@@ -249,7 +205,7 @@ def test_pack_kernel(ctx, softmax):
     rng = np.random.default_rng(4)
     for f in WIDTHS:
         rows, ld_a, ld_dz = 301, f + 3, f + 5
-        pw = RF.packed_width(f, softmax)
+        pw = P.fused_packed_width(f, softmax)
         ld_p = pw + 2
         a, dz = rng.uniform(-1, 1, (rows, ld_a)), rng.uniform(-1, 1, (rows, ld_dz))
         lse, delta = rng.uniform(0, 3, rows), rng.uniform(-1, 1, rows)
@@ -258,7 +214,7 @@ def test_pack_kernel(ctx, softmax):
         ctx.check(lib.hnh_attn_grad_pack_f64(ctx.h, dp.ptr, ld_p, da.ptr, ld_a, ddz.ptr, ld_dz, dl.ptr if softmax else None, dd.ptr if softmax else None,
                                              rows, f, K.STREAM_COMPUTE), "pack")
         got = dp.get()
-        want = RF.pack(a[:, :f], dz[:, :f], lse if softmax else None, delta if softmax else None)
+        want = P.fused_pack(a[:, :f], dz[:, :f], lse if softmax else None, delta if softmax else None)
         assert np.array_equal(got[:rows, :pw], want) and np.all(got[:rows, pw:] == 7.0) and np.all(got[rows] == 7.0), f
         assert lib.hnh_attn_grad_pack_f64(ctx.h, dp.ptr, ld_p + 1, da.ptr, ld_a, ddz.ptr, ld_dz, None, None, rows, f, K.STREAM_COMPUTE) == 1  # odd pitch
         for d in (da, ddz, dl, dd, dp):
@@ -311,11 +267,11 @@ def test_rmat_hub_rows(ctx, column_side, softmax):
         p.d[k].free()
     p.d["rowptr"], p.d["colidx"] = ctx.upload(p.rowptr), ctx.upload(np.concatenate([p.colidx, [0]]).astype(np.int32))
     if softmax:
-        s = RS.leaky(np.einsum("ij,ij->i", p.x[r, :f], p.a_cols[c]), ALPHA)
+        s = R.leaky(np.einsum("ij,ij->i", p.x[r, :f], p.a_cols[c]), ALPHA)
         owner = c if column_side else r
-        _, p.lse = RS.row_softmax(owner, m, s)
+        _, p.lse = R.row_softmax(owner, m, s)
         if column_side:
-            p.y = RF.pack(p.a_cols, p.dz_cols, p.lse, p.delta, ld=p.ld_y)
+            p.y = P.fused_pack(p.a_cols, p.dz_cols, p.lse, p.delta, ld=p.ld_y)
             p.y[np.isnan(p.y)] = 1e300
             p.d["y"].set(p.y)
         else:
@@ -329,40 +285,21 @@ def test_rmat_hub_rows(ctx, column_side, softmax):
 
 
 # ------------------------------------------------------------------------------------------------ the operator
-def hashed_weights(layers, attention, scale_later=40.0):
-    later = scale_later if attention == "none" else 1.0  # (the softmax keeps the later layers' inputs of order one by itself)
-    return {(li, h): O.gat_weight(li, h, fin, fph) * (1.0 if li == 0 else later) for li, (fin, fph, heads) in enumerate(layers) for h in range(heads)}
+def later(attention, scale=40.0):
+    """the scale of the weights after the first layer (the softmax keeps the later layers' inputs of order one by itself)"""
+    return scale if attention == "none" else 1.0
 
 
-def run_gat(world, alg, c, rows, cols, m, x, layers, weights, g_glob, attention, modes, fresh_default=False, ordinary_call=None):
+def run_gat(world, alg, c, rows, cols, m, x, layers, weights, g_glob, attention, modes, ordinary_call=None):
     """Forward once, then one backward per entry of `modes` on the same object; returns this rank's blocks and every round's results."""
-    sp = H.SpmatLocal.from_global(world, m, m, rows, cols, np.ones(len(rows)))
-    d = H.DistributedSparse(world, alg, sp, layers[0][0], c)
-    gnn = H.GAT(d, layers, ALPHA, attention=attention, backward=modes[0])
-    for k, w in weights.items():
-        gnn.set_weight(*k, w)
-    d.setRValue(layers[0][0])
-    subB = d.submatrices(H.BMAT)
-    d.setRValue(layers[-1][1] * layers[-1][2])
-    subA = d.submatrices(H.AMAT)
-    x_d = H.Dense.create(world, *gnn.buffer_shape(0))
-    x_d.upload(T.fill_local(subB, x_d.shape, x))
-    g = H.Dense.create(world, *gnn.buffer_shape(len(layers)))
-    g.upload(T.fill_local(subA, g.shape, g_glob))
-    out = H.Dense.create(world, *gnn.buffer_shape(len(layers)))
-    dx = H.Dense.create(world, *gnn.buffer_shape(0))
-    gnn.set_input(x_d)
-    res = dict(subA=subA, subB=subB, rounds=[])
+    s = G.setup(world, rows, cols, m, x, layers, weights, None, g_glob, alg=alg, c=c, attention=attention, backward=modes[0])
+    gnn, d = s["gnn"], s["d"]
+    res = dict(subA=s["subA"], subB=s["subB"], rounds=[])
     gnn.forwardPass()
     for k, mode in enumerate(modes):
         if k > 0:
             gnn.set_backward(mode)  # no new forward pass
-        gnn.get_output(out)
-        before = out.download()
-        gnn.backwardPass(g)
-        gnn.get_output(out)
-        gnn.get_input_grad(dx)
-        res["rounds"].append(dict(out=before, out_after=out.download(), dx=dx.download(), dw={k2: gnn.weight_grad(*k2) for k2 in weights}))
+        res["rounds"].append(G.one_round(s, weights, False, forward=False, out_after=True))
     if ordinary_call is not None:  # an ordinary call of the same operator afterwards: the landing buffers are in a usable shape
         r = ordinary_call["R"]
         d.setRValue(r)
@@ -377,25 +314,13 @@ def run_gat(world, alg, c, rows, cols, m, x, layers, weights, g_glob, attention,
         res["fused"] = A.download()
         for h in (A, B, S, buf):
             h.free()
-    for h in (x_d, g, out, dx, gnn, d, sp):
-        h.free()
+    G.teardown(s)
     return res
 
 
 def check_round(per_rank, k, rows, cols, m, x, layers, weights, g_glob, attention, label):
-    ref = RS if attention == "softmax" else RN
-    want_dw, want_dx = ref.backward(rows, cols, m, x, layers, ALPHA, g_glob, weights)
-    r0 = per_rank[0]["rounds"][k]
-    errs = {}
-    for key, want in want_dw.items():
-        assert np.abs(want).max() > 0
-        for pr in per_rank:  # replicated: every rank holds the summed gradient
-            assert np.array_equal(pr["rounds"][k]["dw"][key], r0["dw"][key]), "dW must be equal on every rank"
-        errs[key] = T.rel(r0["dw"][key], want)
-    dx = T.assemble_dense([dict(dx=pr["rounds"][k]["dx"], subB=pr["subB"]) for pr in per_rank], "dx", "subB", m, layers[0][0])
-    errs["dx"] = T.rel(dx, want_dx)
-    T.record_observed("gat_fused_backward", case=label, ranks=len(per_rank), worst=max(errs.values()))
-    assert max(errs.values()) <= TOL, errs
+    G.compare(G.assembled(per_rank, k, m, layers), G.reference(rows, cols, m, x, layers, weights, None, g_glob, attention=attention), "gat_fused_backward",
+              label, len(per_rank), check=("dw", "dx"))
 
 
 def fused_vs_unfused(per_rank, kf, ku, weights, label):
@@ -408,17 +333,12 @@ def fused_vs_unfused(per_rank, kf, ku, weights, label):
     assert worst <= TOL, worst
 
 
-def er8():
-    case = T.case_inputs("er8_r16")
-    return case["rows"], case["cols"], case["M"], case["A"] * T.GAT_INPUT_SCALE
-
-
 @pytest.mark.parametrize("attention", ["none", "softmax"])
 @pytest.mark.parametrize("p", [1, 2, 4, 8])
 def test_fused_backward_er8(p, attention):
     rows, cols, m, x = er8()
     layers = T.GAT_LAYERS
-    w = hashed_weights(layers, attention)
+    w = hashed_weights(layers, later(attention))
     g = O.dense_fill(m, layers[-1][1] * layers[-1][2], 9) * 16.0
     per_rank = H.run_spmd(p, lambda wd: run_gat(wd, "15d_fusion2", 1, rows, cols, m, x, layers, w, g, attention, ["fused", "unfused"]))
     check_round(per_rank, 0, rows, cols, m, x, layers, w, g, attention, "er8_r16 %s p%d" % (attention, p))
@@ -438,7 +358,7 @@ def test_fused_backward_widths(shape, p, attention):
     m, layers = WIDE[shape]
     rows, cols = H.generate_er(m, m, m * 16, 77)
     x = O.dense_fill(m, layers[0][0], 41) * 16.0
-    w = hashed_weights(layers, attention, 8.0)
+    w = hashed_weights(layers, later(attention, 8.0))
     g = O.dense_fill(m, layers[-1][1] * layers[-1][2], 3) * 64.0
     per_rank = H.run_spmd(p, lambda wd: run_gat(wd, "15d_fusion2", 1, rows, cols, m, x, layers, w, g, attention, ["fused", "unfused"]))
     check_round(per_rank, 0, rows, cols, m, x, layers, w, g, attention, "%s %s p%d" % (shape, attention, p))
@@ -452,7 +372,7 @@ def test_fused_backward_rmat_hub_rows(p, attention):
     rows, cols = H.generate_rmat(13, m * 16)
     assert np.bincount(rows, minlength=m).max() >= 512 and np.bincount(cols, minlength=m).max() >= 512
     x = O.dense_fill(m, 64, 8) * 8.0
-    w = hashed_weights(layers, attention, 4.0)
+    w = hashed_weights(layers, later(attention, 4.0))
     g = O.dense_fill(m, 64, 4) * 32.0
     per_rank = H.run_spmd(p, lambda wd: run_gat(wd, "15d_fusion2", 1, rows, cols, m, x, layers, w, g, attention, ["fused", "fused", "unfused"]))
     check_round(per_rank, 0, rows, cols, m, x, layers, w, g, attention, "rmat hubs %s p%d" % (attention, p))
@@ -466,7 +386,7 @@ def test_fused_backward_rmat_hub_rows(p, attention):
 def test_two_rounds_are_bit_identical(attention):
     rows, cols, m, x = er8()
     layers = T.GAT_LAYERS
-    w = hashed_weights(layers, attention)
+    w = hashed_weights(layers, later(attention))
     g = O.dense_fill(m, 12, 9) * 16.0
 
     def two_rounds(wd):  # two forward + backward rounds
@@ -487,7 +407,7 @@ def test_mode_switches_leak_nothing(p, attention):
     "unfused" included), and an ordinary sddmmA / fusedSpMM on the same operator afterwards still matches the oracle."""
     rows, cols, m, x = er8()
     layers = T.GAT_LAYERS
-    w = hashed_weights(layers, attention)
+    w = hashed_weights(layers, later(attention))
     g = O.dense_fill(m, 12, 9) * 16.0
     oc = dict(R=16, a=O.dense_fill(m, 16, 1), b=O.dense_fill(m, 16, 2))
 
@@ -526,49 +446,14 @@ def test_mode_switches_leak_nothing(p, attention):
     assert abs(sum(pr["sddmm_sum"] for pr in per_rank) - float(np.sum(want_vals))) <= T.TOL * float(np.sum(np.abs(want_vals)))
 
 
-def sgd(world, rows, cols, m, x, layers, target, steps, lr_scale, attention):
-    sp = H.SpmatLocal.from_global(world, m, m, rows, cols, np.ones(len(rows)))
-    d = H.DistributedSparse(world, "15d_fusion2", sp, layers[0][0], 1)
-    gnn = H.GAT(d, layers, ALPHA, attention=attention, backward="fused")
-    w = hashed_weights(layers, attention)
-    for k, wk in w.items():
-        gnn.set_weight(*k, wk)
-    d.setRValue(layers[0][0])
-    x_d = H.Dense.create(world, *gnn.buffer_shape(0))
-    x_d.upload(T.fill_local(d.submatrices(H.BMAT), x_d.shape, x))
-    d.setRValue(layers[-1][1] * layers[-1][2])
-    tgt = T.fill_local(d.submatrices(H.AMAT), gnn.buffer_shape(len(layers)), target)
-    out = H.Dense.create(world, *gnn.buffer_shape(len(layers)))
-    g = H.Dense.create(world, *gnn.buffer_shape(len(layers)))
-    gnn.set_input(x_d)
-    losses, lr = [], None
-    for step in range(steps + 1):
-        gnn.forwardPass()
-        gnn.get_output(out)
-        diff = out.download() - tgt
-        losses.append(0.5 * float(np.sum(diff * diff)))
-        if step == steps:
-            break
-        g.upload(diff)
-        gnn.backwardPass(g)
-        dw = {k: gnn.weight_grad(*k) for k in w}
-        if lr is None:  # the same on every rank: the gradients are replicated
-            lr = lr_scale * np.sqrt(sum(np.sum(v * v) for v in w.values()) / sum(np.sum(v * v) for v in dw.values()))
-        for k in w:
-            w[k] = w[k] - lr * dw[k]
-            gnn.set_weight(*k, w[k])
-    for h in (x_d, out, g, gnn, d, sp):
-        h.free()
-    return losses
-
-
 @pytest.mark.parametrize("attention,tscale", [("none", 4.0), ("softmax", 0.05)])
 @pytest.mark.parametrize("p", [1, 2])
 def test_sgd_lowers_the_loss(p, attention, tscale):
     rows, cols, m, x = er8()
     target = O.dense_fill(m, 12, 21) * tscale
-    per_rank = H.run_spmd(p, lambda wd: sgd(wd, rows, cols, m, x, T.GAT_LAYERS, target, 5, 0.02, attention))
-    loss = np.sum(np.array(per_rank), axis=0)
+    w = hashed_weights(T.GAT_LAYERS, later(attention))
+    per_rank = H.run_spmd(p, lambda wd: G.sgd(wd, rows, cols, m, x, T.GAT_LAYERS, target, 5, 0.02, w, attention=attention, backward="fused"))
+    loss = np.sum(np.array([pr[0] for pr in per_rank]), axis=0)
     assert all(loss[i + 1] < loss[i] for i in range(5)), loss
 
 

@@ -1,29 +1,21 @@
-"""GAT softmax attention without a GPU: the numpy definition (tests/gat_softmax_ref.py) against finite differences of its forward pass,
+"""GAT softmax attention without a GPU: the numpy definition (tests/gat_ref.py, attention softmax) against finite differences of its forward pass,
 the optional kernel group of include/hnh_attention.h (declared == bound == exported by the HIP library, disjoint from the mandatory
 and grad tables, absent from the CPU test double), and the host calls on the test double: the softmax mode names the missing kernel
 or the unsupported schedule, and the default mode is untouched."""
 import ctypes as C
-import os
 import re
 
 import numpy as np
 import pytest
 
-import gat_softmax_ref as R
+import gat_pass_ref as P
+import gat_ref as R
 import softmax_schedules as S
 import hnh_testlib as T
 from distributed_sddmm_amd import _kernels as K
 from distributed_sddmm_amd import api as H
+from gat_cpu_harness import ROOT, declared
 from oracle import oracle as O
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def declared(header):
-    txt = open(os.path.join(ROOT, "include", header)).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return set(re.findall(r"\b(hnh_[a-z0-9_]+)\s*\(", txt))
-
 
 def fd_problem():
     """A small ER graph (32 vertices, 123 nonzeros) with T.GAT_LAYERS and weights of the usual 1/sqrt(fan-in) scale in BOTH layers:
@@ -40,15 +32,15 @@ def fd_problem():
 def test_reference_backward_matches_finite_differences():
     rows, cols, m, x, w, g = fd_problem()
     layers, alpha, step = T.GAT_LAYERS, T.GAT_ALPHA, 1e-6
-    dws, dx = R.backward(rows, cols, m, x, layers, alpha, g, w)
+    dws, _, dx = R.backward(rows, cols, m, x, layers, alpha, g, w, attention="softmax")
 
     def loss(ww, xx):
-        return float(np.sum(g * R.forward(rows, cols, m, xx, layers, alpha, ww)))
+        return float(np.sum(g * R.forward(rows, cols, m, xx, layers, alpha, ww, attention="softmax")))
 
     # LeakyReLU and ReLU are not differentiable at 0: no pre-activation may lie within +-10 steps of it (exact zeros are rows that
     # are zero whatever the perturbation: a vertex without nonzeros)
     def margin_ok(ww, xx):
-        pre = R.pre_activations(rows, cols, m, xx, layers, alpha, ww)
+        pre = R.kinks(rows, m, R.pre_activations(rows, cols, m, xx, layers, alpha, ww, attention="softmax"))
         return np.abs(pre[pre != 0]).min() > 10 * step
 
     assert margin_ok(w, x)
@@ -106,7 +98,7 @@ def test_attention_kernels_are_an_optional_group():
 
 def test_host_call_declared():
     assert "hnh_gat_set_attention" in declared("hnh_dist.h") and "hnh_gat_set_attention" in H.SIGNATURES
-    txt = open(os.path.join(ROOT, "include", "hnh_dist.h")).read()
+    txt = open(ROOT + "/include/hnh_dist.h").read()
     assert re.search(r"#define HNH_GAT_ATTENTION_NONE 0\b", txt) and re.search(r"#define HNH_GAT_ATTENTION_SOFTMAX 1\b", txt)
 
 
@@ -201,8 +193,8 @@ def test_extended_reference_matches_fp64(width, scale, fsum, tol):
     cols = rng.integers(0, m, len(rows))
     x, y = rng.uniform(-1, 1, (m, width)) * scale, rng.uniform(-1, 1, (m, width)) * scale
     perm = rng.permutation(len(rows))  # the reference takes the nonzeros in any order
-    o, lse, s = R.attention(rows[perm], cols[perm], m, x, y, T.GAT_ALPHA)
-    o_ld, lse_ld, s_ld = R.attention_ld(rows[perm], cols[perm], m, x, y, T.GAT_ALPHA, chunk=1000, fsum=fsum)
+    o, lse, s = P.attention(rows[perm], cols[perm], m, x, y, T.GAT_ALPHA)
+    o_ld, lse_ld, s_ld = P.attention_ld(rows[perm], cols[perm], m, x, y, T.GAT_ALPHA, chunk=1000, fsum=fsum)
     assert o_ld.dtype == np.longdouble and lse_ld.dtype == np.longdouble
     assert T.rel(np.float64(o_ld), o) <= tol and T.rel(np.float64(s_ld), s) <= 1e-13
     assert np.all(np.abs(np.float64(lse_ld) - lse) <= 1e-13 * np.maximum(1.0, np.abs(lse))) and np.all(lse_ld[deg == 0] == 0)
@@ -213,7 +205,7 @@ def test_extended_reference_matches_fp64(width, scale, fsum, tol):
 def test_max_rises():
     rowptr = np.array([0, 0, 1, 5, 9])
     s = np.array([3.0, 1.0, 2.0, 2.0, 5.0, -2.0, 0.0, 0.0, -1.0])
-    got = R.max_rises(rowptr, s)
+    got = P.max_rises(rowptr, s)
     assert [list(g) for g in got] == [[], [0], [0, 1, 3], [0, 1]]
 
 
@@ -225,8 +217,8 @@ def test_forced_schedules_rise_where_designed():
     rowptr, colidx, x, y, rises, group = S.build(m, 16, 3)
     rows = np.repeat(np.arange(m), np.diff(rowptr))
     assert all(np.all(np.diff(colidx[rowptr[i]:rowptr[i + 1]]) >= 0) for i in range(m)), "columns sorted within a row"
-    _, _, s = R.attention(rows, colidx.astype(np.int64), m, x, y, T.GAT_ALPHA)
-    got = R.max_rises(rowptr, s)
+    _, _, s = P.attention(rows, colidx.astype(np.int64), m, x, y, T.GAT_ALPHA)
+    got = P.max_rises(rowptr, s)
     for i in range(m):
         assert np.array_equal(got[i], rises[i]), (i, group[i], got[i], rises[i])
     g = np.array(group)

@@ -1,7 +1,7 @@
 """GAT softmax attention on the GPU (include/hnh_attention.h, GAT attention mode "softmax"): the fused softmax pass against numpy over
 widths and row lengths (empty rows up to hub rows), with forced column panels and scores far beyond exp's range; its independence of
 how a row's nonzeros are grouped into launches; a closed form that does not need numpy; the backward kernels; and the operator's
-forward output, dW of every (layer, head) and dX against tests/gat_softmax_ref.py over loopback ranks, determinism, side effects,
+forward output, dW of every (layer, head) and dX against tests/gat_ref.py over loopback ranks, determinism, side effects,
 SGD training and the schedules that must refuse.
 
 Observed on an MI355X (max |x - ref| / max |ref| per matrix, worst of the output, dW of every (layer, head) and dX): er8_r16 at
@@ -12,114 +12,22 @@ import ctypes as C
 import numpy as np
 import pytest
 
-import gat_softmax_ref as R
+import gat_gpu_harness as G
 import hnh_testlib as T
 from distributed_sddmm_amd import _kernels as K
 from distributed_sddmm_amd import api as H
+from gat_gpu_harness import ALPHA, check_against_numpy, ctx, hashed_weights, hip_backend, mixed_degrees, softmax_pass, square_graph  # noqa: F401
 from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
-TOL = 1e-10
-ALPHA = T.GAT_ALPHA
-
-
-@pytest.fixture(autouse=True, scope="module")
-def hip_backend():
-    assert H.load_backend(None) == "hip-gfx950"
-    yield
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    c = K.Ctx(0)
-    assert K.load().hnh_backend_name() == b"hip-gfx950"
-    yield c
-    c.close()
 
 
 # ------------------------------------------------------------------------------------------------ kernels
-def graph(m, degrees, seed):
-    """CSR (sorted columns, repeated pairs kept) with the given row lengths; returns rowptr, colidx and the nonzeros' rows."""
-    rng = np.random.default_rng(seed)
-    rows = np.repeat(np.arange(m), degrees)
-    cols = rng.integers(0, m, len(rows))
-    order = np.lexsort((cols, rows))
-    rows, cols = rows[order], cols[order]
-    rowptr = np.concatenate([[0], np.cumsum(degrees)]).astype(np.int32)
-    return rowptr, cols.astype(np.int32), rows
-
-
-def mixed_degrees(m, seed):
-    """Rows of length 0 .. 40, a few of 200 .. 300 and hub rows past every long-row threshold (600, 1500)."""
-    rng = np.random.default_rng(seed)
-    d = rng.integers(0, 41, m)
-    d[rng.random(m) < 0.2] = 0
-    d[5::97] = rng.integers(200, 301, len(d[5::97]))
-    d[7] = 600
-    d[m // 2] = 1500
-    return d
-
-
-def softmax_pass(ctx, rowptr, colidx, x, y, alpha, groups=None, nwin=6, off=2):
-    """One softmax pass through hnh_attn_softmax_csr_p.  groups = None: one call over whole rows; else a list of (first, end) window
-    ranges covering [0, nwin) of nwin column windows, one call each.  The head's block starts at column `off` of a relu_dst of pitch
-    R + 4 (an odd off: 8-byte aligned only, the W = 1 instances).  Returns (relu output, lse, row_max, row_sum, values)."""
-    lib = ctx.lib
-    m, R_ = x.shape
-    nnz = int(rowptr[-1])
-    ld = R_ + 4
-    drp, dci = ctx.upload(rowptr), ctx.upload(np.concatenate([colidx, [0]]).astype(np.int32))
-    dx, dy = ctx.upload(x), ctx.upload(y)
-    out = K.DevArray(ctx, m * R_, np.float64)
-    vals = ctx.upload(np.full(max(nnz, 1), 3.0))
-    rmax, rsum, lse = (ctx.upload(np.full(m, 5.0)) for _ in range(3))
-    dst = ctx.upload(np.full((m, ld), 7.0))
-    blk = K.CsrBlock(m, nnz, m, int(np.diff(rowptr).max()), 0, drp.ptr, dci.ptr, None)
-    st = K.AttnState(rmax.ptr, rsum.ptr, lse.ptr, alpha, dst.ptr + off * 8, ld)
-    base = K.FUSED_VALUES_OVERWRITE
-    if groups is None:
-        ctx.check(lib.hnh_attn_softmax_csr_p(ctx.h, C.byref(blk), vals.ptr, dx.ptr, dy.ptr, out.ptr, R_, base | K.FUSED_OUT_OVERWRITE | K.ATTN_FINISH,
-                                             C.byref(st), None, K.STREAM_COMPUTE), "softmax pass")
-    else:
-        bounds = (C.c_int32 * (nwin - 1))(*[int(m * (b + 1) / nwin) for b in range(nwin - 1)])
-        split = K.DevArray(ctx, (nwin - 1) * m, np.int32)
-        ctx.check(lib.hnh_csr_window_bounds(ctx.h, m, drp.ptr, dci.ptr, nwin - 1, bounds, split.ptr, K.STREAM_COMPUTE), "window bounds")
-        for k, (a, b) in enumerate(groups):
-            win = K.CsrWindow(None if a == 0 else split.ptr + (a - 1) * m * 4, None if b == nwin else split.ptr + (b - 1) * m * 4, int(b == nwin))
-            flags = base | (K.FUSED_OUT_OVERWRITE if k == 0 else 0) | (K.ATTN_FINISH if b == nwin else 0)
-            ctx.check(lib.hnh_attn_softmax_csr_p(ctx.h, C.byref(blk), vals.ptr, dx.ptr, dy.ptr, out.ptr, R_, flags, C.byref(st), C.byref(win),
-                                                 K.STREAM_COMPUTE), "softmax window")
-        split.free()
-    ctx.sync()
-    d = dst.get()
-    assert np.all(d[:, :off] == 7.0) and np.all(d[:, off + R_:] == 7.0), "columns outside the head's block are not written"
-    res = (d[:, off:off + R_], lse.get(), rmax.get(), rsum.get(), vals.get()[:nnz])
-    for a in (drp, dci, dx, dy, out, vals, rmax, rsum, lse, dst):
-        a.free()
-    return res
-
-
-def check_against_numpy(got, rows, colidx, m, x, y, sels=None):
-    """The pass against the extended-precision reference (gat_softmax_ref.attention_ld): output, lse, scores and the row state.  sels =
-    boolean row masks: the output and lse bounds hold over each group of rows on its own (groups whose scales differ)."""
-    o, lse, s = (np.float64(v) for v in R.attention_ld(rows, colidx.astype(np.int64), m, x, y, ALPHA))
-    live = np.bincount(rows, minlength=m) > 0
-    assert np.all(np.isfinite(got[0])) and np.all(np.isfinite(got[1]))
-    for sel in (sels if sels is not None else [np.ones(m, dtype=bool)]):
-        assert T.rel(got[0][sel], np.maximum(o[sel], 0.0)) <= 1e-12, T.rel(got[0][sel], np.maximum(o[sel], 0.0))
-        assert np.max(np.abs(got[1][sel] - lse[sel])) <= 1e-12 * max(1.0, np.abs(lse[sel]).max()) and np.all(got[1][~live] == 0.0)
-    assert T.rel(got[4], s) <= 1e-13
-    assert np.all(got[2][~live] == -np.inf) and np.all(got[3][~live] == 0.0)
-    mx = np.full(m, -np.inf)
-    np.maximum.at(mx, rows, s)
-    assert np.max(np.abs(got[2][live] - mx[live]), initial=0.0) <= 1e-13 * max(1.0, np.abs(s).max()) and np.all(got[3][live] >= 1.0)
-
-
 @pytest.mark.parametrize("width", [1, 2, 7, 16, 64, 100, 128, 256])
 def test_softmax_pass_vs_numpy(ctx, width):
     m = 2048
-    deg = mixed_degrees(m, width)
-    rowptr, colidx, rows = graph(m, deg, width + 1)
+    deg = mixed_degrees(m, width, empty=())
+    rowptr, colidx, rows = square_graph(m, deg, width + 1)
     rng = np.random.default_rng(width)
     x, y = rng.uniform(-1, 1, (m, width)), rng.uniform(-1, 1, (m, width))
     got = softmax_pass(ctx, rowptr, colidx, x, y, ALPHA)
@@ -132,7 +40,7 @@ def test_softmax_pass_vs_numpy(ctx, width):
 def test_scores_beyond_the_range_of_exp(ctx, width):
     """Scores up to +-1e3: exp of a raw score would overflow (or underflow to a 0 / 0 row); the online softmax stays exact."""
     m = 1024
-    rowptr, colidx, rows = graph(m, mixed_degrees(m, 3), 4)
+    rowptr, colidx, rows = square_graph(m, mixed_degrees(m, 3, empty=()), 4)
     rng = np.random.default_rng(9)
     scale = np.sqrt(3e3 / np.sqrt(width))
     x, y = rng.uniform(-1, 1, (m, width)) * scale, rng.uniform(-1, 1, (m, width)) * scale
@@ -150,7 +58,7 @@ INSTANCE_WIDTHS = [7, 16, 64, 100, 101, 128, 200, 201, 256, 300]
 def test_forced_panels_are_bit_identical(monkeypatch, width):
     """Column panels (several launches over every row) continue the row state nonzero by nonzero: the same bits as one launch."""
     m = 4096
-    rowptr, colidx, rows = graph(m, mixed_degrees(m, 5), 6)
+    rowptr, colidx, rows = square_graph(m, mixed_degrees(m, 5, empty=()), 6)
     rng = np.random.default_rng(2)
     x, y = rng.uniform(-1, 1, (m, width)), rng.uniform(-1, 1, (m, width))
     c1 = K.Ctx(0)
@@ -172,7 +80,7 @@ def test_grouping_independence(ctx, width):
     """The same block walked with its 6 windows grouped as 1, 2 or 5 launches (and window by window): bit-identical outputs, lse,
     row state and scores — what a launch-local state merged at the end would not give."""
     m = 2048
-    rowptr, colidx, rows = graph(m, mixed_degrees(m, 8), 9)
+    rowptr, colidx, rows = square_graph(m, mixed_degrees(m, 8, empty=()), 9)
     rng = np.random.default_rng(width)
     x, y = rng.uniform(-1, 1, (m, width)) * 3.0, rng.uniform(-1, 1, (m, width)) * 3.0
     results = [softmax_pass(ctx, rowptr, colidx, x, y, ALPHA, groups=g)
@@ -187,7 +95,7 @@ def test_grouping_independence(ctx, width):
 def test_constant_column_closed_form(ctx, width):
     """A with a constant column kappa: the softmax weights of a row sum to 1, so every non-empty row gets kappa there; empty rows 0."""
     m, kappa = 2048, 0.75
-    rowptr, colidx, rows = graph(m, mixed_degrees(m, 11), 12)
+    rowptr, colidx, rows = square_graph(m, mixed_degrees(m, 11, empty=()), 12)
     a = np.random.default_rng(13).uniform(-1, 1, (m, width)) * 2.0
     a[:, 0] = kappa
     got = softmax_pass(ctx, rowptr, colidx, a, a, ALPHA)[0]
@@ -198,7 +106,7 @@ def test_constant_column_closed_form(ctx, width):
 def test_wide_rows_and_bad_calls_are_refused(ctx):
     lib = ctx.lib
     m, width = 64, 600
-    rowptr, colidx, _ = graph(m, np.full(m, 3), 1)
+    rowptr, colidx, _ = square_graph(m, np.full(m, 3), 1)
     drp, dci = ctx.upload(rowptr), ctx.upload(colidx)
     x = ctx.upload(np.ones((m, width)))
     out, dst = K.DevArray(ctx, m * width, np.float64), ctx.upload(np.zeros((m, width)))
@@ -240,59 +148,15 @@ def test_backward_kernels_exact(ctx):
 
 
 # ------------------------------------------------------------------------------------------------ the operator
-def hashed_weights(layers):
-    return {(li, h): O.gat_weight(li, h, fin, fph) for li, (fin, fph, heads) in enumerate(layers) for h in range(heads)}
-
-
 def run_softmax_gat(world, alg, c, rows, cols, m, x, layers, weights, g_glob, rounds=1):
     """Forward + backward with softmax attention on one rank; returns this rank's blocks and the results of every round."""
-    sp = H.SpmatLocal.from_global(world, m, m, rows, cols, np.ones(len(rows)))
-    d = H.DistributedSparse(world, alg, sp, layers[0][0], c)
-    gnn = H.GAT(d, layers, ALPHA, attention="softmax")
-    for k, w in weights.items():
-        gnn.set_weight(*k, w)
-    d.setRValue(layers[0][0])
-    subB = d.submatrices(H.BMAT)
-    d.setRValue(layers[-1][1] * layers[-1][2])
-    subA = d.submatrices(H.AMAT)
-    x_d = H.Dense.create(world, *gnn.buffer_shape(0))
-    x_d.upload(T.fill_local(subB, x_d.shape, x))
-    g = H.Dense.create(world, *gnn.buffer_shape(len(layers)))
-    g.upload(T.fill_local(subA, g.shape, g_glob))
-    out = H.Dense.create(world, *gnn.buffer_shape(len(layers)))
-    dx = H.Dense.create(world, *gnn.buffer_shape(0))
-    gnn.set_input(x_d)
-    res = dict(subA=subA, subB=subB, rounds=[])
-    for _ in range(rounds):
-        gnn.forwardPass()
-        gnn.get_output(out)
-        before = out.download()
-        gnn.backwardPass(g)
-        gnn.get_output(out)
-        gnn.get_input_grad(dx)
-        res["rounds"].append(dict(out=before, out_after=out.download(), dx=dx.download(), dw={k: gnn.weight_grad(*k) for k in weights}))
-    for h in (x_d, g, out, dx, gnn, d, sp):
-        h.free()
-    return res
+    return G.run_rounds(world, rows, cols, m, x, layers, weights, None, g_glob, rounds, out_after=True, alg=alg, c=c, attention="softmax")
 
 
 def check_against_reference(per_rank, rows, cols, m, x, layers, weights, g_glob, label):
-    want_out = R.forward(rows, cols, m, x, layers, ALPHA, weights)
-    want_dw, want_dx = R.backward(rows, cols, m, x, layers, ALPHA, g_glob, weights)
-    width = layers[-1][1] * layers[-1][2]
-    out = T.assemble_dense([dict(o=pr["rounds"][0]["out"], subA=pr["subA"]) for pr in per_rank], "o", "subA", m, width)
-    assert np.count_nonzero(out) > out.size // 10 and np.count_nonzero(out == 0.0) > out.size // 10  # both sides of the ReLU
-    errs = {"out": T.rel(out, want_out)}
-    r0 = per_rank[0]["rounds"][0]
-    for k, want in want_dw.items():
-        assert np.abs(want).max() > 0
-        for pr in per_rank:  # replicated: every rank holds the summed gradient
-            assert np.array_equal(pr["rounds"][0]["dw"][k], r0["dw"][k])
-        errs[k] = T.rel(r0["dw"][k], want)
-    dx = T.assemble_dense([dict(dx=pr["rounds"][0]["dx"], subB=pr["subB"]) for pr in per_rank], "dx", "subB", m, layers[0][0])
-    errs["dx"] = T.rel(dx, want_dx)
-    T.record_observed("gat_softmax", case=label, ranks=len(per_rank), worst=max(errs.values()))
-    assert max(errs.values()) <= TOL, errs
+    got = G.assembled(per_rank, 0, m, layers)
+    assert np.count_nonzero(got["out"]) > got["out"].size // 10 and np.count_nonzero(got["out"] == 0.0) > got["out"].size // 10  # both sides of the ReLU
+    G.compare(got, G.reference(rows, cols, m, x, layers, weights, None, g_glob, attention="softmax"), "gat_softmax", label, len(per_rank))
 
 
 @pytest.mark.parametrize("p", [1, 2, 4, 8])
@@ -352,50 +216,15 @@ def test_two_rounds_are_bit_identical_and_backward_leaves_the_output(graph_kind)
             assert np.array_equal(a["dw"][k], b["dw"][k])
 
 
-def sgd(world, rows, cols, m, x, layers, target, steps, lr_scale):
-    sp = H.SpmatLocal.from_global(world, m, m, rows, cols, np.ones(len(rows)))
-    d = H.DistributedSparse(world, "15d_fusion2", sp, layers[0][0], 1)
-    gnn = H.GAT(d, layers, ALPHA, attention="softmax")
-    w = hashed_weights(layers)
-    for k, wk in w.items():
-        gnn.set_weight(*k, wk)
-    d.setRValue(layers[0][0])
-    x_d = H.Dense.create(world, *gnn.buffer_shape(0))
-    x_d.upload(T.fill_local(d.submatrices(H.BMAT), x_d.shape, x))
-    d.setRValue(layers[-1][1] * layers[-1][2])
-    tgt = T.fill_local(d.submatrices(H.AMAT), gnn.buffer_shape(len(layers)), target)
-    out = H.Dense.create(world, *gnn.buffer_shape(len(layers)))
-    g = H.Dense.create(world, *gnn.buffer_shape(len(layers)))
-    gnn.set_input(x_d)
-    losses, lr = [], None
-    for step in range(steps + 1):
-        gnn.forwardPass()
-        gnn.get_output(out)
-        diff = out.download() - tgt
-        losses.append(0.5 * float(np.sum(diff * diff)))
-        if step == steps:
-            break
-        g.upload(diff)
-        gnn.backwardPass(g)
-        dw = {k: gnn.weight_grad(*k) for k in w}
-        if lr is None:  # the same on every rank: the gradients are replicated
-            lr = lr_scale * np.sqrt(sum(np.sum(v * v) for v in w.values()) / sum(np.sum(v * v) for v in dw.values()))
-        for k in w:
-            w[k] = w[k] - lr * dw[k]
-            gnn.set_weight(*k, w[k])
-    for h in (x_d, out, g, gnn, d, sp):
-        h.free()
-    return losses
-
-
 @pytest.mark.parametrize("p", [1, 2])
 def test_sgd_lowers_the_loss(p):
     case = T.case_inputs("er8_r16")
     rows, cols, m = case["rows"], case["cols"], case["M"]
     x = case["A"] * T.GAT_INPUT_SCALE
     target = O.dense_fill(m, 12, 21) * 0.05
-    per_rank = H.run_spmd(p, lambda wd: sgd(wd, rows, cols, m, x, T.GAT_LAYERS, target, 5, 0.02))
-    loss = np.sum(np.array(per_rank), axis=0)
+    w = hashed_weights(T.GAT_LAYERS)
+    per_rank = H.run_spmd(p, lambda wd: G.sgd(wd, rows, cols, m, x, T.GAT_LAYERS, target, 5, 0.02, w, attention="softmax"))
+    loss = np.sum(np.array([pr[0] for pr in per_rank]), axis=0)
     assert all(loss[i + 1] < loss[i] for i in range(5)), loss
 
 

@@ -1,4 +1,4 @@
-"""The GAT's training step without a GPU: the numpy definition of the loss (tests/gat_train_ref.py) against central finite differences
+"""The GAT's training step without a GPU: the numpy definition of the loss (tests/gat_ref.py) against central finite differences
 for heads "mean" and "concat" and against its extended-precision twin; Adam and SGD against a second, scalar-loop restatement; the
 optional kernel group of include/hnh_train.h (declared == bound == exported by the HIP library, disjoint from the six existing tables and
 headers, absent from the CPU test double); the host calls; on the test double, loss and train_step name a kernel of the group and its
@@ -9,20 +9,17 @@ Observed here: loss gradient against finite differences <= 2.2e-8 of its largest
 finite-difference tests); float64 against longdouble within 1e-14; the vectorised optimizers against the scalar loops within 1e-15."""
 import ctypes as C
 import math
-import os
 import re
 
 import numpy as np
 import pytest
 
-import gat_train_ref as R
+import gat_ref as R
 import hnh_testlib as T
 from distributed_sddmm_amd import _kernels as K
 from distributed_sddmm_amd import api as H
-from test_gat_additive_cpu import declared, make_gat
-from test_gat_dropout_cpu import plain_output
+from gat_cpu_harness import ROOT, declared, make_gat, plain_output
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GROUP = {"hnh_xent_rows_f64_workspace", "hnh_xent_rows_f64", "hnh_optim_step_f64"}
 HOST_CALLS = ("hnh_gat_get_weight", "hnh_gat_get_attn_vectors", "hnh_gat_set_labels", "hnh_gat_loss", "hnh_gat_set_optimizer",
               "hnh_gat_optimizer_step", "hnh_gat_train_step", "hnh_gat_evaluate")
@@ -136,7 +133,7 @@ def test_train_kernels_are_an_optional_group():
         assert not hasattr(dbl, n), "the CPU test double does not export %s" % n
     K.load(T.ORACLE_BACKEND)  # ... and binding it still works
     assert C.sizeof(K.OptimTensor) == 64 and C.sizeof(K.Optim) == 72
-    txt = open(os.path.join(ROOT, "include", "hnh_train.h")).read()
+    txt = open(ROOT + "/include/hnh_train.h").read()
     assert re.search(r"#define HNH_XENT_MAX_WIDTH %d\b" % K.XENT_MAX_WIDTH, txt) and re.search(r"#define HNH_OPTIM_MAX_TENSORS %d\b" % K.OPTIM_MAX_TENSORS, txt)
     assert "ReLU" in txt and "average" in txt, "the header states the known deviation"
 

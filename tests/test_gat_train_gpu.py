@@ -1,6 +1,6 @@
 """The GAT's training step on the GPU (include/hnh_train.h; GAT.set_labels / loss / set_optimizer / optimizer_step / train_step / evaluate).
 
-Kernel level, through ctypes.  hnh_xent_rows_f64 against the extended-precision numpy reference (tests/gat_train_ref.py, xent_rows with
+Kernel level, through ctypes.  hnh_xent_rows_f64 against the extended-precision numpy reference (tests/gat_ref.py, xent_rows with
 np.longdouble) for classes in {1, 2, 3, 7, 8, 40, 64, 65, 256, 1000} x heads in {1, 3, 8} within HNH_XENT_MAX_WIDTH, with pitches wider
 than the row, guard values round G, the result words and the workspace, logits up to +-700, a share of unlabelled rows and rows with
 exact ties (small integers, the same in every head, so the head mean ties exactly); more rows than one grid round takes; a label beyond
@@ -10,13 +10,13 @@ hnh_optim_step_f64 against numpy with the same gradient bits: column blocks of a
 pitches, rows or cols equal to 1, and a table longer than one launch holds; bound T.TOL per tensor.
 Operator level, 15d_fusion2 with c = 1 on 1, 2, 4, 8 loopback ranks: loss with grad_out, then backwardPass, against the reference — loss,
 accuracy, G, every dW, da1, da2 and dX — for score dot (backward unfused and fused) and score additive, heads "mean" and "concat"; bound
-1e-10, the operator bound of test_gat_additive_gpu.py.
-Trajectories: K = 10 train_steps against gat_train_ref.train.  The tolerance is measured: the reference runs a second time with every
+1e-10, the operator bound of the other GAT tests.
+Trajectories: K = 10 train_steps against gat_ref.train.  The tolerance is measured: the reference runs a second time with every
 gradient perturbed by 1e-10 * max|g| * u (1e-10: the bound on one backward pass), and the device may differ from the reference by 10
 times the divergence of that run (the factor covers kink crossings of ReLU / LeakyReLU).  SGD with momentum is the sharp check, Adam the
 loose one (its first steps are ill-conditioned where |g| ~ eps).  Parameters are bit-equal across ranks; a run with dropout (0.6, 0.6)
 uses the masks of seed0 + t; evaluate leaves rates and seed as they were.
-Learning: the planted partition of gat_train_ref.planted_partition, Adam, 40 steps: the final train loss is at most half the first and
+Learning: the planted partition of gat_ref.planted_partition, Adam, 40 steps: the final train loss is at most half the first and
 the held-out accuracy at least 0.8.
 
 The observed errors and the measured bounds are recorded with T.record_observed."""
@@ -25,30 +25,14 @@ import ctypes as C
 import numpy as np
 import pytest
 
-import gat_additive_ref as RA
-import gat_softmax_ref as RS
-import gat_train_ref as R
+import gat_ref as R
 import hnh_testlib as T
 from distributed_sddmm_amd import _kernels as K
 from distributed_sddmm_amd import api as H
-from test_gat_additive_gpu import ALPHA, TOL, er8, hashed_weights, setup, teardown
+from gat_gpu_harness import ALPHA, TOL, ctx, er8, hashed_weights, hip_backend, setup, teardown  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 GUARD = 7.0
-
-
-@pytest.fixture(autouse=True, scope="module")
-def hip_backend():
-    assert H.load_backend(None) == "hip-gfx950"
-    yield
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    c = K.Ctx(0)
-    assert K.load().hnh_backend_name() == b"hip-gfx950"
-    yield c
-    c.close()
 
 
 # ------------------------------------------------------------------------------------------------ the loss kernel
@@ -321,23 +305,17 @@ def test_loss_then_backward_vs_reference(p, config, heads):
     nh, classes = R.heads_of(layers, heads)
     labels, mask = er8_labels(classes)
     w = hashed_weights(layers)
-    av = RA.vectors_of(layers) if config == "additive" else None
+    av = R.vectors_of(layers) if config == "additive" else None
+    mode = dict(attention="softmax", score="additive" if config == "additive" else "dot")
     per_rank = H.run_spmd(p, lambda wd: loss_round(wd, rows, cols, m, x, layers, w, av, labels, mask, heads, **CONFIGS[config]))
     hf = layers[-1][1] * layers[-1][2]
     out = T.assemble_dense(per_rank, "out", "subA", m, hf)
     g = T.assemble_dense(per_rank, "g", "subA", m, hf)
     dx = T.assemble_dense(per_rank, "dx", "subB", m, layers[0][0])
-    if av is None:
-        want_out = RS.forward(rows, cols, m, x, layers, ALPHA, w)
-    else:
-        want_out = RA.forward(rows, cols, m, x, layers, ALPHA, w, av)
+    want_out = R.forward(rows, cols, m, x, layers, ALPHA, w, av, **mode)
     want_loss, want_acc, want_g = R.xent(want_out, labels, mask, nh)
     other_loss, other_acc, _ = R.xent(want_out, labels, ~mask, nh)
-    if av is None:
-        want_dw, want_dx = RS.backward(rows, cols, m, x, layers, ALPHA, want_g, w)
-        want_da = None
-    else:
-        want_dw, want_da, want_dx = RA.backward(rows, cols, m, x, layers, ALPHA, want_g, w, av)
+    want_dw, want_da, want_dx = R.backward(rows, cols, m, x, layers, ALPHA, want_g, w, av, **mode)
     assert np.abs(want_g).max() > 0 and np.abs(want_dx).max() > 0
     r0 = per_rank[0]
     errs = {"out": T.rel(out, want_out), "g": T.rel(g, want_g), "dx": T.rel(dx, want_dx), "loss": abs(r0["loss"] - want_loss) / want_loss,
@@ -349,7 +327,7 @@ def test_loss_then_backward_vs_reference(p, config, heads):
     for key in w:
         assert np.abs(want_dw[key]).max() > 0
         errs[("dw",) + key] = T.rel(r0["dw"][key], want_dw[key])
-        if want_da is not None:
+        if want_da:
             errs[("da1",) + key] = T.rel(r0["da"][key][0], want_da[key][0])
             errs[("da2",) + key] = T.rel(r0["da"][key][1], want_da[key][1])
     worst = max(errs.values())
@@ -460,7 +438,8 @@ def test_trajectory_with_dropout_uses_seed_plus_step(p):
         assert np.array_equal(pr["out_after"], pr["out_again"]) and not np.array_equal(pr["out_after"], pr["out_plain"])
     hf = layers[-1][1] * layers[-1][2]
     out = T.assemble_dense(per_rank, "out_after", "subA", pp["m"], hf)
-    want = R.RD.forward(pp["rows"], pp["cols"], pp["m"], pp["x"], layers, ALPHA, per_rank[0]["w"], per_rank[0]["av"], (0.6, 0.6), (seed0 + steps) & 0xFFFFFFFFFFFFFFFF)
+    want = R.forward(pp["rows"], pp["cols"], pp["m"], pp["x"], layers, ALPHA, per_rank[0]["w"], per_rank[0]["av"], rates=(0.6, 0.6),
+                     seed=(seed0 + steps) & 0xFFFFFFFFFFFFFFFF, **R.TRAINED)
     assert T.rel(out, want) <= TOL, "after evaluate the masks are those of the last step's seed"
 
 

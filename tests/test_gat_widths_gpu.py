@@ -3,9 +3,8 @@
 Every other GAT test uses heads of 4 .. 256 features, powers of two.  Here two layer stacks (input, features per head, heads):
     odd   [(16, 7, 3), (21, 101, 2), (202, 201, 2)]   the softmax instances NX(1,1), NX(2,1), NX(4,1); heads at odd column offsets
     wide  [(24, 200, 2), (400, 300, 1), (300, 512, 1)] NX(2,2), NX(4,2) and the 512 limit
-on er8_r16 and an R-MAT graph with hub rows (2^12 vertices).  Softmax attention (15d_fusion2, c = 1, p = 1 and 4) against
-tests/gat_softmax_ref.py; attention "none" (also a head of 301 features, whose odd width above 256 takes the composed fallback of the
-fused pass and the column-block epilogue kernels) on 15d_fusion2 and 15d_fusion1 grids against tests/gat_backward_ref.py.  A softmax
+on er8_r16 and an R-MAT graph with hub rows (2^12 vertices).  Softmax attention (15d_fusion2, c = 1, p = 1 and 4) and attention "none" (also a head of 301 features, whose odd width above 256 takes the composed fallback of the
+fused pass and the column-block epilogue kernels) on 15d_fusion2 and 15d_fusion1 grids, both against tests/gat_ref.py.  A softmax
 head wider than the one-pass limit is refused with an error that names it.
 
 Observed on an MI355X (max |x - ref| / max |ref| per matrix, worst of the output, dW of every (layer, head) and dX): softmax <= 2.4e-15,
@@ -13,21 +12,15 @@ none <= 3.7e-15.  The bound asserted is 1e-10 (TOL of the other GAT tests)."""
 import numpy as np
 import pytest
 
+import gat_gpu_harness as G
 import hnh_testlib as T
-import test_gat_backward_gpu as BW
-import test_gat_softmax_gpu as SM
 from distributed_sddmm_amd import api as H
+from gat_gpu_harness import hip_backend  # noqa: F401
 from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
 
 STACKS = {"odd": [(16, 7, 3), (21, 101, 2), (202, 201, 2)], "wide": [(24, 200, 2), (400, 300, 1), (300, 512, 1)], "odd301": [(16, 301, 2)]}
-
-
-@pytest.fixture(autouse=True, scope="module")
-def hip_backend():
-    assert H.load_backend(None) == "hip-gfx950"
-    yield
 
 
 def problem(graph, layers):
@@ -50,9 +43,11 @@ def problem(graph, layers):
 def test_softmax_gat_widths(stack, graph, p):
     layers = STACKS[stack]
     rows, cols, m, x, g = problem(graph, layers)
-    w = SM.hashed_weights(layers)
-    per_rank = H.run_spmd(p, lambda wd: SM.run_softmax_gat(wd, "15d_fusion2", 1, rows, cols, m, x, layers, w, g))
-    SM.check_against_reference(per_rank, rows, cols, m, x, layers, w, g, "widths %s %s p%d" % (stack, graph, p))
+    w = G.hashed_weights(layers)
+    per_rank = H.run_spmd(p, lambda wd: G.run_rounds(wd, rows, cols, m, x, layers, w, None, g, out_after=True, attention="softmax"))
+    got = G.assembled(per_rank, 0, m, layers)
+    assert np.count_nonzero(got["out"]) > got["out"].size // 10 and np.count_nonzero(got["out"] == 0.0) > got["out"].size // 10  # both sides of the ReLU
+    G.compare(got, G.reference(rows, cols, m, x, layers, w, None, g, attention="softmax"), "gat_softmax", "widths %s %s p%d" % (stack, graph, p), p)
 
 
 NONE_GRIDS = [("15d_fusion2", 1, 1), ("15d_fusion1", 1, 1), ("15d_fusion1", 4, 1)]
@@ -65,12 +60,11 @@ def test_none_gat_widths(stack, graph, grid):
     alg, p, c = grid
     layers = STACKS[stack]
     rows, cols, m, x, g = problem(graph, layers)
-    w = BW.hashed_weights(layers)
-    per_rank = H.run_spmd(p, lambda wd: BW.run_backward(wd, alg, c, rows, cols, m, x, layers, w, g))
-    out = T.assemble_dense([dict(o=pr["rounds"][0]["out"], subA=pr["subA"]) for pr in per_rank], "o", "subA", m, layers[-1][1] * layers[-1][2])
-    want = BW.R.forward(rows, cols, m, x, layers, T.GAT_ALPHA, w)
-    assert T.rel(out, want) <= BW.TOL, T.rel(out, want)
-    BW.check_against_reference(per_rank, rows, cols, m, x, layers, w, g, "widths %s %s %s p%d c%d" % (stack, graph, alg, p, c))
+    w = G.hashed_weights(layers)
+    per_rank = H.run_spmd(p, lambda wd: G.run_rounds(wd, rows, cols, m, x, layers, w, None, g, out_after=True, alg=alg, c=c))
+    got, want = G.assembled(per_rank, 0, m, layers), G.reference(rows, cols, m, x, layers, w, None, g)
+    assert T.rel(got["out"], want["out"]) <= G.TOL, T.rel(got["out"], want["out"])
+    G.compare(got, want, "gat_backward", "widths %s %s %s p%d c%d" % (stack, graph, alg, p, c), p, check=("dw", "dx"))
 
 
 @pytest.mark.parametrize("layers", [[(16, 301, 2)], [(16, 8, 2), (16, 514, 1)]], ids=["f301", "f514"])

@@ -1,38 +1,8 @@
 """N > 1 across PROCESSES on CPU: world_size 2 and 4 with torch.distributed's gloo backend carrying the
 transport callbacks of the host layer (rendezvous on 127.0.0.1)."""
-import os
-import socket
-import subprocess
-import sys
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
-
-
-def launch(nranks, case, configs, timeout=300):
-    port = free_port()
-    procs = []
-    for r in range(nranks):
-        env = dict(os.environ, RANK=str(r), WORLD_SIZE=str(nranks), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
-                   OMP_NUM_THREADS="2", GLOO_SOCKET_IFNAME="lo")
-        procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "tests", "gloo_worker.py"), case, configs],
-                                      env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True))
-    outs = []
-    try:
-        for p in procs:
-            outs.append(p.communicate(timeout=timeout)[0])
-    finally:
-        for p in procs:
-            if p.poll() is None:
-                p.kill()
-    return procs, outs
+from world_launch import launch
 
 
 @pytest.mark.parametrize("nranks,configs", [

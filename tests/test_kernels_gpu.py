@@ -9,19 +9,11 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from gat_gpu_harness import ctx  # noqa: F401
 from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-11
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    from distributed_sddmm_amd import _kernels as K
-    c = K.Ctx(0)
-    assert K.load().hnh_backend_name() == b"hip-gfx950"
-    yield c
-    c.close()
 
 
 def rel(x, y):

@@ -8,7 +8,7 @@ import sys
 
 import pytest
 
-from test_gloo_world import ROOT, free_port
+from world_launch import ALL_2, ALL_4, ALL_8, ROOT, free_port, launch_ipc
 from bench_line import read_line
 
 pytestmark = pytest.mark.gpu
@@ -36,14 +36,6 @@ def launch(nranks, case, configs, timeout=600):
             if p.poll() is None:
                 p.kill()
     return procs, outs
-
-
-ALL_2 = ("15d_fusion1:1:mesh:4;15d_fusion2:1:mesh:4;15d_fusion2:1:mesh:2;15d_fusion2:1:relay:1;15d_fusion2:2:mesh:4;15d_sparse:1:mesh:4;"
-         "15d_sparse:2:mesh:4;25d_dense_replicate:2:mesh:4;25d_sparse_replicate:2:mesh:4;als@15d_fusion2:1:mesh:4;als@15d_sparse:1:mesh:4")
-ALL_4 = ("15d_fusion2:1:mesh:4;15d_fusion2:1:relay:1;15d_fusion2:2:mesh:2;15d_fusion1:2:mesh:4;15d_sparse:1:mesh:4;25d_dense_replicate:1:mesh:4;"
-         "25d_sparse_replicate:1:mesh:4;als@15d_fusion2:1:mesh:4;als@25d_dense_replicate:1:mesh:4")
-ALL_8 = ("15d_fusion2:1:mesh:4;15d_fusion2:1:mesh:8;15d_fusion2:1:relay:1;15d_fusion2:2:mesh:4;15d_fusion2:4:mesh:2;15d_fusion1:1:mesh:4;"
-         "15d_sparse:2:mesh:4;25d_dense_replicate:2:mesh:4;25d_sparse_replicate:2:mesh:4;als@15d_fusion2:1:mesh:4")
 
 
 @pytest.mark.parametrize("nranks,configs", [(2, ALL_2), (4, ALL_4), (8, ALL_8)], ids=["2", "4", "8"])
@@ -78,7 +70,6 @@ def test_schedules_over_ipc(nranks, configs, pull, flags, cases):
     on forked streams / one gather-copy kernel) and both ways of signalling (stream memory operations / flag kernels)."""
     if gpus() < 1:
         pytest.skip("needs a GPU")
-    from test_ipc_world_cpu import launch_ipc
     for case in cases:
         procs, outs = launch_ipc(nranks, case, configs, backend="hip", timeout=900, extra_env={"HNH_IPC_PULL": pull, "HNH_IPC_FLAGS": flags})
         assert all(p.returncode == 0 for p in procs), "\n".join(o[-1500:] for o in outs)

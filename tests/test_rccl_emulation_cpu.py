@@ -24,7 +24,7 @@ import pytest
 
 import hnh_testlib as T
 from distributed_sddmm_amd import api as H
-from test_multigpu_gpu import ALL_2, ALL_4, ALL_8
+from world_launch import ALL_2, ALL_4, ALL_8, ROOT, can_read_peer_memory, free_port
 
 
 @pytest.fixture(scope="module")
@@ -226,10 +226,10 @@ def test_a_kernel_that_touches_a_buffer_in_flight_is_a_race(checker):
 
 
 def test_random_configurations_over_the_rccl_emulation(checker, monkeypatch):
-    """The fuzz generator of tests/test_fuzz_cpu.py (schedule x grid incl. remainders x sizes incl. M < p x every host switch, ALS twice)
+    """The fuzz generator of tests/fuzz_common.py (schedule x grid incl. remainders x sizes incl. M < p x every host switch, ALS twice)
     with its ranks on RcclWorld: a fixed sample here; a one-off exploration of 4 x 500 draws (1 408 valid configurations) was clean."""
     import random
-    import test_fuzz_cpu as F
+    import fuzz_common as F
     monkeypatch.setenv("HNH_ORACLE_COMM_WAIT_S", "60")
     monkeypatch.setattr(H, "run_spmd", over_rccl)
     saved = {k: os.environ.get(k) for k in F.KNOBS}
@@ -255,8 +255,6 @@ def test_the_gpu_tests_worker_as_processes_over_the_rccl_emulation(nranks, confi
     the emulation's segment lives in shared memory and the bytes move with process_vm_readv."""
     import subprocess
     import sys
-    from test_gloo_world import ROOT, free_port
-    from test_ipc_world_cpu import can_read_peer_memory
     if not can_read_peer_memory():
         pytest.skip("process_vm_readv between own processes is not permitted here")
     port = free_port()

@@ -19,7 +19,7 @@ import numpy as np
 import pytest
 
 import hnh_testlib as T
-from test_ipc_world_cpu import can_read_peer_memory
+from world_launch import can_read_peer_memory
 
 REF = "/root/reference"
 MAINS = ("bench_erdos_renyi", "bench_file", "bench_heatmap", "scratch")

@@ -8,15 +8,10 @@ import pytest
 
 import hnh_testlib as T
 from distributed_sddmm_amd import api as H
+from gat_gpu_harness import hip_backend  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 GRIDS = [(1, 1), (2, 1), (2, 2), (4, 1), (4, 2), (4, 4), (8, 1), (8, 2), (8, 4), (8, 8)]
-
-
-@pytest.fixture(autouse=True, scope="module")
-def hip_backend():
-    assert H.load_backend(None) == "hip-gfx950"  # fails loudly if the HIP library is missing
-    yield
 
 
 def configs(case_name):
@@ -272,16 +267,16 @@ def test_gat_pipelined_forward_is_the_serial_forward(alg, p, c, monkeypatch):
     x = O.dense_fill(m, 128, 9) * 4.0
     case = dict(name="gatpipe", M=m, N=m, R=128, rows=rows, cols=cols, vals=np.ones(len(rows)), A=x / T.GAT_INPUT_SCALE, B=x / T.GAT_INPUT_SCALE)
 
-    def forward():
+    def device_forward():
         per_rank = H.run_spmd(p, lambda w: T.run_gat(w, alg, c, case, layers=layers, alpha=alpha))
         return T.assemble_dense(per_rank, "gat", "subA", m, layers[-1][1] * layers[-1][2])
 
     monkeypatch.setenv("HNH_GAT_SERIAL", "1")
-    serial = forward()
+    serial = device_forward()
     monkeypatch.delenv("HNH_GAT_SERIAL")
     assert np.count_nonzero(serial) > serial.size // 10
     for _ in range(3):
-        assert np.array_equal(forward(), serial)
+        assert np.array_equal(device_forward(), serial)
 
 
 def test_operands_in_torch_memory():

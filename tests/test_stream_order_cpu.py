@@ -288,7 +288,7 @@ def run_over_ipc_threads(alg, p, c, case):
 def test_the_ipc_pull_protocol_is_race_free(checker, monkeypatch, alg, p, c):
     """sender: [write ready] ... [wait done]; receiver: [wait ready] [pull] [write done] — flag words order streams of different ranks like
     events (a wait for value v runs behind the write that raised the word to v); pulls read the peers' blocks."""
-    from test_ipc_world_cpu import can_read_peer_memory
+    from world_launch import can_read_peer_memory
     if not can_read_peer_memory():
         pytest.skip("process_vm_readv is not permitted here")
     monkeypatch.setenv("HNH_IPC_WAIT_S", "120")

@@ -110,7 +110,7 @@ def test_cpp_verify_across_processes_over_ipc(tmp_path):
     import time
     import numpy as np
     from oracle import oracle as O
-    from test_ipc_world_cpu import can_read_peer_memory
+    from world_launch import can_read_peer_memory
     if not can_read_peer_memory():
         import pytest
         pytest.skip("process_vm_readv between own processes is not permitted here")

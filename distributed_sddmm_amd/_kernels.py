@@ -244,6 +244,29 @@ class Optim(C.Structure):
                 ("weight_decay", _dbl), ("bias1", _dbl), ("bias2", _dbl)]
 
 
+# include/hnh_attn_v2.h: GATv2 dynamic attention scores of the GAT, forward and backward; a seventh OPTIONAL group bound only for the
+# product library.  The column pass gathers the packed operand of include/hnh_attn_grad.h (attn_grad_packed_width(f, True)).
+V2_SIGNATURES = {
+    "hnh_attn_v2_fwd_csr_p": (_i32, [_vp, _vp, _vp, C.c_uint, _vp, _i32]),
+    "hnh_attn_v2_row_csr_p": (_i32, [_vp, _vp, _vp, C.c_uint, _vp, _i32]),
+    "hnh_attn_v2_col_csr_p": (_i32, [_vp, _vp, _vp, C.c_uint, _vp, _i32]),
+    "hnh_attn_v2_finish_f64": (_i32, [_vp, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _i32]),
+}
+ATTN_V2_MAX_F = 256  # HNH_ATTN_V2_MAX_F
+
+
+def attn_v2_finish_work(f: int) -> int:
+    """HNH_ATTN_V2_FINISH_WORK: doubles of workspace of hnh_attn_v2_finish_f64"""
+    return 1024 * f
+
+
+class AttnV2(C.Structure):
+    """struct hnh_attn_v2"""
+    _fields_ = [("X", _vp), ("ld_x", _i64), ("a", _vp), ("dZ", _vp), ("ld_dz", _i64), ("lse", _vp), ("delta", _vp), ("Y", _vp), ("ld_y", _i64),
+                ("Out", _vp), ("ld_out", _i64), ("Out2", _vp), ("ld_out2", _i64), ("row_max", _vp), ("row_sum", _vp), ("relu_dst", _vp),
+                ("relu_ld", _i64), ("f", _i32), ("leaky_alpha", _dbl)]
+
+
 class AttnState(C.Structure):
     """struct hnh_attn_state"""
     _fields_ = [("row_max", _vp), ("row_sum", _vp), ("lse", _vp), ("leaky_alpha", _dbl), ("relu_dst", _vp), ("relu_ld", _i64)]
@@ -306,7 +329,8 @@ def load(path: str | None = None) -> C.CDLL:
         fn.restype, fn.argtypes = res, args
     if path is None or os.path.abspath(p) == os.path.abspath(LIB_PATH):
         for name, (res, args) in list(GRAD_SIGNATURES.items()) + list(ATTN_SIGNATURES.items()) + list(ATTN_GRAD_SIGNATURES.items()) + \
-                list(ATTN_ADD_SIGNATURES.items()) + list(ATTN_DROP_SIGNATURES.items()) + list(TRAIN_SIGNATURES.items()):
+                list(ATTN_ADD_SIGNATURES.items()) + list(ATTN_DROP_SIGNATURES.items()) + list(TRAIN_SIGNATURES.items()) + \
+                list(V2_SIGNATURES.items()):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
     if path is None:

@@ -665,6 +665,8 @@ class GAT:
 
     SCORE = {"dot": 0, "additive": 1}  # HNH_GAT_SCORE_DOT / _ADDITIVE
 
+    SCORE_V2 = {"gatv2": 2}  # HNH_GAT_SCORE_GATV2 (include/hnh_attn_v2.h); set_score accepts the union of the two tables
+
     ACTIVATION = {"relu": 0, "elu": 1, "identity": 2}  # HNH_GAT_ACT_RELU / _ELU / _IDENTITY
 
     HEADS = {"mean": 0, "concat": 1}  # HNH_GAT_HEADS_MEAN / _CONCAT
@@ -696,7 +698,7 @@ class GAT:
                 self.set_activation(i, a)
 
     def set_dropout(self, attention_p: float, feature_p: float, seed: int = 0):
-        """Dropout rates in [0, 1) on the normalised attention coefficients (score "additive" only) and on every layer's input, with masks
+        """Dropout rates in [0, 1) on the normalised attention coefficients (score "additive" only: not "dot", not "gatv2") and on every layer's input, with masks
         recomputed in every pass from Philox-4x32-10 keyed by (seed, layer, head, global row, global column)
         (include/hnh_attn_dropout.h): they do not depend on the rank count or the schedule's windows.  (0, 0), the default, runs the
         kernels without dropout at their widths.  Invalidates the stored forward pass; forwardPass raises HnhError where a rate is not
@@ -727,11 +729,14 @@ class GAT:
     def set_score(self, mode: str):
         """"dot" (the default: e_ij = LeakyReLU(<A_i, A_j>)) or "additive" (e_ij = LeakyReLU(<A_i, a1> + <A_j, a2>) with the vectors of
         set_attention_vectors, include/hnh_attn_additive.h; attention "softmax" on 15d_fusion2 with c = 1 and heads of at most 256
-        features only, forwardPass / backwardPass raise HnhError elsewhere).  With "additive" there is one backward implementation:
-        set_backward is not consulted.  A change invalidates the stored forward pass."""
-        if mode not in self.SCORE:
-            raise ValueError("score must be one of %s, not %r" % (sorted(self.SCORE), mode))
-        _check(lib().hnh_gat_set_score(self.h, self.SCORE[mode]), "gat_set_score")
+        features only, forwardPass / backwardPass raise HnhError elsewhere), or "gatv2" (Brody, Alon and Yahav's dynamic attention,
+        e_ij = sum_c a_c LeakyReLU(A_ic + A_jc) with ONE vector per head, the a1 of set_attention_vectors, include/hnh_attn_v2.h; supported
+        where "additive" is, without attention dropout).  With "additive" and "gatv2" there is one backward implementation: set_backward
+        is not consulted.  A change invalidates the stored forward pass."""
+        table = dict(self.SCORE, **self.SCORE_V2)
+        if mode not in table:
+            raise ValueError("score must be one of %s, not %r" % (sorted(table), mode))
+        _check(lib().hnh_gat_set_score(self.h, table[mode]), "gat_set_score")
 
     def set_activation(self, layer: int, mode: str):
         """"relu" (the default on every layer: out = max(o, 0)), "elu" (out = o for o > 0, expm1(o) otherwise) or "identity" (out = o) on the
@@ -746,8 +751,8 @@ class GAT:
         _check(lib().hnh_gat_set_activation(self.h, int(layer), self.ACTIVATION[mode]), "gat_set_activation")
 
     def set_attention_vectors(self, layer: int, head: int, a1: np.ndarray, a2: np.ndarray):
-        """The additive score's vectors of (layer, head): features_per_head entries each, zero until set.  Invalidates the stored
-        forward pass like set_weight."""
+        """The additive score's vectors of (layer, head): features_per_head entries each, zero until set.  Score "gatv2" uses a1 as the
+        head's one vector and keeps a2 without reading it.  Invalidates the stored forward pass like set_weight."""
         f = self.layers[layer][1]
         a1 = np.ascontiguousarray(a1, dtype=np.float64)
         a2 = np.ascontiguousarray(a2, dtype=np.float64)
@@ -755,7 +760,8 @@ class GAT:
         _check(lib().hnh_gat_set_attn_vectors(self.h, layer, head, a1.ctypes.data, a2.ctypes.data), "gat_set_attn_vectors")
 
     def attention_grad(self, layer: int, head: int):
-        """(dL/da1, dL/da2) of (layer, head) after backwardPass with score "additive", summed over every rank."""
+        """(dL/da1, dL/da2) of (layer, head) after backwardPass with score "additive", summed over every rank; with score "gatv2"
+        (dL/da, zeros)."""
         f = self.layers[layer][1]
         da1, da2 = np.empty(f), np.empty(f)
         _check(lib().hnh_gat_get_attn_grads(self.h, layer, head, da1.ctypes.data, da2.ctypes.data), "gat_get_attn_grads")

@@ -1,0 +1,587 @@
+// GATv2 dynamic attention scores of the GAT (include/hnh_attn_v2.h): three sibling templates of the row kernel and one dense pass.  Included
+// at the end of hnh_kernels.hip, after hnh_attn_additive_kernels.hpp, whose neighbours' machinery they use as it is (AgUnroll, the hub-row
+// segment scheme with attn_grad_reduce_kernel / attn_grad_zero_rows_kernel, attn_add_empty_rows_kernel, plans, Infinity-Cache panels,
+// hnh_attn_dispatch.hpp) next to the row kernels' transposed butterfly and group broadcast; kept apart from process_row, attn_grad_process
+// and attn_add_process so that none of the existing instances changes by a register.
+//
+//   PASS 0  forward over S:        A_i, a and the row's softmax state in registers; gathers A_j; z = sum_c a_c LReLU(A_ic + A_jc) through a
+//                                  butterfly of U reductions, the online-softmax step of kFusedSoftmax, acc = acc f + p A_j
+//   PASS 1  backward row pass:     A_i, dZ_i, a, lse_i, delta_i in registers; gathers A_j; z and <dZ_i, A_j> through ONE butterfly of 2 U
+//                                  reductions, the gate per lane (one exp per nonzero), acc_c += g sg_c (a select, not an axpy of A_j)
+//   PASS 2  backward column pass:  A_j, a in registers; gathers the packed P_i = [A_i | dZ_i | lse_i delta_i] (hnh_attn_grad.h); z and
+//                                  <A_j, dZ_i> through one butterfly, the gate with the gathered row's scalars, C_c += g sg_c and
+//                                  dAgg += p dZ_i: two accumulators per row, stored to two outputs
+// Lane layout and batches as in attn_grad_process: U nonzeros per batch in one of two register buffers (the next batch's gathers fly
+// while this one is computed), at most 16 gathered doubles per lane and batch.
+#pragma once
+
+namespace {
+
+struct AvArgs {  // hnh_attn_v2 as the kernels take it
+    const double* X;
+    const double* a;
+    const double* dZ;
+    const double* delta;
+    const double* Y;
+    double* lse;
+    double* Out;
+    double* Out2;
+    double* row_max;
+    double* row_sum;
+    double* relu_dst;
+    int64_t ld_x, ld_dz, ld_y, ld_out, ld_out2, relu_ld;
+    int f, fp;  // fp = f rounded up to even: column of the dZ half of a packed row (its two scalars sit at 2 fp)
+    double alpha;
+};
+
+template <int PASS, int LPR, int VEC, int W, bool EXACT>
+__device__ __forceinline__ void attn_v2_process(int64_t row, int beg, int end, const int32_t* __restrict__ colidx, const AvArgs& a, unsigned flags,
+                                                int lig, double* part_row) {
+    constexpr int U = AgUnroll<PASS == 2 ? 1 : 0, LPR, VEC, W>::value;
+    constexpr int H = PASS == 2 ? 2 : 1;    // halves of a gathered row
+    constexpr int NR = PASS == 0 ? U : 2 * U;  // reductions of a batch's butterfly
+    constexpr int SUB = LPR / NR;           // lanes that end up holding the same reduced value
+    static_assert(SUB >= 1, "needs 2 U <= LPR");
+    bool act[VEC];
+    int coff[VEC];
+    unsigned lane_off[VEC];
+#pragma unroll
+    for (int v = 0; v < VEC; v++) {
+        const int c = (v * LPR + lig) * W;
+        act[v] = EXACT ? true : (c < a.f);
+        coff[v] = c;
+        lane_off[v] = (unsigned)c * (unsigned)sizeof(double);
+    }
+    const bool fresh = part_row != nullptr || (flags & HNH_FUSED_OUT_OVERWRITE);
+
+    // x = the own row of A, av = the head's vector (0 beyond f: such a column adds nothing to z), z = dZ_i (row pass),
+    // acc = the softmax accumulator / R / C, acc2 = dAgg (column pass)
+    double x[VEC][W], av[VEC][W], z[PASS == 1 ? VEC : 1][W], acc[VEC][W], acc2[PASS == 2 ? VEC : 1][W];
+#pragma unroll
+    for (int v = 0; v < VEC; v++) {
+#pragma unroll
+        for (int w = 0; w < W; w++) {
+            x[v][w] = 0.0;
+            av[v][w] = 0.0;
+            acc[v][w] = 0.0;
+            if constexpr (PASS == 1) z[v][w] = 0.0;
+            if constexpr (PASS == 2) acc2[v][w] = 0.0;
+        }
+        if (act[v]) {
+            load_w_stream<W>(x[v], a.X + row * a.ld_x + coff[v]);
+            load_w_stream<W>(av[v], a.a + coff[v]);
+            if constexpr (PASS == 1) load_w_stream<W>(z[v], a.dZ + row * a.ld_dz + coff[v]);
+            if (!fresh) {
+                load_w_stream<W>(acc[v], a.Out + row * a.ld_out + coff[v]);
+                if constexpr (PASS == 2) load_w_stream<W>(acc2[v], a.Out2 + row * a.ld_out2 + coff[v]);
+            }
+        }
+    }
+    double lse_i = 0.0, delta_i = 0.0;  // row pass: the own row's scalars
+    if constexpr (PASS == 1) {
+        lse_i = a.lse[row];
+        delta_i = a.delta[row];
+    }
+    double m_run = -__builtin_inf(), l_run = 0.0;  // forward: the row's running max and sum (hnh_attention.h)
+    if constexpr (PASS == 0) {
+        if (!fresh) {
+            m_run = a.row_max[row];
+            l_run = a.row_sum[row];
+        }
+    }
+    const double alpha = a.alpha;
+    const uint64_t g_base = reinterpret_cast<uint64_t>(a.Y);
+    const uint64_t ld_bytes = (uint64_t)a.ld_y * sizeof(double);
+    const unsigned half_bytes = (unsigned)a.fp * (unsigned)sizeof(double);
+
+    struct Batch {
+        double y[U][H][VEC][W];
+        double sc[PASS == 2 ? U : 1][2];  // column pass: lse and delta of the gathered rows
+    };
+
+    auto load_idx = [&](auto full, int e, int (&c)[U]) {
+        constexpr bool FULL = decltype(full)::value;
+        if constexpr (LPR == 64) {
+#pragma unroll
+            for (int u = 0; u < U; u++) c[u] = (FULL || e + u < end) ? colidx[e + u] : -1;
+        } else {
+            const int my = e + (lig % U);
+            const int cv = (FULL || my < end) ? colidx[my] : -1;
+#pragma unroll
+            for (int u = 0; u < U; u++) c[u] = __shfl(cv, u, LPR);
+        }
+    };
+    auto gather = [&](auto full, const int (&c)[U], Batch& b) {
+        constexpr bool FULL = decltype(full)::value;
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const bool live = FULL || c[u] >= 0;
+            uint64_t rowp = g_base + (uint64_t)(unsigned)(live ? c[u] : 0) * ld_bytes;
+            if constexpr (LPR == 64) {  // wave-uniform: SGPR base + VGPR offset
+                const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)rowp);
+                const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)(rowp >> 32));
+                rowp = ((uint64_t)hi << 32) | lo;
+            }
+#pragma unroll
+            for (int h = 0; h < H; h++)
+#pragma unroll
+                for (int v = 0; v < VEC; v++) {
+#pragma unroll
+                    for (int w = 0; w < W; w++) b.y[u][h][v][w] = 0.0;
+                    if (live && act[v]) {
+                        unsigned off = lane_off[v] + (h ? half_bytes : 0u);
+                        if constexpr (LPR == 64) asm volatile("" : "+v"(off));
+                        load_w_global<W>(b.y[u][h][v], rowp, off);
+                    }
+                }
+            if constexpr (PASS == 2) {
+                b.sc[u][0] = 0.0;
+                b.sc[u][1] = 0.0;
+                if (live) load_w_global<2>(b.sc[u], rowp, 2u * half_bytes);  // (16-byte aligned: an even pitch, 2 fp even)
+            }
+        }
+    };
+    // this lane's part of z_ij = sum_c a_c LReLU(A_ic + A_jc) for the gathered row y
+    auto score_part = [&](const double (&y)[VEC][W]) {
+        double sz = 0.0;
+#pragma unroll
+        for (int v = 0; v < VEC; v++)
+#pragma unroll
+            for (int w = 0; w < W; w++) {
+                const double uu = x[v][w] + y[v][w];
+                sz = fma(av[v][w], uu > 0.0 ? uu : uu * alpha, sz);
+            }
+        return sz;
+    };
+    auto compute = [&](auto full, int e, const Batch& b) {
+        constexpr bool FULL = decltype(full)::value;
+        double d[NR];
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            d[u] = score_part(b.y[u][0]);
+            if constexpr (PASS != 0) {
+                double sd = 0.0;
+#pragma unroll
+                for (int v = 0; v < VEC; v++)
+#pragma unroll
+                    for (int w = 0; w < W; w++) sd = fma(PASS == 1 ? z[v][w] : x[v][w], b.y[u][H - 1][v][w], sd);
+                d[U + u] = sd;
+            }
+        }
+        const double r = group_multi_reduce<LPR, NR>(d, lig);  // reduction number lig / SUB
+        const int umine = (lig / SUB) % U;
+        const bool have = FULL || e + umine < end;
+        if constexpr (PASS == 0) {
+            // the online-softmax step of kFusedSoftmax (process_row), nonzero by nonzero in row order
+            const double s = have ? r : -__builtin_inf();
+            double run = m_run, mprev = m_run, mcur = m_run;
+#pragma unroll
+            for (int u = 0; u < U; u++) {
+                const double t = group_bcast<LPR>(s, u * SUB);
+                const double nx = t > run ? t : run;
+                if (umine == u) { mprev = run; mcur = nx; }
+                run = nx;
+            }
+            const double fac = (mcur == mprev) ? 1.0 : (mprev == -__builtin_inf() ? 0.0 : exp(mprev - mcur));
+            const double pw = have ? exp(s - mcur) : 0.0;
+            m_run = run;
+#pragma unroll
+            for (int u = 0; u < U; u++) {
+                const double fu = group_bcast<LPR>(fac, u * SUB);
+                const double pu = group_bcast<LPR>(pw, u * SUB);
+                if (fu != 1.0) {  // the running max rose (uniform over the group)
+#pragma unroll
+                    for (int v = 0; v < VEC; v++)
+#pragma unroll
+                        for (int w = 0; w < W; w++) acc[v][w] *= fu;
+                    l_run *= fu;
+                }
+                l_run += pu;
+#pragma unroll
+                for (int v = 0; v < VEC; v++)
+#pragma unroll
+                    for (int w = 0; w < W; w++) acc[v][w] = fma(pu, b.y[u][0][v][w], acc[v][w]);
+            }
+        } else {
+            // the lower half of the group holds the z's, the upper half the da's of the same nonzeros
+            const double o = shfl_xor_f64(r, LPR / 2);
+            const bool lower = lig < LPR / 2;
+            const double zv = lower ? r : o, da = lower ? o : r;
+            double l = lse_i, dl = delta_i;
+            if constexpr (PASS == 2) {
+#pragma unroll
+                for (int u = 0; u < U; u++)
+                    if (u == umine) {
+                        l = b.sc[u][0];
+                        dl = b.sc[u][1];
+                    }
+            }
+            double wp = exp(zv - l);
+            double wg = wp * (da - dl);
+            if (!have) {
+                wp = 0.0;
+                wg = 0.0;
+            }
+#pragma unroll
+            for (int u = 0; u < U; u++) {
+                const double gu = group_bcast<LPR>(wg, u * SUB);
+                const double ga = gu * alpha;
+#pragma unroll
+                for (int v = 0; v < VEC; v++)
+#pragma unroll
+                    for (int w = 0; w < W; w++) acc[v][w] += (x[v][w] + b.y[u][0][v][w] > 0.0) ? gu : ga;
+                if constexpr (PASS == 2) {
+                    const double pu = group_bcast<LPR>(wp, u * SUB);
+#pragma unroll
+                    for (int v = 0; v < VEC; v++)
+#pragma unroll
+                        for (int w = 0; w < W; w++) acc2[v][w] = fma(pu, b.y[u][H - 1][v][w], acc2[v][w]);
+                }
+            }
+        }
+        // pin the accumulation here (as process_row does): sunk to the end of the trip it would keep both gather buffers alive
+#pragma unroll
+        for (int v = 0; v < VEC; v++)
+#pragma unroll
+            for (int w = 0; w < W; w++) {
+                asm volatile("" : "+v"(acc[v][w]));
+                if constexpr (PASS == 2) asm volatile("" : "+v"(acc2[v][w]));
+            }
+    };
+    const BoolTag<true> kFull;
+    const BoolTag<false> kMasked;
+
+    int e = beg;
+    Batch ba, bb;
+    if (e + U <= end) {
+        int c0[U], c1[U];
+        load_idx(kFull, e, c0);
+        gather(kFull, c0, ba);
+        for (;;) {
+            const bool more = e + 2 * U <= end;
+            if (more) {  // the next batch's gathers fly while this one is computed
+                load_idx(kFull, e + U, c1);
+                gather(kFull, c1, bb);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            compute(kFull, e, ba);
+            __builtin_amdgcn_sched_barrier(0);
+            e += U;
+            if (!more) break;
+            const bool more2 = e + 2 * U <= end;
+            if (more2) {
+                load_idx(kFull, e + U, c0);
+                gather(kFull, c0, ba);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            compute(kFull, e, bb);
+            __builtin_amdgcn_sched_barrier(0);
+            e += U;
+            if (!more2) break;
+        }
+    }
+    if (e < end) {  // fewer than U nonzeros left: one masked batch
+        int c0[U];
+        load_idx(kMasked, e, c0);
+        gather(kMasked, c0, ba);
+        compute(kMasked, e, ba);
+    }
+
+    if constexpr (PASS == 0) {
+        // the row's state leaves with every launch, as in process_row
+        if (lig == 0) {
+            a.row_max[row] = m_run;
+            a.row_sum[row] = l_run;
+        }
+        if (flags & kInternalEpilogue) {  // finish: o = acc / l through the activation into the head's column block, and lse; Out is scratch
+            const bool live = l_run > 0.0;
+            if (flags & kAttnActMask) {  // ELU / identity in the ReLU's place (wave-uniform)
+#pragma unroll
+                for (int v = 0; v < VEC; v++) {
+                    double o[W];
+#pragma unroll
+                    for (int w = 0; w < W; w++) o[w] = live ? attn_out_act(acc[v][w] / l_run, flags) : 0.0;
+                    if (act[v]) store_w_stream<W>(a.relu_dst + row * a.relu_ld + coff[v], o);
+                }
+            } else {
+#pragma unroll
+                for (int v = 0; v < VEC; v++) {
+                    double o[W];
+#pragma unroll
+                    for (int w = 0; w < W; w++) o[w] = live ? fmax(acc[v][w] / l_run, 0.0) : 0.0;
+                    if (act[v]) store_w_stream<W>(a.relu_dst + row * a.relu_ld + coff[v], o);
+                }
+            }
+            if (lig == 0) a.lse[row] = live ? m_run + log(l_run) : 0.0;
+            return;
+        }
+    }
+#pragma unroll
+    for (int v = 0; v < VEC; v++) {
+        if (!act[v]) continue;
+        if (part_row != nullptr) {  // a hub row's segment [C (0) | dAgg] (or R alone): added up in order afterwards
+            store_w_stream<W>(part_row + coff[v], acc[v]);
+            if constexpr (PASS == 2) store_w_stream<W>(part_row + a.fp + coff[v], acc2[v]);
+        } else {
+            store_w_stream<W>(a.Out + row * a.ld_out + coff[v], acc[v]);
+            if constexpr (PASS == 2) store_w_stream<W>(a.Out2 + row * a.ld_out2 + coff[v], acc2[v]);
+        }
+    }
+}
+
+template <int PASS, int LPR, int VEC, int W, bool EXACT>
+__global__ __launch_bounds__(kBlock) void attn_v2_row_kernel(int64_t rows, const int32_t* __restrict__ rowptr, const int32_t* __restrict__ beg_ptr,
+                                                             const int32_t* __restrict__ end_ptr, const int32_t* __restrict__ colidx, AvArgs a,
+                                                             unsigned flags) {
+    constexpr int GROUPS = kBlock / LPR;
+    const int tid = threadIdx.x;
+    const int lig = tid % LPR;
+    int64_t row = (int64_t)blockIdx.x * GROUPS + tid / LPR;
+    if constexpr (LPR == 64) row = ((int64_t)blockIdx.x * GROUPS) + __builtin_amdgcn_readfirstlane(tid >> 6);
+    if (row >= rows) return;
+    int beg = beg_ptr[row];
+    int end = end_ptr[row];
+    if constexpr (LPR == 64) {
+        beg = __builtin_amdgcn_readfirstlane(beg);
+        end = __builtin_amdgcn_readfirstlane(end);
+    }
+    if constexpr (PASS != 0) {  // (the forward pass walks hub rows whole and visits every row: the reset and the finish apply to empty pieces too)
+        if (flags & kInternalSplitLong) {  // hub rows go to the segment kernel, whose sums are ADDED to the row (as in row_kernel)
+            int full = rowptr[row + 1] - rowptr[row];
+            if constexpr (LPR == 64) full = __builtin_amdgcn_readfirstlane(full);
+            if (full > long_row_of(flags)) {
+                if (flags & HNH_FUSED_OUT_OVERWRITE) end = beg;  // an overwritten row has to start from zero
+                else return;
+            }
+        }
+        if (beg == end && !(flags & HNH_FUSED_OUT_OVERWRITE)) return;  // nothing to add
+    }
+    attn_v2_process<PASS, LPR, VEC, W, EXACT>(row, beg, end, colidx, a, flags, lig, nullptr);
+}
+
+// one work item = kLongSeg consecutive nonzeros of a hub row (the row kernels' work list); every segment writes its partial row.  One group per
+// item over a grid that covers the list's capacity, not a grid-stride loop as in attn_grad_long_kernel: the loop keeps every kernel argument
+// alive across the row's walk, which is more wave-uniform values than the bounds-checked row-pass instances have scalar registers for
+template <int PASS, int LPR, int VEC, int W, bool EXACT>
+__global__ __launch_bounds__(kBlock) void attn_v2_long_kernel(const int2* __restrict__ items, const int* __restrict__ item_count, int capacity,
+                                                              const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colidx, AvArgs a,
+                                                              double* partials, int64_t pitch) {
+    constexpr int GROUPS = kBlock / LPR;
+    const int tid = threadIdx.x;
+    const int lig = tid % LPR;
+    int count = *item_count;
+    if (count > capacity) count = capacity;
+    int it = (int)blockIdx.x * GROUPS + tid / LPR;
+    if constexpr (LPR == 64) it = __builtin_amdgcn_readfirstlane(it);
+    if (it >= count) return;
+    const int2 item = items[it];
+    int rbeg = rowptr[item.x], rend = rowptr[item.x + 1], seg = item.y;
+    int64_t row = item.x;
+    if constexpr (LPR == 64) {
+        rbeg = __builtin_amdgcn_readfirstlane(rbeg);
+        rend = __builtin_amdgcn_readfirstlane(rend);
+        seg = __builtin_amdgcn_readfirstlane(seg);
+        row = __builtin_amdgcn_readfirstlane(item.x);
+    }
+    const int beg = rbeg + seg * kLongSeg;
+    const int end = (beg + kLongSeg < rend) ? beg + kLongSeg : rend;
+    attn_v2_process<PASS, LPR, VEC, W, EXACT>(row, beg, end, colidx, a, HNH_FUSED_OUT_OVERWRITE, lig, partials + (int64_t)it * pitch);
+}
+
+// The dense pass of a head.  A workgroup is kBlock / TPR row lanes of TPR column threads; row lane q of workgroup b takes the rows
+// b RL + q, + gridDim.x RL, ..: dA = dAgg + (R + C) a, and its column sums of A (R + C) in that order into partial row b RL + q.
+__global__ __launch_bounds__(kBlock) void attn_v2_finish_rows_kernel(double* __restrict__ dA, int64_t ld_da, int64_t col0, const double* __restrict__ dAgg,
+                                                                     int64_t ld_g, const double* __restrict__ Rm, int64_t ld_r,
+                                                                     const double* __restrict__ Cm, int64_t ld_c, const double* __restrict__ A, int64_t ld_a,
+                                                                     const double* __restrict__ av, int64_t rows, int f, int tpr, double* __restrict__ work) {
+    const int rl = kBlock / tpr;
+    const int c = (int)threadIdx.x % tpr, q = (int)threadIdx.x / tpr;
+    if (c >= f) return;
+    const double ac = av[c];
+    const int64_t step = (int64_t)gridDim.x * rl;
+    double s = 0.0;
+#pragma unroll 4
+    for (int64_t r = (int64_t)blockIdx.x * rl + q; r < rows; r += step) {
+        const double t = Rm[r * ld_r + c] + Cm[r * ld_c + c];
+        dA[r * ld_da + col0 + c] = fma(t, ac, dAgg[r * ld_g + c]);
+        s = fma(A[r * ld_a + c], t, s);
+    }
+    work[((int64_t)blockIdx.x * rl + q) * f + c] = s;
+}
+
+// da[c] = the `parts` partial rows in a fixed order: thread (k, c) adds partials k, k + K, .. and the K threads of a column are added front to back
+__global__ __launch_bounds__(kBlock) void attn_v2_finish_sum_kernel(double* __restrict__ da, int64_t ld_dav, const double* __restrict__ work, int parts, int f,
+                                                                    int tpr) {
+    __shared__ double s[kBlock];
+    const int K = kBlock / tpr;
+    const int c = (int)threadIdx.x % tpr, k = (int)threadIdx.x / tpr;
+    double acc = 0.0;
+    if (c < f)
+        for (int p = k; p < parts; p += K) acc += work[(int64_t)p * f + c];
+    s[threadIdx.x] = acc;
+    __syncthreads();
+    if (k == 0 && c < f) {
+        double t = 0.0;
+        for (int j = 0; j < K; j++) t += s[j * tpr + c];
+        da[(int64_t)c * ld_dav] = t;
+    }
+}
+
+template <int PASS, int LPR, int VEC, int W, bool EXACT>
+int attn_v2_launch(hnh_ctx* ctx, hipStream_t st, const LongCtl& lc, int64_t rows, const int32_t* rowptr, const int32_t* beg_ptr, const int32_t* end_ptr,
+                   const int32_t* colidx, const AvArgs& a, unsigned flags, bool run_long) {
+    constexpr int GROUPS = kBlock / LPR;
+    const int64_t blocks = (rows + GROUPS - 1) / GROUPS;
+    if (blocks <= 0) return HNH_OK;
+    if (blocks > 0x7fffffffLL) return hnh::fail(ctx, HNH_ERR_UNSUPPORTED, "too many rows for one launch");
+    if (lc.enabled) flags |= kInternalSplitLong | ((unsigned)(lc.threshold / 64) << kLongRowShift);
+    const size_t lds_pad = lc.lds_pad <= 48 * 1024 ? lc.lds_pad : 0;
+    hipLaunchKernelGGL((attn_v2_row_kernel<PASS, LPR, VEC, W, EXACT>), dim3((unsigned)blocks), dim3(kBlock), lds_pad, st, rows, rowptr, beg_ptr, end_ptr,
+                       colidx, a, flags);
+    if (int rc = hnh::check_hip(ctx, hipGetLastError(), "attn_v2_row_kernel launch")) return rc;
+    if constexpr (PASS != 0) {
+        if (lc.enabled && run_long) {  // hub rows once per pass, over their whole length: segments, then the ordered sums
+            const int64_t pitch = PASS == 2 ? 2 * a.fp : a.f;
+            const int seg_blocks = (lc.capacity + GROUPS - 1) / GROUPS;  // one group per item of the list
+            hipLaunchKernelGGL((attn_v2_long_kernel<PASS, LPR, VEC, W, EXACT>), dim3((unsigned)(seg_blocks > 0 ? seg_blocks : 1)), dim3(kBlock), 0, st,
+                               lc.items, lc.count, lc.capacity, rowptr, colidx, a, lc.partials, pitch);
+            if (int rc = hnh::check_hip(ctx, hipGetLastError(), "attn_v2_long_kernel launch")) return rc;
+            hipLaunchKernelGGL(attn_grad_reduce_kernel, dim3(2048), dim3(kBlock), 0, st, lc.hub_rows, lc.count, lc.capacity_rows, lc.partials, pitch, a.Out,
+                               a.ld_out, a.f);
+            if (int rc = hnh::check_hip(ctx, hipGetLastError(), "attn_grad_reduce_kernel launch")) return rc;
+            if (PASS == 2) {
+                hipLaunchKernelGGL(attn_grad_reduce_kernel, dim3(2048), dim3(kBlock), 0, st, lc.hub_rows, lc.count, lc.capacity_rows, lc.partials + a.fp,
+                                   pitch, a.Out2, a.ld_out2, a.f);
+                return hnh::check_hip(ctx, hipGetLastError(), "attn_grad_reduce_kernel launch");
+            }
+        }
+    }
+    return HNH_OK;
+}
+
+template <int PASS>
+int attn_v2_dispatch(hnh_ctx* ctx, const hnh_csr_block* b, const hnh_attn_v2* g, unsigned flags, const hnh_csr_window* win, int stream,
+                     const char* who) {
+    HNH_ENTER(ctx, stream);
+    if (!b || !g) return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": null block or arguments");
+    if (int rc = check_common(ctx, b->rows, g->f, who)) return rc;
+    if (flags & ~(HNH_FUSED_OUT_OVERWRITE | (PASS == 0 ? (HNH_ATTN_FINISH | kAttnActMask) : 0u)))
+        return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": unknown flag");
+    if (int rc = check_attn_act_flags(ctx, flags, who)) return rc;
+    if (g->f > HNH_ATTN_V2_MAX_F)
+        return hnh::fail(ctx, HNH_ERR_UNSUPPORTED, std::string(who) + ": head width " + std::to_string(g->f) + " beyond the limit of " +
+                                                       std::to_string(HNH_ATTN_V2_MAX_F) + " (HNH_ATTN_V2_MAX_F)");
+    const bool finish = PASS == 0 && (flags & HNH_ATTN_FINISH) != 0;
+    if (finish && win != nullptr && !win->last) return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": the finish belongs to the last window");
+    if (b->rows == 0) return HNH_OK;
+    const int f = g->f, fp = f + (f & 1);
+    if (!g->Out || g->ld_out < f) return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": bad output");
+    if (PASS == 2 && (!g->Out2 || g->ld_out2 < f || g->Out2 == g->Out)) return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": bad second output");
+    if (PASS == 0 && (!g->row_max || !g->row_sum || !g->lse || !g->relu_dst || g->relu_ld < f))
+        return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": bad row state");
+    AvArgs a;
+    a.X = g->X; a.a = g->a; a.dZ = g->dZ; a.delta = g->delta; a.Y = g->Y; a.lse = g->lse; a.Out = g->Out; a.Out2 = g->Out2;
+    a.row_max = g->row_max; a.row_sum = g->row_sum; a.relu_dst = g->relu_dst;
+    a.ld_x = g->ld_x; a.ld_dz = g->ld_dz; a.ld_y = g->ld_y; a.ld_out = g->ld_out; a.ld_out2 = g->ld_out2; a.relu_ld = g->relu_ld;
+    a.f = f; a.fp = fp; a.alpha = g->leaky_alpha;
+    hipStream_t st = ctx->streams[stream];
+    const unsigned kflags = (flags & (HNH_FUSED_OUT_OVERWRITE | kAttnActMask)) | (finish ? kInternalEpilogue : 0u);
+    if (b->rowptr == nullptr) {  // a block without nonzeros
+        if (b->nnz > 0) return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": null rowptr");
+        if (PASS == 0) {  // the state reset and the finish of a row whose piece is empty: the additive forward's kernel does exactly that
+            if (!kflags) return HNH_OK;
+            AaArgs e = {};
+            e.lse = g->lse; e.Out = g->Out; e.row_max = g->row_max; e.row_sum = g->row_sum; e.relu_dst = g->relu_dst;
+            e.ld_out = g->ld_out; e.relu_ld = g->relu_ld; e.f = f; e.fp = fp; e.alpha = g->leaky_alpha;
+            const dim3 grid((unsigned)((b->rows * 64 + kBlock - 1) / kBlock));
+            if (kflags & kAttnActMask) hipLaunchKernelGGL(attn_add_empty_rows_kernel<true>, grid, dim3(kBlock), 0, st, b->rows, e, kflags);
+            else hipLaunchKernelGGL(attn_add_empty_rows_kernel<false>, grid, dim3(kBlock), 0, st, b->rows, e, kflags);
+            return hnh::check_hip(ctx, hipGetLastError(), "attn_add_empty_rows_kernel launch");
+        }
+        if (!(flags & HNH_FUSED_OUT_OVERWRITE)) return HNH_OK;
+        hipLaunchKernelGGL(attn_grad_zero_rows_kernel, dim3(ew_grid(b->rows * f)), dim3(kBlock), 0, st, g->Out, g->ld_out, b->rows, f);
+        if (int rc = hnh::check_hip(ctx, hipGetLastError(), "attn_grad_zero_rows_kernel launch")) return rc;
+        if (PASS == 2) {
+            hipLaunchKernelGGL(attn_grad_zero_rows_kernel, dim3(ew_grid(b->rows * f)), dim3(kBlock), 0, st, g->Out2, g->ld_out2, b->rows, f);
+            return hnh::check_hip(ctx, hipGetLastError(), "attn_grad_zero_rows_kernel launch");
+        }
+        return HNH_OK;
+    }
+    if (!b->col_idx || !g->X || !g->Y || !g->a) return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": null pointer");
+    if (g->ld_x < f) return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": ld_x is narrower than f");
+    if ((const double*)g->Out == g->X || (const double*)g->Out == g->Y || (PASS == 2 && ((const double*)g->Out2 == g->X || (const double*)g->Out2 == g->Y)))
+        return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": an output aliases an input");
+    bool w2 = f % 2 == 0 && aligned16(g->X) && g->ld_x % 2 == 0 && aligned16(g->a) && aligned16(g->Y) && g->ld_y % 2 == 0 && aligned16(g->Out) &&
+              g->ld_out % 2 == 0;
+    const int gather_w = PASS == 2 ? HNH_ATTN_GRAD_PACKED_WIDTH(f, 1) : f;
+    if (PASS == 2) {
+        // the packed operand (hnh_attn_grad.h): an even pitch and a 16-byte aligned base, whatever f is
+        if (g->ld_y < gather_w || g->ld_y % 2 != 0 || !aligned16(g->Y))
+            return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": the packed operand needs an even pitch of at least " + std::to_string(gather_w) +
+                                                       " and a 16-byte aligned base");
+        w2 = w2 && aligned16(g->Out2) && g->ld_out2 % 2 == 0;
+    } else if (g->ld_y < f) {
+        return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": ld_y is narrower than f");
+    }
+    if (PASS == 0) w2 = w2 && aligned16(g->relu_dst) && g->relu_ld % 2 == 0;
+    if (PASS == 1) {
+        if (!g->dZ || g->ld_dz < f || !g->lse || !g->delta) return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": bad dZ, lse or delta");
+        if ((const double*)g->Out == g->dZ) return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": an output aliases an input");
+        w2 = w2 && aligned16(g->dZ) && g->ld_dz % 2 == 0;
+    }
+
+    auto launch = [&](const LongCtl& lc, const int32_t* beg_ptr, const int32_t* end_ptr, unsigned fl, bool run_long) {
+        return attn_launch_shape(f, w2, [&](auto l, auto v, auto w, auto ex) {
+            return attn_v2_launch<PASS, decltype(l)::value, decltype(v)::value, decltype(w)::value, decltype(ex)::value>(
+                ctx, st, lc, b->rows, b->rowptr, beg_ptr, end_ptr, b->col_idx, a, fl, run_long);
+        });
+    };
+    // a segment's partial result: R alone or [C (0) | dAgg]; none for the forward pass, which walks hub rows whole
+    return attn_dispatch_tail(ctx, st, stream, b, win, f, w2, PASS == 0 ? 0 : (PASS == 2 ? 2 * fp : f), gather_w, kflags, who, launch);
+}
+
+}  // namespace
+
+extern "C" {
+
+int hnh_attn_v2_fwd_csr_p(hnh_ctx* ctx, const hnh_csr_block* b, const hnh_attn_v2* args, unsigned flags, const hnh_csr_window* window, int stream) {
+    return attn_v2_dispatch<0>(ctx, b, args, flags, window, stream, "hnh_attn_v2_fwd_csr_p");
+}
+
+int hnh_attn_v2_row_csr_p(hnh_ctx* ctx, const hnh_csr_block* b, const hnh_attn_v2* args, unsigned flags, const hnh_csr_window* window, int stream) {
+    return attn_v2_dispatch<1>(ctx, b, args, flags, window, stream, "hnh_attn_v2_row_csr_p");
+}
+
+int hnh_attn_v2_col_csr_p(hnh_ctx* ctx, const hnh_csr_block* b, const hnh_attn_v2* args, unsigned flags, const hnh_csr_window* window, int stream) {
+    return attn_v2_dispatch<2>(ctx, b, args, flags, window, stream, "hnh_attn_v2_col_csr_p");
+}
+
+int hnh_attn_v2_finish_f64(hnh_ctx* ctx, double* dA, int64_t ld_da, int64_t col0, const double* dAgg, int64_t ld_g, const double* Rm, int64_t ld_r,
+                           const double* Cm, int64_t ld_c, const double* A, int64_t ld_a, const double* a, double* da, int64_t ld_dav, int64_t rows,
+                           int f, double* work, int64_t work_doubles, int stream) {
+    HNH_ENTER(ctx, stream);
+    if (int rc = check_common(ctx, rows, f, "hnh_attn_v2_finish_f64")) return rc;
+    if (f > HNH_ATTN_V2_MAX_F)
+        return hnh::fail(ctx, HNH_ERR_UNSUPPORTED, "hnh_attn_v2_finish_f64: head width " + std::to_string(f) + " beyond the limit of " +
+                                                       std::to_string(HNH_ATTN_V2_MAX_F) + " (HNH_ATTN_V2_MAX_F)");
+    if (col0 < 0 || ld_da < col0 + f || ld_g < f || ld_r < f || ld_c < f || ld_a < f || ld_dav < 1)
+        return hnh::fail(ctx, HNH_ERR_INVALID, "hnh_attn_v2_finish_f64: bad pitch");
+    if (!da || !work || work_doubles < HNH_ATTN_V2_FINISH_WORK(f)) return hnh::fail(ctx, HNH_ERR_INVALID, "hnh_attn_v2_finish_f64: null result or short workspace");
+    if (rows > 0 && (!dA || !dAgg || !Rm || !Cm || !A || !a)) return hnh::fail(ctx, HNH_ERR_INVALID, "hnh_attn_v2_finish_f64: null pointer");
+    if (rows > 0 && (dA == dAgg || dA == Rm || dA == Cm || dA == A))
+        return hnh::fail(ctx, HNH_ERR_INVALID, "hnh_attn_v2_finish_f64: dA aliases an input");
+    int tpr = 1;
+    while (tpr < f) tpr *= 2;  // (<= 256 = kBlock)
+    const int rl = kBlock / tpr;
+    int64_t blocks = (rows + rl - 1) / rl;
+    if (blocks > 1024 / rl) blocks = 1024 / rl;  // at most 1024 partial rows: HNH_ATTN_V2_FINISH_WORK
+    if (blocks < 1) blocks = 1;
+    hipStream_t st = ctx->streams[stream];
+    hipLaunchKernelGGL(attn_v2_finish_rows_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, st, dA, ld_da, col0, dAgg, ld_g, Rm, ld_r, Cm, ld_c, A, ld_a, a,
+                       rows, f, tpr, work);
+    if (int rc = hnh::check_hip(ctx, hipGetLastError(), "attn_v2_finish_rows_kernel launch")) return rc;
+    hipLaunchKernelGGL(attn_v2_finish_sum_kernel, dim3(1), dim3(kBlock), 0, st, da, ld_dav, work, (int)(blocks * rl), f, tpr);
+    return hnh::check_hip(ctx, hipGetLastError(), "attn_v2_finish_sum_kernel launch");
+}
+
+}  // extern "C"

@@ -31,6 +31,7 @@
 #include "hnh_attn_grad.h"
 #include "hnh_attn_additive.h"
 #include "hnh_attn_dropout.h"
+#include "hnh_attn_v2.h"
 
 namespace {
 
@@ -2813,3 +2814,6 @@ int hnh_rowdot_cols_f64(hnh_ctx* ctx, double* out, const double* dZ, int64_t ld_
 
 // ---------------------------------------------------------------- GAT dropout (include/hnh_attn_dropout.h)
 #include "hnh_attn_dropout_kernels.hpp"
+
+// ---------------------------------------------------------------- GATv2 attention scores (include/hnh_attn_v2.h)
+#include "hnh_attn_v2_kernels.hpp"

@@ -793,7 +793,7 @@ int hnh_gat_get_attn_grads(hnh_gat* g, int layer, int head, double* da1_host, do
         const GATLayer& l = gat.layers.at(layer);
         if (head < 0 || head >= l.num_heads) throw hnh::Error("Error, GAT head index out of range!");
         if (gat.attn_grads.size() != gat.layers.size() || gat.attn_grads[(size_t)layer].size() == 0)
-            throw hnh::Error("Error, no GAT attention-vector gradient yet: call hnh_gat_backward with score additive first!");
+            throw hnh::Error("Error, no GAT attention-vector gradient yet: call hnh_gat_backward with score additive or gatv2 first!");
         const std::vector<double> all = gat.attn_grads[(size_t)layer].to_host();  // (heads * f) x 2
         const int64_t f = l.features_per_head;
         for (int64_t c = 0; c < f; c++) {

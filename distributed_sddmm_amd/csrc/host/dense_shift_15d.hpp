@@ -339,6 +339,23 @@ public:
         return true;
     }
 
+    // One pass of the GATv2 attention (include/hnh_attn_v2.h): pass 0 = the forward pass over S (`moving` = the head's product A), 1 = the
+    // backward row pass over S (A again), 2 = the backward column pass over S^T (`moving` = the packed operand of include/hnh_attn_grad.h).
+    // Everything as for attnAdditive_pass: the schedule's R must be the MOVING operand's width, the forward pass makes its first and its
+    // closing call also for an absent block, `finish_flags` go to the closing call alone.  Returns false, having done nothing, where a
+    // rank's own launches do not see all of a row's nonzeros.  Not a virtual of Distributed_Sparse, for fusedSoftmax_out's reason.
+    bool attnV2_pass(int pass, DenseMatrix& moving, const hnh_attn_v2& args, int64_t out_rows, bool overwrite, unsigned finish_flags = 0u) {
+        if (fusionApproach != 2 || c != 1) return false;
+        if (pass < 0 || pass > 2) hnh::fatal("Error, attnV2_pass: unknown pass!");
+        if (moving.cols() != R) hnh::fatal("Error, attnV2_pass: the schedule's R must be the moving operand's width!");
+        attn_walk(pass == 2 ? ST.get() : S.get(), moving, args, overwrite, pass == 0,
+                  "Error, the kernel implementation has no gatv2 attention pass (KernelImplementation::attn_v2_local)!",
+                  [&](SpmatLocal& choice, int block_id, const hnh_attn_v2& a, unsigned flags, bool finish) {
+                      return kernel->attn_v2_local(choice, block_id, a, pass, flags | (finish ? finish_flags : 0u), out_rows, finish);
+                  });
+        return true;
+    }
+
 private:
     // ---- merged layout helpers
     // visiting step of global block column b on this rank (block_at(k) == b), or -1 when the rank never visits it

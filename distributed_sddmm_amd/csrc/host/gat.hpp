@@ -52,6 +52,17 @@
 // Supported where the softmax is (15d_fusion2 with c = 1, attention softmax) with heads of at most HNH_ATTN_ADD_MAX_F features; everything
 // else raises before anything is launched.  With score ADDITIVE there is ONE backward implementation: set_backward is not consulted.
 //
+// HNH_GAT_SCORE_GATV2 (an addition; include/hnh_attn_v2.h) is Brody, Alon and Yahav's dynamic attention with shared weights: ONE learned vector
+// per head (the slice [h f, (h + 1) f) of GATLayer::a1; a2 is kept and not used), the nonlinearity inside the contraction and none outside:
+//     u_ijc = A_ic + A_jc,  sg_ijc = u_ijc > 0 ? 1 : alpha,  z_ij = sum_c a_c sg_ijc u_ijc,  then the neighbourhood softmax as above.
+// Forward: one pass on the plain product A through the two-stream head pipeline of score DOT (no scored operand).  Backward, with dZ and delta
+// as above and g_ij = p_ij (<dZ_i, A_j> - delta_i):
+//     R_ic = sum_j g_ij sg_ijc  (row pass over S),  C_jc = sum_i g_ij sg_ijc,  dAgg_j = sum_i p_ij dZ_i  (column pass over S^T, gathering the
+//     packed P_i = [A_i | dZ_i | lse_i delta_i] of the fused backward),  T = R + C,  dA = dAgg + T o a,  da_c = sum_r A_rc T_rc
+// (LReLU(u) = sg (A_ic + A_jc), so sum_ij g sg u splits into the two sides: the gradient of a is one dense column sum, in the finishing pass).
+// attn_grads keeps its (H f) x 2 shape: column 0 = da, column 1 = zeros.  Supported where score ADDITIVE is, without attention dropout; one
+// backward implementation.
+//
 // Dropout (an addition; set_dropout(attention_p, feature_p, seed), both rates 0 by default, which launches exactly the kernels above at
 // their widths).  The masks are never stored: every pass recomputes them from Philox-4x32-10 keyed by (seed, layer, head, global row,
 // global column) (include/hnh_attn_dropout.h), so they do not depend on the rank count, windows, panels or hub-row segments, and the
@@ -147,11 +158,11 @@ public:
         attention_ = mode;
     }
 
-    // HNH_GAT_SCORE_DOT | HNH_GAT_SCORE_ADDITIVE (include/hnh_dist.h); a change invalidates the stored forward pass
+    // HNH_GAT_SCORE_DOT | HNH_GAT_SCORE_ADDITIVE | HNH_GAT_SCORE_GATV2 (include/hnh_dist.h); a change invalidates the stored forward pass
     int score() const { return score_; }
     void set_score(int mode) {
-        if (mode != HNH_GAT_SCORE_DOT && mode != HNH_GAT_SCORE_ADDITIVE)
-            throw hnh::Error("Error, unknown GAT score " + std::to_string(mode) + " (dot = 0, additive = 1)!");
+        if (mode != HNH_GAT_SCORE_DOT && mode != HNH_GAT_SCORE_ADDITIVE && mode != HNH_GAT_SCORE_GATV2)
+            throw hnh::Error("Error, unknown GAT score " + std::to_string(mode) + " (dot = 0, additive = 1, gatv2 = 2)!");
         if (mode != score_) invalidate_forward();
         score_ = mode;
     }
@@ -190,7 +201,7 @@ public:
     }
 
     // The additive score's vectors of a layer (GATLayer::a1 / a2: num_heads * features_per_head entries each, zero until set; head h
-    // uses the slice [h f, (h + 1) f)), allocated on first use.
+    // uses the slice [h f, (h + 1) f)), allocated on first use.  Score GATV2 reads a1 alone.
     void ensure_attn_vectors(int i) {
         GATLayer& L = layers.at((size_t)i);
         const int64_t n = (int64_t)L.num_heads * L.features_per_head;
@@ -237,14 +248,14 @@ public:
     // between two product buffers; the layers' outputs are the reference's, bit for bit (same kernels, same operands).
     // HNH_GAT_SERIAL=1: the reference's order on one stream (A/B measurements).
     void forwardPass() {
-        const bool additive = score_ == HNH_GAT_SCORE_ADDITIVE;
+        const bool additive = score_ == HNH_GAT_SCORE_ADDITIVE, gatv2 = score_ == HNH_GAT_SCORE_GATV2;
         check_dropout_supported();
         check_activation_supported();
-        if (attention_ == HNH_GAT_ATTENTION_SOFTMAX && !additive) check_softmax_supported();
-        if (additive) {
-            check_additive_supported();
+        if (attention_ == HNH_GAT_ATTENTION_SOFTMAX && !additive && !gatv2) check_softmax_supported();
+        if (additive) check_additive_supported();
+        if (gatv2) check_gatv2_supported();
+        if (additive || gatv2)
             for (size_t i = 0; i < layers.size(); i++) ensure_attn_vectors((int)i);  // (on the compute stream, before the marks below)
-        }
         if (std::getenv("HNH_GAT_SERIAL") != nullptr) {
             for (size_t i = 0; i < layers.size(); i++)
                 for (int j = 0; j < layers[i].num_heads; j++) computeSelfAttentionHead((int)i, j);
@@ -303,7 +314,7 @@ public:
             weight_grads.assign((size_t)L, DenseMatrix());
             input_grads.assign((size_t)L, DenseMatrix());
         }
-        if (score_ == HNH_GAT_SCORE_ADDITIVE && (int)attn_grads.size() != L) attn_grads.assign((size_t)L, DenseMatrix());
+        if (learns_vectors() && (int)attn_grads.size() != L) attn_grads.assign((size_t)L, DenseMatrix());
         const DenseMatrix* G = &grad_out;
         for (int i = L - 1; i >= 0; i--) {
             backward_layer(i, *G);
@@ -391,14 +402,14 @@ public:
     }
     int64_t optimizer_steps() const { return optim_steps_; }
 
-    // One optimizer step from the gradients of the last backwardPass: every W, and a1, a2 with score ADDITIVE, in one table.  Invalidates
+    // One optimizer step from the gradients of the last backwardPass: every W, and a1, a2 with score ADDITIVE (a1 with GATV2), in one table.  Invalidates
     // the stored forward pass.  No host synchronisation.
     void optimizer_step() {
         const hnh::Backend* be = d_ops->world->be;
         if (!optimizer_set_) throw hnh::Error("Error, GAT optimizer_step needs set_optimizer first!");
         require_kernels("training", "include/hnh_train.h", {HNH_GAT_KERNEL(hnh_optim_step_f64)});
-        const bool additive = score_ == HNH_GAT_SCORE_ADDITIVE;
-        if (!grads_fresh_ || weight_grads.size() != layers.size() || (additive && attn_grads.size() != layers.size()))
+        const bool additive = score_ == HNH_GAT_SCORE_ADDITIVE, gatv2 = score_ == HNH_GAT_SCORE_GATV2;
+        if (!grads_fresh_ || weight_grads.size() != layers.size() || ((additive || gatv2) && attn_grads.size() != layers.size()))
             throw hnh::Error("Error, GAT optimizer_step needs the gradients of a backwardPass since the last step!");
         std::vector<hnh_optim_tensor> table;
         for (size_t i = 0; i < layers.size(); i++) {
@@ -410,12 +421,12 @@ public:
                 if (dW.rows() != W.rows() || dW.cols() != hf || W.cols() != f) throw hnh::Error("Error, GAT optimizer_step: a weight gradient has the wrong shape!");
                 table.push_back({W.data(), f, dW.data() + (int64_t)h * f, hf, mom_w_[i][(size_t)h].data(), var_w_[i][(size_t)h].data(), W.rows(), f});
             }
-            if (additive) {
+            if (additive || gatv2) {
                 ensure_attn_vectors((int)i);
-                const DenseMatrix& da = attn_grads[i];  // (hf x 2: da1 and da2 interleaved)
+                const DenseMatrix& da = attn_grads[i];  // (hf x 2: da1 and da2 interleaved; score GATV2: da and zeros)
                 if (da.rows() != hf || da.cols() != 2) throw hnh::Error("Error, GAT optimizer_step: an attention-vector gradient has the wrong shape!");
                 table.push_back({L.a1.data(), 1, da.data(), 2, mom_a_[i * 2].data(), var_a_[i * 2].data(), hf, 1});
-                table.push_back({L.a2.data(), 1, da.data() + 1, 2, mom_a_[i * 2 + 1].data(), var_a_[i * 2 + 1].data(), hf, 1});
+                if (additive) table.push_back({L.a2.data(), 1, da.data() + 1, 2, mom_a_[i * 2 + 1].data(), var_a_[i * 2 + 1].data(), hf, 1});  // (GATV2 does not use a2)
             }
         }
         optim_steps_++;
@@ -498,7 +509,8 @@ public:
     }
 
     std::vector<DenseMatrix> weight_grads, input_grads;
-    // score ADDITIVE: attn_grads[i] is (num_heads * features_per_head) x 2 of layer i, row h f + c = (da1_h[c], da2_h[c]), the same on every rank
+    // score ADDITIVE: attn_grads[i] is (num_heads * features_per_head) x 2 of layer i, row h f + c = (da1_h[c], da2_h[c]), the same on every rank;
+    // score GATV2: the same shape, row h f + c = (da_h[c], 0)
     std::vector<DenseMatrix> attn_grads;
 
 private:
@@ -529,6 +541,7 @@ private:
     std::vector<std::vector<DenseMatrix>> mom_w_, var_w_;
     std::vector<DenseMatrix> mom_a_, var_a_;  // [2 layer + (0: a1, 1: a2)]
 
+    bool learns_vectors() const { return score_ == HNH_GAT_SCORE_ADDITIVE || score_ == HNH_GAT_SCORE_GATV2; }
     void check_layer(int i) const {
         if (i < 0 || i >= (int)layers.size()) throw hnh::Error("Error, GAT layer index " + std::to_string(i) + " out of range: " + std::to_string(layers.size()) + " layers!");
     }
@@ -706,7 +719,8 @@ private:
     void check_dropout_supported() {
         if (!(attn_p_ > 0.0) && !(feat_p_ > 0.0)) return;
         if (attn_p_ > 0.0 && score_ != HNH_GAT_SCORE_ADDITIVE)
-            throw hnh::Error("Error, GAT attention dropout supports score additive only, not score dot: the dot-product passes have no mask "
+            throw hnh::Error(std::string("Error, GAT attention dropout supports score additive only, not score ") +
+                             (score_ == HNH_GAT_SCORE_GATV2 ? "gatv2: the gatv2 passes have no mask " : "dot: the dot-product passes have no mask ") +
                              "(include/hnh_attn_dropout.h)");
         if (d_ops->M > 4294967296LL || d_ops->N > 4294967296LL || layers.size() > 65536)
             throw hnh::Error("Error, GAT dropout needs row ids below 2^32 and at most 65536 layers (the generator's counter words)!");
@@ -748,6 +762,7 @@ private:
     // Throws hnh::Error (never a wrong number) where the backward pass is not defined or its kernels are missing.
     void check_backward_supported() {
         if (score_ == HNH_GAT_SCORE_ADDITIVE) check_additive_supported();
+        else if (score_ == HNH_GAT_SCORE_GATV2) check_gatv2_supported();
         else if (backward_ == HNH_GAT_BACKWARD_FUSED) check_fused_backward_supported();
         auto* ds = dynamic_cast<Sparse15D_Dense_Shift*>(d_ops);
         if (ds == nullptr || ds->r_split)
@@ -794,6 +809,26 @@ private:
                          HNH_GAT_KERNEL(hnh_attn_add_scores_f64), HNH_GAT_KERNEL(hnh_attn_add_pack_f64), HNH_GAT_KERNEL(hnh_attn_add_update_f64)});
     }
 
+    // The gatv2 score's own conditions, checked before anything is launched: the attention mode, the schedule (the softmax's), the head
+    // widths, attention dropout (its passes have no mask), then its kernel group and the pack kernel of the fused backward it reuses.
+    void check_gatv2_supported() {
+        if (attention_ != HNH_GAT_ATTENTION_SOFTMAX)
+            throw hnh::Error("Error, GAT score gatv2 supports attention mode softmax only, not attention mode none (include/hnh_attn_v2.h)");
+        require_own_rows("score gatv2");
+        for (const GATLayer& L : layers)
+            if (L.features_per_head > HNH_ATTN_V2_MAX_F)
+                throw hnh::Error("Error, GAT score gatv2 supports heads of at most " + std::to_string(HNH_ATTN_V2_MAX_F) + " features, not " +
+                                 std::to_string(L.features_per_head) + " (include/hnh_attn_v2.h)");
+        if (attn_p_ > 0.0)
+            throw hnh::Error("Error, GAT score gatv2 does not support attention dropout (p = " + std::to_string(attn_p_) +
+                             "): its passes have no mask (include/hnh_attn_v2.h)");
+        const hnh::Backend* be = d_ops->world->be;
+        require_kernels("score gatv2", "include/hnh_attn_v2.h",
+                        {HNH_GAT_KERNEL(hnh_attn_v2_fwd_csr_p), HNH_GAT_KERNEL(hnh_attn_v2_row_csr_p), HNH_GAT_KERNEL(hnh_attn_v2_col_csr_p),
+                         HNH_GAT_KERNEL(hnh_attn_v2_finish_f64)});
+        require_kernels("score gatv2", "include/hnh_attn_grad.h", {HNH_GAT_KERNEL(hnh_attn_grad_pack_f64)});
+    }
+
     // Throws hnh::Error (never a wrong number) where softmax attention is not defined or its kernel is missing: a row's softmax needs
     // all of the row's nonzeros summed by this rank's own launches (require_own_rows).
     void check_softmax_supported() {
@@ -823,9 +858,10 @@ private:
             throw hnh::Error("Error, GAT backwardPass: layer buffers do not have the layer's shape!");
         DenseMatrix& dA_all = scratch(0, rows, hf);
         DenseMatrix& Wt = scratch(1, hf, k);
-        if (score_ == HNH_GAT_SCORE_ADDITIVE) {
+        if (learns_vectors()) {
             DenseMatrix& dav = attn_grads[(size_t)i];
             if (dav.rows() != hf || dav.cols() != 2) dav = DenseMatrix(hf, 2);
+            if (score_ == HNH_GAT_SCORE_GATV2) dav.setZero();  // (column 1 stays zero; column 0 is written head by head)
         }
         d_ops->setRValue(f);
         for (int h = 0; h < H; h++) {
@@ -843,6 +879,7 @@ private:
                          "hnh_act_grad_cols_f64");
             }
             if (score_ == HNH_GAT_SCORE_ADDITIVE) backward_head_additive(i, h, A, dZ, dA_all);
+            else if (score_ == HNH_GAT_SCORE_GATV2) backward_head_gatv2(i, h, A, dZ, dA_all);
             else if (backward_ == HNH_GAT_BACKWARD_FUSED) backward_head_fused(i, h, A, dZ, dA_all);
             else backward_head_unfused(i, h, A, dZ, dA_all);
             w->check(be->hnh_transpose_into_f64(w->ctx, Wt.data(), k, (int64_t)h * f, Wh.data(), k, f, S0), "hnh_transpose_into_f64");
@@ -856,7 +893,7 @@ private:
                                      need, S0),
                  "hnh_gemm_tn_f64");
         w->allreduce_f64(w->world_comm(), dW.data(), (size_t)dW.size(), S0);
-        if (score_ == HNH_GAT_SCORE_ADDITIVE) {
+        if (learns_vectors()) {
             DenseMatrix& dav = attn_grads[(size_t)i];
             w->allreduce_f64(w->world_comm(), dav.data(), (size_t)dav.size(), S0);
         }
@@ -1041,6 +1078,54 @@ private:
                  "hnh_gemm_tn_f64");
     }
 
+    // score GATV2 (include/hnh_attn_v2.h): the pack of the fused backward, the row pass, the column pass and the dense finish, which also
+    // writes the head's rows of attn_grads[i] column 0 (this rank's part)
+    void backward_head_gatv2(int i, int h, DenseMatrix& A, DenseMatrix& dZ, DenseMatrix& dA_all) {
+        hnh::World* w = d_ops->world;
+        const hnh::Backend* be = w->be;
+        const int S0 = HNH_STREAM_COMPUTE;
+        GATLayer& L = layers[(size_t)i];
+        const int H = L.num_heads, f = L.features_per_head;
+        const int64_t rows = A.rows(), hf = (int64_t)H * f;
+        auto* ds = dynamic_cast<Sparse15D_Dense_Shift*>(d_ops);
+        ensure_attn_vectors(i);
+        const int pw = HNH_ATTN_GRAD_PACKED_WIDTH(f, 1), fe = f + (f & 1);
+        DenseMatrix& P = scratch(9, rows, pw);
+        DenseMatrix& Rm = scratch(16, rows, fe);
+        DenseMatrix& Cm = scratch(17, rows, fe);
+        DenseMatrix& dAgg = scratch(18, rows, fe);
+        DenseMatrix& work = scratch(19, HNH_ATTN_V2_FINISH_WORK(f), 1);
+        double* lse = lse_.at((size_t)i).at((size_t)h).data();
+        DenseMatrix& dl = head_delta(i, h, dZ);
+        w->check(be->hnh_attn_grad_pack_f64(w->ctx, P.data(), pw, A.data(), f, dZ.data(), f, lse, dl.data(), rows, f, S0), "hnh_attn_grad_pack_f64");
+        hnh_attn_v2 g = {};
+        g.X = A.data();
+        g.ld_x = f;
+        g.a = L.a1.data() + (int64_t)h * f;
+        g.dZ = dZ.data();
+        g.ld_dz = f;
+        g.lse = lse;
+        g.delta = dl.data();
+        g.Out = Rm.data();
+        g.ld_out = fe;
+        g.f = f;
+        g.leaky_alpha = leaky_relu_alpha;
+        bool ok = ds != nullptr && ds->attnV2_pass(1, A, g, rows, true);  // row side: R
+        if (ok) {
+            // column side: C and dAgg; the moving operand is the packed one
+            ScheduleWidth width(d_ops, pw, f);
+            g.Out = Cm.data();
+            g.Out2 = dAgg.data();
+            g.ld_out2 = fe;
+            ok = ds->attnV2_pass(2, P, g, rows, true);
+        }
+        require_own_rows("score gatv2", !ok);
+        DenseMatrix& dav = attn_grads[(size_t)i];
+        w->check(be->hnh_attn_v2_finish_f64(w->ctx, dA_all.data(), hf, (int64_t)h * f, dAgg.data(), fe, Rm.data(), fe, Cm.data(), fe, A.data(), f, g.a,
+                                            dav.data() + (int64_t)h * f * 2, 2, rows, f, work.data(), HNH_ATTN_V2_FINISH_WORK(f), S0),
+                 "hnh_attn_v2_finish_f64");
+    }
+
     DenseMatrix product[2];  // X * W_j of the head in flight and of the next one
     void* ev_input = nullptr;
     void* ev_gemm[2] = {nullptr, nullptr};
@@ -1126,6 +1211,30 @@ private:
                 ok = ds->attnAdditive_pass(0, A, g, rows, true, attn_p_ > 0.0 ? &dr : nullptr, activation_flag(i));
             }
             require_own_rows("score additive", !ok);
+            return;
+        }
+
+        if (score_ == HNH_GAT_SCORE_GATV2) {
+            // one pass on the plain product with the softmax pass's row state (include/hnh_attn_v2.h): the schedule runs at the head's f
+            const int f = layers[i].features_per_head;
+            const int64_t rows = A.rows();
+            DenseMatrix& lse = softmax_row_state(i, j, rows);
+            DenseMatrix H(rows, f + (f & 1));
+            hnh_attn_v2 g = {};
+            g.X = A.data();
+            g.ld_x = A.cols();
+            g.a = layers[i].a1.data() + (int64_t)j * f;
+            g.lse = lse.data();
+            g.Out = H.data();
+            g.ld_out = H.cols();
+            g.row_max = row_max_.data();
+            g.row_sum = row_sum_.data();
+            g.relu_dst = out.data() + (int64_t)j * f;
+            g.relu_ld = out.cols();
+            g.f = f;
+            g.leaky_alpha = leaky_relu_alpha;
+            auto* ds = dynamic_cast<Sparse15D_Dense_Shift*>(d_ops);
+            require_own_rows("score gatv2", ds == nullptr || !ds->attnV2_pass(0, A, g, rows, true, activation_flag(i)));
             return;
         }
 

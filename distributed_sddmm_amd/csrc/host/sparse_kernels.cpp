@@ -237,6 +237,27 @@ bool StandardKernel::attn_additive_block(SpmatLocal& S, int block, const hnh_att
     return true;
 }
 
+bool KernelImplementation::attn_v2_local(SpmatLocal& S, int block, const hnh_attn_v2& args, int pass, unsigned flags, int64_t rows, bool finish) {
+    StandardKernel* k = dynamic_cast<StandardKernel*>(this);
+    return k != nullptr && k->attn_v2_block(S, block, args, pass, flags, rows, finish);
+}
+
+// The three sparse passes of the GATv2 attention (include/hnh_attn_v2.h), next to attn_additive_block: same block and window handling.
+bool StandardKernel::attn_v2_block(SpmatLocal& S, int block, const hnh_attn_v2& args, int pass, unsigned flags, int64_t rows, bool finish) {
+    hnh::World* w = S.world;
+    auto fn = pass == 0 ? w->be->hnh_attn_v2_fwd_csr_p : (pass == 1 ? w->be->hnh_attn_v2_row_csr_p : w->be->hnh_attn_v2_col_csr_p);
+    const char* name = pass == 0 ? "hnh_attn_v2_fwd_csr_p" : (pass == 1 ? "hnh_attn_v2_row_csr_p" : "hnh_attn_v2_col_csr_p");
+    if (fn == nullptr)
+        throw hnh::Error(std::string("Error, the gatv2 attention score needs the kernel ") + name + ", which the kernel library " + w->be->path +
+                         " does not export (include/hnh_attn_v2.h)");
+    const unsigned f = flags | ((pass == 0 && finish) ? HNH_ATTN_FINISH : 0u);
+    const char* finish_text = (pass == 0 && finish) ? "Error, the gatv2 forward finish belongs to the block's last window!" : nullptr;
+    attn_block_call(S, block, rows, "the gatv2 attention pass", finish_text, pass == 2 ? HNH_ATTN_GRAD_PACKED_WIDTH(args.f, 1) : args.f, profile,
+                    [&](const hnh_csr_block& d, const hnh_csr_window* win) { w->check(fn(w->ctx, &d, &args, f, win, HNH_STREAM_COMPUTE), name); },
+                    [&] { begin(w); }, [&](long launches) { end(w, launches); });
+    return true;
+}
+
 void StandardKernel::begin(hnh::World* w) {
     if (!profile) return;
     if (evw_ != nullptr && evw_ != w) hnh::fatal("Error, a profiled StandardKernel belongs to one world!");

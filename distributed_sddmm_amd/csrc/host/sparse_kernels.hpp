@@ -85,6 +85,13 @@ public:
     bool attn_additive_local(SpmatLocal& S, int block, const hnh_attn_add& args, int pass, unsigned flags, int64_t rows, bool finish,
                              const hnh_attn_drop* drop);
 
+    // One pass of the GATv2 attention (include/hnh_attn_v2.h, the GAT's score "gatv2") on one block, or the selected window(s) of it: pass
+    // 0 = forward over a block of S (continues the rows' running state; `finish` = the pass's last call, which a schedule makes also when
+    // the block is absent), 1 = backward row pass over a block of S, 2 = backward column pass over a block of S^T whose gathered operand
+    // is the packed one of include/hnh_attn_grad.h.  `args` and `rows` as for attn_additive_local.  Returns false, having done nothing,
+    // when the implementation has no such pass.  NOT virtual, for softmax_local's reason.
+    bool attn_v2_local(SpmatLocal& S, int block, const hnh_attn_v2& args, int pass, unsigned flags, int64_t rows, bool finish);
+
     // Row windows (CSRLocal::window): a schedule may select one column range of a block before calling the kernels, to
     // work on data that arrives piece by piece.  An implementation that honours CSRLocal::window says so here; for the
     // others (plugins written against the reference's two pure virtuals) the schedule waits for the whole block instead.
@@ -167,6 +174,8 @@ public:
     bool attn_additive_block(SpmatLocal& S, int block, const hnh_attn_add& args, int pass, unsigned flags, int64_t rows, bool finish);
     bool attn_additive_block(SpmatLocal& S, int block, const hnh_attn_add& args, int pass, unsigned flags, int64_t rows, bool finish,
                              const hnh_attn_drop* drop);
+    // KernelImplementation::attn_v2_local's pass (non-virtual: see there)
+    bool attn_v2_block(SpmatLocal& S, int block, const hnh_attn_v2& args, int pass, unsigned flags, int64_t rows, bool finish);
     ~StandardKernel() override;
 
 private:

@@ -253,9 +253,15 @@ int hnh_gat_set_backward(hnh_gat* g, int mode);
  * naming the schedule, the mode or the width, or the missing symbol when the kernel library lacks the group.  With ADDITIVE there is one
  * backward implementation: the backward mode is not consulted.  A change of score invalidates the stored forward pass; an unknown one fails.
  * a1 / a2 (features_per_head doubles each, per layer and head) are zero until set; setting them invalidates the forward pass like
- * hnh_gat_set_weight.  Their gradients (summed over all ranks) are available after hnh_gat_backward with score ADDITIVE. */
+ * hnh_gat_set_weight.  Their gradients (summed over all ranks) are available after hnh_gat_backward with score ADDITIVE.
+ * GATV2 (Brody, Alon, Yahav: dynamic attention): e_ij = sum_c a_hc LeakyReLU(A_ic + A_jc) with ONE learned vector per head, the nonlinearity
+ * inside the contraction and none outside (include/hnh_attn_v2.h; shared weights: the same A scores and is aggregated), forward and backward;
+ * attention SOFTMAX on 15d_fusion2 with c = 1, heads of at most 256 features and no attention dropout only, refused elsewhere like ADDITIVE, and
+ * like it with one backward implementation.  The head's vector is a1 of hnh_gat_set_attn_vectors (a2 is kept and not used); after
+ * hnh_gat_backward hnh_gat_get_attn_grads returns its gradient as da1 and zeros as da2. */
 #define HNH_GAT_SCORE_DOT 0
 #define HNH_GAT_SCORE_ADDITIVE 1
+#define HNH_GAT_SCORE_GATV2 2
 int hnh_gat_set_score(hnh_gat* g, int mode);
 /* Output activation of a layer (an addition).  RELU (the default of hnh_gat_create on every layer): out = max(o, 0), everything above.  ELU:
  * out = o for o > 0 and expm1(o) otherwise.  IDENTITY: out = o.  The backward pass works from the stored output alone (include/hnh_grad.h,

@@ -267,6 +267,23 @@ class AttnV2(C.Structure):
                 ("relu_ld", _i64), ("f", _i32), ("leaky_alpha", _dbl)]
 
 
+# include/hnh_attn_coef.h: export of the GAT's per-edge attention coefficients in every score mode; an eighth OPTIONAL group bound only for the
+# product library
+ATTN_COEF_SIGNATURES = {
+    "hnh_attn_coef_csr_p": (_i32, [_vp, _vp, _vp, _vp, _vp, C.c_uint, _vp, _i32]),
+    "hnh_attn_coef_scores_f64": (_i32, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i32, _i64, _i32]),
+}
+ATTN_COEF_MAX_F = 256  # HNH_ATTN_COEF_MAX_F
+ATTN_COEF_PAIR_WIDTH = 2  # HNH_ATTN_COEF_PAIR_WIDTH: [t | id]
+ATTN_COEF_DOT, ATTN_COEF_ADDITIVE, ATTN_COEF_GATV2 = 0, 1, 2  # HNH_ATTN_COEF_*
+
+
+class AttnCoef(C.Structure):
+    """struct hnh_attn_coef"""
+    _fields_ = [("X", _vp), ("ld_x", _i64), ("a", _vp), ("s", _vp), ("lse", _vp), ("Y", _vp), ("ld_y", _i64), ("f", _i32), ("score", _i32),
+                ("leaky_alpha", _dbl)]
+
+
 class AttnState(C.Structure):
     """struct hnh_attn_state"""
     _fields_ = [("row_max", _vp), ("row_sum", _vp), ("lse", _vp), ("leaky_alpha", _dbl), ("relu_dst", _vp), ("relu_ld", _i64)]
@@ -330,7 +347,7 @@ def load(path: str | None = None) -> C.CDLL:
     if path is None or os.path.abspath(p) == os.path.abspath(LIB_PATH):
         for name, (res, args) in list(GRAD_SIGNATURES.items()) + list(ATTN_SIGNATURES.items()) + list(ATTN_GRAD_SIGNATURES.items()) + \
                 list(ATTN_ADD_SIGNATURES.items()) + list(ATTN_DROP_SIGNATURES.items()) + list(TRAIN_SIGNATURES.items()) + \
-                list(V2_SIGNATURES.items()):
+                list(V2_SIGNATURES.items()) + list(ATTN_COEF_SIGNATURES.items()):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
     if path is None:

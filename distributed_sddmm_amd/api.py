@@ -129,6 +129,7 @@ SIGNATURES = {
     "hnh_gat_buffer_shape": (_i32, [_vp, _i32, _pi64]),
     "hnh_gat_forward": (_i32, [_vp]),
     "hnh_gat_backward": (_i32, [_vp, _vp]),
+    "hnh_gat_attention_coefficients": (_i32, [_vp, _i32, _i32, _i32, _vp]),
     "hnh_gat_get_weight_grad": (_i32, [_vp, _i32, _i32, _vp]),
     "hnh_gat_get_input_grad": (_i32, [_vp, _vp]),
     "hnh_gat_set_attention": (_i32, [_vp, _i32]),
@@ -568,6 +569,54 @@ class DistributedSparse:
     def fusedSpMM(self, a, b, s, buf, matmode: int):
         _check(lib().hnh_dist_fusedSpMM(self.h, a.h, b.h, s.h, buf.h, matmode), "fusedSpMM")
 
+    def _coordinates(self, transposed: bool):
+        """Two probe SDDMMs at the operator's own R (nothing is changed, nothing is cached): the first with A[i, 0] = i, B[j, 0] = 1 gives every
+        value slot its global row of S, the second with A[i, 0] = 1, B[j, 0] = j its column; each value is one integer below max(M, N), exact in
+        fp64 for any M, N (no i * N + j product is formed)."""
+        def fill(subs, shape, ramp):
+            loc = np.zeros(shape)
+            flat, off = loc.reshape(-1), 0
+            for top, left, rc, cc in subs:
+                blk = np.zeros((rc, cc))
+                if left <= 0 < left + cc:
+                    blk[:, 0 - left] = np.arange(top, top + rc, dtype=np.float64) if ramp else 1.0
+                flat[off:off + rc * cc] = blk.reshape(-1)
+                off += rc * cc
+            return loc
+
+        mode = K_SDDMM_B if transposed else K_SDDMM_A
+        like = self.like_ST_values if transposed else self.like_S_values
+        a, b, ones = self.like_A_matrix(0.0), self.like_B_matrix(0.0), like(1.0)
+        sub_a, sub_b = self.submatrices(AMAT), self.submatrices(BMAT)
+        found = []
+        try:
+            for by_row in (True, False):
+                a.upload(fill(sub_a, a.shape, by_row))
+                b.upload(fill(sub_b, b.shape, not by_row))
+                res = like(0.0)
+                try:
+                    self.initial_shift(a, b, mode)
+                    (self.sddmmB if transposed else self.sddmmA)(a, b, ones, res)
+                    self.de_shift(a, b, mode)
+                    found.append(np.rint(res.download()).astype(np.int64))
+                finally:
+                    res.free()
+        finally:
+            for x in (a, b, ones):
+                x.free()
+        return found[0], found[1]
+
+    def S_coordinates(self):
+        """(rows, cols): int64 arrays with the global coordinates of every entry of a like_S_values vector on this rank, in that vector's
+        order, on any schedule (what GAT.attention_coefficients and sddmmA's results are indexed by).  Collective: two SDDMMs at the
+        operator's current R, which stays what it was; nothing is cached, so a later setRValue cannot invalidate anything."""
+        return self._coordinates(False)
+
+    def ST_coordinates(self):
+        """S_coordinates for a like_ST_values vector: (rows, cols) of the entries of S^T, i.e. rows are columns of S and cols rows of S."""
+        r, c = self._coordinates(True)
+        return c, r
+
     def hold_moving_operand(self, m=None):
         """Distributed_Sparse::hold_moving_operand(m) / release_moving_operand() (m = None)."""
         _check(lib().hnh_dist_hold_moving_operand(self.h, m.h if m else None), "hold_moving_operand")
@@ -795,6 +844,25 @@ class GAT:
         """Gradients of L from grad_out = dL/d(output) (the layout of get_output): needs a forwardPass since the last set_weight /
         set_input; 15d_fusion1 and 15d_fusion2 with c = 1 only (HnhError otherwise)."""
         _check(lib().hnh_gat_backward(self.h, grad_out.h), "backwardPass")
+
+    def attention_coefficients(self, layer: int, head: int, out: Vec | None = None, dropped: bool = False) -> Vec:
+        """The attention coefficients a_ij = exp(z_ij - lse_i) of (layer, head) of the stored forward pass, one per nonzero of S on this
+        rank, in the like_S_values layout (op.S_coordinates() gives every entry's global row and column); every score mode
+        (include/hnh_attn_coef.h).  dropped=True under a nonzero attention dropout rate: c m_ij a_ij, the weights the aggregate used;
+        dropped=False always gives the normalised a_ij over all edges.  `out` is allocated with op.like_S_values when None.  Needs a
+        forwardPass since the last set_weight / set_input / optimizer_step and attention "softmax" (15d_fusion2 with c = 1, heads of at
+        most 256 features): HnhError elsewhere, before anything is launched.  Leaves the stored pass, the gradients, the seed and the
+        optimizer state as they are."""
+        made = out is None
+        if made:
+            out = self.op.like_S_values(0.0)
+        try:
+            _check(lib().hnh_gat_attention_coefficients(self.h, int(layer), int(head), int(bool(dropped)), out.h), "gat_attention_coefficients")
+        except BaseException:
+            if made:
+                out.free()
+            raise
+        return out
 
     def weight_grad(self, layer: int, head: int) -> np.ndarray:
         """dL/dW of (layer, head) after backwardPass, summed over every rank (the same on all of them)."""

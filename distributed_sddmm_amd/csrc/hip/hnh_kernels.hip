@@ -2817,3 +2817,6 @@ int hnh_rowdot_cols_f64(hnh_ctx* ctx, double* out, const double* dZ, int64_t ld_
 
 // ---------------------------------------------------------------- GATv2 attention scores (include/hnh_attn_v2.h)
 #include "hnh_attn_v2_kernels.hpp"
+
+// ---------------------------------------------------------------- export of the attention coefficients (include/hnh_attn_coef.h)
+#include "hnh_attn_coef_kernels.hpp"

@@ -10,6 +10,7 @@
 #include "hnh_attn_additive.h"
 #include "hnh_attn_dropout.h"
 #include "hnh_attn_grad.h"
+#include "hnh_attn_coef.h"
 #include "hnh_attn_v2.h"
 #include "hnh_grad.h"
 #include "hnh_kernels.h"
@@ -65,6 +66,8 @@ struct Backend {
     HNH_FN(hnh_xent_rows_f64_workspace) HNH_FN(hnh_xent_rows_f64) HNH_FN(hnh_optim_step_f64)
     // OPTIONAL group (include/hnh_attn_v2.h), bound the same way: only the GAT's gatv2 score needs it
     HNH_FN(hnh_attn_v2_fwd_csr_p) HNH_FN(hnh_attn_v2_row_csr_p) HNH_FN(hnh_attn_v2_col_csr_p) HNH_FN(hnh_attn_v2_finish_f64)
+    // OPTIONAL group (include/hnh_attn_coef.h), bound the same way: only GAT::attention_coefficients needs it
+    HNH_FN(hnh_attn_coef_csr_p) HNH_FN(hnh_attn_coef_scores_f64)
 #ifdef HNH_MEASUREMENT_AIDS
     HNH_FN(hnh_stream_delay_us) HNH_FN(hnh_stream_paced_copy) HNH_FN(hnh_stream_pace_begin) HNH_FN(hnh_stream_pace_end)
 #endif

@@ -865,6 +865,12 @@ int hnh_gat_evaluate(hnh_gat* g, const uint8_t* mask_or_null, int64_t n, double*
         if (accuracy) *accuracy = r.second;
     });
 }
+int hnh_gat_attention_coefficients(hnh_gat* g, int layer, int head, int dropped, hnh_vec* out) {
+    return guarded(g->w, [&] {
+        if (!out) throw hnh::Error("Error, hnh_gat_attention_coefficients: null vector!");
+        g->g->attention_coefficients(layer, head, out->v, dropped != 0);
+    });
+}
 int hnh_gat_backward(hnh_gat* g, hnh_dense* grad_out) {
     return guarded(g->w, [&] { g->g->backwardPass(grad_out->m); });
 }

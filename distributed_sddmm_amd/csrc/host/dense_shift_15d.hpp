@@ -356,6 +356,36 @@ public:
         return true;
     }
 
+    // The export of the attention coefficients (include/hnh_attn_coef.h) over S: `moving` is the gathered operand (the head's product A for
+    // the scores dot and gatv2, the packed pair [t | id] for additive) and, as for attnV2_pass, the schedule's R must be its width.  The
+    // blocks are walked in attn_walk's order (the own block, then the fetched blocks by window or adaptive group, or the ring); block i
+    // stores its nonzeros' coefficients into out_values[blockStarts[i] ..), the like_S_values layout that lendSddmmTargets defines, and the
+    // lent slices are reclaimed before the pass returns.  Returns false, having done nothing, where a rank's own launches do not see all of
+    // a row's nonzeros (the stored lse belongs to whole rows).  Not a virtual of Distributed_Sparse, for fusedSoftmax_out's reason.
+    bool attnCoef_pass(DenseMatrix& moving, const hnh_attn_coef& args, VectorXd& out_values, const hnh_attn_drop* drop = nullptr) {
+        if (fusionApproach != 2 || c != 1) return false;
+        if (moving.cols() != R) hnh::fatal("Error, attnCoef_pass: the schedule's R must be the moving operand's width!");
+        SpmatLocal* s = S.get();
+        if (!s->blockStarts.empty() && (uint64_t)out_values.size() < s->blockStarts.back()) hnh::fatal("Error, sparse value vector has the wrong length!");
+        const int64_t rows = (int64_t)localArows * c;  // (every block of S holds the rank's rows)
+        for (size_t i = 0; i + 1 < s->blockStarts.size(); i++) {
+            CSRLocal* blk = s->csr_blocks[i];
+            if (blk == nullptr) continue;
+            if (blk->shifting) hnh::fatal("Error, attnCoef_pass: a travelling block cannot borrow a value slice!");
+            blk->sddmm_dst = out_values.data() + s->blockStarts[i];
+        }
+        struct Reclaim {
+            SpmatLocal* s;
+            ~Reclaim() { s->reclaimValueArrays(); }
+        } reclaim{s};
+        attn_walk(s, moving, args, false, false,
+                  "Error, the kernel implementation has no attention-coefficient export (KernelImplementation::attn_coef_local)!",
+                  [&](SpmatLocal& choice, int block_id, const hnh_attn_coef& a, unsigned, bool) {
+                      return kernel->attn_coef_local(choice, block_id, a, rows, drop);
+                  });
+        return true;
+    }
+
 private:
     // ---- merged layout helpers
     // visiting step of global block column b on this rank (block_at(k) == b), or -1 when the rank never visits it

@@ -323,6 +323,77 @@ public:
         grads_fresh_ = true;  // (optimizer_step takes them once)
     }
 
+    // The attention coefficients of (layer i, head h) of the STORED forward pass, one per nonzero of S on this rank, into `out` in the
+    // like_S_values layout (Distributed_Sparse::S_coordinates gives the global (row, column) of every entry): a_ij = exp(z_ij - lse_i) with
+    // the lse the forward pass kept, normalised over ALL edges of the row.  `dropped` with a nonzero attention rate: c m_ij a_ij instead, the
+    // weights the aggregate actually used (rate 0: no difference).  One pass over the nonzeros (include/hnh_attn_coef.h): A = layer_input(i)
+    // W_h is recomputed (Xd under feature dropout, what the forward pass used); the scores dot and gatv2 gather A, score additive gathers
+    // the packed pair [t | id] built from A, and the schedule runs at that operand's width and at its previous R again afterwards.  Reads
+    // the stored pass and writes `out` and scratch of its own: buffers, lse, gradients, seed and optimizer state stay as they are, and so
+    // does the validity of the forward pass.  Attention softmax on 15d_fusion2 with c = 1 and heads of at most HNH_ATTN_COEF_MAX_F
+    // features; everything else raises before anything is launched (arguments, mode, schedule, width, kernel group, then the stored pass).
+    void attention_coefficients(int i, int h, VectorXd& out, bool dropped) {
+        const std::string what = "attention_coefficients";
+        check_layer_head(i, h);
+        auto* ds = dynamic_cast<Sparse15D_Dense_Shift*>(d_ops);
+        if (ds != nullptr) {
+            SpmatLocal* s = ds->fusionApproach == 1 ? ds->ST.get() : ds->S.get();
+            const int64_t want = (int64_t)(s->owned_coords_end - s->owned_coords_start);
+            if (out.size() != want)
+                throw hnh::Error("Error, GAT " + what + " needs a vector of like_S_values length: " + std::to_string(want) + " entries, not " +
+                                 std::to_string(out.size()) + "!");
+        }
+        if (attention_ != HNH_GAT_ATTENTION_SOFTMAX)
+            throw hnh::Error("Error, GAT " + what + " supports attention mode softmax only, not attention mode none: its weights are what sddmmA and "
+                             "hnh_leaky_relu_f64 give (include/hnh_attn_coef.h)");
+        require_own_rows(what);
+        GATLayer& L = layers[(size_t)i];
+        const int f = L.features_per_head;
+        if (f > HNH_ATTN_COEF_MAX_F)
+            throw hnh::Error("Error, GAT " + what + " supports heads of at most " + std::to_string(HNH_ATTN_COEF_MAX_F) + " features, not " + std::to_string(f) +
+                             " (include/hnh_attn_coef.h)");
+        hnh::World* w = d_ops->world;
+        const hnh::Backend* be = w->be;
+        const bool additive = score_ == HNH_GAT_SCORE_ADDITIVE;
+        require_kernels(what, "include/hnh_attn_coef.h", {HNH_GAT_KERNEL(hnh_attn_coef_csr_p)});
+        if (additive) require_kernels(what, "include/hnh_attn_coef.h", {HNH_GAT_KERNEL(hnh_attn_coef_scores_f64)});
+        if (!forward_valid_ || lse_.size() != layers.size() || lse_[(size_t)i].size() != (size_t)L.num_heads)
+            throw hnh::Error("Error, GAT " + what + " needs a forwardPass first (and a new one after set_weight / set_input / optimizer_step)!");
+        const int S0 = HNH_STREAM_COMPUTE;
+        DenseMatrix& X = layer_input(i);
+        DenseMatrix& Wh = L.wMats[(size_t)h];
+        const int64_t rows = X.rows();
+        DenseMatrix& A = scratch(20, rows, f);
+        w->check(be->hnh_gemm_f64(w->ctx, rows, f, X.cols(), X.data(), Wh.data(), A.data(), S0), "hnh_gemm_f64");
+        hnh_attn_coef g = {};
+        g.lse = lse_[(size_t)i][(size_t)h].data();
+        g.f = f;
+        g.leaky_alpha = leaky_relu_alpha;
+        const int r0 = d_ops->R;
+        bool ok;
+        if (additive) {
+            DenseMatrix& sv = scratch(21, rows, 1);
+            DenseMatrix& T = scratch(22, rows, HNH_ATTN_COEF_PAIR_WIDTH);
+            w->check(be->hnh_attn_coef_scores_f64(w->ctx, sv.data(), T.data(), T.cols(), A.data(), f, L.a1.data() + (int64_t)h * f, L.a2.data() + (int64_t)h * f,
+                                                  rows, f, d_ops->aSubmatrices[0].topRow, S0),
+                     "hnh_attn_coef_scores_f64");
+            g.score = HNH_ATTN_COEF_ADDITIVE;
+            g.s = sv.data();
+            const bool drop = dropped && attn_p_ > 0.0;
+            const hnh_attn_drop dr = attn_drop_args(i, h);
+            ScheduleWidth width(d_ops, HNH_ATTN_COEF_PAIR_WIDTH, r0);
+            ok = ds->attnCoef_pass(T, g, out, drop ? &dr : nullptr);
+        } else {
+            g.score = score_ == HNH_GAT_SCORE_GATV2 ? HNH_ATTN_COEF_GATV2 : HNH_ATTN_COEF_DOT;
+            g.X = A.data();
+            g.ld_x = f;
+            g.a = score_ == HNH_GAT_SCORE_GATV2 ? L.a1.data() + (int64_t)h * f : nullptr;
+            ScheduleWidth width(d_ops, f, r0);
+            ok = ds->attnCoef_pass(A, g, out);
+        }
+        require_own_rows(what, !ok);
+    }
+
     // ---- training (include/hnh_train.h)
     // Labels and training mask as HOST arrays of d_ops->M entries in the operator's global row numbering (mask == nullptr: every row with
     // a label >= 0).  heads_mode: HNH_GAT_HEADS_MEAN (classes = the last layer's features_per_head) | HNH_GAT_HEADS_CONCAT (classes =

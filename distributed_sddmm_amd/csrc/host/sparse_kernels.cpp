@@ -258,6 +258,30 @@ bool StandardKernel::attn_v2_block(SpmatLocal& S, int block, const hnh_attn_v2& 
     return true;
 }
 
+bool KernelImplementation::attn_coef_local(SpmatLocal& S, int block, const hnh_attn_coef& args, int64_t rows, const hnh_attn_drop* drop) {
+    StandardKernel* k = dynamic_cast<StandardKernel*>(this);
+    return k != nullptr && k->attn_coef_block(S, block, args, rows, drop);
+}
+
+// The export of the attention coefficients (include/hnh_attn_coef.h), next to attn_v2_block: same block and window handling; the values go
+// where an SDDMM's would (a lent slice of the caller's vector, or the block's own array).
+bool StandardKernel::attn_coef_block(SpmatLocal& S, int block, const hnh_attn_coef& args, int64_t rows, const hnh_attn_drop* drop) {
+    hnh::World* w = S.world;
+    const char* name = "hnh_attn_coef_csr_p";
+    if (w->be->hnh_attn_coef_csr_p == nullptr)
+        throw hnh::Error(std::string("Error, the export of the attention coefficients needs the kernel ") + name + ", which the kernel library " +
+                         w->be->path + " does not export (include/hnh_attn_coef.h)");
+    CSRLocal* blk = S.csr_blocks[block];
+    double* dst = blk == nullptr ? nullptr : (blk->sddmm_dst ? blk->sddmm_dst : blk->getActive()->values);
+    attn_block_call(S, block, rows, "the attention-coefficient export", nullptr,
+                    args.score == HNH_ATTN_COEF_ADDITIVE ? HNH_ATTN_COEF_PAIR_WIDTH : args.f, profile,
+                    [&](const hnh_csr_block& d, const hnh_csr_window* win) {
+                        w->check(w->be->hnh_attn_coef_csr_p(w->ctx, &d, dst, &args, drop, 0u, win, HNH_STREAM_COMPUTE), name);
+                    },
+                    [&] { begin(w); }, [&](long launches) { end(w, launches); });
+    return true;
+}
+
 void StandardKernel::begin(hnh::World* w) {
     if (!profile) return;
     if (evw_ != nullptr && evw_ != w) hnh::fatal("Error, a profiled StandardKernel belongs to one world!");

@@ -92,6 +92,13 @@ public:
     // when the implementation has no such pass.  NOT virtual, for softmax_local's reason.
     bool attn_v2_local(SpmatLocal& S, int block, const hnh_attn_v2& args, int pass, unsigned flags, int64_t rows, bool finish);
 
+    // The export of the attention coefficients (include/hnh_attn_coef.h) on one block of S, or the selected window(s) of it: every nonzero
+    // of the call gets its coefficient in the block's value slice, which the schedule has lent from the caller's vector (CSRLocal::sddmm_dst)
+    // as for an SDDMM; without a lent slice the block's own value array takes them.  An absent or empty block has nothing to store.  `rows`
+    // as for attn_additive_local; `drop` (score additive only) or nullptr.  Returns false, having done nothing, when the implementation has
+    // no such pass.  NOT virtual, for softmax_local's reason.
+    bool attn_coef_local(SpmatLocal& S, int block, const hnh_attn_coef& args, int64_t rows, const hnh_attn_drop* drop);
+
     // Row windows (CSRLocal::window): a schedule may select one column range of a block before calling the kernels, to
     // work on data that arrives piece by piece.  An implementation that honours CSRLocal::window says so here; for the
     // others (plugins written against the reference's two pure virtuals) the schedule waits for the whole block instead.
@@ -176,6 +183,8 @@ public:
                              const hnh_attn_drop* drop);
     // KernelImplementation::attn_v2_local's pass (non-virtual: see there)
     bool attn_v2_block(SpmatLocal& S, int block, const hnh_attn_v2& args, int pass, unsigned flags, int64_t rows, bool finish);
+    // KernelImplementation::attn_coef_local's pass (non-virtual: see there)
+    bool attn_coef_block(SpmatLocal& S, int block, const hnh_attn_coef& args, int64_t rows, const hnh_attn_drop* drop);
     ~StandardKernel() override;
 
 private:

@@ -233,6 +233,13 @@ int hnh_gat_forward(hnh_gat* g);                                                
 int hnh_gat_backward(hnh_gat* g, hnh_dense* grad_out);
 int hnh_gat_get_weight_grad(hnh_gat* g, int layer, int head, double* host); /* dL/dW (hnh_gat_weight_shape), summed over all ranks */
 int hnh_gat_get_input_grad(hnh_gat* g, hnh_dense* out);                     /* dL/d(buffers[0]) in its layout (copied)          */
+/* Export of the attention coefficients (an addition; include/hnh_attn_coef.h).  out (hnh_vec_like's S layout: one entry per nonzero of S on
+ * this rank) receives a_ij = exp(z_ij - lse_i) of (layer, head) of the STORED forward pass, in every score mode; with dropped != 0 and a
+ * nonzero attention dropout rate c m_ij a_ij, the weights the aggregate used.  One pass over the nonzeros on the compute stream; the stored
+ * pass, the gradients, the seed and the optimizer state are not touched, and the operator's R is what it was.  Attention SOFTMAX on 15d_fusion2
+ * with c = 1, heads of at most 256 features; fails elsewhere before anything is launched, naming the argument, the mode (attention NONE: those
+ * weights are what hnh_dist_sddmmA and hnh_leaky_relu_f64 give), the schedule, the width, the missing symbol, or the missing forward pass. */
+int hnh_gat_attention_coefficients(hnh_gat* g, int layer, int head, int dropped, hnh_vec* out);
 /* Attention mode (an addition).  NONE (the default of hnh_gat_create): the LeakyReLU scores are the edge weights, as in the
  * reference.  SOFTMAX: they are normalised over each row's neighbourhood, a_ij = exp(s_ij - lse_i), forward and backward; 15d_fusion2
  * with c = 1 only (the forward pass returns HNH_ERR_INVALID elsewhere, and when the kernel library lacks include/hnh_attention.h).

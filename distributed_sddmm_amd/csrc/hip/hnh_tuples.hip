@@ -345,6 +345,7 @@ int hnh_tuples_dedup_max(hnh_ctx* ctx, hnh_tuple* sorted, int64_t n, int64_t* n_
     unsigned* pos = reinterpret_cast<unsigned*>(base + o_pos);
     hnh_tuple* out = reinterpret_cast<hnh_tuple*>(base + o_out);
     hipLaunchKernelGGL(head_flags_kernel, dim3(grid_for(n)), dim3(kBlock), 0, st, sorted, (long long)n, flag);
+    HNH_TRY_HIP(ctx, hipGetLastError());
     HNH_TRY_HIP(ctx, rocprim::inclusive_scan(base + o_tmp, scan_bytes, flag, pos, un, rocprim::plus<unsigned>(), st));
     hipLaunchKernelGGL(compact_max_kernel, dim3(grid_for(n)), dim3(kBlock), 0, st, sorted, (long long)n, flag, pos, out);
     HNH_TRY_HIP(ctx, hipGetLastError());
@@ -395,6 +396,7 @@ int hnh_tuples_to_csr(hnh_ctx* ctx, const hnh_tuple* sorted, int64_t n, int64_t 
     HNH_ENTER(ctx, stream);
     if (n < 0 || rows < 0 || cols < 0) return hnh::fail(ctx, HNH_ERR_INVALID, "hnh_tuples_to_csr: negative size");
     if (n > 0x7fffffffLL) return hnh::fail(ctx, HNH_ERR_UNSUPPORTED, "hnh_tuples_to_csr: block has more than 2^31 nonzeros");
+    if (cols > 0x7fffffffLL) return hnh::fail(ctx, HNH_ERR_UNSUPPORTED, "hnh_tuples_to_csr: block has more than 2^31 - 1 columns");
     if (!rowptr || (n > 0 && (!sorted || !col_idx || !values))) return hnh::fail(ctx, HNH_ERR_INVALID, "hnh_tuples_to_csr: null pointer");
     hipStream_t st = ctx->streams[stream];
     Scratch s;

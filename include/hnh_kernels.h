@@ -235,7 +235,8 @@ int hnh_sum_chunked_blocks_f64(hnh_ctx* ctx, double* dst, const double* src, int
  * hnh_tuples_transform     r <-> c when swap_rc, then r %= rmod, c %= cmod (0 = leave): transposition and the
  *                          "make indices block-local" loops of the schedule constructors (15D_dense_shift.hpp:96-100)
  * hnh_tuples_to_csr        tuples in HNH_KEY_ROW_COL order -> rowptr (rows + 1), col_idx, values of one block; reports the
- *                          longest row; HNH_ERR_INVALID when a tuple lies outside rows x cols; synchronous */
+ *                          longest row; HNH_ERR_INVALID when a tuple lies outside rows x cols; synchronous.  col_idx holds
+ *                          32-bit indices: cols > 2^31 - 1 is HNH_ERR_UNSUPPORTED, and nothing is written */
 typedef struct hnh_tuple {
     uint64_t r, c;
     double value;

@@ -981,6 +981,7 @@ int hnh_tuples_remap_cols(hnh_ctx* c, hnh_tuple* t, int64_t n, int64_t div, int6
 int hnh_tuples_to_csr(hnh_ctx* c, const hnh_tuple* t, int64_t n, int64_t rows, int64_t cols, int32_t* rowptr, int32_t* col_idx,
                       double* values, int* max_row, int stream) {
     if (n < 0 || rows < 0 || cols < 0 || !rowptr) return fail(c, HNH_ERR_INVALID, "bad argument");
+    if (cols > INT32_MAX) return fail(c, HNH_ERR_UNSUPPORTED, "block has more than 2^31 - 1 columns");
     HB_OP(c, stream, "hnh_tuples_to_csr");
     HB_R(t, (size_t)n * sizeof(hnh_tuple));
     HB_W(rowptr, (size_t)(rows + 1) * sizeof(int32_t));
@@ -1016,6 +1017,7 @@ static int u64_cmp(const void* a, const void* b) {
 }
 int hnh_generate_er_keys(hnh_ctx* c, uint64_t m, uint64_t n, uint64_t draws, uint64_t seed, uint64_t* keys, int64_t* n_unique, int stream) {
     if (!n_unique || m == 0 || n == 0) return fail(c, HNH_ERR_INVALID, "bad argument");
+    if (draws > 0 && m > UINT64_MAX / n) return fail(c, HNH_ERR_UNSUPPORTED, "m * n overflows 64 bits");
     HB_OP(c, stream, "hnh_generate_er_keys");
     HB_W(keys, (size_t)draws * sizeof(uint64_t));
     const uint64_t G = 0x9E3779B97F4A7C15ull;

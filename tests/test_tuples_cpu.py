@@ -49,6 +49,18 @@ def test_c_test_double_round6_primitives():
     tuples_common.run_round6_primitives(DoubleApi())
 
 
+@pytest.fixture(scope="module")
+def double_api():
+    return DoubleApi()
+
+
+@pytest.mark.parametrize("body", tuples_common.EDGE_BODIES, ids=lambda f: f.__name__)
+def test_c_test_double_setup_primitive_at_its_edges(double_api, body):
+    """One set-up primitive at its edges (tuples_common.EDGE_BODIES) on the test double; test_tuples_gpu.py holds the HIP library to
+    the same statement.  The double ignores key_bits: what the sort bodies say about minimal key bits binds the HIP backend only."""
+    body(double_api)
+
+
 def test_world_identities_say_where_every_rank_runs():
     """World::identities() (hnh_world_identities): one record per rank — pid, device ordinal, the GPU's PCI bus id — the same list on every
     rank; bench.py builds its workload sentence from the number of distinct bus ids."""

@@ -21,6 +21,22 @@ def test_hip_round6_primitives():
     ctx.close()
 
 
+@pytest.fixture(scope="module")
+def hip_ctx():
+    from distributed_sddmm_amd import _kernels as K
+    ctx = K.Ctx(0)
+    assert K.load().hnh_backend_name() == b"hip-gfx950"
+    yield ctx
+    ctx.close()
+
+
+@pytest.mark.parametrize("body", tuples_common.EDGE_BODIES, ids=lambda f: f.__name__)
+def test_hip_setup_primitive_at_its_edges(hip_ctx, body):
+    """One set-up primitive at its edges (tuples_common.EDGE_BODIES) on the HIP library: the body the CPU double runs in
+    test_tuples_cpu.py, exact against numpy.  Here key_bits decides how many radix passes run."""
+    body(hip_ctx)
+
+
 def test_sort_at_scale_is_a_permutation_in_order():
     """1e7 tuples (size-independent properties): sorted by key, same multiset of values."""
     import ctypes as C

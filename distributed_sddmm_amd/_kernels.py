@@ -278,6 +278,17 @@ ATTN_COEF_PAIR_WIDTH = 2  # HNH_ATTN_COEF_PAIR_WIDTH: [t | id]
 ATTN_COEF_DOT, ATTN_COEF_ADDITIVE, ATTN_COEF_GATV2 = 0, 1, 2  # HNH_ATTN_COEF_*
 
 
+# include/hnh_gat_skip.h: bias and skip connections of the GAT layers (the addend flag of the finishing calls and three dense kernels); a
+# ninth OPTIONAL group bound only for the product library
+SKIP_SIGNATURES = {
+    "hnh_skip_addend_cols_f64": (_i32, [_vp, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _i64, _i32]),
+    "hnh_skip_grad_cols_f64": (_i32, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _i32]),
+    "hnh_colsum_f64_workspace": (_i64, [_i64, _i64]),
+    "hnh_colsum_f64": (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _i32]),
+}
+ATTN_ADDEND = 0x40  # HNH_ATTN_ADDEND: the finishing call adds what waits in relu_dst before the activation
+
+
 class AttnCoef(C.Structure):
     """struct hnh_attn_coef"""
     _fields_ = [("X", _vp), ("ld_x", _i64), ("a", _vp), ("s", _vp), ("lse", _vp), ("Y", _vp), ("ld_y", _i64), ("f", _i32), ("score", _i32),
@@ -347,7 +358,7 @@ def load(path: str | None = None) -> C.CDLL:
     if path is None or os.path.abspath(p) == os.path.abspath(LIB_PATH):
         for name, (res, args) in list(GRAD_SIGNATURES.items()) + list(ATTN_SIGNATURES.items()) + list(ATTN_GRAD_SIGNATURES.items()) + \
                 list(ATTN_ADD_SIGNATURES.items()) + list(ATTN_DROP_SIGNATURES.items()) + list(TRAIN_SIGNATURES.items()) + \
-                list(V2_SIGNATURES.items()) + list(ATTN_COEF_SIGNATURES.items()):
+                list(V2_SIGNATURES.items()) + list(ATTN_COEF_SIGNATURES.items()) + list(SKIP_SIGNATURES.items()):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
     if path is None:

@@ -137,6 +137,13 @@ SIGNATURES = {
     "hnh_gat_set_score": (_i32, [_vp, _i32]),
     "hnh_gat_set_activation": (_i32, [_vp, _i32, _i32]),
     "hnh_gat_set_attn_vectors": (_i32, [_vp, _i32, _i32, _vp, _vp]),
+    "hnh_gat_set_residual": (_i32, [_vp, _i32, _i32]),
+    "hnh_gat_set_residual_weight": (_i32, [_vp, _i32, _vp]),
+    "hnh_gat_get_residual_weight": (_i32, [_vp, _i32, _vp]),
+    "hnh_gat_get_residual_weight_grad": (_i32, [_vp, _i32, _vp]),
+    "hnh_gat_set_bias": (_i32, [_vp, _i32, _vp]),
+    "hnh_gat_get_bias": (_i32, [_vp, _i32, _vp]),
+    "hnh_gat_get_bias_grad": (_i32, [_vp, _i32, _vp]),
     "hnh_gat_get_attn_grads": (_i32, [_vp, _i32, _i32, _vp, _vp]),
     "hnh_gat_set_dropout": (_i32, [_vp, _dbl, _dbl, C.c_uint64]),
     "hnh_gat_set_dropout_seed": (_i32, [_vp, C.c_uint64]),
@@ -718,13 +725,24 @@ class GAT:
 
     ACTIVATION = {"relu": 0, "elu": 1, "identity": 2}  # HNH_GAT_ACT_RELU / _ELU / _IDENTITY
 
+    RESIDUAL = {"none": 0, "identity": 1, "projection": 2}  # HNH_GAT_RESIDUAL_NONE / _IDENTITY / _PROJECTION
+
     HEADS = {"mean": 0, "concat": 1}  # HNH_GAT_HEADS_MEAN / _CONCAT
 
     OPTIMIZER = {"adam": 0, "sgd": 1}  # HNH_GAT_OPTIMIZER_ADAM / _SGD
 
     def __init__(self, op: DistributedSparse, layers, leaky_relu_alpha: float = 0.2, attention: str = "none", backward: str = "unfused",
-                 score: str = "dot", dropout=(0.0, 0.0), seed: int = 0, activation="relu"):
+                 score: str = "dot", dropout=(0.0, 0.0), seed: int = 0, activation="relu", residual="none", bias=False):
         self.op, self.layers = op, [tuple(l) for l in layers]
+        ress = [residual] * len(self.layers) if isinstance(residual, str) else list(residual)
+        if len(ress) != len(self.layers):
+            raise ValueError("residual is one name or one name per layer: %d layers, not %d names" % (len(self.layers), len(ress)))
+        for r in ress:
+            if r not in self.RESIDUAL:
+                raise ValueError("residual must be one of %s, not %r" % (sorted(self.RESIDUAL), r))
+        biases = [bool(bias)] * len(self.layers) if isinstance(bias, (bool, np.bool_)) else [bool(b) for b in bias]
+        if len(biases) != len(self.layers):
+            raise ValueError("bias is one flag or one flag per layer: %d layers, not %d flags" % (len(self.layers), len(biases)))
         acts = [activation] * len(self.layers) if isinstance(activation, str) else list(activation)
         if len(acts) != len(self.layers):
             raise ValueError("activation is one name or one name per layer: %d layers, not %d names" % (len(self.layers), len(acts)))
@@ -745,6 +763,16 @@ class GAT:
         for i, a in enumerate(acts):
             if a != "relu":
                 self.set_activation(i, a)
+        try:
+            for i, r in enumerate(ress):
+                if r != "none":
+                    self.set_residual(i, r)
+            for i, b in enumerate(biases):
+                if b:
+                    self.set_bias(i, np.zeros(self.layers[i][1] * self.layers[i][2]))
+        except BaseException:
+            self.free()
+            raise
 
     def set_dropout(self, attention_p: float, feature_p: float, seed: int = 0):
         """Dropout rates in [0, 1) on the normalised attention coefficients (score "additive" only: not "dot", not "gatv2") and on every layer's input, with masks
@@ -798,6 +826,72 @@ class GAT:
         if not (0 <= int(layer) < len(self.layers)):
             raise ValueError("layer %r out of range: %d layers" % (layer, len(self.layers)))
         _check(lib().hnh_gat_set_activation(self.h, int(layer), self.ACTIVATION[mode]), "gat_set_activation")
+
+    # ---- bias and skip connections (include/hnh_gat_skip.h)
+    def _layer(self, layer):
+        if not (0 <= int(layer) < len(self.layers)):
+            raise ValueError("layer %r out of range: %d layers" % (layer, len(self.layers)))
+        return int(layer)
+
+    def _width(self, layer):
+        return self.layers[layer][1] * self.layers[layer][2]
+
+    def set_residual(self, layer: int, mode: str):
+        """The layer's skip connection, added before the activation: out = act(o + r + b) with r "none" (the default), "identity" (the layer
+        input; needs input_features == heads * features_per_head) or "projection" (input @ W_res, W_res learned: set_residual_weight, zero
+        until set).  Needs attention "softmax" (every score, both backward modes, any dropout the score allows, any activation) on
+        15d_fusion2 with c = 1: forwardPass / backwardPass / train_step / evaluate raise HnhError elsewhere, before anything is launched.
+        A change invalidates the stored forward pass."""
+        if mode not in self.RESIDUAL:
+            raise ValueError("residual must be one of %s, not %r" % (sorted(self.RESIDUAL), mode))
+        _check(lib().hnh_gat_set_residual(self.h, self._layer(layer), self.RESIDUAL[mode]), "gat_set_residual")
+
+    def set_residual_weight(self, layer: int, w: np.ndarray):
+        """W_res of the layer: input_features x (heads * features_per_head), column block h belongs to head h.  Invalidates the stored
+        forward pass like set_weight."""
+        layer = self._layer(layer)
+        w = np.ascontiguousarray(w, dtype=np.float64)
+        if w.shape != (self.layers[layer][0], self._width(layer)):
+            raise ValueError("the residual weight of layer %d is %d x %d, not %r" % (layer, self.layers[layer][0], self._width(layer), w.shape))
+        _check(lib().hnh_gat_set_residual_weight(self.h, layer, w.ctypes.data), "gat_set_residual_weight")
+
+    def get_residual_weight(self, layer: int) -> np.ndarray:
+        layer = self._layer(layer)
+        out = np.empty((self.layers[layer][0], self._width(layer)))
+        _check(lib().hnh_gat_get_residual_weight(self.h, layer, out.ctypes.data), "gat_get_residual_weight")
+        return out
+
+    def residual_weight_grad(self, layer: int) -> np.ndarray:
+        """dL/dW_res of the layer after backwardPass with residual "projection", summed over every rank."""
+        layer = self._layer(layer)
+        out = np.empty((self.layers[layer][0], self._width(layer)))
+        _check(lib().hnh_gat_get_residual_weight_grad(self.h, layer, out.ctypes.data), "gat_get_residual_weight_grad")
+        return out
+
+    def set_bias(self, layer: int, b):
+        """The layer's learned bias (heads * features_per_head entries), added before the activation; None switches it off (the default).
+        Supported where set_residual is.  Invalidates the stored forward pass."""
+        layer = self._layer(layer)
+        if b is None:
+            _check(lib().hnh_gat_set_bias(self.h, layer, None), "gat_set_bias")
+            return
+        b = np.ascontiguousarray(b, dtype=np.float64)
+        if b.shape != (self._width(layer),):
+            raise ValueError("the bias of layer %d has %d entries, not shape %r" % (layer, self._width(layer), b.shape))
+        _check(lib().hnh_gat_set_bias(self.h, layer, b.ctypes.data), "gat_set_bias")
+
+    def get_bias(self, layer: int) -> np.ndarray:
+        layer = self._layer(layer)
+        out = np.empty(self._width(layer))
+        _check(lib().hnh_gat_get_bias(self.h, layer, out.ctypes.data), "gat_get_bias")
+        return out
+
+    def bias_grad(self, layer: int) -> np.ndarray:
+        """dL/db of the layer after backwardPass with a bias, summed over every rank."""
+        layer = self._layer(layer)
+        out = np.empty(self._width(layer))
+        _check(lib().hnh_gat_get_bias_grad(self.h, layer, out.ctypes.data), "gat_get_bias_grad")
+        return out
 
     def set_attention_vectors(self, layer: int, head: int, a1: np.ndarray, a2: np.ndarray):
         """The additive score's vectors of (layer, head): features_per_head entries each, zero until set.  Score "gatv2" uses a1 as the
@@ -922,7 +1016,8 @@ class GAT:
 
     def set_optimizer(self, kind: str, lr: float, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8, momentum: float = 0.0,
                       weight_decay: float = 0.0):
-        """"adam" or "sgd" (with momentum) over every W, and a1, a2 with score "additive"; weight decay is added to the gradient.
+        """"adam" or "sgd" (with momentum) over every W, a1, a2 with score "additive", and every enabled bias and residual weight; weight
+        decay is added to the gradient of each of them.
         (Re)allocates zeroed moments and resets the step count."""
         if kind not in self.OPTIMIZER:
             raise ValueError("optimizer must be one of %s, not %r" % (sorted(self.OPTIMIZER), kind))

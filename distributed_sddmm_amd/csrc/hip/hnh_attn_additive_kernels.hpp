@@ -320,7 +320,18 @@ __device__ __forceinline__ void attn_add_process(int64_t row, int beg, int end, 
         }
         if (flags & kInternalEpilogue) {  // finish: o = acc / l through the ReLU into the head's column block, and lse; Out is scratch
             const bool live = l_run > 0.0;
-            if (flags & kAttnActMask) {  // ELU / identity in the ReLU's place (wave-uniform)
+            if (flags & HNH_ATTN_ADDEND) {  // act(o + addend), the addend read from the destination by the lane that overwrites it (wave-uniform)
+#pragma unroll
+                for (int v = 0; v < VEC; v++) {
+                    double o[W];
+#pragma unroll
+                    for (int w = 0; w < W; w++) o[w] = 0.0;
+                    if (act[v]) load_w_stream<W>(o, a.relu_dst + row * a.relu_ld + coff[v]);
+#pragma unroll
+                    for (int w = 0; w < W; w++) o[w] = attn_out_addend(live ? acc[v][w] / l_run : 0.0, o[w], flags);
+                    if (act[v]) store_w_stream<W>(a.relu_dst + row * a.relu_ld + coff[v], o);
+                }
+            } else if (flags & kAttnActMask) {  // ELU / identity in the ReLU's place (wave-uniform)
 #pragma unroll
                 for (int v = 0; v < VEC; v++) {
                     double o[W];
@@ -417,7 +428,8 @@ __global__ __launch_bounds__(kBlock) void attn_add_long_kernel(const int2* __res
 }
 
 // a block without any nonzero, forward: the state reset of HNH_FUSED_OUT_OVERWRITE and the finish, as attn_add_process does them for a
-// row whose piece is empty (one wave per row).  ACT: the finish applies ELU / the identity (flags) instead of the ReLU, its own instance
+// row whose piece is empty (one wave per row).  ACT: the finish applies ELU / the identity (flags) instead of the ReLU, or adds the addend
+// that waits in the destination (HNH_ATTN_ADDEND, any activation), its own instance
 template <bool ACT>
 __global__ __launch_bounds__(kBlock) void attn_add_empty_rows_kernel(int64_t rows, AaArgs a, unsigned flags) {
     const int64_t row = ((int64_t)blockIdx.x * kBlock + threadIdx.x) / 64;
@@ -428,8 +440,11 @@ __global__ __launch_bounds__(kBlock) void attn_add_empty_rows_kernel(int64_t row
     const double l = fresh ? 0.0 : a.row_sum[row];
     for (int c = lane; c < a.f; c += 64) {
         const double v = fresh ? 0.0 : a.Out[row * a.ld_out + c];
-        if (finish) a.relu_dst[row * a.relu_ld + c] = l > 0.0 ? (ACT ? attn_out_act(v / l, flags) : fmax(v / l, 0.0)) : 0.0;
-        else a.Out[row * a.ld_out + c] = v;
+        if (finish) {
+            double* d = a.relu_dst + row * a.relu_ld + c;
+            if (ACT && (flags & HNH_ATTN_ADDEND)) *d = attn_out_addend(l > 0.0 ? v / l : 0.0, *d, flags);
+            else *d = l > 0.0 ? (ACT ? attn_out_act(v / l, flags) : fmax(v / l, 0.0)) : 0.0;
+        } else a.Out[row * a.ld_out + c] = v;
     }
     if (lane == 0) {
         a.row_max[row] = m;
@@ -526,7 +541,7 @@ int attn_add_dispatch(hnh_ctx* ctx, const hnh_csr_block* b, const hnh_attn_add* 
     HNH_ENTER(ctx, stream);
     if (!b || !g || (DROP && !drop)) return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": null block or arguments");
     if (int rc = check_common(ctx, b->rows, g->f, who)) return rc;
-    if (flags & ~(HNH_FUSED_OUT_OVERWRITE | (PASS == 0 ? (HNH_ATTN_FINISH | kAttnActMask) : 0u)))
+    if (flags & ~(HNH_FUSED_OUT_OVERWRITE | (PASS == 0 ? (HNH_ATTN_FINISH | kAttnActMask | HNH_ATTN_ADDEND) : 0u)))
         return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": unknown flag");
     if (int rc = check_attn_act_flags(ctx, flags, who)) return rc;
     if (g->f > HNH_ATTN_ADD_MAX_F)
@@ -557,13 +572,13 @@ int attn_add_dispatch(hnh_ctx* ctx, const hnh_csr_block* b, const hnh_attn_add* 
     a.ld_m = g->ld_m; a.ld_dz = g->ld_dz; a.ld_y = g->ld_y; a.ld_out = g->ld_out; a.ld_vec = g->ld_vec; a.relu_ld = g->relu_ld;
     a.f = f; a.fp = fp; a.alpha = g->leaky_alpha;
     hipStream_t st = ctx->streams[stream];
-    const unsigned kflags = (flags & (HNH_FUSED_OUT_OVERWRITE | kAttnActMask)) | (finish ? kInternalEpilogue : 0u);
+    const unsigned kflags = (flags & (HNH_FUSED_OUT_OVERWRITE | kAttnActMask | HNH_ATTN_ADDEND)) | (finish ? kInternalEpilogue : 0u);
     if (b->rowptr == nullptr) {  // a block without nonzeros
         if (b->nnz > 0) return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": null rowptr");
         if (PASS == 0) {
             if (!kflags) return HNH_OK;
             const dim3 grid((unsigned)((b->rows * 64 + kBlock - 1) / kBlock));
-            if (kflags & kAttnActMask) hipLaunchKernelGGL(attn_add_empty_rows_kernel<true>, grid, dim3(kBlock), 0, st, b->rows, a, kflags);
+            if (kflags & (kAttnActMask | HNH_ATTN_ADDEND)) hipLaunchKernelGGL(attn_add_empty_rows_kernel<true>, grid, dim3(kBlock), 0, st, b->rows, a, kflags);
             else hipLaunchKernelGGL(attn_add_empty_rows_kernel<false>, grid, dim3(kBlock), 0, st, b->rows, a, kflags);
             return hnh::check_hip(ctx, hipGetLastError(), "attn_add_empty_rows_kernel launch");
         }

@@ -295,7 +295,18 @@ __device__ __forceinline__ void attn_v2_process(int64_t row, int beg, int end, c
         }
         if (flags & kInternalEpilogue) {  // finish: o = acc / l through the activation into the head's column block, and lse; Out is scratch
             const bool live = l_run > 0.0;
-            if (flags & kAttnActMask) {  // ELU / identity in the ReLU's place (wave-uniform)
+            if (flags & HNH_ATTN_ADDEND) {  // act(o + addend), the addend read from the destination by the lane that overwrites it (wave-uniform)
+#pragma unroll
+                for (int v = 0; v < VEC; v++) {
+                    double o[W];
+#pragma unroll
+                    for (int w = 0; w < W; w++) o[w] = 0.0;
+                    if (act[v]) load_w_stream<W>(o, a.relu_dst + row * a.relu_ld + coff[v]);
+#pragma unroll
+                    for (int w = 0; w < W; w++) o[w] = attn_out_addend(live ? acc[v][w] / l_run : 0.0, o[w], flags);
+                    if (act[v]) store_w_stream<W>(a.relu_dst + row * a.relu_ld + coff[v], o);
+                }
+            } else if (flags & kAttnActMask) {  // ELU / identity in the ReLU's place (wave-uniform)
 #pragma unroll
                 for (int v = 0; v < VEC; v++) {
                     double o[W];
@@ -465,7 +476,7 @@ int attn_v2_dispatch(hnh_ctx* ctx, const hnh_csr_block* b, const hnh_attn_v2* g,
     HNH_ENTER(ctx, stream);
     if (!b || !g) return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": null block or arguments");
     if (int rc = check_common(ctx, b->rows, g->f, who)) return rc;
-    if (flags & ~(HNH_FUSED_OUT_OVERWRITE | (PASS == 0 ? (HNH_ATTN_FINISH | kAttnActMask) : 0u)))
+    if (flags & ~(HNH_FUSED_OUT_OVERWRITE | (PASS == 0 ? (HNH_ATTN_FINISH | kAttnActMask | HNH_ATTN_ADDEND) : 0u)))
         return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": unknown flag");
     if (int rc = check_attn_act_flags(ctx, flags, who)) return rc;
     if (g->f > HNH_ATTN_V2_MAX_F)
@@ -485,7 +496,7 @@ int attn_v2_dispatch(hnh_ctx* ctx, const hnh_csr_block* b, const hnh_attn_v2* g,
     a.ld_x = g->ld_x; a.ld_dz = g->ld_dz; a.ld_y = g->ld_y; a.ld_out = g->ld_out; a.ld_out2 = g->ld_out2; a.relu_ld = g->relu_ld;
     a.f = f; a.fp = fp; a.alpha = g->leaky_alpha;
     hipStream_t st = ctx->streams[stream];
-    const unsigned kflags = (flags & (HNH_FUSED_OUT_OVERWRITE | kAttnActMask)) | (finish ? kInternalEpilogue : 0u);
+    const unsigned kflags = (flags & (HNH_FUSED_OUT_OVERWRITE | kAttnActMask | HNH_ATTN_ADDEND)) | (finish ? kInternalEpilogue : 0u);
     if (b->rowptr == nullptr) {  // a block without nonzeros
         if (b->nnz > 0) return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": null rowptr");
         if (PASS == 0) {  // the state reset and the finish of a row whose piece is empty: the additive forward's kernel does exactly that
@@ -494,7 +505,7 @@ int attn_v2_dispatch(hnh_ctx* ctx, const hnh_csr_block* b, const hnh_attn_v2* g,
             e.lse = g->lse; e.Out = g->Out; e.row_max = g->row_max; e.row_sum = g->row_sum; e.relu_dst = g->relu_dst;
             e.ld_out = g->ld_out; e.relu_ld = g->relu_ld; e.f = f; e.fp = fp; e.alpha = g->leaky_alpha;
             const dim3 grid((unsigned)((b->rows * 64 + kBlock - 1) / kBlock));
-            if (kflags & kAttnActMask) hipLaunchKernelGGL(attn_add_empty_rows_kernel<true>, grid, dim3(kBlock), 0, st, b->rows, e, kflags);
+            if (kflags & (kAttnActMask | HNH_ATTN_ADDEND)) hipLaunchKernelGGL(attn_add_empty_rows_kernel<true>, grid, dim3(kBlock), 0, st, b->rows, e, kflags);
             else hipLaunchKernelGGL(attn_add_empty_rows_kernel<false>, grid, dim3(kBlock), 0, st, b->rows, e, kflags);
             return hnh::check_hip(ctx, hipGetLastError(), "attn_add_empty_rows_kernel launch");
         }

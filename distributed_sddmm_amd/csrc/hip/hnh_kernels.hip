@@ -32,6 +32,7 @@
 #include "hnh_attn_additive.h"
 #include "hnh_attn_dropout.h"
 #include "hnh_attn_v2.h"
+#include "hnh_gat_skip.h"
 
 namespace {
 
@@ -220,15 +221,26 @@ constexpr unsigned kInternalEpilogue = 0x200u;   // flag bit: apply Extras::x_sc
 // the public activation bits of a finishing attention call (hnh_attention.h) travel to the kernels in their flags word as they are
 constexpr unsigned kAttnActMask = HNH_ATTN_ACT_ELU | HNH_ATTN_ACT_IDENTITY;
 static_assert((kAttnActMask & (kInternalSplitLong | kInternalEpilogue | (0x1fu << kLongRowShift) | HNH_FUSED_VALUES_OVERWRITE | HNH_FUSED_OUT_OVERWRITE |
-                               HNH_FUSED_LEAKY_RELU | HNH_ATTN_FINISH)) == 0,
+                               HNH_FUSED_LEAKY_RELU | HNH_ATTN_FINISH | HNH_ATTN_ADDEND)) == 0,
               "the activation bits must not meet another flag");
+// ... and the addend bit (hnh_gat_skip.h) travels the same way
+static_assert((HNH_ATTN_ADDEND & (kInternalSplitLong | kInternalEpilogue | (0x1fu << kLongRowShift) | HNH_FUSED_VALUES_OVERWRITE | HNH_FUSED_OUT_OVERWRITE |
+                                  HNH_FUSED_LEAKY_RELU | HNH_ATTN_FINISH)) == 0,
+              "the addend bit must not meet another flag");
 // ELU or the identity on a finished attention row's value (a wave-uniform choice; the ReLU default stays where it was)
 __device__ __forceinline__ double attn_out_act(double o, unsigned flags) {
     return (flags & HNH_ATTN_ACT_IDENTITY) ? o : (o > 0.0 ? o : expm1(o));
 }
-// the flag checks the three finishing entry points share: 0, or the status of the complaint
+// HNH_ATTN_ADDEND (hnh_gat_skip.h): the finished row's value with the addend that waited in the destination, through whichever
+// activation the flags name (a wave-uniform choice; never reached by a call without the flag)
+__device__ __forceinline__ double attn_out_addend(double o, double addend, unsigned flags) {
+    const double z = o + addend;
+    return (flags & kAttnActMask) ? attn_out_act(z, flags) : fmax(z, 0.0);
+}
+// the flag checks the finishing entry points share: 0, or the status of the complaint
 inline int check_attn_act_flags(hnh_ctx* ctx, unsigned flags, const char* who) {
     const unsigned act = flags & kAttnActMask;
+    if ((flags & HNH_ATTN_ADDEND) && !(flags & HNH_ATTN_FINISH)) return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": HNH_ATTN_ADDEND needs HNH_ATTN_FINISH");
     if (act == kAttnActMask) return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": HNH_ATTN_ACT_ELU and HNH_ATTN_ACT_IDENTITY exclude each other");
     if (act != 0 && !(flags & HNH_ATTN_FINISH)) return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": an activation flag needs HNH_ATTN_FINISH");
     return HNH_OK;
@@ -748,7 +760,18 @@ __device__ __forceinline__ void process_row(int64_t row, int beg, int end, bool 
         }
         if (flags & kInternalEpilogue) {  // finish: o = Out / l through the ReLU into the head's column block, and lse; Out is scratch
             const bool live = l_run > 0.0;
-            if (flags & kAttnActMask) {  // ELU / identity in the ReLU's place (wave-uniform)
+            if (flags & HNH_ATTN_ADDEND) {  // act(o + addend), the addend read from the destination by the lane that overwrites it (wave-uniform)
+#pragma unroll
+                for (int v = 0; v < VEC; v++) {
+                    double o[W];
+#pragma unroll
+                    for (int w = 0; w < W; w++) o[w] = 0.0;
+                    if (act[v]) load_w_stream<W>(o, ex.relu_dst + row * ex.relu_ld + coff[v]);
+#pragma unroll
+                    for (int w = 0; w < W; w++) o[w] = attn_out_addend(live ? acc[v][w] / l_run : 0.0, o[w], flags);
+                    if (act[v]) store_w_stream<W>(ex.relu_dst + row * ex.relu_ld + coff[v], o);
+                }
+            } else if (flags & kAttnActMask) {  // ELU / identity in the ReLU's place (wave-uniform)
 #pragma unroll
                 for (int v = 0; v < VEC; v++) {
                     double o[W];
@@ -2686,7 +2709,8 @@ int hnh_expand_rowptr(hnh_ctx* ctx, int64_t rows, const int32_t* rowptr, int32_t
 // ---------------------------------------------------------------- neighbourhood-softmax attention (include/hnh_attention.h)
 namespace {
 // a block without any nonzero: the state reset of HNH_FUSED_OUT_OVERWRITE and the finish of HNH_ATTN_FINISH, as process_row does them
-// for a row whose piece is empty (one wave per row).  ACT: the finish applies ELU / the identity (flags) instead of the ReLU, its own instance
+// for a row whose piece is empty (one wave per row).  ACT: the finish applies ELU / the identity (flags) instead of the ReLU, or adds the
+// addend that waits in the destination (HNH_ATTN_ADDEND, any activation), its own instance
 template <bool ACT>
 __global__ __launch_bounds__(kBlock) void attn_empty_rows_kernel(int64_t rows, double* __restrict__ Out, int R, unsigned flags, Extras ex) {
     const int64_t row = ((int64_t)blockIdx.x * kBlock + threadIdx.x) / 64;
@@ -2697,8 +2721,11 @@ __global__ __launch_bounds__(kBlock) void attn_empty_rows_kernel(int64_t rows, d
     const double l = fresh ? 0.0 : ex.row_sum[row];
     for (int c = lane; c < R; c += 64) {
         const double a = fresh ? 0.0 : Out[row * R + c];
-        if (finish) ex.relu_dst[row * ex.relu_ld + c] = l > 0.0 ? (ACT ? attn_out_act(a / l, flags) : fmax(a / l, 0.0)) : 0.0;
-        else Out[row * R + c] = a;
+        if (finish) {
+            double* d = ex.relu_dst + row * ex.relu_ld + c;
+            if (ACT && (flags & HNH_ATTN_ADDEND)) *d = attn_out_addend(l > 0.0 ? a / l : 0.0, *d, flags);
+            else *d = l > 0.0 ? (ACT ? attn_out_act(a / l, flags) : fmax(a / l, 0.0)) : 0.0;
+        } else Out[row * R + c] = a;
     }
     if (lane == 0) {
         ex.row_max[row] = m;
@@ -2740,7 +2767,7 @@ int hnh_attn_softmax_csr_p(hnh_ctx* ctx, const hnh_csr_block* b, double* values,
     const char* who = "hnh_attn_softmax_csr_p";
     if (!b || !state) return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": null block or state");
     if (int rc = check_common(ctx, b->rows, R, who)) return rc;
-    if (flags & ~(HNH_FUSED_VALUES_OVERWRITE | HNH_FUSED_OUT_OVERWRITE | HNH_ATTN_FINISH | kAttnActMask))
+    if (flags & ~(HNH_FUSED_VALUES_OVERWRITE | HNH_FUSED_OUT_OVERWRITE | HNH_ATTN_FINISH | kAttnActMask | HNH_ATTN_ADDEND))
         return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": unknown flag");
     if (int rc = check_attn_act_flags(ctx, flags, who)) return rc;
     const bool finish = (flags & HNH_ATTN_FINISH) != 0;
@@ -2759,9 +2786,9 @@ int hnh_attn_softmax_csr_p(hnh_ctx* ctx, const hnh_csr_block* b, double* values,
     hipStream_t st = ctx->streams[stream];
     if (b->rowptr == nullptr) {  // a block without nonzeros
         if (b->nnz > 0) return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": null rowptr");
-        const unsigned f = (flags & (HNH_FUSED_OUT_OVERWRITE | kAttnActMask)) | (finish ? kInternalEpilogue : 0u);
+        const unsigned f = (flags & (HNH_FUSED_OUT_OVERWRITE | kAttnActMask | HNH_ATTN_ADDEND)) | (finish ? kInternalEpilogue : 0u);
         const dim3 grid((unsigned)((b->rows * 64 + kBlock - 1) / kBlock));
-        if (f & kAttnActMask) hipLaunchKernelGGL(attn_empty_rows_kernel<true>, grid, dim3(kBlock), 0, st, b->rows, Out, R, f, ex);
+        if (f & (kAttnActMask | HNH_ATTN_ADDEND)) hipLaunchKernelGGL(attn_empty_rows_kernel<true>, grid, dim3(kBlock), 0, st, b->rows, Out, R, f, ex);
         else hipLaunchKernelGGL(attn_empty_rows_kernel<false>, grid, dim3(kBlock), 0, st, b->rows, Out, R, f, ex);
         return hnh::check_hip(ctx, hipGetLastError(), "attn_empty_rows_kernel launch");
     }
@@ -2775,7 +2802,7 @@ int hnh_attn_softmax_csr_p(hnh_ctx* ctx, const hnh_csr_block* b, double* values,
                                                        " beyond the one-pass instances (R <= 512 even with X, Y, Out and relu_dst 16-byte aligned and relu_ld "
                                                        "even, R <= 256 otherwise; a softmax cannot be composed of two passes)");
     bool done = false;
-    const unsigned f = (flags & (HNH_FUSED_VALUES_OVERWRITE | HNH_FUSED_OUT_OVERWRITE | kAttnActMask)) | HNH_FUSED_LEAKY_RELU;
+    const unsigned f = (flags & (HNH_FUSED_VALUES_OVERWRITE | HNH_FUSED_OUT_OVERWRITE | kAttnActMask | HNH_ATTN_ADDEND)) | HNH_FUSED_LEAKY_RELU;
     if (int rc = dispatch_row<Op::kFusedSoftmax>(ctx, st, stream, s, b->rows, b->nnz, b->max_row_nnz, window ? -1 : b->cols, b->rowptr, b->col_idx, values,
                                                  nullptr, X, Y, Out, R, f, ex, finish ? &done : nullptr, window, b->plan))
         return rc;

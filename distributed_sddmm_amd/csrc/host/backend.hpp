@@ -12,6 +12,7 @@
 #include "hnh_attn_grad.h"
 #include "hnh_attn_coef.h"
 #include "hnh_attn_v2.h"
+#include "hnh_gat_skip.h"
 #include "hnh_grad.h"
 #include "hnh_kernels.h"
 #include "hnh_train.h"
@@ -68,6 +69,9 @@ struct Backend {
     HNH_FN(hnh_attn_v2_fwd_csr_p) HNH_FN(hnh_attn_v2_row_csr_p) HNH_FN(hnh_attn_v2_col_csr_p) HNH_FN(hnh_attn_v2_finish_f64)
     // OPTIONAL group (include/hnh_attn_coef.h), bound the same way: only GAT::attention_coefficients needs it
     HNH_FN(hnh_attn_coef_csr_p) HNH_FN(hnh_attn_coef_scores_f64)
+    // OPTIONAL group (include/hnh_gat_skip.h), bound the same way: only a GAT layer with a bias or a skip connection needs it
+    // (its presence also says that the library knows the HNH_ATTN_ADDEND flag)
+    HNH_FN(hnh_skip_addend_cols_f64) HNH_FN(hnh_skip_grad_cols_f64) HNH_FN(hnh_colsum_f64_workspace) HNH_FN(hnh_colsum_f64)
 #ifdef HNH_MEASUREMENT_AIDS
     HNH_FN(hnh_stream_delay_us) HNH_FN(hnh_stream_paced_copy) HNH_FN(hnh_stream_pace_begin) HNH_FN(hnh_stream_pace_end)
 #endif

@@ -780,6 +780,41 @@ int hnh_gat_set_score(hnh_gat* g, int mode) {
 int hnh_gat_set_activation(hnh_gat* g, int layer, int mode) {
     return guarded(g->w, [&] { g->g->set_activation(layer, mode); });
 }
+int hnh_gat_set_residual(hnh_gat* g, int layer, int mode) {
+    return guarded(g->w, [&] { g->g->set_residual(layer, mode); });
+}
+int hnh_gat_set_residual_weight(hnh_gat* g, int layer, const double* host) {
+    return guarded(g->w, [&] { g->g->set_residual_weight(layer, host); });
+}
+int hnh_gat_get_residual_weight(hnh_gat* g, int layer, double* host) {
+    return guarded(g->w, [&] { g->g->get_residual_weight(layer, host); });
+}
+int hnh_gat_get_residual_weight_grad(hnh_gat* g, int layer, double* host) {
+    return guarded(g->w, [&] {
+        GAT& gat = *g->g;
+        gat.residual(layer);  // (the layer index)
+        if (!host) throw hnh::Error("Error, hnh_gat_get_residual_weight_grad: null pointer!");
+        if (gat.res_weight_grads.size() != gat.layers.size() || gat.res_weight_grads[(size_t)layer].size() == 0)
+            throw hnh::Error("Error, no GAT residual-weight gradient yet: call hnh_gat_backward with residual projection on this layer first!");
+        gat.res_weight_grads[(size_t)layer].copy_to_host(host);
+    });
+}
+int hnh_gat_set_bias(hnh_gat* g, int layer, const double* host_or_null) {
+    return guarded(g->w, [&] { g->g->set_bias(layer, host_or_null); });
+}
+int hnh_gat_get_bias(hnh_gat* g, int layer, double* host) {
+    return guarded(g->w, [&] { g->g->get_bias(layer, host); });
+}
+int hnh_gat_get_bias_grad(hnh_gat* g, int layer, double* host) {
+    return guarded(g->w, [&] {
+        GAT& gat = *g->g;
+        gat.has_bias(layer);  // (the layer index)
+        if (!host) throw hnh::Error("Error, hnh_gat_get_bias_grad: null pointer!");
+        if (gat.bias_grads.size() != gat.layers.size() || gat.bias_grads[(size_t)layer].size() == 0)
+            throw hnh::Error("Error, no GAT bias gradient yet: call hnh_gat_backward with a bias on this layer first!");
+        gat.bias_grads[(size_t)layer].copy_to_host(host);
+    });
+}
 int hnh_gat_set_attn_vectors(hnh_gat* g, int layer, int head, const double* a1_host, const double* a2_host) {
     return guarded(g->w, [&] {
         if (layer < 0 || layer >= (int)g->g->layers.size()) throw hnh::Error("Error, GAT layer index out of range!");

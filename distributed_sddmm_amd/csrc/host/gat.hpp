@@ -94,11 +94,31 @@
 // on 15d_fusion2 with c = 1; attention none keeps ReLU only, and everything else raises before anything is launched.
 // The published network is activation elu on the hidden layers and identity on the last with HNH_GAT_HEADS_MEAN: the loss then averages the raw
 // head aggregates.  With the default relu on the last layer the heads pass through the ReLU epilogue before they are averaged.
+//
+// Bias and skip connections (an addition; include/hnh_gat_skip.h; set_bias(layer, b), set_residual(layer, mode), both off by default, which
+// launches exactly the kernels above).  out[:, h f ..] = phi_l(o_h + r[:, h f ..] + b[h f ..]) with r = 0 (HNH_GAT_RESIDUAL_NONE), the layer
+// input X (IDENTITY, needs input_features == H f) or X W_res (PROJECTION, W_res learned, kept per head as input_features x f operands of
+// hnh_gemm_f64); X is Xd under feature dropout, what the head products use.  Forward: the addend r + b of head h belongs to the head's
+// product stage (the auxiliary stream, next to head_product and head_scores): for PROJECTION one more product X W_res_h into a scratch,
+// then hnh_skip_addend_cols_f64 writes the addend into the head's column block of buffers[l + 1], where the head's finishing launch on
+// the compute stream reads it and overwrites it with the activated sum (HNH_ATTN_ADDEND next to activation_flag).  Order: ev_gemm of the
+// head's stage orders the addend before the finish; the two streams write disjoint column blocks; and every earlier reader of
+// buffers[l + 1] (the next layer's feature mask, the loss, the backward pass, the coefficient export, copies to the host) runs on the
+// compute stream before the layer's ev_input mark, which the auxiliary stream awaits before its first write, or on the auxiliary stream
+// itself (the next layer's products of the previous pass), which is in order.  Backward: hnh_skip_grad_cols_f64 in place of
+// hnh_relu_grad_cols_f64 / hnh_act_grad_cols_f64, with res = X's column block (IDENTITY) or the recomputed X W_res_h (PROJECTION): the same dZ,
+// delta_i = <dZ_i, phi^{-1}(out_i) - r_i - b> (head_delta hands it out, ReLU included), and every head's dZ also into dZ_all (rows x H f).
+// After the head loop, on the compute stream: bias_grads[l] = colsum(dZ_all) (hnh_colsum_f64) and res_weight_grads[l] = X^T dZ_all
+// (hnh_gemm_tn_f64), both summed over the world like dW, and dX += dZ_all W_res^T (PROJECTION) or dZ_all (IDENTITY) before the feature
+// mask.  Neither a pre-activation nor an addend is kept between the passes.  Supported with attention softmax (every score, both backward
+// modes, any dropout the score allows, any activation) on 15d_fusion2 with c = 1; everything else raises before anything is launched
+// (check_skip_supported).  optimizer_step appends every enabled bias and W_res to its table; weight decay applies to them as to W.
 #pragma once
 #include "dense_shift_15d.hpp"
 #include "distributed_sparse.hpp"
 #include <cmath>
 #include <cstdlib>
+#include <cstring>
 #include <map>
 #include <tuple>
 #include "hnh_dist.h"
@@ -126,6 +146,10 @@ public:
         world_ = d_ops->world;  // not owned by the operator: benchmark_dist.cpp:166 deletes d_ops while its GAT is still alive
         layers = l_input;
         act_.assign(layers.size(), HNH_GAT_ACT_RELU);
+        res_mode_.assign(layers.size(), HNH_GAT_RESIDUAL_NONE);
+        bias_on_.assign(layers.size(), 0);
+        bias_.assign(layers.size(), DenseMatrix());
+        w_res_.assign(layers.size(), std::vector<DenseMatrix>());
         d_ops->setRValue(layers[0].input_features);
         buffers.push_back(d_ops->like_B_matrix(0.0));
         for (size_t i = 0; i < layers.size(); i++) {
@@ -181,6 +205,76 @@ public:
         act_[(size_t)i] = mode;
     }
 
+    // Skip connection of layer i (include/hnh_dist.h): HNH_GAT_RESIDUAL_NONE | _IDENTITY | _PROJECTION; a change invalidates the stored forward
+    // pass.  PROJECTION allocates W_res (zero until set) on first use.  Kept here, not in GATLayer, for set_activation's reason.
+    int residual(int i) const {
+        check_layer(i);
+        return res_mode_[(size_t)i];
+    }
+    void set_residual(int i, int mode) {
+        check_layer(i);
+        if (mode != HNH_GAT_RESIDUAL_NONE && mode != HNH_GAT_RESIDUAL_IDENTITY && mode != HNH_GAT_RESIDUAL_PROJECTION)
+            throw hnh::Error("Error, unknown GAT residual mode " + std::to_string(mode) + " (none = 0, identity = 1, projection = 2)!");
+        const GATLayer& L = layers[(size_t)i];
+        if (mode == HNH_GAT_RESIDUAL_IDENTITY && L.input_features != L.num_heads * L.features_per_head)
+            throw hnh::Error("Error, GAT residual identity of layer " + std::to_string(i) + " needs input_features == num_heads * features_per_head, not " +
+                             std::to_string(L.input_features) + " and " + std::to_string(L.num_heads * L.features_per_head) + ": use residual projection!");
+        if (mode == HNH_GAT_RESIDUAL_PROJECTION) ensure_residual_weight(i);
+        if (mode != res_mode_[(size_t)i]) invalidate_forward();
+        res_mode_[(size_t)i] = mode;
+    }
+    // W_res of layer i as one HOST matrix, row-major input_features x (num_heads * features_per_head); the device keeps it per head
+    void set_residual_weight(int i, const double* host) {
+        check_layer(i);
+        if (host == nullptr) throw hnh::Error("Error, GAT set_residual_weight: null pointer!");
+        ensure_residual_weight(i);
+        const GATLayer& L = layers[(size_t)i];
+        const int64_t k = L.input_features, f = L.features_per_head, hf = (int64_t)L.num_heads * f;
+        std::vector<double> head((size_t)(k * f));
+        for (int h = 0; h < L.num_heads; h++) {
+            for (int64_t r = 0; r < k; r++) std::memcpy(head.data() + r * f, host + r * hf + (int64_t)h * f, sizeof(double) * (size_t)f);
+            w_res_[(size_t)i][(size_t)h].copy_from_host(head.data());  // (waits for the copy: `head` is reused)
+        }
+        invalidate_forward();
+    }
+    void get_residual_weight(int i, double* host) {
+        check_layer(i);
+        if (host == nullptr) throw hnh::Error("Error, GAT get_residual_weight: null pointer!");
+        if (w_res_[(size_t)i].empty()) throw hnh::Error("Error, GAT layer " + std::to_string(i) + " has no residual weight: set_residual(layer, projection) first!");
+        const GATLayer& L = layers[(size_t)i];
+        const int64_t k = L.input_features, f = L.features_per_head, hf = (int64_t)L.num_heads * f;
+        for (int h = 0; h < L.num_heads; h++) {
+            const std::vector<double> head = w_res_[(size_t)i][(size_t)h].to_host();
+            for (int64_t r = 0; r < k; r++) std::memcpy(host + r * hf + (int64_t)h * f, head.data() + r * f, sizeof(double) * (size_t)f);
+        }
+    }
+    // The bias of layer i (num_heads * features_per_head HOST entries); nullptr switches it off.  Invalidates the stored forward pass.
+    bool has_bias(int i) const {
+        check_layer(i);
+        return bias_on_[(size_t)i] != 0;
+    }
+    void set_bias(int i, const double* host) {
+        check_layer(i);
+        if (host == nullptr) {
+            if (bias_on_[(size_t)i]) invalidate_forward();
+            bias_on_[(size_t)i] = 0;
+            return;
+        }
+        const GATLayer& L = layers[(size_t)i];
+        const int64_t hf = (int64_t)L.num_heads * L.features_per_head;
+        DenseMatrix& b = bias_[(size_t)i];
+        if (b.rows() != hf || b.cols() != 1) b = DenseMatrix(hf, 1);
+        b.copy_from_host(host);
+        bias_on_[(size_t)i] = 1;
+        invalidate_forward();
+    }
+    void get_bias(int i, double* host) {
+        check_layer(i);
+        if (host == nullptr) throw hnh::Error("Error, GAT get_bias: null pointer!");
+        if (!bias_on_[(size_t)i]) throw hnh::Error("Error, GAT layer " + std::to_string(i) + " has no bias: set_bias first!");
+        bias_[(size_t)i].copy_to_host(host);
+    }
+
     // Dropout (include/hnh_attn_dropout.h): rates in [0, 1) on the attention coefficients (score ADDITIVE only; checked by forwardPass)
     // and on every layer's input, masks keyed by `seed`.  (0, 0) is the default: today's kernels at today's widths.  A change
     // invalidates the stored forward pass.
@@ -234,6 +328,7 @@ public:
         DenseMatrix A;
         if (j == 0) drop_input(i);
         head_product(i, j, A, HNH_STREAM_COMPUTE);
+        head_addend(i, j, HNH_STREAM_COMPUTE);
         if (score_ == HNH_GAT_SCORE_ADDITIVE) {
             shape_scored(i, scored[0]);
             head_scores(i, j, A, scored[0], HNH_STREAM_COMPUTE);
@@ -251,6 +346,7 @@ public:
         const bool additive = score_ == HNH_GAT_SCORE_ADDITIVE, gatv2 = score_ == HNH_GAT_SCORE_GATV2;
         check_dropout_supported();
         check_activation_supported();
+        check_skip_supported();
         if (attention_ == HNH_GAT_ATTENTION_SOFTMAX && !additive && !gatv2) check_softmax_supported();
         if (additive) check_additive_supported();
         if (gatv2) check_gatv2_supported();
@@ -272,11 +368,13 @@ public:
                 shape_product((int)i, product[b]);
                 if (additive) shape_scored((int)i, scored[b]);
             }
+            shape_residual((int)i);
             drop_input((int)i);  // (Xd: allocated and made on the compute stream, before the mark below)
             // the layer's input is complete, and both product buffers are free, once the compute stream gets here
             w->event_record(ev_input, HNH_STREAM_COMPUTE);
             w->event_wait(ev_input, HNH_STREAM_AUX);
             head_product((int)i, 0, product[0], HNH_STREAM_AUX);
+            head_addend((int)i, 0, HNH_STREAM_AUX);  // (the head's addend into its column block of buffers[i + 1]: the product stage too)
             if (additive) head_scores((int)i, 0, product[0], scored[0], HNH_STREAM_AUX);  // (the score kernel belongs to the product stage)
             w->event_record(ev_gemm[0], HNH_STREAM_AUX);
             for (int j = 0; j < H; j++) {
@@ -285,6 +383,7 @@ public:
                     // product[(j + 1) % 2] was last read by head j - 1, which the compute stream has been given already
                     if (j >= 1) w->event_wait(ev_head[(j - 1) % 2], HNH_STREAM_AUX);
                     head_product((int)i, j + 1, product[(j + 1) % 2], HNH_STREAM_AUX);
+                    head_addend((int)i, j + 1, HNH_STREAM_AUX);
                     if (additive) head_scores((int)i, j + 1, product[(j + 1) % 2], scored[(j + 1) % 2], HNH_STREAM_AUX);
                     w->event_record(ev_gemm[(j + 1) % 2], HNH_STREAM_AUX);
                 }
@@ -305,6 +404,7 @@ public:
     void backwardPass(const DenseMatrix& grad_out) {
         check_dropout_supported();
         check_activation_supported();
+        check_skip_supported();
         check_backward_supported();
         if (!forward_valid_) throw hnh::Error("Error, GAT backwardPass needs a forwardPass first (and a new one after set_weight / set_input)!");
         const DenseMatrix& last = buffers.back();
@@ -315,6 +415,10 @@ public:
             input_grads.assign((size_t)L, DenseMatrix());
         }
         if (learns_vectors() && (int)attn_grads.size() != L) attn_grads.assign((size_t)L, DenseMatrix());
+        if ((int)bias_grads.size() != L) {
+            bias_grads.assign((size_t)L, DenseMatrix());
+            res_weight_grads.assign((size_t)L, DenseMatrix());
+        }
         const DenseMatrix* G = &grad_out;
         for (int i = L - 1; i >= 0; i--) {
             backward_layer(i, *G);
@@ -468,12 +572,18 @@ public:
                 var_a_[i * 2 + q] = DenseMatrix::Constant(hf, 1, 0.0);
             }
         }
+        mom_b_.assign(L, DenseMatrix());
+        var_b_.assign(L, DenseMatrix());
+        mom_r_.assign(L, std::vector<DenseMatrix>());
+        var_r_.assign(L, std::vector<DenseMatrix>());
+        ensure_skip_moments();
         optim_steps_ = 0;
         optimizer_set_ = true;
     }
     int64_t optimizer_steps() const { return optim_steps_; }
 
-    // One optimizer step from the gradients of the last backwardPass: every W, and a1, a2 with score ADDITIVE (a1 with GATV2), in one table.  Invalidates
+    // One optimizer step from the gradients of the last backwardPass: every W, a1, a2 with score ADDITIVE (a1 with GATV2), and every enabled
+    // bias and W_res (include/hnh_gat_skip.h), in one table.  Invalidates
     // the stored forward pass.  No host synchronisation.
     void optimizer_step() {
         const hnh::Backend* be = d_ops->world->be;
@@ -500,6 +610,23 @@ public:
                 if (additive) table.push_back({L.a2.data(), 1, da.data() + 1, 2, mom_a_[i * 2 + 1].data(), var_a_[i * 2 + 1].data(), hf, 1});  // (GATV2 does not use a2)
             }
         }
+        ensure_skip_moments();  // (a bias or a projection enabled after set_optimizer starts from zero moments)
+        for (size_t i = 0; i < layers.size(); i++) {
+            GATLayer& L = layers[i];
+            const int64_t f = L.features_per_head, hf = (int64_t)L.num_heads * f, k = L.input_features;
+            if (bias_on_[i]) {
+                if (bias_grads.size() != layers.size() || bias_grads[i].rows() != hf || bias_grads[i].cols() != 1)
+                    throw hnh::Error("Error, GAT optimizer_step needs the bias gradient of a backwardPass since set_bias!");
+                table.push_back({bias_[i].data(), 1, bias_grads[i].data(), 1, mom_b_[i].data(), var_b_[i].data(), hf, 1});
+            }
+            if (res_mode_[i] == HNH_GAT_RESIDUAL_PROJECTION) {
+                if (res_weight_grads.size() != layers.size() || res_weight_grads[i].rows() != k || res_weight_grads[i].cols() != hf)
+                    throw hnh::Error("Error, GAT optimizer_step needs the residual-weight gradient of a backwardPass since set_residual!");
+                for (int h = 0; h < L.num_heads; h++)
+                    table.push_back({w_res_[i][(size_t)h].data(), f, res_weight_grads[i].data() + (int64_t)h * f, hf, mom_r_[i][(size_t)h].data(),
+                                     var_r_[i][(size_t)h].data(), k, f});
+            }
+        }
         optim_steps_++;
         hnh_optim hy = optim_;
         hy.bias1 = 1.0 - std::pow(hy.beta1, (double)optim_steps_);
@@ -516,6 +643,7 @@ public:
         check_train_supported(true);
         check_dropout_supported();
         check_activation_supported();
+        check_skip_supported();
         check_backward_supported();
         const uint64_t seed0 = seed_;
         const int64_t steps0 = optim_steps_;
@@ -540,6 +668,7 @@ public:
         check_train_supported(false);
         check_dropout_supported();  // (an object that forwardPass and train_step refuse is not evaluated either)
         check_activation_supported();
+        check_skip_supported();
         if (mask != nullptr && n != d_ops->M) throw hnh::Error("Error, GAT evaluate: the mask needs " + std::to_string(d_ops->M) + " entries, not " + std::to_string(n) + "!");
         LabelSet other;
         if (mask != nullptr) other = make_label_set(mask);
@@ -583,6 +712,9 @@ public:
     // score ADDITIVE: attn_grads[i] is (num_heads * features_per_head) x 2 of layer i, row h f + c = (da1_h[c], da2_h[c]), the same on every rank;
     // score GATV2: the same shape, row h f + c = (da_h[c], 0)
     std::vector<DenseMatrix> attn_grads;
+    // bias_grads[i] ((num_heads * features_per_head) x 1, a layer with a bias) and res_weight_grads[i] (input_features x (num_heads *
+    // features_per_head), residual projection) of layer i, the same on every rank; empty for a layer without
+    std::vector<DenseMatrix> bias_grads, res_weight_grads;
 
 private:
     hnh::World* world_ = nullptr;
@@ -595,6 +727,16 @@ private:
     std::vector<int> act_;                // HNH_GAT_ACT_* of every layer's output
     DenseMatrix act_delta_;               // a non-ReLU layer's delta of the head in hand: backward_layer writes it, head_delta hands it out
     std::vector<DenseMatrix> xd_;         // feature dropout: Xd of every layer (allocated only then)
+    // bias and skip connections (include/hnh_gat_skip.h): per layer the residual mode, W_res per head (input_features x f each, the
+    // contiguous operand of hnh_gemm_f64; projection only), the bias (H f x 1) with its enabled bit; the projection of the head in
+    // flight (the auxiliary stream's scratch) and the moments of both parameters
+    std::vector<int> res_mode_;
+    std::vector<char> bias_on_;
+    std::vector<DenseMatrix> bias_;
+    std::vector<std::vector<DenseMatrix>> w_res_;
+    DenseMatrix res_product_;
+    std::vector<DenseMatrix> mom_b_, var_b_;
+    std::vector<std::vector<DenseMatrix>> mom_r_, var_r_;
     // training (include/hnh_train.h): this rank's labels on the device (-1: not in the loss) with the world's labelled count; the host's
     // copy of all labels and of the training mask (loss / evaluate build other sets from them); the optimizer and its moments
     struct LabelSet {
@@ -814,6 +956,95 @@ private:
         const int m = act_[(size_t)i];
         return m == HNH_GAT_ACT_ELU ? HNH_ATTN_ACT_ELU : (m == HNH_GAT_ACT_IDENTITY ? HNH_ATTN_ACT_IDENTITY : 0u);
     }
+    // ---- bias and skip connections (include/hnh_gat_skip.h)
+    bool has_addend(int i) const { return bias_on_[(size_t)i] != 0 || res_mode_[(size_t)i] != HNH_GAT_RESIDUAL_NONE; }
+    // the finishing call's HNH_ATTN_ADDEND of a layer whose heads have an addend; 0 without: today's launches
+    unsigned addend_flag(int i) const { return has_addend(i) ? HNH_ATTN_ADDEND : 0u; }
+    void ensure_residual_weight(int i) {
+        GATLayer& L = layers[(size_t)i];
+        std::vector<DenseMatrix>& wr = w_res_[(size_t)i];
+        if (wr.size() == (size_t)L.num_heads) return;
+        wr.clear();
+        for (int h = 0; h < L.num_heads; h++) wr.push_back(DenseMatrix::Constant(L.wMats[(size_t)h].rows(), L.wMats[(size_t)h].cols(), 0.0));
+    }
+    // zeroed moments for every enabled bias and W_res that has none yet (set_optimizer emptied them all)
+    void ensure_skip_moments() {
+        if (mom_b_.size() != layers.size()) return;  // (no optimizer yet)
+        const bool adam = optim_.kind == HNH_OPTIM_ADAM;
+        for (size_t i = 0; i < layers.size(); i++) {
+            const int64_t hf = (int64_t)layers[i].num_heads * layers[i].features_per_head;
+            if (bias_on_[i] && var_b_[i].rows() != hf) {
+                if (adam) mom_b_[i] = DenseMatrix::Constant(hf, 1, 0.0);
+                var_b_[i] = DenseMatrix::Constant(hf, 1, 0.0);
+            }
+            if (res_mode_[i] == HNH_GAT_RESIDUAL_PROJECTION && var_r_[i].size() != w_res_[i].size()) {
+                mom_r_[i].clear();
+                var_r_[i].clear();
+                for (const DenseMatrix& W : w_res_[i]) {
+                    mom_r_[i].push_back(adam ? DenseMatrix::Constant(W.rows(), W.cols(), 0.0) : DenseMatrix());
+                    var_r_[i].push_back(DenseMatrix::Constant(W.rows(), W.cols(), 0.0));
+                }
+            }
+        }
+    }
+    static const char* residual_name(int mode) { return mode == HNH_GAT_RESIDUAL_IDENTITY ? "identity" : (mode == HNH_GAT_RESIDUAL_PROJECTION ? "projection" : "none"); }
+    // The conditions of a layer with a bias or a skip connection, checked before anything is launched: the attention mode (the finish of
+    // a softmax pass takes the addend), the schedule (the softmax's), the shapes of residual identity, then the kernel group.  Every
+    // layer without: nothing to check, today's launches.
+    void check_skip_supported() {
+        for (size_t i = 0; i < layers.size(); i++) {
+            if (!has_addend((int)i)) continue;
+            const std::string what = (res_mode_[i] != HNH_GAT_RESIDUAL_NONE ? std::string("residual ") + residual_name(res_mode_[i]) : std::string("bias")) +
+                                     " of layer " + std::to_string(i);
+            if (attention_ != HNH_GAT_ATTENTION_SOFTMAX)
+                throw hnh::Error("Error, GAT " + what + " supports attention mode softmax only, not attention mode none: its passes have no addend "
+                                 "(include/hnh_gat_skip.h)");
+            require_own_rows(what);
+            if (res_mode_[i] == HNH_GAT_RESIDUAL_IDENTITY) {
+                const DenseMatrix &X = buffers[i], &out = buffers[i + 1];
+                // (layer 0's input is laid out like B: its local row r must be the output's local row r)
+                const bool same_rows = i > 0 || (whole_rows(true) && d_ops->bSubmatrices[0].topRow == d_ops->aSubmatrices[0].topRow);
+                if (layers[i].input_features != layers[i].num_heads * layers[i].features_per_head || X.rows() != out.rows() || X.cols() != out.cols() || !same_rows)
+                    throw hnh::Error("Error, GAT " + what + " needs an input and an output of the same shape, not " + std::to_string(X.rows()) + " x " +
+                                     std::to_string(X.cols()) + " and " + std::to_string(out.rows()) + " x " + std::to_string(out.cols()) +
+                                     ": use residual projection!");
+            }
+            const hnh::Backend* be = d_ops->world->be;
+            require_kernels(what, "include/hnh_gat_skip.h",
+                            {HNH_GAT_KERNEL(hnh_skip_addend_cols_f64), HNH_GAT_KERNEL(hnh_skip_grad_cols_f64), HNH_GAT_KERNEL(hnh_colsum_f64_workspace),
+                             HNH_GAT_KERNEL(hnh_colsum_f64)});
+        }
+    }
+    // the auxiliary stream's scratch for X W_res_h (allocated before the layer's ev_input mark, like the product buffers)
+    void shape_residual(int i) {
+        if (res_mode_[(size_t)i] != HNH_GAT_RESIDUAL_PROJECTION) return;
+        const int64_t rows = buffers[(size_t)i].rows(), f = layers[(size_t)i].features_per_head;
+        if (res_product_.rows() != rows || res_product_.cols() != f) res_product_ = DenseMatrix(rows, f);
+    }
+    // the addend r + b of (layer i, head j) into the head's column block of buffers[i + 1], on `stream`; nothing for a layer without
+    void head_addend(int i, int j, int stream) {
+        if (!has_addend(i)) return;
+        hnh::World* w = d_ops->world;
+        const hnh::Backend* be = w->be;
+        DenseMatrix& X = layer_input(i);
+        DenseMatrix& out = buffers[(size_t)i + 1];
+        const int64_t f = layers[(size_t)i].features_per_head, rows = out.rows();
+        const double* res = nullptr;
+        int64_t ld_res = 0;
+        if (res_mode_[(size_t)i] == HNH_GAT_RESIDUAL_IDENTITY) {
+            res = X.data() + (int64_t)j * f;
+            ld_res = X.cols();
+        } else if (res_mode_[(size_t)i] == HNH_GAT_RESIDUAL_PROJECTION) {
+            shape_residual(i);
+            DenseMatrix& Wr = w_res_[(size_t)i].at((size_t)j);
+            w->check(be->hnh_gemm_f64(w->ctx, X.rows(), f, X.cols(), X.data(), Wr.data(), res_product_.data(), stream), "hnh_gemm_f64");
+            res = res_product_.data();
+            ld_res = f;
+        }
+        const double* b = bias_on_[(size_t)i] ? bias_[(size_t)i].data() + (int64_t)j * f : nullptr;
+        w->check(be->hnh_skip_addend_cols_f64(w->ctx, out.data(), out.cols(), (int64_t)j * f, res, ld_res, b, rows, f, stream), "hnh_skip_addend_cols_f64");
+    }
+
     // A non-ReLU layer's own conditions, checked before anything is launched: the attention mode (attention none ends in the fused pair's
     // or the un-fused route's ReLU), the schedule (the softmax's), then a kernel library that knows the activation flags, which is one
     // that exports hnh_act_grad_cols_f64.  Every layer at relu: nothing to check, today's launches.
@@ -934,13 +1165,33 @@ private:
             if (dav.rows() != hf || dav.cols() != 2) dav = DenseMatrix(hf, 2);
             if (score_ == HNH_GAT_SCORE_GATV2) dav.setZero();  // (column 1 stays zero; column 0 is written head by head)
         }
+        const bool skip = has_addend(i);
+        const int rmode = res_mode_[(size_t)i];
+        DenseMatrix* dZ_all = skip ? &scratch(24, rows, hf) : nullptr;
         d_ops->setRValue(f);
         for (int h = 0; h < H; h++) {
             DenseMatrix& Wh = layers[(size_t)i].wMats[(size_t)h];
             DenseMatrix& A = scratch(2, rows, f);
             DenseMatrix& dZ = scratch(3, rows, f);
             w->check(be->hnh_gemm_f64(w->ctx, rows, f, k, X.data(), Wh.data(), A.data(), S0), "hnh_gemm_f64");
-            if (act_[(size_t)i] == HNH_GAT_ACT_RELU)
+            if (skip) {  // dZ (also into dZ_all) and delta with the addend taken out of the recovered pre-activation (include/hnh_gat_skip.h)
+                const double* res = nullptr;
+                int64_t ld_res = 0;
+                if (rmode == HNH_GAT_RESIDUAL_IDENTITY) {
+                    res = X.data() + (int64_t)h * f;
+                    ld_res = k;
+                } else if (rmode == HNH_GAT_RESIDUAL_PROJECTION) {  // recomputed: no addend is kept between the passes
+                    DenseMatrix& P = scratch(23, rows, f);
+                    w->check(be->hnh_gemm_f64(w->ctx, rows, f, k, X.data(), w_res_[(size_t)i].at((size_t)h).data(), P.data(), S0), "hnh_gemm_f64");
+                    res = P.data();
+                    ld_res = f;
+                }
+                if (act_delta_.rows() != rows || act_delta_.cols() != 1) act_delta_ = DenseMatrix(rows, 1);
+                const int act = act_[(size_t)i] == HNH_GAT_ACT_ELU ? HNH_ACT_ELU : (act_[(size_t)i] == HNH_GAT_ACT_IDENTITY ? HNH_ACT_IDENTITY : HNH_ACT_RELU);
+                w->check(be->hnh_skip_grad_cols_f64(w->ctx, dZ.data(), f, dZ_all->data(), hf, act_delta_.data(), G.data(), hf, out.data(), hf, (int64_t)h * f, res,
+                                                    ld_res, bias_on_[(size_t)i] ? bias_[(size_t)i].data() + (int64_t)h * f : nullptr, rows, f, act, S0),
+                         "hnh_skip_grad_cols_f64");
+            } else if (act_[(size_t)i] == HNH_GAT_ACT_RELU)
                 w->check(be->hnh_relu_grad_cols_f64(w->ctx, dZ.data(), f, G.data(), hf, out.data(), hf, (int64_t)h * f, rows, f, S0),
                          "hnh_relu_grad_cols_f64");
             else {  // dZ and delta from one read of G and the stored output; the delta waits in act_delta_ for head_delta
@@ -972,7 +1223,42 @@ private:
         DenseMatrix& dX = input_grads[(size_t)i];
         if (dX.rows() != rows || dX.cols() != k) dX = DenseMatrix(rows, k);
         w->check(be->hnh_gemm_f64(w->ctx, rows, k, hf, dA_all.data(), Wt.data(), dX.data(), S0), "hnh_gemm_f64");
+        if (skip) backward_skip(i, X, *dZ_all, Wt, dX);
         if (feat_p_ > 0.0) feature_mask(i, dX, dX);  // dL/dX = c_q mask o dL/dXd
+    }
+    // The bias's and the skip connection's share of layer i's backward pass, after the head loop, on the compute stream: db = colsum(dZ_all)
+    // and dW_res = X^T dZ_all, both summed over the world like dW, and dX += dZ_all W_res^T (projection; Wt, free by now, takes W_res^T) or
+    // dZ_all (identity)
+    void backward_skip(int i, DenseMatrix& X, DenseMatrix& dZ_all, DenseMatrix& Wt, DenseMatrix& dX) {
+        hnh::World* w = d_ops->world;
+        const hnh::Backend* be = w->be;
+        const int S0 = HNH_STREAM_COMPUTE;
+        const int H = layers[(size_t)i].num_heads, f = layers[(size_t)i].features_per_head;
+        const int64_t rows = X.rows(), k = X.cols(), hf = (int64_t)H * f;
+        if (bias_on_[(size_t)i]) {
+            DenseMatrix& db = bias_grads[(size_t)i];
+            if (db.rows() != hf || db.cols() != 1) db = DenseMatrix(hf, 1);
+            const int64_t need = be->hnh_colsum_f64_workspace(rows, hf);
+            DenseMatrix* work = need > 0 ? &scratch(25, need, 1) : nullptr;
+            w->check(be->hnh_colsum_f64(w->ctx, db.data(), dZ_all.data(), hf, rows, hf, work ? work->data() : nullptr, need, S0), "hnh_colsum_f64");
+            w->allreduce_f64(w->world_comm(), db.data(), (size_t)db.size(), S0);
+        }
+        if (res_mode_[(size_t)i] == HNH_GAT_RESIDUAL_PROJECTION) {
+            DenseMatrix& dWr = res_weight_grads[(size_t)i];
+            if (dWr.rows() != k || dWr.cols() != hf) dWr = DenseMatrix(k, hf);
+            const int64_t need = be->hnh_gemm_tn_f64_workspace(k, hf, rows);
+            DenseMatrix* work = need > 0 ? &scratch(7, need, 1) : nullptr;
+            w->check(be->hnh_gemm_tn_f64(w->ctx, k, hf, rows, X.data(), k, dZ_all.data(), hf, dWr.data(), hf, work ? work->data() : nullptr, need, S0),
+                     "hnh_gemm_tn_f64");
+            w->allreduce_f64(w->world_comm(), dWr.data(), (size_t)dWr.size(), S0);
+            for (int h = 0; h < H; h++)
+                w->check(be->hnh_transpose_into_f64(w->ctx, Wt.data(), k, (int64_t)h * f, w_res_[(size_t)i].at((size_t)h).data(), k, f, S0), "hnh_transpose_into_f64");
+            DenseMatrix& dXr = scratch(26, rows, k);
+            w->check(be->hnh_gemm_f64(w->ctx, rows, k, hf, dZ_all.data(), Wt.data(), dXr.data(), S0), "hnh_gemm_f64");
+            w->check(be->hnh_axpy_f64(w->ctx, dX.data(), dXr.data(), 1.0, dX.size(), S0), "hnh_axpy_f64");
+        } else if (res_mode_[(size_t)i] == HNH_GAT_RESIDUAL_IDENTITY) {
+            w->check(be->hnh_axpy_f64(w->ctx, dX.data(), dZ_all.data(), 1.0, dX.size(), S0), "hnh_axpy_f64");  // (k == H f: the same shape)
+        }
     }
     // The three implementations of one head of the backward pass.  A = X W_h and dZ are backward_layer's; the head's column block of dA_all
     // is the result.
@@ -981,7 +1267,7 @@ private:
     // its own, which nothing else writes)
     DenseMatrix& head_delta(int i, int h, const DenseMatrix& dZ) {
         hnh::World* w = d_ops->world;
-        if (act_[(size_t)i] != HNH_GAT_ACT_RELU) {
+        if (act_[(size_t)i] != HNH_GAT_ACT_RELU || has_addend(i)) {  // (a layer with an addend: hnh_skip_grad_cols_f64's delta, ReLU included)
             if (act_delta_.rows() != dZ.rows() || act_delta_.cols() != 1)
                 throw hnh::Error("Error, GAT backwardPass: the activation's delta does not have the head's rows!");
             return act_delta_;
@@ -1279,7 +1565,7 @@ private:
             if (ds != nullptr) {
                 ScheduleWidth width(d_ops, (int)A.cols(), f);
                 const hnh_attn_drop dr = attn_drop_args(i, j);
-                ok = ds->attnAdditive_pass(0, A, g, rows, true, attn_p_ > 0.0 ? &dr : nullptr, activation_flag(i));
+                ok = ds->attnAdditive_pass(0, A, g, rows, true, attn_p_ > 0.0 ? &dr : nullptr, activation_flag(i) | addend_flag(i));
             }
             require_own_rows("score additive", !ok);
             return;
@@ -1305,7 +1591,7 @@ private:
             g.f = f;
             g.leaky_alpha = leaky_relu_alpha;
             auto* ds = dynamic_cast<Sparse15D_Dense_Shift*>(d_ops);
-            require_own_rows("score gatv2", ds == nullptr || !ds->attnV2_pass(0, A, g, rows, true, activation_flag(i)));
+            require_own_rows("score gatv2", ds == nullptr || !ds->attnV2_pass(0, A, g, rows, true, activation_flag(i) | addend_flag(i)));
             return;
         }
 
@@ -1318,7 +1604,7 @@ private:
             const hnh_attn_state st = {row_max_.data(), row_sum_.data(), lse.data(), leaky_relu_alpha,
                                        out.data() + (int64_t)j * A.cols(), (int64_t)out.cols()};
             auto* ds = dynamic_cast<Sparse15D_Dense_Shift*>(d_ops);
-            require_own_rows("softmax attention", ds == nullptr || !ds->fusedSoftmax_out(A, A, Amat, H, st, activation_flag(i)));
+            require_own_rows("softmax attention", ds == nullptr || !ds->fusedSoftmax_out(A, A, Amat, H, st, activation_flag(i) | addend_flag(i)));
             return;
         }
 

@@ -31,7 +31,7 @@ extern "C" {
  * HNH_ATTN_ACT_ELU writes o for o > 0 and expm1(o) otherwise, HNH_ATTN_ACT_IDENTITY writes o_i itself.  Meaningful only together with
  * HNH_ATTN_FINISH: both bits at once, or one without HNH_ATTN_FINISH, return HNH_ERR_INVALID and write nothing.  The same bits serve
  * hnh_attn_add_fwd_csr_p (hnh_attn_additive.h) and hnh_attn_drop_fwd_csr_p (hnh_attn_dropout.h).  A library that exports
- * hnh_act_grad_cols_f64 (hnh_grad.h) knows them. */
+ * hnh_act_grad_cols_f64 (hnh_grad.h) knows them.  (A further public bit of the finishing call, HNH_ATTN_ADDEND = 0x40: hnh_gat_skip.h.) */
 #define HNH_ATTN_ACT_ELU 0x10u
 #define HNH_ATTN_ACT_IDENTITY 0x20u
 

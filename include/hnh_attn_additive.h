@@ -67,7 +67,7 @@ typedef struct hnh_attn_add {
  * CONTINUES from it nonzero by nonzero, exactly as hnh_attn_softmax_csr_p does with s_u = LeakyReLU(s_i + t_j): results do not depend
  * on how a row's nonzeros are split into column panels, windows or groups of windows.  flags: HNH_FUSED_OUT_OVERWRITE (every row of the
  * call starts from the empty state), HNH_ATTN_FINISH (this call finishes the rows: ReLU(acc / l) into relu_dst, lse; the whole pass
- * or the window with `last` set), and with it HNH_ATTN_ACT_ELU or HNH_ATTN_ACT_IDENTITY (hnh_attention.h: the activation in ReLU's place).  Hub rows are walked whole by one group.  b->rowptr == NULL: a block of b->rows rows without any
+ * or the window with `last` set), and with it HNH_ATTN_ACT_ELU or HNH_ATTN_ACT_IDENTITY (hnh_attention.h: the activation in ReLU's place) and HNH_ATTN_ADDEND (hnh_gat_skip.h: the addend that waits in relu_dst).  Hub rows are walked whole by one group.  b->rowptr == NULL: a block of b->rows rows without any
  * nonzero (the reset and the finish still apply). */
 int hnh_attn_add_fwd_csr_p(hnh_ctx* ctx, const hnh_csr_block* b, const hnh_attn_add* args, unsigned flags, const hnh_csr_window* window,
                            int stream);

@@ -64,7 +64,7 @@ typedef struct hnh_attn_v2 {   /* 152 bytes: seventeen pointers and pitches, an 
  * CONTINUES from it nonzero by nonzero, exactly as hnh_attn_softmax_csr_p does with s_u = z_ij: results do not depend on how a row's
  * nonzeros are split into column panels, windows or groups of windows.  flags: HNH_FUSED_OUT_OVERWRITE (every row of the call starts from
  * the empty state), HNH_ATTN_FINISH (this call finishes the rows: act(acc / l) into relu_dst, lse; the whole pass or the window with
- * `last` set), and with it HNH_ATTN_ACT_ELU or HNH_ATTN_ACT_IDENTITY.  Hub rows are walked whole by one group.  b->rowptr == NULL: a
+ * `last` set), and with it HNH_ATTN_ACT_ELU or HNH_ATTN_ACT_IDENTITY and HNH_ATTN_ADDEND (hnh_gat_skip.h: the addend that waits in relu_dst).  Hub rows are walked whole by one group.  b->rowptr == NULL: a
  * block of b->rows rows without any nonzero (the reset and the finish still apply). */
 int hnh_attn_v2_fwd_csr_p(hnh_ctx* ctx, const hnh_csr_block* b, const hnh_attn_v2* args, unsigned flags, const hnh_csr_window* window,
                           int stream);

@@ -281,6 +281,26 @@ int hnh_gat_set_score(hnh_gat* g, int mode);
 #define HNH_GAT_ACT_ELU 1
 #define HNH_GAT_ACT_IDENTITY 2
 int hnh_gat_set_activation(hnh_gat* g, int layer, int mode);
+/* Bias and skip connection of a layer (an addition; kernels: include/hnh_gat_skip.h, an optional group).  The layer's output becomes
+ * out[:, block h] = act(o_h + r[:, block h] + b[block h]): r = 0 (NONE, the default), the layer input X (IDENTITY: input_features must equal
+ * num_heads * features_per_head, refused here otherwise) or X W_res (PROJECTION: W_res is learned, input_features x (num_heads *
+ * features_per_head), zero until set); b is the learned bias (num_heads * features_per_head entries; hnh_gat_set_bias with NULL switches
+ * it off, the default).  All arrays are HOST memory, row-major.  Supported with attention SOFTMAX (every score, both backward modes, any
+ * dropout the score allows, any activation) on 15d_fusion2 with c = 1; hnh_gat_forward / hnh_gat_backward / hnh_gat_train_step /
+ * hnh_gat_evaluate fail elsewhere before anything is launched, naming the layer and the mode, the schedule, the shapes, or the missing symbol
+ * when the kernel library lacks the group.  A layer with neither launches what it launched before.  Every setter invalidates the stored
+ * forward pass.  After hnh_gat_backward the gradients (summed over all ranks like dW, the same on every rank) can be read;
+ * hnh_gat_optimizer_step updates every enabled bias and W_res with the other parameters, weight decay included. */
+#define HNH_GAT_RESIDUAL_NONE 0
+#define HNH_GAT_RESIDUAL_IDENTITY 1
+#define HNH_GAT_RESIDUAL_PROJECTION 2
+int hnh_gat_set_residual(hnh_gat* g, int layer, int mode);
+int hnh_gat_set_residual_weight(hnh_gat* g, int layer, const double* host);
+int hnh_gat_get_residual_weight(hnh_gat* g, int layer, double* host);
+int hnh_gat_get_residual_weight_grad(hnh_gat* g, int layer, double* host);
+int hnh_gat_set_bias(hnh_gat* g, int layer, const double* host_or_null);
+int hnh_gat_get_bias(hnh_gat* g, int layer, double* host);
+int hnh_gat_get_bias_grad(hnh_gat* g, int layer, double* host);
 int hnh_gat_set_attn_vectors(hnh_gat* g, int layer, int head, const double* a1_host, const double* a2_host);
 int hnh_gat_get_attn_grads(hnh_gat* g, int layer, int head, double* da1_host, double* da2_host);
 
@@ -319,8 +339,8 @@ int hnh_gat_loss(hnh_gat* g, const uint8_t* mask_or_null, int64_t n, hnh_dense* 
 #define HNH_GAT_OPTIMIZER_ADAM 0
 #define HNH_GAT_OPTIMIZER_SGD 1
 int hnh_gat_set_optimizer(hnh_gat* g, int kind, double lr, double beta1, double beta2, double eps, double momentum, double weight_decay);
-/* Applies the optimizer to the gradients of the last hnh_gat_backward — every W, and a1, a2 with score ADDITIVE — in one table-driven
- * launch, and invalidates the stored forward pass.  The gradients are the same on every rank, so the parameters stay equal bit for bit. */
+/* Applies the optimizer to the gradients of the last hnh_gat_backward — every W, a1, a2 with score ADDITIVE, and every enabled bias and
+ * residual weight (weight decay applies to them as to every other tensor) — in one table-driven launch, and invalidates the stored forward pass.  The gradients are the same on every rank, so the parameters stay equal bit for bit. */
 int hnh_gat_optimizer_step(hnh_gat* g);
 /* One training step on the compute stream: [seed + 1 (mod 2^64) when a dropout rate is nonzero,] forward pass, loss over the training
  * rows into an internal gradient, backward pass, optimizer step.  *loss and *accuracy are those of the parameters BEFORE the update; reading

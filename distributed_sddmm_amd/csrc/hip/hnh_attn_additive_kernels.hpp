@@ -1,6 +1,6 @@
 // Additive (a1, a2) attention scores of the GAT (include/hnh_attn_additive.h): three sibling templates of the row kernel.  Included at the
-// end of hnh_kernels.hip, after hnh_attn_grad_kernels.hpp, whose machinery they use as it is (AgUnroll, the hub-row segment scheme with
-// attn_grad_reduce_kernel / attn_grad_zero_rows_kernel, plans, Infinity-Cache panels) next to the row kernels' transposed butterfly and
+// end of hnh_kernels.hip, after hnh_attn_grad_kernels.hpp, whose machinery they use as it is (AgUnroll; from hnh_attn_dispatch.hpp the row
+// and segment kernels, the hub-row segment scheme and the dispatcher's head and tail) next to the row kernels' transposed butterfly and
 // group broadcast; kept apart from process_row and attn_grad_process so that none of the existing instances changes by a register.
 //
 //   PASS 0  forward over S:        s_i and the row's softmax state in registers; gathers M_j = [A_j | s_j t_j]; z = s_i + t_j (no dot product,
@@ -368,64 +368,16 @@ __device__ __forceinline__ void attn_add_process(int64_t row, int beg, int end, 
     }
 }
 
+// the instance's name for the shells of hnh_attn_dispatch.hpp (attn_rows_kernel, attn_segments_kernel)
 template <int PASS, int LPR, int VEC, int W, bool EXACT, bool DROP = false>
-__global__ __launch_bounds__(kBlock) void attn_add_row_kernel(int64_t rows, const int32_t* __restrict__ rowptr, const int32_t* __restrict__ beg_ptr,
-                                                              const int32_t* __restrict__ end_ptr, const int32_t* __restrict__ colidx,
-                                                              typename AaKernelArgs<DROP>::type a, unsigned flags) {
-    constexpr int GROUPS = kBlock / LPR;
-    const int tid = threadIdx.x;
-    const int lig = tid % LPR;
-    int64_t row = (int64_t)blockIdx.x * GROUPS + tid / LPR;
-    if constexpr (LPR == 64) row = ((int64_t)blockIdx.x * GROUPS) + __builtin_amdgcn_readfirstlane(tid >> 6);
-    if (row >= rows) return;
-    int beg = beg_ptr[row];
-    int end = end_ptr[row];
-    if constexpr (LPR == 64) {
-        beg = __builtin_amdgcn_readfirstlane(beg);
-        end = __builtin_amdgcn_readfirstlane(end);
+struct AaPass {
+    using Args = typename AaKernelArgs<DROP>::type;
+    static constexpr int lpr = LPR;
+    static __device__ __forceinline__ void run(int64_t row, int beg, int end, const int32_t* __restrict__ colidx, const Args& a, unsigned flags, int lig,
+                                               double* part_row) {
+        attn_add_process<PASS, LPR, VEC, W, EXACT, DROP>(row, beg, end, colidx, a, flags, lig, part_row);
     }
-    if constexpr (PASS != 0) {  // (the forward pass walks hub rows whole and visits every row: the reset and the finish apply to empty pieces too)
-        if (flags & kInternalSplitLong) {  // hub rows go to the segment kernel, whose sums are ADDED to the row (as in row_kernel)
-            int full = rowptr[row + 1] - rowptr[row];
-            if constexpr (LPR == 64) full = __builtin_amdgcn_readfirstlane(full);
-            if (full > long_row_of(flags)) {
-                if (flags & HNH_FUSED_OUT_OVERWRITE) end = beg;  // an overwritten row has to start from zero
-                else return;
-            }
-        }
-        if (beg == end && !(flags & HNH_FUSED_OUT_OVERWRITE)) return;  // nothing to add
-    }
-    attn_add_process<PASS, LPR, VEC, W, EXACT, DROP>(row, beg, end, colidx, a, flags, lig, nullptr);
-}
-
-// one work item = kLongSeg consecutive nonzeros of a hub row (the row kernels' work list); every segment writes its partial result
-template <int PASS, int LPR, int VEC, int W, bool EXACT, bool DROP = false>
-__global__ __launch_bounds__(kBlock) void attn_add_long_kernel(const int2* __restrict__ items, const int* __restrict__ item_count, int capacity,
-                                                               const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colidx,
-                                                               typename AaKernelArgs<DROP>::type a, double* partials, int64_t pitch) {
-    constexpr int GROUPS = kBlock / LPR;
-    const int tid = threadIdx.x;
-    const int lig = tid % LPR;
-    int count = *item_count;
-    if (count > capacity) count = capacity;
-    const int ngroups = (int)gridDim.x * GROUPS;
-    int first = (int)blockIdx.x * GROUPS + tid / LPR;
-    if constexpr (LPR == 64) first = __builtin_amdgcn_readfirstlane(first);
-    for (int it = first; it < count; it += ngroups) {
-        const int2 item = items[it];
-        int rbeg = rowptr[item.x], rend = rowptr[item.x + 1], seg = item.y;
-        int64_t row = item.x;
-        if constexpr (LPR == 64) {
-            rbeg = __builtin_amdgcn_readfirstlane(rbeg);
-            rend = __builtin_amdgcn_readfirstlane(rend);
-            seg = __builtin_amdgcn_readfirstlane(seg);
-            row = __builtin_amdgcn_readfirstlane(item.x);
-        }
-        const int beg = rbeg + seg * kLongSeg;
-        const int end = (beg + kLongSeg < rend) ? beg + kLongSeg : rend;
-        attn_add_process<PASS, LPR, VEC, W, EXACT, DROP>(row, beg, end, colidx, a, HNH_FUSED_OUT_OVERWRITE, lig, partials + (int64_t)it * pitch);
-    }
-}
+};
 
 // a block without any nonzero, forward: the state reset of HNH_FUSED_OUT_OVERWRITE and the finish, as attn_add_process does them for a
 // row whose piece is empty (one wave per row).  ACT: the finish applies ELU / the identity (flags) instead of the ReLU, or adds the addend
@@ -451,6 +403,29 @@ __global__ __launch_bounds__(kBlock) void attn_add_empty_rows_kernel(int64_t row
         a.row_sum[row] = l;
         if (finish) a.lse[row] = l > 0.0 ? m + log(l) : 0.0;
     }
+}
+
+// (declared in hnh_attn_dispatch.hpp) the forward passes of every family share the kernel above: it reads the row state and nothing else
+int attn_dispatch_no_nonzeros(hnh_ctx* ctx, hipStream_t st, const hnh_csr_block* b, unsigned kflags, const AttnRowState* state, const AttnSums& sums,
+                              const char* who) {
+    if (b->nnz > 0) return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": null rowptr");
+    if (state != nullptr) {
+        if (!kflags) return HNH_OK;
+        AaArgs e = {};
+        e.lse = state->lse; e.Out = state->Out; e.row_max = state->row_max; e.row_sum = state->row_sum; e.relu_dst = state->relu_dst;
+        e.ld_out = state->ld_out; e.relu_ld = state->relu_ld; e.f = state->f;
+        const dim3 grid((unsigned)((b->rows * 64 + kBlock - 1) / kBlock));
+        if (kflags & (kAttnActMask | HNH_ATTN_ADDEND)) hipLaunchKernelGGL(attn_add_empty_rows_kernel<true>, grid, dim3(kBlock), 0, st, b->rows, e, kflags);
+        else hipLaunchKernelGGL(attn_add_empty_rows_kernel<false>, grid, dim3(kBlock), 0, st, b->rows, e, kflags);
+        return hnh::check_hip(ctx, hipGetLastError(), "attn_add_empty_rows_kernel launch");
+    }
+    if (!(kflags & HNH_FUSED_OUT_OVERWRITE)) return HNH_OK;
+    for (int i = 0; i < sums.n; i++) {
+        const AttnSums::Sum& s = sums.s[i];
+        hipLaunchKernelGGL(attn_grad_zero_rows_kernel, dim3(ew_grid(b->rows * s.width)), dim3(kBlock), 0, st, s.dst, s.ld, b->rows, s.width);
+        if (int rc = hnh::check_hip(ctx, hipGetLastError(), "attn_grad_zero_rows_kernel launch")) return rc;
+    }
+    return HNH_OK;
 }
 
 // M[r, :] = [A_r (0) | <A_r, a1> <A_r, a2>], one wave per row
@@ -504,51 +479,12 @@ __global__ __launch_bounds__(kBlock) void attn_add_update_kernel(double* __restr
     }
 }
 
-template <int PASS, int LPR, int VEC, int W, bool EXACT, bool DROP>
-int attn_add_launch(hnh_ctx* ctx, hipStream_t st, const LongCtl& lc, int64_t rows, const int32_t* rowptr, const int32_t* beg_ptr,
-                    const int32_t* end_ptr, const int32_t* colidx, const typename AaKernelArgs<DROP>::type& a, unsigned flags, bool run_long) {
-    constexpr int GROUPS = kBlock / LPR;
-    const int64_t blocks = (rows + GROUPS - 1) / GROUPS;
-    if (blocks <= 0) return HNH_OK;
-    if (blocks > 0x7fffffffLL) return hnh::fail(ctx, HNH_ERR_UNSUPPORTED, "too many rows for one launch");
-    if (lc.enabled) flags |= kInternalSplitLong | ((unsigned)(lc.threshold / 64) << kLongRowShift);
-    const size_t lds_pad = lc.lds_pad <= 48 * 1024 ? lc.lds_pad : 0;
-    hipLaunchKernelGGL((attn_add_row_kernel<PASS, LPR, VEC, W, EXACT, DROP>), dim3((unsigned)blocks), dim3(kBlock), lds_pad, st, rows, rowptr, beg_ptr, end_ptr,
-                       colidx, a, flags);
-    if (int rc = hnh::check_hip(ctx, hipGetLastError(), "attn_add_row_kernel launch")) return rc;
-    if constexpr (PASS != 0) {
-        if (lc.enabled && run_long) {  // hub rows once per pass, over their whole length: segments, then the ordered sums
-            const int64_t pitch = PASS == 2 ? a.fp + 2 : 2;
-            hipLaunchKernelGGL((attn_add_long_kernel<PASS, LPR, VEC, W, EXACT, DROP>), dim3((unsigned)ctx->long_grid), dim3(kBlock), 0, st, lc.items, lc.count,
-                               lc.capacity, rowptr, colidx, a, lc.partials, pitch);
-            if (int rc = hnh::check_hip(ctx, hipGetLastError(), "attn_add_long_kernel launch")) return rc;
-            if (PASS == 2) {
-                hipLaunchKernelGGL(attn_grad_reduce_kernel, dim3(2048), dim3(kBlock), 0, st, lc.hub_rows, lc.count, lc.capacity_rows, lc.partials, pitch,
-                                   a.Out, a.ld_out, a.f);
-                if (int rc = hnh::check_hip(ctx, hipGetLastError(), "attn_grad_reduce_kernel launch")) return rc;
-            }
-            hipLaunchKernelGGL(attn_grad_reduce_kernel, dim3(2048), dim3(kBlock), 0, st, lc.hub_rows, lc.count, lc.capacity_rows,
-                               lc.partials + (PASS == 2 ? a.fp : 0), pitch, a.vec, a.ld_vec, 1);
-            return hnh::check_hip(ctx, hipGetLastError(), "attn_grad_reduce_kernel launch");
-        }
-    }
-    return HNH_OK;
-}
-
 template <int PASS, bool DROP = false>
 int attn_add_dispatch(hnh_ctx* ctx, const hnh_csr_block* b, const hnh_attn_add* g, unsigned flags, const hnh_csr_window* win, int stream,
                       const char* who, const hnh_attn_drop* drop = nullptr) {
     HNH_ENTER(ctx, stream);
-    if (!b || !g || (DROP && !drop)) return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": null block or arguments");
-    if (int rc = check_common(ctx, b->rows, g->f, who)) return rc;
-    if (flags & ~(HNH_FUSED_OUT_OVERWRITE | (PASS == 0 ? (HNH_ATTN_FINISH | kAttnActMask | HNH_ATTN_ADDEND) : 0u)))
-        return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": unknown flag");
-    if (int rc = check_attn_act_flags(ctx, flags, who)) return rc;
-    if (g->f > HNH_ATTN_ADD_MAX_F)
-        return hnh::fail(ctx, HNH_ERR_UNSUPPORTED, std::string(who) + ": head width " + std::to_string(g->f) + " beyond the limit of " +
-                                                       std::to_string(HNH_ATTN_ADD_MAX_F) + " (HNH_ATTN_ADD_MAX_F)");
+    if (int rc = attn_dispatch_head(ctx, b, g && (!DROP || drop), g ? g->f : 0, HNH_ATTN_ADD_MAX_F, "HNH_ATTN_ADD_MAX_F", PASS == 0, flags, win, who)) return rc;
     const bool finish = PASS == 0 && (flags & HNH_ATTN_FINISH) != 0;
-    if (finish && win != nullptr && !win->last) return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": the finish belongs to the last window");
     if (b->rows == 0) return HNH_OK;
     const int f = g->f, fp = f + (f & 1);
     if (PASS != 1 && (!g->Out || g->ld_out < f)) return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": bad output");
@@ -573,22 +509,14 @@ int attn_add_dispatch(hnh_ctx* ctx, const hnh_csr_block* b, const hnh_attn_add* 
     a.f = f; a.fp = fp; a.alpha = g->leaky_alpha;
     hipStream_t st = ctx->streams[stream];
     const unsigned kflags = (flags & (HNH_FUSED_OUT_OVERWRITE | kAttnActMask | HNH_ATTN_ADDEND)) | (finish ? kInternalEpilogue : 0u);
-    if (b->rowptr == nullptr) {  // a block without nonzeros
-        if (b->nnz > 0) return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": null rowptr");
-        if (PASS == 0) {
-            if (!kflags) return HNH_OK;
-            const dim3 grid((unsigned)((b->rows * 64 + kBlock - 1) / kBlock));
-            if (kflags & (kAttnActMask | HNH_ATTN_ADDEND)) hipLaunchKernelGGL(attn_add_empty_rows_kernel<true>, grid, dim3(kBlock), 0, st, b->rows, a, kflags);
-            else hipLaunchKernelGGL(attn_add_empty_rows_kernel<false>, grid, dim3(kBlock), 0, st, b->rows, a, kflags);
-            return hnh::check_hip(ctx, hipGetLastError(), "attn_add_empty_rows_kernel launch");
-        }
-        if (!(flags & HNH_FUSED_OUT_OVERWRITE)) return HNH_OK;
-        if (PASS == 2) {
-            hipLaunchKernelGGL(attn_grad_zero_rows_kernel, dim3(ew_grid(b->rows * f)), dim3(kBlock), 0, st, g->Out, g->ld_out, b->rows, f);
-            if (int rc = hnh::check_hip(ctx, hipGetLastError(), "attn_grad_zero_rows_kernel launch")) return rc;
-        }
-        hipLaunchKernelGGL(attn_grad_zero_rows_kernel, dim3(ew_grid(b->rows)), dim3(kBlock), 0, st, g->vec, g->ld_vec, b->rows, 1);
-        return hnh::check_hip(ctx, hipGetLastError(), "attn_grad_zero_rows_kernel launch");
+    // a segment's partial result: [dAgg (0) | dt] (column pass) or ds alone; none for the forward pass, which walks hub rows whole
+    const int64_t pitch = PASS == 0 ? 0 : (PASS == 2 ? fp + 2 : 2);
+    AttnSums sums;
+    if (PASS == 2) sums.add(0, g->Out, g->ld_out, f);
+    if (PASS != 0) sums.add(PASS == 2 ? fp : 0, g->vec, g->ld_vec, 1);
+    if (b->rowptr == nullptr) {
+        const AttnRowState state = {g->lse, g->Out, g->row_max, g->row_sum, g->relu_dst, g->ld_out, g->relu_ld, f};
+        return attn_dispatch_no_nonzeros(ctx, st, b, kflags, PASS == 0 ? &state : nullptr, sums, who);
     }
     if (!b->col_idx || !g->M || !g->Y) return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": null pointer");
     if (g->ld_m < fp + 2) return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": ld_m is narrower than the scored width");
@@ -609,12 +537,11 @@ int attn_add_dispatch(hnh_ctx* ctx, const hnh_csr_block* b, const hnh_attn_add* 
 
     auto launch = [&](const LongCtl& lc, const int32_t* beg_ptr, const int32_t* end_ptr, unsigned fl, bool run_long) {
         return attn_launch_shape(f, w2, [&](auto l, auto v, auto w, auto ex) {
-            return attn_add_launch<PASS, decltype(l)::value, decltype(v)::value, decltype(w)::value, decltype(ex)::value, DROP>(
-                ctx, st, lc, b->rows, b->rowptr, beg_ptr, end_ptr, b->col_idx, a, fl, run_long);
+            return attn_launch<AaPass<PASS, decltype(l)::value, decltype(v)::value, decltype(w)::value, decltype(ex)::value, DROP>, PASS == 0, true>(
+                ctx, st, lc, b->rows, b->rowptr, beg_ptr, end_ptr, b->col_idx, a, fl, run_long, pitch, sums);
         });
     };
-    // a segment's partial result: [dAgg (0) | dt] (column pass) or ds alone; none for the forward pass, which walks hub rows whole
-    return attn_dispatch_tail(ctx, st, stream, b, win, f, w2, PASS == 0 ? 0 : (PASS == 2 ? fp + 2 : 2), gather_w, kflags, who, launch);
+    return attn_dispatch_tail(ctx, st, stream, b, win, f, w2, pitch, gather_w, kflags, who, launch);
 }
 
 }  // namespace

@@ -1,6 +1,12 @@
-// What the dispatchers of the attention passes share (hnh_attn_grad_kernels.hpp, hnh_attn_additive_kernels.hpp and, through the latter,
-// the DROP instances): host code only.  Included by the first of them, inside hnh_kernels.hip, whose plans, hub-row work lists, LDS pad
-// and Infinity-Cache panels it drives; every pass keeps its own argument checks, its own kernel arguments and its own launcher.
+// What the attention passes share (hnh_attn_grad_kernels.hpp, hnh_attn_additive_kernels.hpp with its DROP instances, hnh_attn_v2_kernels.hpp):
+// the row kernel and the hub-row segment kernel round a family's per-row process function, the ordered sum of the segments' partial rows,
+// the launcher of the three, and the head and the tail of a dispatcher.  Included by the first of them, inside hnh_kernels.hip, whose plans,
+// hub-row work lists, LDS pad and Infinity-Cache panels it drives; every pass keeps its own process function (attn_grad_process,
+// attn_add_process, attn_v2_process: apart, so that none of their instances changes by a register), its own argument checks and its own
+// kernel arguments.  A family names an instance to the shells with a tag type
+//     struct Tag { using Args = <kernel arguments>;  static constexpr int lpr = <lanes per row>;
+//                  static __device__ void run(row, beg, end, colidx, const Args&, flags, lig, part_row); };
+// which is what a `rocprofv3 --kernel-trace --stats` listing shows: attn_rows_kernel<AgPass<1, 64, 2, 2, true>, false> and so on.
 #pragma once
 
 namespace {
@@ -25,6 +31,172 @@ int attn_launch_shape(int f, bool w2, Go&& go) {
     HNH_ATTN_SHAPE(64, 4, 1, false);
 #undef HNH_ATTN_SHAPE
 }
+
+// The row kernel: a group of P::lpr lanes per sparse row.  WHOLE: this pass walks hub rows whole and visits every row (a forward pass: a
+// row's scores are combined in row order, and the reset and the finish apply to empty pieces too).
+template <typename P, bool WHOLE>
+__global__ __launch_bounds__(kBlock) void attn_rows_kernel(int64_t rows, const int32_t* __restrict__ rowptr, const int32_t* __restrict__ beg_ptr,
+                                                           const int32_t* __restrict__ end_ptr, const int32_t* __restrict__ colidx, typename P::Args a,
+                                                           unsigned flags) {
+    constexpr int LPR = P::lpr;
+    constexpr int GROUPS = kBlock / LPR;
+    const int tid = threadIdx.x;
+    const int lig = tid % LPR;
+    int64_t row = (int64_t)blockIdx.x * GROUPS + tid / LPR;
+    if constexpr (LPR == 64) row = ((int64_t)blockIdx.x * GROUPS) + __builtin_amdgcn_readfirstlane(tid >> 6);
+    if (row >= rows) return;
+    int beg = beg_ptr[row];
+    int end = end_ptr[row];
+    if constexpr (LPR == 64) {
+        beg = __builtin_amdgcn_readfirstlane(beg);
+        end = __builtin_amdgcn_readfirstlane(end);
+    }
+    if constexpr (!WHOLE) {
+        if (flags & kInternalSplitLong) {  // hub rows go to the segment kernel, whose sums are ADDED to the row (as in row_kernel)
+            int full = rowptr[row + 1] - rowptr[row];
+            if constexpr (LPR == 64) full = __builtin_amdgcn_readfirstlane(full);
+            if (full > long_row_of(flags)) {
+                if (flags & HNH_FUSED_OUT_OVERWRITE) end = beg;  // an overwritten row has to start from zero
+                else return;
+            }
+        }
+        if (beg == end && !(flags & HNH_FUSED_OUT_OVERWRITE)) return;  // nothing to add
+    }
+    P::run(row, beg, end, colidx, a, flags, lig, nullptr);
+}
+
+// The hub-row segment kernel: one work item = kLongSeg consecutive nonzeros of a hub row (the row kernels' work list); every segment writes
+// its partial row.  LOOP: a grid-stride loop over the work list (ctx->long_grid workgroups).  Otherwise one group per item over a grid that
+// covers the list's capacity: the loop keeps every kernel argument alive across the row's walk, which in the GATv2 passes is more
+// wave-uniform values than the bounds-checked row-pass instances have scalar registers for.
+template <typename P, bool LOOP>
+__global__ __launch_bounds__(kBlock) void attn_segments_kernel(const int2* __restrict__ items, const int* __restrict__ item_count, int capacity,
+                                                               const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colidx,
+                                                               typename P::Args a, double* partials, int64_t pitch) {
+    constexpr int LPR = P::lpr;
+    constexpr int GROUPS = kBlock / LPR;
+    const int tid = threadIdx.x;
+    const int lig = tid % LPR;
+    int count = *item_count;
+    if (count > capacity) count = capacity;
+    const int ngroups = (int)gridDim.x * GROUPS;
+    int first = (int)blockIdx.x * GROUPS + tid / LPR;
+    if constexpr (LPR == 64) first = __builtin_amdgcn_readfirstlane(first);
+    for (int it = first; it < count; it += ngroups) {
+        const int2 item = items[it];
+        int rbeg = rowptr[item.x], rend = rowptr[item.x + 1], seg = item.y;
+        int64_t row = item.x;
+        if constexpr (LPR == 64) {
+            rbeg = __builtin_amdgcn_readfirstlane(rbeg);
+            rend = __builtin_amdgcn_readfirstlane(rend);
+            seg = __builtin_amdgcn_readfirstlane(seg);
+            row = __builtin_amdgcn_readfirstlane(item.x);
+        }
+        const int beg = rbeg + seg * kLongSeg;
+        const int end = (beg + kLongSeg < rend) ? beg + kLongSeg : rend;
+        P::run(row, beg, end, colidx, a, HNH_FUSED_OUT_OVERWRITE, lig, partials + (int64_t)it * pitch);
+        if constexpr (!LOOP) break;  // one item per group
+    }
+}
+
+// Out[row, 0 : f) += the row's segments' partial rows, front to back: one workgroup per hub row, one thread per column
+__global__ __launch_bounds__(kBlock) void attn_grad_reduce_kernel(const int4* __restrict__ hub_rows, const int* __restrict__ counts, int capacity_rows,
+                                                                  const double* __restrict__ partials, int64_t pitch, double* __restrict__ Out,
+                                                                  int64_t ld_out, int f) {
+    int nrows = counts[1];
+    if (nrows > capacity_rows) nrows = capacity_rows;
+    for (int e = (int)blockIdx.x; e < nrows; e += (int)gridDim.x) {
+        const int4 h = hub_rows[e];  // (row, first item, segments, -)
+        for (int c = threadIdx.x; c < f; c += kBlock) {
+            const double* p = partials + (int64_t)h.y * pitch + c;
+            double sum = 0.0;
+#pragma unroll 8
+            for (int s = 0; s < h.z; s++) sum += p[(int64_t)s * pitch];
+            Out[(int64_t)h.x * ld_out + c] += sum;
+        }
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void attn_grad_zero_rows_kernel(double* __restrict__ Out, int64_t ld_out, int64_t rows, int f) {
+    const int64_t stride = (int64_t)gridDim.x * kBlock, total = rows * f;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < total; i += stride) Out[(i / f) * ld_out + i % f] = 0.0;
+}
+
+struct AttnRowState {  // what a forward pass keeps per row
+    double* lse;
+    double* Out;
+    double* row_max;
+    double* row_sum;
+    double* relu_dst;
+    int64_t ld_out, relu_ld;
+    int f;
+};
+
+// Where a backward pass's results go: dst[row, 0 : width) is columns [col, col + width) of a hub row's partial rows, added up in segment
+// order; the same list names what HNH_FUSED_OUT_OVERWRITE zeroes in a block without nonzeros.  A forward pass has none.
+struct AttnSums {
+    struct Sum {
+        int64_t col;
+        double* dst;
+        int64_t ld;
+        int width;
+    } s[2];
+    int n = 0;
+    void add(int64_t col, double* dst, int64_t ld, int width) { s[n++] = Sum{col, dst, ld, width}; }
+};
+
+// One launch of a pass's instance P over the rows' pieces [beg_ptr, end_ptr); with run_long the hub rows, once per pass and over their whole
+// length: segments with partial rows of `pitch` doubles, then the ordered sums.  WHOLE and LOOP as in the kernels above.
+template <typename P, bool WHOLE, bool LOOP>
+int attn_launch(hnh_ctx* ctx, hipStream_t st, const LongCtl& lc, int64_t rows, const int32_t* rowptr, const int32_t* beg_ptr, const int32_t* end_ptr,
+                const int32_t* colidx, const typename P::Args& a, unsigned flags, bool run_long, int64_t pitch, const AttnSums& sums) {
+    constexpr int GROUPS = kBlock / P::lpr;
+    const int64_t blocks = (rows + GROUPS - 1) / GROUPS;
+    if (blocks <= 0) return HNH_OK;
+    if (blocks > 0x7fffffffLL) return hnh::fail(ctx, HNH_ERR_UNSUPPORTED, "too many rows for one launch");
+    if (lc.enabled) flags |= kInternalSplitLong | ((unsigned)(lc.threshold / 64) << kLongRowShift);
+    const size_t lds_pad = lc.lds_pad <= 48 * 1024 ? lc.lds_pad : 0;
+    hipLaunchKernelGGL((attn_rows_kernel<P, WHOLE>), dim3((unsigned)blocks), dim3(kBlock), lds_pad, st, rows, rowptr, beg_ptr, end_ptr, colidx, a, flags);
+    if (int rc = hnh::check_hip(ctx, hipGetLastError(), "attn_rows_kernel launch")) return rc;
+    if constexpr (!WHOLE) {
+        if (lc.enabled && run_long) {
+            const int seg_blocks = LOOP ? ctx->long_grid : (lc.capacity + GROUPS - 1) / GROUPS;  // (one group per item of the list)
+            hipLaunchKernelGGL((attn_segments_kernel<P, LOOP>), dim3((unsigned)(seg_blocks > 0 ? seg_blocks : 1)), dim3(kBlock), 0, st, lc.items, lc.count,
+                               lc.capacity, rowptr, colidx, a, lc.partials, pitch);
+            if (int rc = hnh::check_hip(ctx, hipGetLastError(), "attn_segments_kernel launch")) return rc;
+            for (int i = 0; i < sums.n; i++) {
+                const AttnSums::Sum& s = sums.s[i];
+                hipLaunchKernelGGL(attn_grad_reduce_kernel, dim3(2048), dim3(kBlock), 0, st, lc.hub_rows, lc.count, lc.capacity_rows, lc.partials + s.col,
+                                   pitch, s.dst, s.ld, s.width);
+                if (int rc = hnh::check_hip(ctx, hipGetLastError(), "attn_grad_reduce_kernel launch")) return rc;
+            }
+        }
+    }
+    return HNH_OK;
+}
+
+// The head of a pass's dispatcher, in front of what is the family's own: the arguments are there, the flags are the pass's (a forward pass
+// takes the finish, its activation and its addend), the head width is within the family's limit.  The caller goes on with `rows == 0`.
+inline int attn_dispatch_head(hnh_ctx* ctx, const hnh_csr_block* b, bool have_args, int f, int max_f, const char* max_f_name, bool forward,
+                              unsigned flags, const hnh_csr_window* win, const char* who) {
+    if (!b || !have_args) return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": null block or arguments");
+    if (int rc = check_common(ctx, b->rows, f, who)) return rc;
+    if (flags & ~(HNH_FUSED_OUT_OVERWRITE | (forward ? (HNH_ATTN_FINISH | kAttnActMask | HNH_ATTN_ADDEND) : 0u)))
+        return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": unknown flag");
+    if (int rc = check_attn_act_flags(ctx, flags, who)) return rc;
+    if (f > max_f)
+        return hnh::fail(ctx, HNH_ERR_UNSUPPORTED, std::string(who) + ": head width " + std::to_string(f) + " beyond the limit of " +
+                                                       std::to_string(max_f) + " (" + max_f_name + ")");
+    if (forward && (flags & HNH_ATTN_FINISH) && win != nullptr && !win->last)
+        return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": the finish belongs to the last window");
+    return HNH_OK;
+}
+
+// A block without nonzeros (rowptr == nullptr), behind the family's checks of its outputs.  A forward pass (`state`, with the kernels' flags)
+// resets and finishes every row; a backward pass zeroes what it would have overwritten.  (Defined in hnh_attn_additive_kernels.hpp, next to
+// the forward passes' attn_add_empty_rows_kernel.)
+int attn_dispatch_no_nonzeros(hnh_ctx* ctx, hipStream_t st, const hnh_csr_block* b, unsigned kflags, const AttnRowState* state, const AttnSums& sums,
+                              const char* who);
 
 // The tail of a pass's dispatcher, behind its argument checks: the block's structure plan; the hub rows' work list with a partial result
 // of `pitch` doubles per segment (pitch 0: hub rows are walked whole, as the forward passes do: a row's scores are combined in row order,

@@ -1,6 +1,6 @@
 // Dropout for the GAT (include/hnh_attn_dropout.h).  Included at the end of hnh_kernels.hip, after hnh_attn_additive_kernels.hpp: the three
-// passes are the DROP instances of attn_add_process / attn_add_row_kernel / attn_add_long_kernel there (a template parameter and
-// `if constexpr`: the plain instances are compiled from the same text and keep their registers), with the parents' dispatch — windows,
+// passes are the DROP instances of attn_add_process and its tag AaPass there, in the shells attn_rows_kernel / attn_segments_kernel (a template
+// parameter and `if constexpr`: the plain instances are compiled from the same text and keep their registers), with the parents' dispatch — windows,
 // plans, cache panels, hub-row segments, the sequential row-state protocol.  The lane that owns a nonzero of a batch computes its exp AND
 // its Philox word; the factor c m_ij goes round with the group broadcast.  Here: the entry points and the elementwise kernels.
 #pragma once

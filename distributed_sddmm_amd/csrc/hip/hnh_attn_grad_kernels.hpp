@@ -3,10 +3,10 @@
 // work lists and partial-row scratch, structure plans, Infinity-Cache panels) — and kept apart from process_row so that none of the
 // existing instances changes by a register.
 //
-//   attn_grad_row_kernel<0, ..>   ROW pass over S:      x = A_i, z = dZ_i, lse_i, delta_i in registers; gathers y = A_j (f wide)
-//                                 e = <x, y>, da = <z, y>, gate, acc += de y
-//   attn_grad_row_kernel<1, ..>   COLUMN pass over S^T: x = A_j in registers; gathers the packed P_i = [A_i | dZ_i | lse_i delta_i]
-//                                 e = <x, ya>, da = <x, yz>, gate with the gathered row's scalars, acc += a yz + de ya
+//   AgPass<0, ..>   ROW pass over S:      x = A_i, z = dZ_i, lse_i, delta_i in registers; gathers y = A_j (f wide)
+//                   e = <x, y>, da = <z, y>, gate, acc += de y
+//   AgPass<1, ..>   COLUMN pass over S^T: x = A_j in registers; gathers the packed P_i = [A_i | dZ_i | lse_i delta_i]
+//                   e = <x, ya>, da = <x, yz>, gate with the gathered row's scalars, acc += a yz + de ya
 // Lane layout as in process_row: a group of LPR lanes owns a sparse row, lane l holds elements (v LPR + l) W .. + W of a dense row for
 // v < VEC.  U nonzeros are gathered per batch into one of two register buffers (the next batch's gathers fly while this one is
 // computed); their 2 U dot products go through ONE transposed butterfly of 2 U reductions, after which the lower half of the group
@@ -252,85 +252,16 @@ __device__ __forceinline__ void attn_grad_process(int64_t row, int beg, int end,
     }
 }
 
+// the instance's name for the shells of hnh_attn_dispatch.hpp (attn_rows_kernel, attn_segments_kernel)
 template <int PASS, int LPR, int VEC, int W, bool EXACT>
-__global__ __launch_bounds__(kBlock) void attn_grad_row_kernel(int64_t rows, const int32_t* __restrict__ rowptr, const int32_t* __restrict__ beg_ptr,
-                                                               const int32_t* __restrict__ end_ptr, const int32_t* __restrict__ colidx, AgArgs a,
-                                                               unsigned flags) {
-    constexpr int GROUPS = kBlock / LPR;
-    const int tid = threadIdx.x;
-    const int lig = tid % LPR;
-    int64_t row = (int64_t)blockIdx.x * GROUPS + tid / LPR;
-    if constexpr (LPR == 64) row = ((int64_t)blockIdx.x * GROUPS) + __builtin_amdgcn_readfirstlane(tid >> 6);
-    if (row >= rows) return;
-    int beg = beg_ptr[row];
-    int end = end_ptr[row];
-    if constexpr (LPR == 64) {
-        beg = __builtin_amdgcn_readfirstlane(beg);
-        end = __builtin_amdgcn_readfirstlane(end);
+struct AgPass {
+    using Args = AgArgs;
+    static constexpr int lpr = LPR;
+    static __device__ __forceinline__ void run(int64_t row, int beg, int end, const int32_t* __restrict__ colidx, const AgArgs& a, unsigned flags, int lig,
+                                               double* part_row) {
+        attn_grad_process<PASS, LPR, VEC, W, EXACT>(row, beg, end, colidx, a, flags, lig, part_row);
     }
-    if (flags & kInternalSplitLong) {  // hub rows go to the segment kernel, whose sums are ADDED to the row (as in row_kernel)
-        int full = rowptr[row + 1] - rowptr[row];
-        if constexpr (LPR == 64) full = __builtin_amdgcn_readfirstlane(full);
-        if (full > long_row_of(flags)) {
-            if (flags & HNH_FUSED_OUT_OVERWRITE) end = beg;  // an overwritten row has to start from zero
-            else return;
-        }
-    }
-    if (beg == end && !(flags & HNH_FUSED_OUT_OVERWRITE)) return;  // nothing to add
-    attn_grad_process<PASS, LPR, VEC, W, EXACT>(row, beg, end, colidx, a, flags, lig, nullptr);
-}
-
-// one work item = kLongSeg consecutive nonzeros of a hub row (the row kernels' work list); every segment writes its partial row
-template <int PASS, int LPR, int VEC, int W, bool EXACT>
-__global__ __launch_bounds__(kBlock) void attn_grad_long_kernel(const int2* __restrict__ items, const int* __restrict__ item_count, int capacity,
-                                                                const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colidx, AgArgs a,
-                                                                double* partials, int64_t pitch) {
-    constexpr int GROUPS = kBlock / LPR;
-    const int tid = threadIdx.x;
-    const int lig = tid % LPR;
-    int count = *item_count;
-    if (count > capacity) count = capacity;
-    const int ngroups = (int)gridDim.x * GROUPS;
-    int first = (int)blockIdx.x * GROUPS + tid / LPR;
-    if constexpr (LPR == 64) first = __builtin_amdgcn_readfirstlane(first);
-    for (int it = first; it < count; it += ngroups) {
-        const int2 item = items[it];
-        int rbeg = rowptr[item.x], rend = rowptr[item.x + 1], seg = item.y;
-        int64_t row = item.x;
-        if constexpr (LPR == 64) {
-            rbeg = __builtin_amdgcn_readfirstlane(rbeg);
-            rend = __builtin_amdgcn_readfirstlane(rend);
-            seg = __builtin_amdgcn_readfirstlane(seg);
-            row = __builtin_amdgcn_readfirstlane(item.x);
-        }
-        const int beg = rbeg + seg * kLongSeg;
-        const int end = (beg + kLongSeg < rend) ? beg + kLongSeg : rend;
-        attn_grad_process<PASS, LPR, VEC, W, EXACT>(row, beg, end, colidx, a, HNH_FUSED_OUT_OVERWRITE, lig, partials + (int64_t)it * pitch);
-    }
-}
-
-// Out[row, 0 : f) += the row's segments' partial rows, front to back: one workgroup per hub row, one thread per column
-__global__ __launch_bounds__(kBlock) void attn_grad_reduce_kernel(const int4* __restrict__ hub_rows, const int* __restrict__ counts, int capacity_rows,
-                                                                  const double* __restrict__ partials, int64_t pitch, double* __restrict__ Out,
-                                                                  int64_t ld_out, int f) {
-    int nrows = counts[1];
-    if (nrows > capacity_rows) nrows = capacity_rows;
-    for (int e = (int)blockIdx.x; e < nrows; e += (int)gridDim.x) {
-        const int4 h = hub_rows[e];  // (row, first item, segments, -)
-        for (int c = threadIdx.x; c < f; c += kBlock) {
-            const double* p = partials + (int64_t)h.y * pitch + c;
-            double sum = 0.0;
-#pragma unroll 8
-            for (int s = 0; s < h.z; s++) sum += p[(int64_t)s * pitch];
-            Out[(int64_t)h.x * ld_out + c] += sum;
-        }
-    }
-}
-
-__global__ __launch_bounds__(kBlock) void attn_grad_zero_rows_kernel(double* __restrict__ Out, int64_t ld_out, int64_t rows, int f) {
-    const int64_t stride = (int64_t)gridDim.x * kBlock, total = rows * f;
-    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < total; i += stride) Out[(i / f) * ld_out + i % f] = 0.0;
-}
+};
 
 // P[r, :] = [A_r (0) | dZ_r (0) | lse_r delta_r], the layout of include/hnh_attn_grad.h
 __global__ __launch_bounds__(kBlock) void attn_grad_pack_kernel(double* __restrict__ P, int64_t ld_p, const double* __restrict__ A, int64_t ld_a,
@@ -349,51 +280,20 @@ __global__ __launch_bounds__(kBlock) void attn_grad_pack_kernel(double* __restri
     }
 }
 
-template <int PASS, int LPR, int VEC, int W, bool EXACT>
-int attn_grad_launch(hnh_ctx* ctx, hipStream_t st, const LongCtl& lc, int64_t rows, const int32_t* rowptr, const int32_t* beg_ptr,
-                     const int32_t* end_ptr, const int32_t* colidx, const AgArgs& a, unsigned flags, bool run_long) {
-    constexpr int GROUPS = kBlock / LPR;
-    const int64_t blocks = (rows + GROUPS - 1) / GROUPS;
-    if (blocks <= 0) return HNH_OK;
-    if (blocks > 0x7fffffffLL) return hnh::fail(ctx, HNH_ERR_UNSUPPORTED, "too many rows for one launch");
-    if (lc.enabled) flags |= kInternalSplitLong | ((unsigned)(lc.threshold / 64) << kLongRowShift);
-    const size_t lds_pad = lc.lds_pad <= 48 * 1024 ? lc.lds_pad : 0;
-    hipLaunchKernelGGL((attn_grad_row_kernel<PASS, LPR, VEC, W, EXACT>), dim3((unsigned)blocks), dim3(kBlock), lds_pad, st, rows, rowptr, beg_ptr, end_ptr,
-                       colidx, a, flags);
-    if (int rc = hnh::check_hip(ctx, hipGetLastError(), "attn_grad_row_kernel launch")) return rc;
-    if (lc.enabled && run_long) {  // hub rows once per pass, over their whole length: segments, then the ordered sum
-        const int64_t pitch = a.f;
-        hipLaunchKernelGGL((attn_grad_long_kernel<PASS, LPR, VEC, W, EXACT>), dim3((unsigned)ctx->long_grid), dim3(kBlock), 0, st, lc.items, lc.count,
-                           lc.capacity, rowptr, colidx, a, lc.partials, pitch);
-        if (int rc = hnh::check_hip(ctx, hipGetLastError(), "attn_grad_long_kernel launch")) return rc;
-        hipLaunchKernelGGL(attn_grad_reduce_kernel, dim3(2048), dim3(kBlock), 0, st, lc.hub_rows, lc.count, lc.capacity_rows, lc.partials, pitch, a.Out,
-                           a.ld_out, a.f);
-        return hnh::check_hip(ctx, hipGetLastError(), "attn_grad_reduce_kernel launch");
-    }
-    return HNH_OK;
-}
-
 template <int PASS>
 int attn_grad_dispatch(hnh_ctx* ctx, const hnh_csr_block* b, const hnh_attn_grad* g, unsigned flags, const hnh_csr_window* win, int stream,
                        const char* who) {
     HNH_ENTER(ctx, stream);
-    if (!b || !g) return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": null block or arguments");
-    if (int rc = check_common(ctx, b->rows, g->f, who)) return rc;
-    if (flags & ~HNH_FUSED_OUT_OVERWRITE) return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": unknown flag");
-    if (g->f > HNH_ATTN_GRAD_MAX_F)
-        return hnh::fail(ctx, HNH_ERR_UNSUPPORTED, std::string(who) + ": head width " + std::to_string(g->f) + " beyond the limit of " +
-                                                       std::to_string(HNH_ATTN_GRAD_MAX_F) + " (HNH_ATTN_GRAD_MAX_F)");
+    if (int rc = attn_dispatch_head(ctx, b, g != nullptr, g ? g->f : 0, HNH_ATTN_GRAD_MAX_F, "HNH_ATTN_GRAD_MAX_F", false, flags, win, who)) return rc;
     if (b->rows == 0) return HNH_OK;
     const int f = g->f, fp = f + (f & 1);
     const bool softmax = PASS == 0 ? (g->lse != nullptr) : (g->softmax != 0);
     if (!g->Out || g->ld_out < f) return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": bad output");
     hipStream_t st = ctx->streams[stream];
-    if (b->rowptr == nullptr) {  // a block without nonzeros
-        if (b->nnz > 0) return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": null rowptr");
-        if (!(flags & HNH_FUSED_OUT_OVERWRITE)) return HNH_OK;
-        hipLaunchKernelGGL(attn_grad_zero_rows_kernel, dim3(ew_grid(b->rows * f)), dim3(kBlock), 0, st, g->Out, g->ld_out, b->rows, f);
-        return hnh::check_hip(ctx, hipGetLastError(), "attn_grad_zero_rows_kernel launch");
-    }
+    const int64_t pitch = f;  // a segment's partial result: its row
+    AttnSums sums;
+    sums.add(0, g->Out, g->ld_out, f);
+    if (b->rowptr == nullptr) return attn_dispatch_no_nonzeros(ctx, st, b, flags, nullptr, sums, who);
     if (!b->col_idx || !g->X || !g->Y) return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": null pointer");
     if (g->ld_x < f) return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": ld_x is narrower than f");
     if (g->X == g->Out || g->Y == g->Out) return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": Out aliases an input");
@@ -417,11 +317,11 @@ int attn_grad_dispatch(hnh_ctx* ctx, const hnh_csr_block* b, const hnh_attn_grad
     const int gather_w = PASS == 1 ? HNH_ATTN_GRAD_PACKED_WIDTH(f, softmax) : f;
     auto launch = [&](const LongCtl& lc, const int32_t* beg_ptr, const int32_t* end_ptr, unsigned fl, bool run_long) {
         return attn_launch_shape(f, w2, [&](auto l, auto v, auto w, auto ex) {
-            return attn_grad_launch<PASS, decltype(l)::value, decltype(v)::value, decltype(w)::value, decltype(ex)::value>(
-                ctx, st, lc, b->rows, b->rowptr, beg_ptr, end_ptr, b->col_idx, a, fl, run_long);
+            return attn_launch<AgPass<PASS, decltype(l)::value, decltype(v)::value, decltype(w)::value, decltype(ex)::value>, false, true>(
+                ctx, st, lc, b->rows, b->rowptr, beg_ptr, end_ptr, b->col_idx, a, fl, run_long, pitch, sums);
         });
     };
-    return attn_dispatch_tail(ctx, st, stream, b, win, f, w2, (int64_t)f, gather_w, flags, who, launch);  // (a segment's partial result: its row)
+    return attn_dispatch_tail(ctx, st, stream, b, win, f, w2, pitch, gather_w, flags, who, launch);
 }
 
 }  // namespace

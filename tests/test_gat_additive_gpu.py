@@ -1,7 +1,7 @@
 """The GAT's additive (a1, a2) attention score on the GPU (include/hnh_attn_additive.h, GAT score "additive").
 
 Kernel level, through ctypes: the forward pass against the extended-precision numpy reference (tests/gat_pass_ref.py, fwd_pass_ld),
-the backward row and column passes against numpy, at widths 1, 2, 7, 16, 64, 100, 128, 256 on blocks with empty rows, rows of 200 - 300,
+the backward row and column passes against numpy, at widths 1, 2, 7, 16, 64, 100, 128, 200, 256 on blocks with empty rows, rows of 200 - 300,
 hub rows of 600 and 1500 and repeated pairs, with pitches wider than the widths, an output block at an odd column offset of an odd
 pitch, guard values around every output, and scores far outside exp's range (|z| about 800); their independence of how a row's
 nonzeros are split into launches (whole rows, one call per window, two uneven groupings of six windows, forced Infinity-Cache panels),
@@ -33,7 +33,7 @@ from gat_gpu_harness import (ALPHA, COL, FTOL, FWD, GROUPINGS, PASS_NAMES, ROW, 
 from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
-WIDTHS = [1, 2, 7, 16, 64, 100, 128, 256]
+WIDTHS = [1, 2, 7, 16, 64, 100, 128, 200, 256]
 MODE = dict(attention="softmax", score="additive")
 
 

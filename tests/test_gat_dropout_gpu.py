@@ -1,7 +1,7 @@
 """The GAT's dropout on the GPU (include/hnh_attn_dropout.h, GAT.set_dropout).
 
 Kernel level, through ctypes: the device generator against numpy bit for bit; the three masked passes against the numpy reference
-(tests/gat_pass_ref.py with `drop`; the forward pass against its extended-precision twin) at widths 1, 7, 33, 64, 100, 128, 255, 256 on the
+(tests/gat_pass_ref.py with `drop`; the forward pass against its extended-precision twin) at widths 1, 7, 33, 64, 100, 101, 128, 200, 255, 256 on the
 blocks of gat_gpu_harness.Problem (empty rows, hub rows of 600 and 1500, repeated pairs, guards round every output) and on a block with
 an R-MAT graph's degrees, with own-row ids that cross 2^31 and gathered-row ids that are a scattered relabelling; independence of
 windows, groups of windows and forced Infinity-Cache panels, bit for bit; the helper kernels exactly.
@@ -26,7 +26,7 @@ from gat_gpu_harness import (COL, FTOL, FWD, GROUPINGS, PASS_NAMES, ROW, TOL, Dr
 from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
-WIDTHS = [1, 7, 33, 64, 100, 128, 255, 256]
+WIDTHS = [1, 7, 33, 64, 100, 101, 128, 200, 255, 256]
 MODE = dict(attention="softmax", score="additive")
 
 

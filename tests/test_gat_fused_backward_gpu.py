@@ -31,7 +31,7 @@ from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
 KTOL = {False: T.TOL, True: 1e-10}  # kernel level, by softmax
-WIDTHS = [1, 7, 8, 16, 33, 64, 100, 128, 200, 255, 256]
+WIDTHS = [1, 7, 8, 16, 33, 64, 100, 101, 128, 200, 255, 256]
 
 
 # ------------------------------------------------------------------------------------------------ kernels

@@ -10,7 +10,7 @@ include/hnh_grad.h) on one GPU.
                                                     pass, and the ratios to relu.
 A build without the option (an earlier commit's) runs `--activations relu` — its own passes, which relu launches unchanged — and that is
 how the two builds are compared in one session.  Under `rocprofv3 --kernel-trace --stats` the run splits into kernels: the finishing
-launch of attn_add_row_kernel<0 ..> carries the activation, and act_grad_cols_kernel replaces relu_grad_cols_kernel and rowdot_cols_kernel
+launch of attn_rows_kernel<AaPass<0 ..>, true> carries the activation, and act_grad_cols_kernel replaces relu_grad_cols_kernel and rowdot_cols_kernel
 in the backward pass of a non-ReLU layer.
 """
 import os, sys, time

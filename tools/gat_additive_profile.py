@@ -8,8 +8,8 @@ fused; "additive": e_ij = LeakyReLU(<A_i, a1> + <A_j, a2>), include/hnh_attn_add
                                                     every pass runs between two device synchronisations; mean and min .. max per pass,
                                                     and the additive / dot ratios.
 A build without the additive score (an earlier commit's) runs `--score dot`, which is how the two builds are compared in one session.
-Under `rocprofv3 --kernel-trace --stats` the run splits into kernels (attn_add_row_kernel<0 ..> = forward, <1 ..> = backward row pass,
-<2 ..> = backward column pass).
+Under `rocprofv3 --kernel-trace --stats` the run splits into kernels (attn_rows_kernel<AaPass<0 ..>, true> = forward,
+attn_rows_kernel / attn_segments_kernel<AaPass<1 ..> ..> = backward row pass, <AaPass<2 ..> ..> = backward column pass).
 """
 import os, sys, time
 import numpy as np

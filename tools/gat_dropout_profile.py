@@ -9,8 +9,8 @@
                                                     and min .. max per pass, and the ratios to rates (0, 0).
 A build without dropout (an earlier commit's) runs `--rates none` — its additive passes, which rates (0, 0) launch unchanged — and that
 is how the two builds are compared in one session.  Under `rocprofv3 --kernel-trace --stats` the run splits into kernels: the trailing
-template argument of attn_add_row_kernel / attn_add_long_kernel is true for the masked instances (<0 ..> = forward, <1 ..> = backward
-row pass, <2 ..> = backward column pass); feat_drop_kernel is the feature mask.
+argument of the tag AaPass in attn_rows_kernel / attn_segments_kernel<AaPass<..> ..> is true for the masked instances (AaPass<0 ..> =
+forward, <1 ..> = backward row pass, <2 ..> = backward column pass); feat_drop_kernel is the feature mask.
 """
 import os, sys, time
 import numpy as np

@@ -122,7 +122,10 @@
 #include <map>
 #include <tuple>
 #include "hnh_dist.h"
-#define HNH_GAT_KERNEL(name) {(const void*)be->name, #name}  // (require_kernels; `be` = the backend in scope)
+// HNH_GAT_KERNEL(name): an entry of require_kernels' list.  HNH_GAT_CALL(name, arguments after the context): one kernel call on the
+// operator's world, refused with the kernel's name.
+#define HNH_GAT_KERNEL(name) {(const void*)d_ops->world->be->name, #name}
+#define HNH_GAT_CALL(name, ...) d_ops->world->check(d_ops->world->be->name(d_ops->world->ctx, __VA_ARGS__), #name)
 
 class GATLayer {
 public:
@@ -228,25 +231,14 @@ public:
         check_layer(i);
         if (host == nullptr) throw hnh::Error("Error, GAT set_residual_weight: null pointer!");
         ensure_residual_weight(i);
-        const GATLayer& L = layers[(size_t)i];
-        const int64_t k = L.input_features, f = L.features_per_head, hf = (int64_t)L.num_heads * f;
-        std::vector<double> head((size_t)(k * f));
-        for (int h = 0; h < L.num_heads; h++) {
-            for (int64_t r = 0; r < k; r++) std::memcpy(head.data() + r * f, host + r * hf + (int64_t)h * f, sizeof(double) * (size_t)f);
-            w_res_[(size_t)i][(size_t)h].copy_from_host(head.data());  // (waits for the copy: `head` is reused)
-        }
+        copy_residual_weight(i, host, nullptr);
         invalidate_forward();
     }
     void get_residual_weight(int i, double* host) {
         check_layer(i);
         if (host == nullptr) throw hnh::Error("Error, GAT get_residual_weight: null pointer!");
         if (w_res_[(size_t)i].empty()) throw hnh::Error("Error, GAT layer " + std::to_string(i) + " has no residual weight: set_residual(layer, projection) first!");
-        const GATLayer& L = layers[(size_t)i];
-        const int64_t k = L.input_features, f = L.features_per_head, hf = (int64_t)L.num_heads * f;
-        for (int h = 0; h < L.num_heads; h++) {
-            const std::vector<double> head = w_res_[(size_t)i][(size_t)h].to_host();
-            for (int64_t r = 0; r < k; r++) std::memcpy(host + r * hf + (int64_t)h * f, head.data() + r * f, sizeof(double) * (size_t)f);
-        }
+        copy_residual_weight(i, nullptr, host);
     }
     // The bias of layer i (num_heads * features_per_head HOST entries); nullptr switches it off.  Invalidates the stored forward pass.
     bool has_bias(int i) const {
@@ -304,13 +296,8 @@ public:
     }
     void set_attn_vectors(int i, int h, const double* a1_host, const double* a2_host) {
         ensure_attn_vectors(i);
-        GATLayer& L = layers.at((size_t)i);
-        if (h < 0 || h >= L.num_heads) throw hnh::Error("Error, GAT head index out of range!");
-        const int f = L.features_per_head;
-        hnh::World* w = d_ops->world;
-        w->copy(L.a1.data() + (int64_t)h * f, a1_host, (size_t)f * sizeof(double), HNH_COPY_H2D, HNH_STREAM_COMPUTE);
-        w->copy(L.a2.data() + (int64_t)h * f, a2_host, (size_t)f * sizeof(double), HNH_COPY_H2D, HNH_STREAM_COMPUTE);
-        w->sync(HNH_STREAM_COMPUTE);
+        if (h < 0 || h >= layers[(size_t)i].num_heads) throw hnh::Error("Error, GAT head index out of range!");
+        copy_attn_vectors(i, h, const_cast<double*>(a1_host), const_cast<double*>(a2_host), HNH_COPY_H2D);
         invalidate_forward();
     }
 
@@ -343,14 +330,9 @@ public:
     // between two product buffers; the layers' outputs are the reference's, bit for bit (same kernels, same operands).
     // HNH_GAT_SERIAL=1: the reference's order on one stream (A/B measurements).
     void forwardPass() {
-        const bool additive = score_ == HNH_GAT_SCORE_ADDITIVE, gatv2 = score_ == HNH_GAT_SCORE_GATV2;
-        check_dropout_supported();
-        check_activation_supported();
-        check_skip_supported();
-        if (attention_ == HNH_GAT_ATTENTION_SOFTMAX && !additive && !gatv2) check_softmax_supported();
-        if (additive) check_additive_supported();
-        if (gatv2) check_gatv2_supported();
-        if (additive || gatv2)
+        const bool additive = score_ == HNH_GAT_SCORE_ADDITIVE;
+        check_supported(OP_FORWARD);
+        if (learns_vectors())
             for (size_t i = 0; i < layers.size(); i++) ensure_attn_vectors((int)i);  // (on the compute stream, before the marks below)
         if (std::getenv("HNH_GAT_SERIAL") != nullptr) {
             for (size_t i = 0; i < layers.size(); i++)
@@ -402,10 +384,7 @@ public:
     // Results: weight_grads[i] (input_features x H f of layer i, column block h = dW_h, the same on every rank) and input_grads[i]
     // (dL/d(buffers[i]); input_grads[0] is the input gradient).  Buffers are allocated on the first call and reused.
     void backwardPass(const DenseMatrix& grad_out) {
-        check_dropout_supported();
-        check_activation_supported();
-        check_skip_supported();
-        check_backward_supported();
+        check_supported(OP_BACKWARD);
         if (!forward_valid_) throw hnh::Error("Error, GAT backwardPass needs a forwardPass first (and a new one after set_weight / set_input)!");
         const DenseMatrix& last = buffers.back();
         if (grad_out.rows() != last.rows() || grad_out.cols() != last.cols()) throw hnh::Error("Error, GAT output gradient has the wrong shape!");
@@ -447,17 +426,11 @@ public:
                 throw hnh::Error("Error, GAT " + what + " needs a vector of like_S_values length: " + std::to_string(want) + " entries, not " +
                                  std::to_string(out.size()) + "!");
         }
-        if (attention_ != HNH_GAT_ATTENTION_SOFTMAX)
-            throw hnh::Error("Error, GAT " + what + " supports attention mode softmax only, not attention mode none: its weights are what sddmmA and "
-                             "hnh_leaky_relu_f64 give (include/hnh_attn_coef.h)");
+        require_softmax(what, ": its weights are what sddmmA and hnh_leaky_relu_f64 give", "include/hnh_attn_coef.h");
         require_own_rows(what);
+        require_head_width(what, HNH_ATTN_COEF_MAX_F, "include/hnh_attn_coef.h", i);
         GATLayer& L = layers[(size_t)i];
         const int f = L.features_per_head;
-        if (f > HNH_ATTN_COEF_MAX_F)
-            throw hnh::Error("Error, GAT " + what + " supports heads of at most " + std::to_string(HNH_ATTN_COEF_MAX_F) + " features, not " + std::to_string(f) +
-                             " (include/hnh_attn_coef.h)");
-        hnh::World* w = d_ops->world;
-        const hnh::Backend* be = w->be;
         const bool additive = score_ == HNH_GAT_SCORE_ADDITIVE;
         require_kernels(what, "include/hnh_attn_coef.h", {HNH_GAT_KERNEL(hnh_attn_coef_csr_p)});
         if (additive) require_kernels(what, "include/hnh_attn_coef.h", {HNH_GAT_KERNEL(hnh_attn_coef_scores_f64)});
@@ -465,10 +438,9 @@ public:
             throw hnh::Error("Error, GAT " + what + " needs a forwardPass first (and a new one after set_weight / set_input / optimizer_step)!");
         const int S0 = HNH_STREAM_COMPUTE;
         DenseMatrix& X = layer_input(i);
-        DenseMatrix& Wh = L.wMats[(size_t)h];
         const int64_t rows = X.rows();
-        DenseMatrix& A = scratch(20, rows, f);
-        w->check(be->hnh_gemm_f64(w->ctx, rows, f, X.cols(), X.data(), Wh.data(), A.data(), S0), "hnh_gemm_f64");
+        DenseMatrix& A = scratch(SC_COEF_A, rows, f);
+        HNH_GAT_CALL(hnh_gemm_f64, rows, f, X.cols(), X.data(), L.wMats[(size_t)h].data(), A.data(), S0);
         hnh_attn_coef g = {};
         g.lse = lse_[(size_t)i][(size_t)h].data();
         g.f = f;
@@ -476,11 +448,10 @@ public:
         const int r0 = d_ops->R;
         bool ok;
         if (additive) {
-            DenseMatrix& sv = scratch(21, rows, 1);
-            DenseMatrix& T = scratch(22, rows, HNH_ATTN_COEF_PAIR_WIDTH);
-            w->check(be->hnh_attn_coef_scores_f64(w->ctx, sv.data(), T.data(), T.cols(), A.data(), f, L.a1.data() + (int64_t)h * f, L.a2.data() + (int64_t)h * f,
-                                                  rows, f, d_ops->aSubmatrices[0].topRow, S0),
-                     "hnh_attn_coef_scores_f64");
+            DenseMatrix& sv = scratch(SC_COEF_S, rows, 1);
+            DenseMatrix& T = scratch(SC_COEF_T, rows, HNH_ATTN_COEF_PAIR_WIDTH);
+            HNH_GAT_CALL(hnh_attn_coef_scores_f64, sv.data(), T.data(), T.cols(), A.data(), f, attn_vector(i, h, 0), attn_vector(i, h, 1), rows, f,
+                         d_ops->aSubmatrices[0].topRow, S0);
             g.score = HNH_ATTN_COEF_ADDITIVE;
             g.s = sv.data();
             const bool drop = dropped && attn_p_ > 0.0;
@@ -491,7 +462,7 @@ public:
             g.score = score_ == HNH_GAT_SCORE_GATV2 ? HNH_ATTN_COEF_GATV2 : HNH_ATTN_COEF_DOT;
             g.X = A.data();
             g.ld_x = f;
-            g.a = score_ == HNH_GAT_SCORE_GATV2 ? L.a1.data() + (int64_t)h * f : nullptr;
+            g.a = score_ == HNH_GAT_SCORE_GATV2 ? attn_vector(i, h, 0) : nullptr;
             ScheduleWidth width(d_ops, f, r0);
             ok = ds->attnCoef_pass(A, g, out);
         }
@@ -529,7 +500,7 @@ public:
     // (loss, accuracy) of the stored forward pass over the rows of `mask` (HOST, global numbering; nullptr: the training rows of set_labels);
     // grad_out != nullptr also receives dL/d(output) in the last buffer's layout, which backwardPass takes.  Collective.
     std::pair<double, double> loss(const uint8_t* mask, int64_t n, DenseMatrix* grad_out) {
-        check_train_supported(false);
+        check_supported(OP_LOSS);
         if (!forward_valid_) throw hnh::Error("Error, GAT loss needs a forwardPass first (and a new one after set_weight / set_input / optimizer_step)!");
         if (mask != nullptr && n != d_ops->M) throw hnh::Error("Error, GAT loss: the mask needs " + std::to_string(d_ops->M) + " entries, not " + std::to_string(n) + "!");
         const DenseMatrix& last = buffers.back();
@@ -542,7 +513,7 @@ public:
         return loss_read(ls);
     }
 
-    // (Re)allocates zeroed moments and resets the step count.  kind: HNH_OPTIM_ADAM | HNH_OPTIM_SGD (include/hnh_train.h).
+    // Sets the hyper-parameters, drops every moment and resets the step count.  kind: HNH_OPTIM_ADAM | HNH_OPTIM_SGD (include/hnh_train.h).
     void set_optimizer(int kind, double lr, double beta1, double beta2, double eps, double momentum, double weight_decay) {
         if (kind != HNH_OPTIM_ADAM && kind != HNH_OPTIM_SGD) throw hnh::Error("Error, unknown GAT optimizer " + std::to_string(kind) + " (adam = 0, sgd = 1)!");
         if (!(lr >= 0.0) || !std::isfinite(lr) || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0) || !(eps >= 0.0) || !(momentum >= 0.0 && momentum < 1.0) ||
@@ -556,83 +527,32 @@ public:
         optim_.eps = eps;
         optim_.momentum = momentum;
         optim_.weight_decay = weight_decay;
-        const size_t L = layers.size();
-        mom_w_.assign(L, std::vector<DenseMatrix>());
-        var_w_.assign(L, std::vector<DenseMatrix>());
-        mom_a_.assign(L * 2, DenseMatrix());
-        var_a_.assign(L * 2, DenseMatrix());
-        for (size_t i = 0; i < L; i++) {
-            const int64_t hf = (int64_t)layers[i].num_heads * layers[i].features_per_head;
-            for (const DenseMatrix& W : layers[i].wMats) {
-                mom_w_[i].push_back(kind == HNH_OPTIM_ADAM ? DenseMatrix::Constant(W.rows(), W.cols(), 0.0) : DenseMatrix());
-                var_w_[i].push_back(DenseMatrix::Constant(W.rows(), W.cols(), 0.0));
-            }
-            for (int q = 0; q < 2; q++) {
-                if (kind == HNH_OPTIM_ADAM) mom_a_[i * 2 + q] = DenseMatrix::Constant(hf, 1, 0.0);
-                var_a_[i * 2 + q] = DenseMatrix::Constant(hf, 1, 0.0);
-            }
-        }
-        mom_b_.assign(L, DenseMatrix());
-        var_b_.assign(L, DenseMatrix());
-        mom_r_.assign(L, std::vector<DenseMatrix>());
-        var_r_.assign(L, std::vector<DenseMatrix>());
-        ensure_skip_moments();
+        moments_.clear();
         optim_steps_ = 0;
         optimizer_set_ = true;
     }
     int64_t optimizer_steps() const { return optim_steps_; }
 
-    // One optimizer step from the gradients of the last backwardPass: every W, a1, a2 with score ADDITIVE (a1 with GATV2), and every enabled
-    // bias and W_res (include/hnh_gat_skip.h), in one table.  Invalidates
-    // the stored forward pass.  No host synchronisation.
+    // One optimizer step from the gradients of the last backwardPass over learned_parameters(), in one table.  Invalidates the stored
+    // forward pass.  No host synchronisation.
     void optimizer_step() {
-        const hnh::Backend* be = d_ops->world->be;
         if (!optimizer_set_) throw hnh::Error("Error, GAT optimizer_step needs set_optimizer first!");
         require_kernels("training", "include/hnh_train.h", {HNH_GAT_KERNEL(hnh_optim_step_f64)});
-        const bool additive = score_ == HNH_GAT_SCORE_ADDITIVE, gatv2 = score_ == HNH_GAT_SCORE_GATV2;
-        if (!grads_fresh_ || weight_grads.size() != layers.size() || ((additive || gatv2) && attn_grads.size() != layers.size()))
+        if (!grads_fresh_ || weight_grads.size() != layers.size() || (learns_vectors() && attn_grads.size() != layers.size()))
             throw hnh::Error("Error, GAT optimizer_step needs the gradients of a backwardPass since the last step!");
+        const std::vector<Learned> learned = learned_parameters();
+        for (const Learned& t : learned)
+            if (t.g == nullptr) throw hnh::Error(t.refusal);
         std::vector<hnh_optim_tensor> table;
-        for (size_t i = 0; i < layers.size(); i++) {
-            GATLayer& L = layers[i];
-            const int64_t f = L.features_per_head, hf = (int64_t)L.num_heads * f;
-            const DenseMatrix& dW = weight_grads[i];
-            for (int h = 0; h < L.num_heads; h++) {
-                DenseMatrix& W = L.wMats[(size_t)h];
-                if (dW.rows() != W.rows() || dW.cols() != hf || W.cols() != f) throw hnh::Error("Error, GAT optimizer_step: a weight gradient has the wrong shape!");
-                table.push_back({W.data(), f, dW.data() + (int64_t)h * f, hf, mom_w_[i][(size_t)h].data(), var_w_[i][(size_t)h].data(), W.rows(), f});
-            }
-            if (additive || gatv2) {
-                ensure_attn_vectors((int)i);
-                const DenseMatrix& da = attn_grads[i];  // (hf x 2: da1 and da2 interleaved; score GATV2: da and zeros)
-                if (da.rows() != hf || da.cols() != 2) throw hnh::Error("Error, GAT optimizer_step: an attention-vector gradient has the wrong shape!");
-                table.push_back({L.a1.data(), 1, da.data(), 2, mom_a_[i * 2].data(), var_a_[i * 2].data(), hf, 1});
-                if (additive) table.push_back({L.a2.data(), 1, da.data() + 1, 2, mom_a_[i * 2 + 1].data(), var_a_[i * 2 + 1].data(), hf, 1});  // (GATV2 does not use a2)
-            }
-        }
-        ensure_skip_moments();  // (a bias or a projection enabled after set_optimizer starts from zero moments)
-        for (size_t i = 0; i < layers.size(); i++) {
-            GATLayer& L = layers[i];
-            const int64_t f = L.features_per_head, hf = (int64_t)L.num_heads * f, k = L.input_features;
-            if (bias_on_[i]) {
-                if (bias_grads.size() != layers.size() || bias_grads[i].rows() != hf || bias_grads[i].cols() != 1)
-                    throw hnh::Error("Error, GAT optimizer_step needs the bias gradient of a backwardPass since set_bias!");
-                table.push_back({bias_[i].data(), 1, bias_grads[i].data(), 1, mom_b_[i].data(), var_b_[i].data(), hf, 1});
-            }
-            if (res_mode_[i] == HNH_GAT_RESIDUAL_PROJECTION) {
-                if (res_weight_grads.size() != layers.size() || res_weight_grads[i].rows() != k || res_weight_grads[i].cols() != hf)
-                    throw hnh::Error("Error, GAT optimizer_step needs the residual-weight gradient of a backwardPass since set_residual!");
-                for (int h = 0; h < L.num_heads; h++)
-                    table.push_back({w_res_[i][(size_t)h].data(), f, res_weight_grads[i].data() + (int64_t)h * f, hf, mom_r_[i][(size_t)h].data(),
-                                     var_r_[i][(size_t)h].data(), k, f});
-            }
+        for (const Learned& t : learned) {
+            const Moments& m = ensure_moments(t);
+            table.push_back({t.p, t.ld_p, t.g, t.ld_g, m.first.data(), m.second.data(), t.rows, t.cols});
         }
         optim_steps_++;
         hnh_optim hy = optim_;
         hy.bias1 = 1.0 - std::pow(hy.beta1, (double)optim_steps_);
         hy.bias2 = 1.0 - std::pow(hy.beta2, (double)optim_steps_);
-        hnh::World* w = d_ops->world;
-        w->check(be->hnh_optim_step_f64(w->ctx, table.data(), (int)table.size(), &hy, HNH_STREAM_COMPUTE), "hnh_optim_step_f64");
+        HNH_GAT_CALL(hnh_optim_step_f64, table.data(), (int)table.size(), &hy, HNH_STREAM_COMPUTE);
         grads_fresh_ = false;
         invalidate_forward();
     }
@@ -640,11 +560,7 @@ public:
     // One training step; returns (loss, accuracy) over the training rows, of the parameters before the update.  With a nonzero dropout
     // rate the seed advances by one first, so step t of a run uses the masks of seed0 + t.
     std::pair<double, double> train_step() {
-        check_train_supported(true);
-        check_dropout_supported();
-        check_activation_supported();
-        check_skip_supported();
-        check_backward_supported();
+        check_supported(OP_TRAIN_STEP);
         const uint64_t seed0 = seed_;
         const int64_t steps0 = optim_steps_;
         if (attn_p_ > 0.0 || feat_p_ > 0.0) seed_ += 1;  // (mod 2^64)
@@ -665,10 +581,7 @@ public:
     // (loss, accuracy) over the rows of `mask` (nullptr: the training rows) from a forward pass without dropout and without a gradient.
     // Rates and seed are as before afterwards; the stored forward pass is valid only if both rates were 0.
     std::pair<double, double> evaluate(const uint8_t* mask, int64_t n) {
-        check_train_supported(false);
-        check_dropout_supported();  // (an object that forwardPass and train_step refuse is not evaluated either)
-        check_activation_supported();
-        check_skip_supported();
+        check_supported(OP_EVALUATE);
         if (mask != nullptr && n != d_ops->M) throw hnh::Error("Error, GAT evaluate: the mask needs " + std::to_string(d_ops->M) + " entries, not " + std::to_string(n) + "!");
         LabelSet other;
         if (mask != nullptr) other = make_label_set(mask);
@@ -699,13 +612,8 @@ public:
     void get_attn_vectors(int i, int h, double* a1_host, double* a2_host) {
         check_layer_head(i, h);
         ensure_attn_vectors(i);
-        GATLayer& L = layers[(size_t)i];
-        const int f = L.features_per_head;
-        hnh::World* w = d_ops->world;
-        w->sync_all();
-        w->copy(a1_host, L.a1.data() + (int64_t)h * f, (size_t)f * sizeof(double), HNH_COPY_D2H, HNH_STREAM_COMPUTE);
-        w->copy(a2_host, L.a2.data() + (int64_t)h * f, (size_t)f * sizeof(double), HNH_COPY_D2H, HNH_STREAM_COMPUTE);
-        w->sync(HNH_STREAM_COMPUTE);
+        d_ops->world->sync_all();
+        copy_attn_vectors(i, h, a1_host, a2_host, HNH_COPY_D2H);
     }
 
     std::vector<DenseMatrix> weight_grads, input_grads;
@@ -725,18 +633,16 @@ private:
     double attn_p_ = 0.0, feat_p_ = 0.0;  // dropout rates and the masks' seed (include/hnh_attn_dropout.h)
     uint64_t seed_ = 0;
     std::vector<int> act_;                // HNH_GAT_ACT_* of every layer's output
-    DenseMatrix act_delta_;               // a non-ReLU layer's delta of the head in hand: backward_layer writes it, head_delta hands it out
+    DenseMatrix act_delta_;               // the delta of the head in hand where one launch makes dZ and delta: head_dz writes it, head_delta hands it out
     std::vector<DenseMatrix> xd_;         // feature dropout: Xd of every layer (allocated only then)
     // bias and skip connections (include/hnh_gat_skip.h): per layer the residual mode, W_res per head (input_features x f each, the
     // contiguous operand of hnh_gemm_f64; projection only), the bias (H f x 1) with its enabled bit; the projection of the head in
-    // flight (the auxiliary stream's scratch) and the moments of both parameters
+    // flight (the auxiliary stream's scratch)
     std::vector<int> res_mode_;
     std::vector<char> bias_on_;
     std::vector<DenseMatrix> bias_;
     std::vector<std::vector<DenseMatrix>> w_res_;
     DenseMatrix res_product_;
-    std::vector<DenseMatrix> mom_b_, var_b_;
-    std::vector<std::vector<DenseMatrix>> mom_r_, var_r_;
     // training (include/hnh_train.h): this rank's labels on the device (-1: not in the loss) with the world's labelled count; the host's
     // copy of all labels and of the training mask (loss / evaluate build other sets from them); the optimizer and its moments
     struct LabelSet {
@@ -751,8 +657,71 @@ private:
     DenseMatrix train_grad_, loss_result_;
     hnh_optim optim_ = {};
     int64_t optim_steps_ = 0;
-    std::vector<std::vector<DenseMatrix>> mom_w_, var_w_;
-    std::vector<DenseMatrix> mom_a_, var_a_;  // [2 layer + (0: a1, 1: a2)]
+    // Every learned tensor of the model is one row of optimizer_step's table (learned_parameters()); its moments live under its key.
+    enum ParamKind { PARAM_W, PARAM_A1, PARAM_A2, PARAM_BIAS, PARAM_W_RES };
+    typedef std::tuple<int, int, int> ParamKey;            // (kind, layer, head; head 0 for a tensor of the whole layer)
+    typedef std::pair<DenseMatrix, DenseMatrix> Moments;   // (first moment: Adam only, SGD keeps none; second moment, or SGD's momentum buffer)
+    struct Learned {
+        ParamKey key;
+        double* p;        // the value, rows x cols at pitch ld_p
+        int64_t ld_p;
+        const double* g;  // its gradient at pitch ld_g; nullptr where the gradient container does not hold it: `refusal` says so
+        int64_t ld_g, rows, cols;
+        const char* refusal;
+    };
+    std::map<ParamKey, Moments> moments_;
+
+    // The table's rows in order: per layer W_0 .. W_{H-1}, then a1, then a2 (score ADDITIVE; GATV2 learns a1 alone); after all layers, per
+    // layer the enabled bias, then W_res_0 .. W_res_{H-1} of a projection (include/hnh_gat_skip.h).  Weight decay applies to all alike.
+    std::vector<Learned> learned_parameters() {
+        std::vector<Learned> all;
+        const size_t n = layers.size();
+        // grads[i] where the container holds a rows x cols gradient of layer i
+        auto held = [&](const std::vector<DenseMatrix>& grads, size_t i, int64_t rows, int64_t cols) -> const DenseMatrix* {
+            return grads.size() == n && grads[i].rows() == rows && grads[i].cols() == cols ? &grads[i] : nullptr;
+        };
+        // one row: the gradient is the block of `grad` that starts at its column `at`
+        auto add = [&](int kind, size_t i, int h, double* p, int64_t ld_p, int64_t rows, int64_t cols, const DenseMatrix* grad, int64_t at, const char* refusal) {
+            all.push_back({ParamKey(kind, (int)i, h), p, ld_p, grad ? grad->data() + at : nullptr, grad ? grad->cols() : 0, rows, cols, refusal});
+        };
+        for (size_t i = 0; i < n; i++) {
+            GATLayer& L = layers[i];
+            const int64_t f = L.features_per_head, hf = (int64_t)L.num_heads * f;
+            for (int h = 0; h < L.num_heads; h++) {
+                DenseMatrix& W = L.wMats[(size_t)h];
+                add(PARAM_W, i, h, W.data(), f, W.rows(), f, W.cols() == f ? held(weight_grads, i, W.rows(), hf) : nullptr, (int64_t)h * f,
+                    "Error, GAT optimizer_step: a weight gradient has the wrong shape!");
+            }
+            if (!learns_vectors()) continue;
+            ensure_attn_vectors((int)i);
+            const DenseMatrix* da = held(attn_grads, i, hf, 2);  // (hf x 2: da1 and da2 interleaved; score GATV2: da and zeros)
+            const char* refusal = "Error, GAT optimizer_step: an attention-vector gradient has the wrong shape!";
+            add(PARAM_A1, i, 0, L.a1.data(), 1, hf, 1, da, 0, refusal);
+            if (score_ == HNH_GAT_SCORE_ADDITIVE) add(PARAM_A2, i, 0, L.a2.data(), 1, hf, 1, da, 1, refusal);
+        }
+        for (size_t i = 0; i < n; i++) {
+            const GATLayer& L = layers[i];
+            const int64_t f = L.features_per_head, hf = (int64_t)L.num_heads * f, k = L.input_features;
+            if (bias_on_[i])
+                add(PARAM_BIAS, i, 0, bias_[i].data(), 1, hf, 1, held(bias_grads, i, hf, 1), 0,
+                    "Error, GAT optimizer_step needs the bias gradient of a backwardPass since set_bias!");
+            if (res_mode_[i] != HNH_GAT_RESIDUAL_PROJECTION) continue;
+            for (int h = 0; h < L.num_heads; h++)
+                add(PARAM_W_RES, i, h, w_res_[i][(size_t)h].data(), f, k, f, held(res_weight_grads, i, k, hf), (int64_t)h * f,
+                    "Error, GAT optimizer_step needs the residual-weight gradient of a backwardPass since set_residual!");
+        }
+        return all;
+    }
+    // The moments of a learned tensor, on the compute stream: zeroed when the tensor is first learned after set_optimizer (the bias
+    // correction is the global step count's), kept from then on, also while the tensor is switched off.
+    const Moments& ensure_moments(const Learned& t) {
+        Moments& m = moments_[t.key];
+        if (m.second.rows() != t.rows || m.second.cols() != t.cols) {
+            if (optim_.kind == HNH_OPTIM_ADAM) m.first = DenseMatrix::Constant(t.rows, t.cols, 0.0);
+            m.second = DenseMatrix::Constant(t.rows, t.cols, 0.0);
+        }
+        return m;
+    }
 
     bool learns_vectors() const { return score_ == HNH_GAT_SCORE_ADDITIVE || score_ == HNH_GAT_SCORE_GATV2; }
     void check_layer(int i) const {
@@ -811,7 +780,6 @@ private:
     void check_train_supported(bool need_optimizer) {
         if (!labels_set_) throw hnh::Error("Error, GAT loss / train_step / evaluate need set_labels first!");
         if (need_optimizer && !optimizer_set_) throw hnh::Error("Error, GAT train_step needs set_optimizer first!");
-        const hnh::Backend* be = d_ops->world->be;
         require_kernels("training", "include/hnh_train.h", {HNH_GAT_KERNEL(hnh_xent_rows_f64_workspace), HNH_GAT_KERNEL(hnh_xent_rows_f64)});
         if (need_optimizer) require_kernels("training", "include/hnh_train.h", {HNH_GAT_KERNEL(hnh_optim_step_f64)});
         const int64_t width = (int64_t)layers.back().num_heads * layers.back().features_per_head;
@@ -857,19 +825,17 @@ private:
         return ls;
     }
     // the loss pass and the all-reduce of its two sums on the compute stream; G == nullptr: no gradient
+    // the loss pass and the all-reduce of its two sums on the compute stream; G == nullptr: no gradient
     void loss_enqueue(const LabelSet& ls, DenseMatrix* G) {
-        hnh::World* w = d_ops->world;
-        const hnh::Backend* be = w->be;
         const DenseMatrix& out = buffers.back();
         const GATLayer& L = layers.back();
         const int heads = label_heads_ == HNH_GAT_HEADS_MEAN ? L.num_heads : 1;
         if (loss_result_.size() != 2) loss_result_ = DenseMatrix(2, 1);
-        const int64_t need = be->hnh_xent_rows_f64_workspace(out.rows());
-        DenseMatrix& work = scratch(15, need, 1);
-        w->check(be->hnh_xent_rows_f64(w->ctx, out.data(), out.cols(), (const int32_t*)ls.labels.ptr(), out.rows(), heads, label_classes(), 1.0 / ls.count,
-                                       G ? G->data() : nullptr, out.cols(), loss_result_.data(), work.data(), need, HNH_STREAM_COMPUTE),
-                 "hnh_xent_rows_f64");
-        w->allreduce_f64(w->world_comm(), loss_result_.data(), 2, HNH_STREAM_COMPUTE);
+        const int64_t need = d_ops->world->be->hnh_xent_rows_f64_workspace(out.rows());
+        DenseMatrix& work = scratch(SC_XENT_WORK, need, 1);
+        HNH_GAT_CALL(hnh_xent_rows_f64, out.data(), out.cols(), (const int32_t*)ls.labels.ptr(), out.rows(), heads, label_classes(), 1.0 / ls.count,
+                     G ? G->data() : nullptr, out.cols(), loss_result_.data(), work.data(), need, HNH_STREAM_COMPUTE);
+        sum_over_world(loss_result_);
     }
     std::pair<double, double> loss_read(const LabelSet& ls) {
         hnh::World* w = d_ops->world;
@@ -889,12 +855,35 @@ private:
     std::vector<std::vector<DenseMatrix>> lse_;
     VectorXd lse_S_, delta_S_, lse_ST_, delta_ST_;
     VectorXd ones_S_, ones_ST_, e_S_, d_S_, e_ST_, d_ST_;  // backward: S values (= 1) and the recomputed / gated value vectors
-    std::map<std::tuple<int, int64_t, int64_t>, DenseMatrix> scratch_;  // backward work buffers by (role, rows, cols)
+    // Work buffers by (role, rows, cols).  A role has one call site, but for two that are shared on purpose: SC_TN_WORK, the split-K
+    // workspace of every X^T D product of gemm_tn, and SC_PACKED, the packed P = [A | dZ | lse delta] of the fused and the gatv2 backward.
+    enum ScratchRole { SC_DA_ALL, SC_WT, SC_A, SC_DZ, SC_DA_ROW, SC_T1, SC_T2, SC_TN_WORK, SC_DELTA, SC_PACKED, SC_ADD_M, SC_ADD_Q, SC_ADD_D, SC_ADD_DAGG,
+                       SC_ADD_TN_WORK, SC_XENT_WORK, SC_V2_R, SC_V2_C, SC_V2_DAGG, SC_V2_WORK, SC_COEF_A, SC_COEF_S, SC_COEF_T, SC_RES_PRODUCT, SC_DZ_ALL,
+                       SC_COLSUM_WORK, SC_DX_RES };
+    std::map<std::tuple<int, int64_t, int64_t>, DenseMatrix> scratch_;
 
-    DenseMatrix& scratch(int role, int64_t rows, int64_t cols) {
-        DenseMatrix& m = scratch_[std::make_tuple(role, rows, cols)];
+    // m at rows x cols: allocated anew (on the compute stream) unless it has that shape already
+    static DenseMatrix& shaped(DenseMatrix& m, int64_t rows, int64_t cols) {
         if (m.rows() != rows || m.cols() != cols) m = DenseMatrix(rows, cols);
         return m;
+    }
+    DenseMatrix& scratch_slot(ScratchRole role, int64_t rows, int64_t cols) { return scratch_[std::make_tuple((int)role, rows, cols)]; }  // (not shaped yet)
+    DenseMatrix& scratch(ScratchRole role, int64_t rows, int64_t cols) { return shaped(scratch_slot(role, rows, cols), rows, cols); }
+    void sum_over_world(DenseMatrix& m) {
+        hnh::World* w = d_ops->world;
+        w->allreduce_f64(w->world_comm(), m.data(), (size_t)m.size(), HNH_STREAM_COMPUTE);
+    }
+    // C (m x n at pitch ldc) = A^T B over `rows` local rows on the compute stream, the split-K workspace of hnh_gemm_tn_f64 from the scratch
+    void gemm_tn(int64_t m, int64_t n, int64_t rows, const double* A, int64_t lda, const double* B, int64_t ldb, double* C, int64_t ldc, ScratchRole work_role) {
+        const int64_t need = d_ops->world->be->hnh_gemm_tn_f64_workspace(m, n, rows);
+        double* work = need > 0 ? scratch(work_role, need, 1).data() : nullptr;
+        HNH_GAT_CALL(hnh_gemm_tn_f64, m, n, rows, A, lda, B, ldb, C, ldc, work, need, HNH_STREAM_COMPUTE);
+    }
+    // grad = X^T D over the local rows, then over every rank (the dense rows of the 1.5D layout are not replicated)
+    void world_grad_tn(DenseMatrix& grad, const DenseMatrix& X, const DenseMatrix& D) {
+        shaped(grad, X.cols(), D.cols());
+        gemm_tn(X.cols(), D.cols(), X.rows(), X.data(), X.cols(), D.data(), D.cols(), grad.data(), D.cols(), SC_TN_WORK);
+        sum_over_world(grad);
     }
 
     static uint32_t drop_threshold(double p) { return (uint32_t)std::floor(p * 4294967296.0); }  // keep iff word 0 >= floor(p 2^32)
@@ -912,19 +901,15 @@ private:
     DenseMatrix& layer_input(int i) { return feat_p_ > 0.0 ? xd_.at((size_t)i) : buffers[(size_t)i]; }
     // dst = c_q mask o src with layer i's feature mask (dst == src allowed), on the compute stream
     void feature_mask(int i, DenseMatrix& dst, const DenseMatrix& src) {
-        hnh::World* w = d_ops->world;
         const DenseSubmatrix& sub = i == 0 ? d_ops->bSubmatrices[0] : d_ops->aSubmatrices[0];  // (buffers[0] is laid out like B)
-        w->check(w->be->hnh_feat_drop_f64(w->ctx, dst.data(), dst.cols(), src.data(), src.cols(), src.rows(), src.cols(), sub.topRow, seed_, (uint32_t)i,
-                                          drop_threshold(feat_p_), 1.0 / (1.0 - feat_p_), HNH_STREAM_COMPUTE),
-                 "hnh_feat_drop_f64");
+        HNH_GAT_CALL(hnh_feat_drop_f64, dst.data(), dst.cols(), src.data(), src.cols(), src.rows(), src.cols(), sub.topRow, seed_, (uint32_t)i,
+                     drop_threshold(feat_p_), 1.0 / (1.0 - feat_p_), HNH_STREAM_COMPUTE);
     }
     void drop_input(int i) {
         if (!(feat_p_ > 0.0)) return;
         if (xd_.size() != buffers.size() - 1) xd_.assign(buffers.size() - 1, DenseMatrix());
         DenseMatrix& X = buffers[(size_t)i];
-        DenseMatrix& Xd = xd_[(size_t)i];
-        if (Xd.rows() != X.rows() || Xd.cols() != X.cols()) Xd = DenseMatrix(X.rows(), X.cols());
-        feature_mask(i, Xd, X);
+        feature_mask(i, shaped(xd_[(size_t)i], X.rows(), X.cols()), X);
     }
 
     // Dropout's own conditions, checked before anything is launched (and before the additive score's, whose kernel group a library
@@ -942,7 +927,6 @@ private:
                 throw hnh::Error("Error, GAT dropout needs at most 65536 heads per layer (the generator's counter words)!");
         if (feat_p_ > 0.0 && !whole_rows(true))
             throw hnh::Error("Error, GAT feature dropout needs one dense block of whole rows per rank, which " + d_ops->algorithm_name + " does not have!");
-        const hnh::Backend* be = d_ops->world->be;
         if (attn_p_ > 0.0)
             require_kernels("dropout", "include/hnh_attn_dropout.h",
                             {HNH_GAT_KERNEL(hnh_attn_drop_fwd_csr_p), HNH_GAT_KERNEL(hnh_attn_drop_row_csr_p), HNH_GAT_KERNEL(hnh_attn_drop_col_csr_p),
@@ -967,38 +951,93 @@ private:
         wr.clear();
         for (int h = 0; h < L.num_heads; h++) wr.push_back(DenseMatrix::Constant(L.wMats[(size_t)h].rows(), L.wMats[(size_t)h].cols(), 0.0));
     }
-    // zeroed moments for every enabled bias and W_res that has none yet (set_optimizer emptied them all)
-    void ensure_skip_moments() {
-        if (mom_b_.size() != layers.size()) return;  // (no optimizer yet)
-        const bool adam = optim_.kind == HNH_OPTIM_ADAM;
-        for (size_t i = 0; i < layers.size(); i++) {
-            const int64_t hf = (int64_t)layers[i].num_heads * layers[i].features_per_head;
-            if (bias_on_[i] && var_b_[i].rows() != hf) {
-                if (adam) mom_b_[i] = DenseMatrix::Constant(hf, 1, 0.0);
-                var_b_[i] = DenseMatrix::Constant(hf, 1, 0.0);
+    // W_res of layer i between one HOST matrix and the per-head operands: from `src` to the device, or from the device into `dst`
+    void copy_residual_weight(int i, const double* src, double* dst) {
+        const GATLayer& L = layers[(size_t)i];
+        const int64_t k = L.input_features, f = L.features_per_head, hf = (int64_t)L.num_heads * f;
+        std::vector<double> head((size_t)(k * f));
+        for (int h = 0; h < L.num_heads; h++) {
+            DenseMatrix& Wr = w_res_[(size_t)i][(size_t)h];
+            if (dst && Wr.size()) Wr.copy_to_host(head.data());
+            for (int64_t r = 0; r < k; r++) {
+                const int64_t at = r * hf + (int64_t)h * f;
+                if (dst) std::memcpy(dst + at, head.data() + r * f, sizeof(double) * (size_t)f);
+                else std::memcpy(head.data() + r * f, src + at, sizeof(double) * (size_t)f);
             }
-            if (res_mode_[i] == HNH_GAT_RESIDUAL_PROJECTION && var_r_[i].size() != w_res_[i].size()) {
-                mom_r_[i].clear();
-                var_r_[i].clear();
-                for (const DenseMatrix& W : w_res_[i]) {
-                    mom_r_[i].push_back(adam ? DenseMatrix::Constant(W.rows(), W.cols(), 0.0) : DenseMatrix());
-                    var_r_[i].push_back(DenseMatrix::Constant(W.rows(), W.cols(), 0.0));
-                }
-            }
+            if (src) Wr.copy_from_host(head.data());  // (waits for the copy: `head` is reused)
         }
     }
+    // head h's slice of layer i's a1 (q = 0) or a2 (q = 1), after ensure_attn_vectors
+    double* attn_vector(int i, int h, int q) {
+        GATLayer& L = layers[(size_t)i];
+        return (q == 0 ? L.a1 : L.a2).data() + (int64_t)h * L.features_per_head;
+    }
+    // both slices of (layer i, head h) from the host (HNH_COPY_H2D) or to it (HNH_COPY_D2H) on the compute stream, waited for
+    void copy_attn_vectors(int i, int h, double* a1_host, double* a2_host, int kind) {
+        hnh::World* w = d_ops->world;
+        double* host[2] = {a1_host, a2_host};
+        const size_t bytes = (size_t)layers[(size_t)i].features_per_head * sizeof(double);
+        for (int q = 0; q < 2; q++) {
+            double* dev = attn_vector(i, h, q);
+            w->copy(kind == HNH_COPY_H2D ? dev : host[q], kind == HNH_COPY_H2D ? host[q] : dev, bytes, kind, HNH_STREAM_COMPUTE);
+        }
+        w->sync(HNH_STREAM_COMPUTE);
+    }
     static const char* residual_name(int mode) { return mode == HNH_GAT_RESIDUAL_IDENTITY ? "identity" : (mode == HNH_GAT_RESIDUAL_PROJECTION ? "projection" : "none"); }
-    // The conditions of a layer with a bias or a skip connection, checked before anything is launched: the attention mode (the finish of
-    // a softmax pass takes the addend), the schedule (the softmax's), the shapes of residual identity, then the kernel group.  Every
-    // layer without: nothing to check, today's launches.
+    // the auxiliary stream's scratch for X W_res_h (allocated before the layer's ev_input mark, like the product buffers)
+    void shape_residual(int i) {
+        if (res_mode_[(size_t)i] == HNH_GAT_RESIDUAL_PROJECTION) shaped(res_product_, buffers[(size_t)i].rows(), layers[(size_t)i].features_per_head);
+    }
+    // The residual r of (layer i, head h) as the skip kernels take it: none, the head's column block of X (identity), or X W_res_h computed
+    // on `stream` into `buffer` (projection; shaped here if it is not yet).  No addend is kept between the passes: the forward pass computes
+    // the product on the stream of the head's product stage into res_product_, the backward pass again on the compute stream into its scratch.
+    struct Operand {
+        const double* data;
+        int64_t ld;
+    };
+    Operand residual_operand(int i, int h, int stream, DenseMatrix& buffer) {
+        DenseMatrix& X = layer_input(i);
+        const int64_t f = layers[(size_t)i].features_per_head;
+        if (res_mode_[(size_t)i] == HNH_GAT_RESIDUAL_IDENTITY) return {X.data() + (int64_t)h * f, X.cols()};
+        if (res_mode_[(size_t)i] != HNH_GAT_RESIDUAL_PROJECTION) return {nullptr, 0};
+        shaped(buffer, X.rows(), f);
+        HNH_GAT_CALL(hnh_gemm_f64, X.rows(), f, X.cols(), X.data(), w_res_[(size_t)i].at((size_t)h).data(), buffer.data(), stream);
+        return {buffer.data(), f};
+    }
+    const double* head_bias(int i, int h) const {
+        return bias_on_[(size_t)i] ? bias_[(size_t)i].data() + (int64_t)h * layers[(size_t)i].features_per_head : nullptr;
+    }
+    // the addend r + b of (layer i, head j) into the head's column block of buffers[i + 1], on `stream`; nothing for a layer without
+    void head_addend(int i, int j, int stream) {
+        if (!has_addend(i)) return;
+        DenseMatrix& out = buffers[(size_t)i + 1];
+        const int64_t f = layers[(size_t)i].features_per_head;
+        const Operand res = residual_operand(i, j, stream, res_product_);
+        HNH_GAT_CALL(hnh_skip_addend_cols_f64, out.data(), out.cols(), (int64_t)j * f, res.data, res.ld, head_bias(i, j), out.rows(), f, stream);
+    }
+
+    // ---- support.  Four conditions recur in the optional features' checks: attention softmax (require_softmax), a schedule on which a rank's
+    // own launches see whole rows (require_own_rows), a head width (require_head_width) and a kernel group (require_kernels).  Each feature's
+    // check below runs its conditions in its own order, and check_supported runs the features' checks in the entry point's order; every
+    // refusal happens before anything is launched.
+    void require_softmax(const std::string& what, const char* why, const char* header) const {
+        if (attention_ != HNH_GAT_ATTENTION_SOFTMAX)
+            throw hnh::Error("Error, GAT " + what + " supports attention mode softmax only, not attention mode none" + why + " (" + header + ")");
+    }
+    // heads of at most `limit` features on layer `only`, or on every layer
+    void require_head_width(const std::string& what, int limit, const char* header, int only = -1) const {
+        for (size_t i = 0; i < layers.size(); i++)
+            if ((only < 0 || (int)i == only) && layers[i].features_per_head > limit)
+                throw hnh::Error("Error, GAT " + what + " supports heads of at most " + std::to_string(limit) + " features, not " +
+                                 std::to_string(layers[i].features_per_head) + " (" + header + ")");
+    }
+    // A layer with a bias or a skip connection: the finish of a softmax pass takes the addend; the shapes of residual identity.
     void check_skip_supported() {
         for (size_t i = 0; i < layers.size(); i++) {
             if (!has_addend((int)i)) continue;
             const std::string what = (res_mode_[i] != HNH_GAT_RESIDUAL_NONE ? std::string("residual ") + residual_name(res_mode_[i]) : std::string("bias")) +
                                      " of layer " + std::to_string(i);
-            if (attention_ != HNH_GAT_ATTENTION_SOFTMAX)
-                throw hnh::Error("Error, GAT " + what + " supports attention mode softmax only, not attention mode none: its passes have no addend "
-                                 "(include/hnh_gat_skip.h)");
+            require_softmax(what, ": its passes have no addend", "include/hnh_gat_skip.h");
             require_own_rows(what);
             if (res_mode_[i] == HNH_GAT_RESIDUAL_IDENTITY) {
                 const DenseMatrix &X = buffers[i], &out = buffers[i + 1];
@@ -1009,59 +1048,23 @@ private:
                                      std::to_string(X.cols()) + " and " + std::to_string(out.rows()) + " x " + std::to_string(out.cols()) +
                                      ": use residual projection!");
             }
-            const hnh::Backend* be = d_ops->world->be;
             require_kernels(what, "include/hnh_gat_skip.h",
                             {HNH_GAT_KERNEL(hnh_skip_addend_cols_f64), HNH_GAT_KERNEL(hnh_skip_grad_cols_f64), HNH_GAT_KERNEL(hnh_colsum_f64_workspace),
                              HNH_GAT_KERNEL(hnh_colsum_f64)});
         }
     }
-    // the auxiliary stream's scratch for X W_res_h (allocated before the layer's ev_input mark, like the product buffers)
-    void shape_residual(int i) {
-        if (res_mode_[(size_t)i] != HNH_GAT_RESIDUAL_PROJECTION) return;
-        const int64_t rows = buffers[(size_t)i].rows(), f = layers[(size_t)i].features_per_head;
-        if (res_product_.rows() != rows || res_product_.cols() != f) res_product_ = DenseMatrix(rows, f);
-    }
-    // the addend r + b of (layer i, head j) into the head's column block of buffers[i + 1], on `stream`; nothing for a layer without
-    void head_addend(int i, int j, int stream) {
-        if (!has_addend(i)) return;
-        hnh::World* w = d_ops->world;
-        const hnh::Backend* be = w->be;
-        DenseMatrix& X = layer_input(i);
-        DenseMatrix& out = buffers[(size_t)i + 1];
-        const int64_t f = layers[(size_t)i].features_per_head, rows = out.rows();
-        const double* res = nullptr;
-        int64_t ld_res = 0;
-        if (res_mode_[(size_t)i] == HNH_GAT_RESIDUAL_IDENTITY) {
-            res = X.data() + (int64_t)j * f;
-            ld_res = X.cols();
-        } else if (res_mode_[(size_t)i] == HNH_GAT_RESIDUAL_PROJECTION) {
-            shape_residual(i);
-            DenseMatrix& Wr = w_res_[(size_t)i].at((size_t)j);
-            w->check(be->hnh_gemm_f64(w->ctx, X.rows(), f, X.cols(), X.data(), Wr.data(), res_product_.data(), stream), "hnh_gemm_f64");
-            res = res_product_.data();
-            ld_res = f;
-        }
-        const double* b = bias_on_[(size_t)i] ? bias_[(size_t)i].data() + (int64_t)j * f : nullptr;
-        w->check(be->hnh_skip_addend_cols_f64(w->ctx, out.data(), out.cols(), (int64_t)j * f, res, ld_res, b, rows, f, stream), "hnh_skip_addend_cols_f64");
-    }
-
-    // A non-ReLU layer's own conditions, checked before anything is launched: the attention mode (attention none ends in the fused pair's
-    // or the un-fused route's ReLU), the schedule (the softmax's), then a kernel library that knows the activation flags, which is one
-    // that exports hnh_act_grad_cols_f64.  Every layer at relu: nothing to check, today's launches.
+    // A non-ReLU layer: attention none ends in the fused pair's or the un-fused route's ReLU; a kernel library that knows the activation
+    // flags is one that exports hnh_act_grad_cols_f64.
     void check_activation_supported() {
         for (size_t i = 0; i < layers.size(); i++) {
             if (act_[i] == HNH_GAT_ACT_RELU) continue;
             const std::string what = std::string("activation ") + activation_name(act_[i]) + " of layer " + std::to_string(i);
-            if (attention_ != HNH_GAT_ATTENTION_SOFTMAX)
-                throw hnh::Error("Error, GAT " + what + " supports attention mode softmax only, not attention mode none: its passes end in a ReLU "
-                                 "(include/hnh_attention.h)");
+            require_softmax(what, ": its passes end in a ReLU", "include/hnh_attention.h");
             require_own_rows(what);
-            const hnh::Backend* be = d_ops->world->be;
             require_kernels(what, "include/hnh_grad.h", {HNH_GAT_KERNEL(hnh_act_grad_cols_f64)});
         }
     }
-
-    // Throws hnh::Error (never a wrong number) where the backward pass is not defined or its kernels are missing.
+    // The backward pass: the score's or the fused mode's own conditions first, then the plain pass's schedules and kernel groups.
     void check_backward_supported() {
         if (score_ == HNH_GAT_SCORE_ADDITIVE) check_additive_supported();
         else if (score_ == HNH_GAT_SCORE_GATV2) check_gatv2_supported();
@@ -1072,7 +1075,6 @@ private:
                              d_ops->algorithm_name);
         if (ds->fusionApproach == 2 && ds->c != 1)
             throw hnh::Error("Error, GAT backwardPass does not support 15d_fusion2 with c > 1 (its forward pass reproduces a quirk of the reference)");
-        const hnh::Backend* be = d_ops->world->be;
         require_kernels("backwardPass", "include/hnh_grad.h",
                         {HNH_GAT_KERNEL(hnh_gemm_tn_f64_workspace), HNH_GAT_KERNEL(hnh_gemm_tn_f64), HNH_GAT_KERNEL(hnh_leaky_relu_grad_f64),
                          HNH_GAT_KERNEL(hnh_relu_grad_cols_f64), HNH_GAT_KERNEL(hnh_sum3_cols_f64), HNH_GAT_KERNEL(hnh_transpose_into_f64)});
@@ -1080,59 +1082,35 @@ private:
             require_kernels("backwardPass with softmax attention", "include/hnh_attention.h",
                             {HNH_GAT_KERNEL(hnh_softmax_gate_f64), HNH_GAT_KERNEL(hnh_rowdot_cols_f64)});
     }
-
-    // The fused backward mode's own conditions, checked before anything is launched: its kernel group first, then the schedule (a rank's
-    // own launches must see all of a row's nonzeros and no output row may be summed across ranks: 15d_fusion2 with c = 1, the condition
-    // of the fused forward), then the head widths.
+    // The fused backward mode: its kernel group first.
     void check_fused_backward_supported() {
-        const hnh::Backend* be = d_ops->world->be;
         require_kernels("backwardPass in fused mode", "include/hnh_attn_grad.h",
                         {HNH_GAT_KERNEL(hnh_attn_grad_row_csr_p), HNH_GAT_KERNEL(hnh_attn_grad_col_csr_p), HNH_GAT_KERNEL(hnh_attn_grad_pack_f64)});
         require_own_rows("fused backward");
-        for (const GATLayer& L : layers)
-            if (L.features_per_head > HNH_ATTN_GRAD_MAX_F)
-                throw hnh::Error("Error, GAT fused backward supports heads of at most " + std::to_string(HNH_ATTN_GRAD_MAX_F) + " features, not " +
-                                 std::to_string(L.features_per_head) + " (include/hnh_attn_grad.h)");
+        require_head_width("fused backward", HNH_ATTN_GRAD_MAX_F, "include/hnh_attn_grad.h");
     }
-
-    // The additive score's own conditions, checked before anything is launched: the attention mode, the schedule (the softmax's: a
-    // rank's own launches see all of a row's nonzeros), the head widths, then its kernel group.
     void check_additive_supported() {
-        if (attention_ != HNH_GAT_ATTENTION_SOFTMAX)
-            throw hnh::Error("Error, GAT score additive supports attention mode softmax only, not attention mode none (include/hnh_attn_additive.h)");
+        require_softmax("score additive", "", "include/hnh_attn_additive.h");
         require_own_rows("score additive");
-        for (const GATLayer& L : layers)
-            if (L.features_per_head > HNH_ATTN_ADD_MAX_F)
-                throw hnh::Error("Error, GAT score additive supports heads of at most " + std::to_string(HNH_ATTN_ADD_MAX_F) + " features, not " +
-                                 std::to_string(L.features_per_head) + " (include/hnh_attn_additive.h)");
-        const hnh::Backend* be = d_ops->world->be;
+        require_head_width("score additive", HNH_ATTN_ADD_MAX_F, "include/hnh_attn_additive.h");
         require_kernels("score additive", "include/hnh_attn_additive.h",
                         {HNH_GAT_KERNEL(hnh_attn_add_fwd_csr_p), HNH_GAT_KERNEL(hnh_attn_add_row_csr_p), HNH_GAT_KERNEL(hnh_attn_add_col_csr_p),
                          HNH_GAT_KERNEL(hnh_attn_add_scores_f64), HNH_GAT_KERNEL(hnh_attn_add_pack_f64), HNH_GAT_KERNEL(hnh_attn_add_update_f64)});
     }
-
-    // The gatv2 score's own conditions, checked before anything is launched: the attention mode, the schedule (the softmax's), the head
-    // widths, attention dropout (its passes have no mask), then its kernel group and the pack kernel of the fused backward it reuses.
+    // The gatv2 score: no attention dropout (its passes have no mask); its kernel group and the pack kernel of the fused backward it reuses.
     void check_gatv2_supported() {
-        if (attention_ != HNH_GAT_ATTENTION_SOFTMAX)
-            throw hnh::Error("Error, GAT score gatv2 supports attention mode softmax only, not attention mode none (include/hnh_attn_v2.h)");
+        require_softmax("score gatv2", "", "include/hnh_attn_v2.h");
         require_own_rows("score gatv2");
-        for (const GATLayer& L : layers)
-            if (L.features_per_head > HNH_ATTN_V2_MAX_F)
-                throw hnh::Error("Error, GAT score gatv2 supports heads of at most " + std::to_string(HNH_ATTN_V2_MAX_F) + " features, not " +
-                                 std::to_string(L.features_per_head) + " (include/hnh_attn_v2.h)");
+        require_head_width("score gatv2", HNH_ATTN_V2_MAX_F, "include/hnh_attn_v2.h");
         if (attn_p_ > 0.0)
             throw hnh::Error("Error, GAT score gatv2 does not support attention dropout (p = " + std::to_string(attn_p_) +
                              "): its passes have no mask (include/hnh_attn_v2.h)");
-        const hnh::Backend* be = d_ops->world->be;
         require_kernels("score gatv2", "include/hnh_attn_v2.h",
                         {HNH_GAT_KERNEL(hnh_attn_v2_fwd_csr_p), HNH_GAT_KERNEL(hnh_attn_v2_row_csr_p), HNH_GAT_KERNEL(hnh_attn_v2_col_csr_p),
                          HNH_GAT_KERNEL(hnh_attn_v2_finish_f64)});
         require_kernels("score gatv2", "include/hnh_attn_grad.h", {HNH_GAT_KERNEL(hnh_attn_grad_pack_f64)});
     }
-
-    // Throws hnh::Error (never a wrong number) where softmax attention is not defined or its kernel is missing: a row's softmax needs
-    // all of the row's nonzeros summed by this rank's own launches (require_own_rows).
+    // Softmax attention with score dot: a row's softmax needs all of the row's nonzeros summed by this rank's own launches.
     void check_softmax_supported() {
         require_own_rows("softmax attention");
         // a head is one pass over its columns (include/hnh_attention.h); its operands are whole allocations and column blocks at an even
@@ -1143,14 +1121,50 @@ private:
                 throw hnh::Error("Error, GAT softmax attention supports heads of at most 512 features (256 when odd), not " + std::to_string(f) +
                                  ": a row's softmax is one pass over its columns (include/hnh_attention.h)");
         }
-        const hnh::Backend* be = d_ops->world->be;
         require_kernels("softmax attention", "include/hnh_attention.h", {HNH_GAT_KERNEL(hnh_attn_softmax_csr_p)});
     }
+    // What an entry point refuses, in one order: the training state (labels, optimizer, training kernels, output width, whole rows), then
+    // dropout, the activations, bias and skip connections, then the backward pass's conditions or, for a forward pass, the score's own.  The
+    // stored forward pass and the shapes of the arguments are the entry point's own checks, afterwards.
+    enum Op { OP_FORWARD, OP_BACKWARD, OP_TRAIN_STEP, OP_EVALUATE, OP_LOSS };
+    void check_supported(Op op) {
+        if (op == OP_TRAIN_STEP || op == OP_EVALUATE || op == OP_LOSS) check_train_supported(op == OP_TRAIN_STEP);
+        if (op == OP_LOSS) return;
+        check_dropout_supported();
+        check_activation_supported();
+        check_skip_supported();
+        if (op == OP_BACKWARD || op == OP_TRAIN_STEP) check_backward_supported();
+        if (op != OP_FORWARD) return;  // (evaluate's forwardPass checks the score)
+        if (score_ == HNH_GAT_SCORE_ADDITIVE) check_additive_supported();
+        else if (score_ == HNH_GAT_SCORE_GATV2) check_gatv2_supported();
+        else if (attention_ == HNH_GAT_ATTENTION_SOFTMAX) check_softmax_supported();
+    }
 
+    // the kernels' HNH_ACT_* (include/hnh_grad.h) of a layer's HNH_GAT_ACT_*
+    static int kernel_activation(int mode) { return mode == HNH_GAT_ACT_ELU ? HNH_ACT_ELU : (mode == HNH_GAT_ACT_IDENTITY ? HNH_ACT_IDENTITY : HNH_ACT_RELU); }
+    // dZ of (layer i, head h) from G and the stored output, on the compute stream.  A plain ReLU layer: hnh_relu_grad_cols_f64 (head_delta
+    // computes the delta where a softmax needs one).  Another activation: one launch makes dZ and delta, which waits in act_delta_ for
+    // head_delta.  A layer with an addend: the same with the addend taken out of the recovered pre-activation (include/hnh_gat_skip.h), ReLU
+    // included, and dZ also into the head's column block of dZ_all.
+    void head_dz(int i, int h, const DenseMatrix& G, DenseMatrix& dZ, DenseMatrix* dZ_all) {
+        const int S0 = HNH_STREAM_COMPUTE;
+        const DenseMatrix& out = buffers[(size_t)i + 1];
+        const int64_t rows = dZ.rows(), f = dZ.cols(), hf = out.cols(), at = (int64_t)h * f;
+        const int act = act_[(size_t)i];
+        if (dZ_all != nullptr) {
+            const Operand res = residual_operand(i, h, S0, scratch_slot(SC_RES_PRODUCT, rows, f));
+            shaped(act_delta_, rows, 1);
+            HNH_GAT_CALL(hnh_skip_grad_cols_f64, dZ.data(), f, dZ_all->data(), hf, act_delta_.data(), G.data(), hf, out.data(), hf, at, res.data, res.ld,
+                         head_bias(i, h), rows, f, kernel_activation(act), S0);
+        } else if (act == HNH_GAT_ACT_RELU) {
+            HNH_GAT_CALL(hnh_relu_grad_cols_f64, dZ.data(), f, G.data(), hf, out.data(), hf, at, rows, f, S0);
+        } else {
+            shaped(act_delta_, rows, 1);
+            HNH_GAT_CALL(hnh_act_grad_cols_f64, dZ.data(), f, act_delta_.data(), G.data(), hf, out.data(), hf, at, rows, f, kernel_activation(act), S0);
+        }
+    }
     // one layer of the backward pass: G = dL/d(buffers[i + 1]) -> weight_grads[i], input_grads[i]
     void backward_layer(int i, const DenseMatrix& G) {
-        hnh::World* w = d_ops->world;
-        const hnh::Backend* be = w->be;
         const int S0 = HNH_STREAM_COMPUTE;
         DenseMatrix& X = layer_input(i);  // (Xd with feature dropout: the forward pass's products used it)
         const DenseMatrix& out = buffers[(size_t)i + 1];
@@ -1158,131 +1172,76 @@ private:
         const int64_t rows = X.rows(), k = X.cols(), hf = (int64_t)H * f;
         if (out.rows() != rows || out.cols() != hf || G.rows() != rows || G.cols() != hf)
             throw hnh::Error("Error, GAT backwardPass: layer buffers do not have the layer's shape!");
-        DenseMatrix& dA_all = scratch(0, rows, hf);
-        DenseMatrix& Wt = scratch(1, hf, k);
-        if (learns_vectors()) {
-            DenseMatrix& dav = attn_grads[(size_t)i];
-            if (dav.rows() != hf || dav.cols() != 2) dav = DenseMatrix(hf, 2);
-            if (score_ == HNH_GAT_SCORE_GATV2) dav.setZero();  // (column 1 stays zero; column 0 is written head by head)
-        }
-        const bool skip = has_addend(i);
-        const int rmode = res_mode_[(size_t)i];
-        DenseMatrix* dZ_all = skip ? &scratch(24, rows, hf) : nullptr;
+        DenseMatrix& dA_all = scratch(SC_DA_ALL, rows, hf);
+        DenseMatrix& Wt = scratch(SC_WT, hf, k);
+        if (learns_vectors() && score_ == HNH_GAT_SCORE_GATV2) shaped(attn_grads[(size_t)i], hf, 2).setZero();  // (column 1 stays zero; column 0 is written head by head)
+        else if (learns_vectors()) shaped(attn_grads[(size_t)i], hf, 2);
+        DenseMatrix* dZ_all = has_addend(i) ? &scratch(SC_DZ_ALL, rows, hf) : nullptr;
         d_ops->setRValue(f);
         for (int h = 0; h < H; h++) {
             DenseMatrix& Wh = layers[(size_t)i].wMats[(size_t)h];
-            DenseMatrix& A = scratch(2, rows, f);
-            DenseMatrix& dZ = scratch(3, rows, f);
-            w->check(be->hnh_gemm_f64(w->ctx, rows, f, k, X.data(), Wh.data(), A.data(), S0), "hnh_gemm_f64");
-            if (skip) {  // dZ (also into dZ_all) and delta with the addend taken out of the recovered pre-activation (include/hnh_gat_skip.h)
-                const double* res = nullptr;
-                int64_t ld_res = 0;
-                if (rmode == HNH_GAT_RESIDUAL_IDENTITY) {
-                    res = X.data() + (int64_t)h * f;
-                    ld_res = k;
-                } else if (rmode == HNH_GAT_RESIDUAL_PROJECTION) {  // recomputed: no addend is kept between the passes
-                    DenseMatrix& P = scratch(23, rows, f);
-                    w->check(be->hnh_gemm_f64(w->ctx, rows, f, k, X.data(), w_res_[(size_t)i].at((size_t)h).data(), P.data(), S0), "hnh_gemm_f64");
-                    res = P.data();
-                    ld_res = f;
-                }
-                if (act_delta_.rows() != rows || act_delta_.cols() != 1) act_delta_ = DenseMatrix(rows, 1);
-                const int act = act_[(size_t)i] == HNH_GAT_ACT_ELU ? HNH_ACT_ELU : (act_[(size_t)i] == HNH_GAT_ACT_IDENTITY ? HNH_ACT_IDENTITY : HNH_ACT_RELU);
-                w->check(be->hnh_skip_grad_cols_f64(w->ctx, dZ.data(), f, dZ_all->data(), hf, act_delta_.data(), G.data(), hf, out.data(), hf, (int64_t)h * f, res,
-                                                    ld_res, bias_on_[(size_t)i] ? bias_[(size_t)i].data() + (int64_t)h * f : nullptr, rows, f, act, S0),
-                         "hnh_skip_grad_cols_f64");
-            } else if (act_[(size_t)i] == HNH_GAT_ACT_RELU)
-                w->check(be->hnh_relu_grad_cols_f64(w->ctx, dZ.data(), f, G.data(), hf, out.data(), hf, (int64_t)h * f, rows, f, S0),
-                         "hnh_relu_grad_cols_f64");
-            else {  // dZ and delta from one read of G and the stored output; the delta waits in act_delta_ for head_delta
-                if (act_delta_.rows() != rows || act_delta_.cols() != 1) act_delta_ = DenseMatrix(rows, 1);
-                w->check(be->hnh_act_grad_cols_f64(w->ctx, dZ.data(), f, act_delta_.data(), G.data(), hf, out.data(), hf, (int64_t)h * f, rows, f,
-                                                   act_[(size_t)i] == HNH_GAT_ACT_ELU ? HNH_ACT_ELU : HNH_ACT_IDENTITY, S0),
-                         "hnh_act_grad_cols_f64");
-            }
+            DenseMatrix& A = scratch(SC_A, rows, f);
+            DenseMatrix& dZ = scratch(SC_DZ, rows, f);
+            HNH_GAT_CALL(hnh_gemm_f64, rows, f, k, X.data(), Wh.data(), A.data(), S0);
+            head_dz(i, h, G, dZ, dZ_all);
             if (score_ == HNH_GAT_SCORE_ADDITIVE) backward_head_additive(i, h, A, dZ, dA_all);
             else if (score_ == HNH_GAT_SCORE_GATV2) backward_head_gatv2(i, h, A, dZ, dA_all);
             else if (backward_ == HNH_GAT_BACKWARD_FUSED) backward_head_fused(i, h, A, dZ, dA_all);
             else backward_head_unfused(i, h, A, dZ, dA_all);
-            w->check(be->hnh_transpose_into_f64(w->ctx, Wt.data(), k, (int64_t)h * f, Wh.data(), k, f, S0), "hnh_transpose_into_f64");
+            HNH_GAT_CALL(hnh_transpose_into_f64, Wt.data(), k, (int64_t)h * f, Wh.data(), k, f, S0);
         }
-        // dW_all = X^T dA_all over the local rows, then over every rank (the dense rows of the 1.5D layout are not replicated)
-        DenseMatrix& dW = weight_grads[(size_t)i];
-        if (dW.rows() != k || dW.cols() != hf) dW = DenseMatrix(k, hf);
-        const int64_t need = be->hnh_gemm_tn_f64_workspace(k, hf, rows);
-        DenseMatrix* work = need > 0 ? &scratch(7, need, 1) : nullptr;
-        w->check(be->hnh_gemm_tn_f64(w->ctx, k, hf, rows, X.data(), k, dA_all.data(), hf, dW.data(), hf, work ? work->data() : nullptr,
-                                     need, S0),
-                 "hnh_gemm_tn_f64");
-        w->allreduce_f64(w->world_comm(), dW.data(), (size_t)dW.size(), S0);
-        if (learns_vectors()) {
-            DenseMatrix& dav = attn_grads[(size_t)i];
-            w->allreduce_f64(w->world_comm(), dav.data(), (size_t)dav.size(), S0);
-        }
+        world_grad_tn(weight_grads[(size_t)i], X, dA_all);  // dW_all = X^T dA_all
+        if (learns_vectors()) sum_over_world(attn_grads[(size_t)i]);
         // dX = dA_all [W_1^T; ..; W_H^T]
-        DenseMatrix& dX = input_grads[(size_t)i];
-        if (dX.rows() != rows || dX.cols() != k) dX = DenseMatrix(rows, k);
-        w->check(be->hnh_gemm_f64(w->ctx, rows, k, hf, dA_all.data(), Wt.data(), dX.data(), S0), "hnh_gemm_f64");
-        if (skip) backward_skip(i, X, *dZ_all, Wt, dX);
+        DenseMatrix& dX = shaped(input_grads[(size_t)i], rows, k);
+        HNH_GAT_CALL(hnh_gemm_f64, rows, k, hf, dA_all.data(), Wt.data(), dX.data(), S0);
+        if (dZ_all != nullptr) backward_skip(i, X, *dZ_all, Wt, dX);
         if (feat_p_ > 0.0) feature_mask(i, dX, dX);  // dL/dX = c_q mask o dL/dXd
     }
     // The bias's and the skip connection's share of layer i's backward pass, after the head loop, on the compute stream: db = colsum(dZ_all)
     // and dW_res = X^T dZ_all, both summed over the world like dW, and dX += dZ_all W_res^T (projection; Wt, free by now, takes W_res^T) or
     // dZ_all (identity)
     void backward_skip(int i, DenseMatrix& X, DenseMatrix& dZ_all, DenseMatrix& Wt, DenseMatrix& dX) {
-        hnh::World* w = d_ops->world;
-        const hnh::Backend* be = w->be;
         const int S0 = HNH_STREAM_COMPUTE;
         const int H = layers[(size_t)i].num_heads, f = layers[(size_t)i].features_per_head;
         const int64_t rows = X.rows(), k = X.cols(), hf = (int64_t)H * f;
         if (bias_on_[(size_t)i]) {
-            DenseMatrix& db = bias_grads[(size_t)i];
-            if (db.rows() != hf || db.cols() != 1) db = DenseMatrix(hf, 1);
-            const int64_t need = be->hnh_colsum_f64_workspace(rows, hf);
-            DenseMatrix* work = need > 0 ? &scratch(25, need, 1) : nullptr;
-            w->check(be->hnh_colsum_f64(w->ctx, db.data(), dZ_all.data(), hf, rows, hf, work ? work->data() : nullptr, need, S0), "hnh_colsum_f64");
-            w->allreduce_f64(w->world_comm(), db.data(), (size_t)db.size(), S0);
+            DenseMatrix& db = shaped(bias_grads[(size_t)i], hf, 1);
+            const int64_t need = d_ops->world->be->hnh_colsum_f64_workspace(rows, hf);
+            double* work = need > 0 ? scratch(SC_COLSUM_WORK, need, 1).data() : nullptr;
+            HNH_GAT_CALL(hnh_colsum_f64, db.data(), dZ_all.data(), hf, rows, hf, work, need, S0);
+            sum_over_world(db);
         }
         if (res_mode_[(size_t)i] == HNH_GAT_RESIDUAL_PROJECTION) {
-            DenseMatrix& dWr = res_weight_grads[(size_t)i];
-            if (dWr.rows() != k || dWr.cols() != hf) dWr = DenseMatrix(k, hf);
-            const int64_t need = be->hnh_gemm_tn_f64_workspace(k, hf, rows);
-            DenseMatrix* work = need > 0 ? &scratch(7, need, 1) : nullptr;
-            w->check(be->hnh_gemm_tn_f64(w->ctx, k, hf, rows, X.data(), k, dZ_all.data(), hf, dWr.data(), hf, work ? work->data() : nullptr, need, S0),
-                     "hnh_gemm_tn_f64");
-            w->allreduce_f64(w->world_comm(), dWr.data(), (size_t)dWr.size(), S0);
+            world_grad_tn(res_weight_grads[(size_t)i], X, dZ_all);
             for (int h = 0; h < H; h++)
-                w->check(be->hnh_transpose_into_f64(w->ctx, Wt.data(), k, (int64_t)h * f, w_res_[(size_t)i].at((size_t)h).data(), k, f, S0), "hnh_transpose_into_f64");
-            DenseMatrix& dXr = scratch(26, rows, k);
-            w->check(be->hnh_gemm_f64(w->ctx, rows, k, hf, dZ_all.data(), Wt.data(), dXr.data(), S0), "hnh_gemm_f64");
-            w->check(be->hnh_axpy_f64(w->ctx, dX.data(), dXr.data(), 1.0, dX.size(), S0), "hnh_axpy_f64");
+                HNH_GAT_CALL(hnh_transpose_into_f64, Wt.data(), k, (int64_t)h * f, w_res_[(size_t)i].at((size_t)h).data(), k, f, S0);
+            DenseMatrix& dXr = scratch(SC_DX_RES, rows, k);
+            HNH_GAT_CALL(hnh_gemm_f64, rows, k, hf, dZ_all.data(), Wt.data(), dXr.data(), S0);
+            HNH_GAT_CALL(hnh_axpy_f64, dX.data(), dXr.data(), 1.0, dX.size(), S0);
         } else if (res_mode_[(size_t)i] == HNH_GAT_RESIDUAL_IDENTITY) {
-            w->check(be->hnh_axpy_f64(w->ctx, dX.data(), dZ_all.data(), 1.0, dX.size(), S0), "hnh_axpy_f64");  // (k == H f: the same shape)
+            HNH_GAT_CALL(hnh_axpy_f64, dX.data(), dZ_all.data(), 1.0, dX.size(), S0);  // (k == H f: the same shape)
         }
     }
-    // The three implementations of one head of the backward pass.  A = X W_h and dZ are backward_layer's; the head's column block of dA_all
+    // The four implementations of one head of the backward pass.  A = X W_h and dZ are backward_layer's; the head's column block of dA_all
     // is the result.
     // delta_i = <dZ_i, out_i> of head h (= <dZ_i, o_i>: dZ is 0 where out is), the softmax's row scalar, on the compute stream; for a
-    // non-ReLU layer delta_i = <dZ_i, o_i> is what backward_layer's hnh_act_grad_cols_f64 call of this head left in act_delta_ (a buffer of
-    // its own, which nothing else writes)
+    // non-ReLU layer or a layer with an addend it is what head_dz's launch for this head left in act_delta_ (a buffer of its own, which
+    // nothing else writes)
     DenseMatrix& head_delta(int i, int h, const DenseMatrix& dZ) {
-        hnh::World* w = d_ops->world;
-        if (act_[(size_t)i] != HNH_GAT_ACT_RELU || has_addend(i)) {  // (a layer with an addend: hnh_skip_grad_cols_f64's delta, ReLU included)
+        if (act_[(size_t)i] != HNH_GAT_ACT_RELU || has_addend(i)) {
             if (act_delta_.rows() != dZ.rows() || act_delta_.cols() != 1)
                 throw hnh::Error("Error, GAT backwardPass: the activation's delta does not have the head's rows!");
             return act_delta_;
         }
         const DenseMatrix& out = buffers[(size_t)i + 1];
         const int64_t f = dZ.cols();
-        DenseMatrix& delta = scratch(8, dZ.rows(), 1);
-        w->check(w->be->hnh_rowdot_cols_f64(w->ctx, delta.data(), dZ.data(), f, out.data(), out.cols(), (int64_t)h * f, dZ.rows(), f, HNH_STREAM_COMPUTE),
-                 "hnh_rowdot_cols_f64");
+        DenseMatrix& delta = scratch(SC_DELTA, dZ.rows(), 1);
+        HNH_GAT_CALL(hnh_rowdot_cols_f64, delta.data(), dZ.data(), f, out.data(), out.cols(), (int64_t)h * f, dZ.rows(), f, HNH_STREAM_COMPUTE);
         return delta;
     }
     // HNH_GAT_BACKWARD_UNFUSED: seven operator calls through value vectors on the nonzeros of both layouts (allocated on first use)
     void backward_head_unfused(int i, int h, DenseMatrix& A, DenseMatrix& dZ, DenseMatrix& dA_all) {
-        hnh::World* w = d_ops->world;
-        const hnh::Backend* be = w->be;
         const int S0 = HNH_STREAM_COMPUTE;
         const bool softmax = attention_ == HNH_GAT_ATTENTION_SOFTMAX;
         const int64_t rows = A.rows(), f = A.cols();
@@ -1300,9 +1259,9 @@ private:
             lse_ST_ = VectorXd(ones_ST_.size());
             delta_ST_ = VectorXd(ones_ST_.size());
         }
-        DenseMatrix& dArow = scratch(4, rows, f);
-        DenseMatrix& T1 = scratch(5, rows, f);
-        DenseMatrix& T2 = scratch(6, rows, f);
+        DenseMatrix& dArow = scratch(SC_DA_ROW, rows, f);
+        DenseMatrix& T1 = scratch(SC_T1, rows, f);
+        DenseMatrix& T2 = scratch(SC_T2, rows, f);
         if (softmax) {
             // lse_i and delta_i onto the nonzeros of both layouts: width-1 SDDMMs whose first operand is the S-row side in both, so S^T gets
             // the per-row scalars from the rank that owns them
@@ -1318,11 +1277,8 @@ private:
         }
         // the gate: e -> a (LeakyReLU(e), or its softmax weight), da -> de
         auto gate = [&](VectorXd& e, VectorXd& d, VectorXd& lse_nz, VectorXd& delta_nz) {
-            if (softmax)
-                w->check(be->hnh_softmax_gate_f64(w->ctx, e.data(), d.data(), lse_nz.data(), delta_nz.data(), leaky_relu_alpha, e.size(), S0),
-                         "hnh_softmax_gate_f64");
-            else
-                w->check(be->hnh_leaky_relu_grad_f64(w->ctx, e.data(), d.data(), leaky_relu_alpha, e.size(), S0), "hnh_leaky_relu_grad_f64");
+            if (softmax) HNH_GAT_CALL(hnh_softmax_gate_f64, e.data(), d.data(), lse_nz.data(), delta_nz.data(), leaky_relu_alpha, e.size(), S0);
+            else HNH_GAT_CALL(hnh_leaky_relu_grad_f64, e.data(), d.data(), leaky_relu_alpha, e.size(), S0);
         };
         // S layout: e_ij = <A_i, A_j>, da_ij = <dZ_i, A_j>, gate, row side dA_i = sum_j de_ij A_j
         d_ops->sddmmA(A, A, ones_S_, e_S_);
@@ -1335,12 +1291,10 @@ private:
         gate(e_ST_, d_ST_, lse_ST_, delta_ST_);
         d_ops->spmmB(dZ, T1, e_ST_);
         d_ops->spmmB(A, T2, d_ST_);
-        w->check(be->hnh_sum3_cols_f64(w->ctx, dA_all.data(), dA_all.cols(), (int64_t)h * f, dArow.data(), T1.data(), T2.data(), rows, f, S0),
-                 "hnh_sum3_cols_f64");
+        HNH_GAT_CALL(hnh_sum3_cols_f64, dA_all.data(), dA_all.cols(), (int64_t)h * f, dArow.data(), T1.data(), T2.data(), rows, f, S0);
     }
     // HNH_GAT_BACKWARD_FUSED: two passes straight into the head's column block of dA_all (include/hnh_attn_grad.h)
     void backward_head_fused(int i, int h, DenseMatrix& A, DenseMatrix& dZ, DenseMatrix& dA_all) {
-        hnh::World* w = d_ops->world;
         const bool softmax = attention_ == HNH_GAT_ATTENTION_SOFTMAX;
         const int f = (int)A.cols();
         const int64_t rows = A.rows();
@@ -1352,8 +1306,8 @@ private:
             lse = lse_.at((size_t)i).at((size_t)h).data();
         }
         const int pw = HNH_ATTN_GRAD_PACKED_WIDTH(f, softmax);
-        DenseMatrix& P = scratch(9, rows, pw);
-        w->check(w->be->hnh_attn_grad_pack_f64(w->ctx, P.data(), pw, A.data(), f, dZ.data(), f, lse, delta, rows, f, HNH_STREAM_COMPUTE), "hnh_attn_grad_pack_f64");
+        DenseMatrix& P = scratch(SC_PACKED, rows, pw);
+        HNH_GAT_CALL(hnh_attn_grad_pack_f64, P.data(), pw, A.data(), f, dZ.data(), f, lse, delta, rows, f, HNH_STREAM_COMPUTE);
         hnh_attn_grad g = {};
         g.X = A.data();
         g.ld_x = f;
@@ -1376,30 +1330,23 @@ private:
     }
     // score ADDITIVE (include/hnh_attn_additive.h): also the head's rows of attn_grads[i] (this rank's part)
     void backward_head_additive(int i, int h, DenseMatrix& A, DenseMatrix& dZ, DenseMatrix& dA_all) {
-        hnh::World* w = d_ops->world;
-        const hnh::Backend* be = w->be;
         const int S0 = HNH_STREAM_COMPUTE;
-        GATLayer& L = layers[(size_t)i];
-        const int H = L.num_heads, f = L.features_per_head;
-        const int64_t rows = A.rows(), hf = (int64_t)H * f;
+        const int f = layers[(size_t)i].features_per_head;
+        const int64_t rows = A.rows(), hf = (int64_t)layers[(size_t)i].num_heads * f;
         auto* ds = dynamic_cast<Sparse15D_Dense_Shift*>(d_ops);
         ensure_attn_vectors(i);
-        const double* a1 = L.a1.data() + (int64_t)h * f;
-        const double* a2 = L.a2.data() + (int64_t)h * f;
         const bool drop = attn_p_ > 0.0;  // M', Q' and the DROP instances (include/hnh_attn_dropout.h)
         const hnh_attn_drop dr = attn_drop_args(i, h);
         const int mw = drop ? HNH_ATTN_DROP_SCORED_WIDTH(f) : HNH_ATTN_ADD_SCORED_WIDTH(f), qw = HNH_ATTN_ADD_PACKED_WIDTH(f);
-        DenseMatrix& M = scratch(10, rows, mw);
-        DenseMatrix& Q = scratch(11, rows, qw);
-        DenseMatrix& D = scratch(12, rows, 2);      // [ds dt]
-        DenseMatrix& dAgg = scratch(13, rows, f);
+        DenseMatrix& M = scratch(SC_ADD_M, rows, mw);
+        DenseMatrix& Q = scratch(SC_ADD_Q, rows, qw);
+        DenseMatrix& D = scratch(SC_ADD_D, rows, 2);  // [ds dt]
+        DenseMatrix& dAgg = scratch(SC_ADD_DAGG, rows, f);
         double* lse = lse_.at((size_t)i).at((size_t)h).data();
         head_scores(i, h, A, M, S0);
         DenseMatrix& dl = head_delta(i, h, dZ);
-        if (drop)
-            w->check(be->hnh_attn_drop_pack_f64(w->ctx, Q.data(), qw, dZ.data(), f, M.data(), mw, lse, dl.data(), rows, f, dr.row_id0, S0),
-                     "hnh_attn_drop_pack_f64");
-        else w->check(be->hnh_attn_add_pack_f64(w->ctx, Q.data(), qw, dZ.data(), f, M.data(), mw, lse, dl.data(), rows, f, S0), "hnh_attn_add_pack_f64");
+        if (drop) HNH_GAT_CALL(hnh_attn_drop_pack_f64, Q.data(), qw, dZ.data(), f, M.data(), mw, lse, dl.data(), rows, f, dr.row_id0, S0);
+        else HNH_GAT_CALL(hnh_attn_add_pack_f64, Q.data(), qw, dZ.data(), f, M.data(), mw, lse, dl.data(), rows, f, S0);
         hnh_attn_add g = {};
         g.M = M.data();
         g.ld_m = mw;
@@ -1424,41 +1371,32 @@ private:
             }
         }
         require_own_rows("score additive", !ok);
-        w->check(be->hnh_attn_add_update_f64(w->ctx, dA_all.data(), hf, (int64_t)h * f, dAgg.data(), f, D.data(), 2, a1, a2, rows, f, S0),
-                 "hnh_attn_add_update_f64");
+        HNH_GAT_CALL(hnh_attn_add_update_f64, dA_all.data(), hf, (int64_t)h * f, dAgg.data(), f, D.data(), 2, attn_vector(i, h, 0), attn_vector(i, h, 1), rows, f, S0);
         // [da1_h da2_h] = A^T [ds dt] over the local rows (A = the first f columns of M)
-        DenseMatrix& dav = attn_grads[(size_t)i];
-        const int64_t need = be->hnh_gemm_tn_f64_workspace(f, 2, rows);
-        DenseMatrix* work = need > 0 ? &scratch(14, need, 1) : nullptr;
-        w->check(be->hnh_gemm_tn_f64(w->ctx, f, 2, rows, M.data(), mw, D.data(), 2, dav.data() + (int64_t)h * f * 2, 2, work ? work->data() : nullptr,
-                                     need, S0),
-                 "hnh_gemm_tn_f64");
+        gemm_tn(f, 2, rows, M.data(), mw, D.data(), 2, attn_grads[(size_t)i].data() + (int64_t)h * f * 2, 2, SC_ADD_TN_WORK);
     }
 
     // score GATV2 (include/hnh_attn_v2.h): the pack of the fused backward, the row pass, the column pass and the dense finish, which also
     // writes the head's rows of attn_grads[i] column 0 (this rank's part)
     void backward_head_gatv2(int i, int h, DenseMatrix& A, DenseMatrix& dZ, DenseMatrix& dA_all) {
-        hnh::World* w = d_ops->world;
-        const hnh::Backend* be = w->be;
         const int S0 = HNH_STREAM_COMPUTE;
-        GATLayer& L = layers[(size_t)i];
-        const int H = L.num_heads, f = L.features_per_head;
-        const int64_t rows = A.rows(), hf = (int64_t)H * f;
+        const int f = layers[(size_t)i].features_per_head;
+        const int64_t rows = A.rows(), hf = (int64_t)layers[(size_t)i].num_heads * f;
         auto* ds = dynamic_cast<Sparse15D_Dense_Shift*>(d_ops);
         ensure_attn_vectors(i);
         const int pw = HNH_ATTN_GRAD_PACKED_WIDTH(f, 1), fe = f + (f & 1);
-        DenseMatrix& P = scratch(9, rows, pw);
-        DenseMatrix& Rm = scratch(16, rows, fe);
-        DenseMatrix& Cm = scratch(17, rows, fe);
-        DenseMatrix& dAgg = scratch(18, rows, fe);
-        DenseMatrix& work = scratch(19, HNH_ATTN_V2_FINISH_WORK(f), 1);
+        DenseMatrix& P = scratch(SC_PACKED, rows, pw);
+        DenseMatrix& Rm = scratch(SC_V2_R, rows, fe);
+        DenseMatrix& Cm = scratch(SC_V2_C, rows, fe);
+        DenseMatrix& dAgg = scratch(SC_V2_DAGG, rows, fe);
+        DenseMatrix& work = scratch(SC_V2_WORK, HNH_ATTN_V2_FINISH_WORK(f), 1);
         double* lse = lse_.at((size_t)i).at((size_t)h).data();
         DenseMatrix& dl = head_delta(i, h, dZ);
-        w->check(be->hnh_attn_grad_pack_f64(w->ctx, P.data(), pw, A.data(), f, dZ.data(), f, lse, dl.data(), rows, f, S0), "hnh_attn_grad_pack_f64");
+        HNH_GAT_CALL(hnh_attn_grad_pack_f64, P.data(), pw, A.data(), f, dZ.data(), f, lse, dl.data(), rows, f, S0);
         hnh_attn_v2 g = {};
         g.X = A.data();
         g.ld_x = f;
-        g.a = L.a1.data() + (int64_t)h * f;
+        g.a = attn_vector(i, h, 0);
         g.dZ = dZ.data();
         g.ld_dz = f;
         g.lse = lse;
@@ -1477,10 +1415,8 @@ private:
             ok = ds->attnV2_pass(2, P, g, rows, true);
         }
         require_own_rows("score gatv2", !ok);
-        DenseMatrix& dav = attn_grads[(size_t)i];
-        w->check(be->hnh_attn_v2_finish_f64(w->ctx, dA_all.data(), hf, (int64_t)h * f, dAgg.data(), fe, Rm.data(), fe, Cm.data(), fe, A.data(), f, g.a,
-                                            dav.data() + (int64_t)h * f * 2, 2, rows, f, work.data(), HNH_ATTN_V2_FINISH_WORK(f), S0),
-                 "hnh_attn_v2_finish_f64");
+        HNH_GAT_CALL(hnh_attn_v2_finish_f64, dA_all.data(), hf, (int64_t)h * f, dAgg.data(), fe, Rm.data(), fe, Cm.data(), fe, A.data(), f, g.a,
+                     attn_grads[(size_t)i].data() + (int64_t)h * f * 2, 2, rows, f, work.data(), HNH_ATTN_V2_FINISH_WORK(f), S0);
     }
 
     DenseMatrix product[2];  // X * W_j of the head in flight and of the next one
@@ -1488,10 +1424,7 @@ private:
     void* ev_gemm[2] = {nullptr, nullptr};
     void* ev_head[2] = {nullptr, nullptr};
 
-    void shape_product(int i, DenseMatrix& A) {
-        const int64_t rows = buffers[i].rows(), cols = layers[i].wMats[0].cols();
-        if (A.rows() != rows || A.cols() != cols) A = DenseMatrix(rows, cols);
-    }
+    void shape_product(int i, DenseMatrix& A) { shaped(A, buffers[i].rows(), layers[i].wMats[0].cols()); }
 
     // the softmax passes' row state: the running max / sum of `rows` rows (shared by the heads) and the lse vector of (layer i, head j)
     DenseMatrix& softmax_row_state(int i, int j, int64_t rows) {
@@ -1508,103 +1441,100 @@ private:
 
     void shape_scored(int i, DenseMatrix& M) {
         const int f = layers[i].features_per_head;
-        const int64_t rows = buffers[i].rows(), cols = attn_p_ > 0.0 ? HNH_ATTN_DROP_SCORED_WIDTH(f) : HNH_ATTN_ADD_SCORED_WIDTH(f);
-        if (M.rows() != rows || M.cols() != cols) M = DenseMatrix(rows, cols);
+        shaped(M, buffers[i].rows(), attn_p_ > 0.0 ? HNH_ATTN_DROP_SCORED_WIDTH(f) : HNH_ATTN_ADD_SCORED_WIDTH(f));
     }
 
     // The scored operand of (layer i, head j) from the head's product A, on `stream`: M = [A (0) | <A, a1_j> <A, a2_j>]
     // (include/hnh_attn_additive.h) or, with attention dropout, M' = [A (0) | s t | id 0] at M's own width
     void head_scores(int i, int j, DenseMatrix& A, DenseMatrix& M, int stream) {
-        hnh::World* w = d_ops->world;
         const int f = layers[i].features_per_head;
-        const double* a1 = layers[i].a1.data() + (int64_t)j * f;
-        const double* a2 = layers[i].a2.data() + (int64_t)j * f;
+        const double *a1 = attn_vector(i, j, 0), *a2 = attn_vector(i, j, 1);
         if (attn_p_ > 0.0)
-            w->check(w->be->hnh_attn_drop_scores_f64(w->ctx, M.data(), M.cols(), A.data(), A.cols(), a1, a2, A.rows(), f, d_ops->aSubmatrices[0].topRow, stream),
-                     "hnh_attn_drop_scores_f64");
-        else w->check(w->be->hnh_attn_add_scores_f64(w->ctx, M.data(), M.cols(), A.data(), A.cols(), a1, a2, A.rows(), f, stream), "hnh_attn_add_scores_f64");
+            HNH_GAT_CALL(hnh_attn_drop_scores_f64, M.data(), M.cols(), A.data(), A.cols(), a1, a2, A.rows(), f, d_ops->aSubmatrices[0].topRow, stream);
+        else HNH_GAT_CALL(hnh_attn_add_scores_f64, M.data(), M.cols(), A.data(), A.cols(), a1, a2, A.rows(), f, stream);
     }
 
     // A = buffers[i] * W_j (gat.hpp:88) on `stream`
     void head_product(int i, int j, DenseMatrix& A, int stream) {
-        hnh::World* w = d_ops->world;
         DenseMatrix& X = layer_input(i);
         DenseMatrix& W = layers[i].wMats[j];
         if (X.cols() != W.rows()) hnh::fatal("Error, GAT weight shape does not match the layer input!");
         shape_product(i, A);
-        w->check(w->be->hnh_gemm_f64(w->ctx, X.rows(), W.cols(), X.cols(), X.data(), W.data(), A.data(), stream), "hnh_gemm_f64");
+        HNH_GAT_CALL(hnh_gemm_f64, X.rows(), W.cols(), X.cols(), X.data(), W.data(), A.data(), stream);
+    }
+
+    // What the three scores' softmax passes share for one head: the row state and the head's lse vector (softmax_row_state), the carrier H
+    // of the unnormalised rows between the launches of the pass (allocated here, per head, on the compute stream), the head's column block
+    // of the layer output, and the finishing launch's activation and addend flags.
+    struct SoftmaxHead {
+        DenseMatrix H;
+        double *lse, *row_max, *row_sum, *dst;
+        int64_t ld_dst;
+        int f;
+        double leaky_alpha;
+        unsigned flags;
+        template <class Args>
+        void fill(Args& g) const {  // the members hnh_attn_add and hnh_attn_v2 have in common
+            g.lse = lse;
+            g.Out = H.data();
+            g.ld_out = H.cols();
+            g.row_max = row_max;
+            g.row_sum = row_sum;
+            g.relu_dst = dst;
+            g.relu_ld = ld_dst;
+            g.f = f;
+            g.leaky_alpha = leaky_alpha;
+        }
+    };
+    SoftmaxHead softmax_head(int i, int j, int64_t rows, int64_t carrier_cols) {
+        DenseMatrix& out = buffers[i + 1];
+        const int f = layers[i].features_per_head;
+        double* lse = softmax_row_state(i, j, rows).data();
+        return {DenseMatrix(rows, carrier_cols), lse, row_max_.data(), row_sum_.data(), out.data() + (int64_t)j * f, out.cols(), f, leaky_relu_alpha,
+                activation_flag(i) | addend_flag(i)};
     }
 
     // the rest of the head (gat.hpp:89-101) from its product A, on the compute stream; A is consumed (the unfused route zeroes it)
     void head_attention(int i, int j, DenseMatrix& A) {
-        hnh::World* w = d_ops->world;
-        d_ops->setRValue(layers[i].features_per_head);
+        const int f = layers[i].features_per_head;
+        d_ops->setRValue(f);
         DenseMatrix& out = buffers[i + 1];
+        auto* ds = dynamic_cast<Sparse15D_Dense_Shift*>(d_ops);
 
         if (score_ == HNH_GAT_SCORE_ADDITIVE) {
             // A is the scored operand M = [A (0) | s t]: one pass that gathers one row of M per nonzero (include/hnh_attn_additive.h), with
             // the softmax pass's row state; the schedule runs at M's width for it
-            const int f = layers[i].features_per_head;
-            const int64_t rows = A.rows();
-            DenseMatrix& lse = softmax_row_state(i, j, rows);
-            DenseMatrix H(rows, f + (f & 1));
+            const SoftmaxHead s = softmax_head(i, j, A.rows(), f + (f & 1));
             hnh_attn_add g = {};
             g.M = A.data();
             g.ld_m = A.cols();
-            g.lse = lse.data();
-            g.Out = H.data();
-            g.ld_out = H.cols();
-            g.row_max = row_max_.data();
-            g.row_sum = row_sum_.data();
-            g.relu_dst = out.data() + (int64_t)j * f;
-            g.relu_ld = out.cols();
-            g.f = f;
-            g.leaky_alpha = leaky_relu_alpha;
-            auto* ds = dynamic_cast<Sparse15D_Dense_Shift*>(d_ops);
+            s.fill(g);
             bool ok = false;
             if (ds != nullptr) {
                 ScheduleWidth width(d_ops, (int)A.cols(), f);
                 const hnh_attn_drop dr = attn_drop_args(i, j);
-                ok = ds->attnAdditive_pass(0, A, g, rows, true, attn_p_ > 0.0 ? &dr : nullptr, activation_flag(i) | addend_flag(i));
+                ok = ds->attnAdditive_pass(0, A, g, A.rows(), true, attn_p_ > 0.0 ? &dr : nullptr, s.flags);
             }
             require_own_rows("score additive", !ok);
             return;
         }
-
         if (score_ == HNH_GAT_SCORE_GATV2) {
             // one pass on the plain product with the softmax pass's row state (include/hnh_attn_v2.h): the schedule runs at the head's f
-            const int f = layers[i].features_per_head;
-            const int64_t rows = A.rows();
-            DenseMatrix& lse = softmax_row_state(i, j, rows);
-            DenseMatrix H(rows, f + (f & 1));
+            const SoftmaxHead s = softmax_head(i, j, A.rows(), f + (f & 1));
             hnh_attn_v2 g = {};
             g.X = A.data();
             g.ld_x = A.cols();
-            g.a = layers[i].a1.data() + (int64_t)j * f;
-            g.lse = lse.data();
-            g.Out = H.data();
-            g.ld_out = H.cols();
-            g.row_max = row_max_.data();
-            g.row_sum = row_sum_.data();
-            g.relu_dst = out.data() + (int64_t)j * f;
-            g.relu_ld = out.cols();
-            g.f = f;
-            g.leaky_alpha = leaky_relu_alpha;
-            auto* ds = dynamic_cast<Sparse15D_Dense_Shift*>(d_ops);
-            require_own_rows("score gatv2", ds == nullptr || !ds->attnV2_pass(0, A, g, rows, true, activation_flag(i) | addend_flag(i)));
+            g.a = attn_vector(i, j, 0);
+            s.fill(g);
+            require_own_rows("score gatv2", ds == nullptr || !ds->attnV2_pass(0, A, g, A.rows(), true, s.flags));
             return;
         }
-
         if (attention_ == HNH_GAT_ATTENTION_SOFTMAX) {
             // one fused pass with the online softmax (include/hnh_attention.h): the head's activated output leaves the finishing launch
             // straight into its column block, lse into this head's vector; H carries the unnormalised rows between the launches
-            const int64_t rows = A.rows();
-            DenseMatrix& lse = softmax_row_state(i, j, rows);
-            DenseMatrix H(A.rows(), A.cols());
-            const hnh_attn_state st = {row_max_.data(), row_sum_.data(), lse.data(), leaky_relu_alpha,
-                                       out.data() + (int64_t)j * A.cols(), (int64_t)out.cols()};
-            auto* ds = dynamic_cast<Sparse15D_Dense_Shift*>(d_ops);
-            require_own_rows("softmax attention", ds == nullptr || !ds->fusedSoftmax_out(A, A, Amat, H, st, activation_flag(i) | addend_flag(i)));
+            SoftmaxHead s = softmax_head(i, j, A.rows(), A.cols());
+            const hnh_attn_state st = {s.row_max, s.row_sum, s.lse, leaky_relu_alpha, s.dst, s.ld_dst};
+            require_own_rows("softmax attention", ds == nullptr || !ds->fusedSoftmax_out(A, A, Amat, s.H, st, s.flags));
             return;
         }
 
@@ -1625,12 +1555,10 @@ private:
 
         d_ops->algorithm(A, B, Svalues, &sddmm_buffer, k_sddmmA, true);  // SDDMM phase
         A.setZero();
-        w->check(w->be->hnh_leaky_relu_f64(w->ctx, sddmm_buffer.data(), leaky_relu_alpha, sddmm_buffer.size(), HNH_STREAM_COMPUTE),
-                 "hnh_leaky_relu_f64");
+        HNH_GAT_CALL(hnh_leaky_relu_f64, sddmm_buffer.data(), leaky_relu_alpha, sddmm_buffer.size(), HNH_STREAM_COMPUTE);
         d_ops->algorithm(A, B, sddmm_buffer, nullptr, k_spmmA, false);   // SpMM phase, replication reused
-        w->check(w->be->hnh_relu_store_cols_f64(w->ctx, out.data(), out.cols(), (int64_t)j * A.cols(), A.data(), A.rows(), A.cols(),
-                                                HNH_STREAM_COMPUTE),
-                 "hnh_relu_store_cols_f64");
+        HNH_GAT_CALL(hnh_relu_store_cols_f64, out.data(), out.cols(), (int64_t)j * A.cols(), A.data(), A.rows(), A.cols(), HNH_STREAM_COMPUTE);
     }
 };
 #undef HNH_GAT_KERNEL
+#undef HNH_GAT_CALL

@@ -267,6 +267,24 @@ class AttnV2(C.Structure):
                 ("relu_ld", _i64), ("f", _i32), ("leaky_alpha", _dbl)]
 
 
+# include/hnh_attn_qkv.h: query/key/value attention scores of the GAT (score "transformer"), forward and backward; a tenth OPTIONAL group
+# bound only for the product library.  Every pass gathers a packed operand of include/hnh_attn_grad.h: attn_grad_packed_width(f, False) for
+# the forward and the row pass ([K | V]), attn_grad_packed_width(f, True) for the column pass ([Q | dZ | lse delta]).
+QKV_SIGNATURES = {
+    "hnh_attn_qkv_fwd_csr_p": (_i32, [_vp, _vp, _vp, C.c_uint, _vp, _i32]),
+    "hnh_attn_qkv_row_csr_p": (_i32, [_vp, _vp, _vp, C.c_uint, _vp, _i32]),
+    "hnh_attn_qkv_col_csr_p": (_i32, [_vp, _vp, _vp, C.c_uint, _vp, _i32]),
+}
+ATTN_QKV_MAX_F = 256  # HNH_ATTN_QKV_MAX_F
+
+
+class AttnQKV(C.Structure):
+    """struct hnh_attn_qkv"""
+    _fields_ = [("X", _vp), ("ld_x", _i64), ("X2", _vp), ("ld_x2", _i64), ("dZ", _vp), ("ld_dz", _i64), ("lse", _vp), ("delta", _vp), ("Y", _vp),
+                ("ld_y", _i64), ("Out", _vp), ("ld_out", _i64), ("Out2", _vp), ("ld_out2", _i64), ("row_max", _vp), ("row_sum", _vp),
+                ("relu_dst", _vp), ("relu_ld", _i64), ("values", _vp), ("f", _i32), ("scale", _dbl)]
+
+
 # include/hnh_attn_coef.h: export of the GAT's per-edge attention coefficients in every score mode; an eighth OPTIONAL group bound only for the
 # product library
 ATTN_COEF_SIGNATURES = {
@@ -358,7 +376,8 @@ def load(path: str | None = None) -> C.CDLL:
     if path is None or os.path.abspath(p) == os.path.abspath(LIB_PATH):
         for name, (res, args) in list(GRAD_SIGNATURES.items()) + list(ATTN_SIGNATURES.items()) + list(ATTN_GRAD_SIGNATURES.items()) + \
                 list(ATTN_ADD_SIGNATURES.items()) + list(ATTN_DROP_SIGNATURES.items()) + list(TRAIN_SIGNATURES.items()) + \
-                list(V2_SIGNATURES.items()) + list(ATTN_COEF_SIGNATURES.items()) + list(SKIP_SIGNATURES.items()):
+                list(V2_SIGNATURES.items()) + list(ATTN_COEF_SIGNATURES.items()) + list(SKIP_SIGNATURES.items()) + \
+                list(QKV_SIGNATURES.items()):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
     if path is None:

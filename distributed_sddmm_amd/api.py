@@ -135,6 +135,9 @@ SIGNATURES = {
     "hnh_gat_set_attention": (_i32, [_vp, _i32]),
     "hnh_gat_set_backward": (_i32, [_vp, _i32]),
     "hnh_gat_set_score": (_i32, [_vp, _i32]),
+    "hnh_gat_set_qk_weight": (_i32, [_vp, _i32, _i32, _i32, _vp]),
+    "hnh_gat_get_qk_weight": (_i32, [_vp, _i32, _i32, _i32, _vp]),
+    "hnh_gat_get_qk_weight_grad": (_i32, [_vp, _i32, _i32, _i32, _vp]),
     "hnh_gat_set_activation": (_i32, [_vp, _i32, _i32]),
     "hnh_gat_set_attn_vectors": (_i32, [_vp, _i32, _i32, _vp, _vp]),
     "hnh_gat_set_residual": (_i32, [_vp, _i32, _i32]),
@@ -721,7 +724,8 @@ class GAT:
 
     SCORE = {"dot": 0, "additive": 1}  # HNH_GAT_SCORE_DOT / _ADDITIVE
 
-    SCORE_V2 = {"gatv2": 2}  # HNH_GAT_SCORE_GATV2 (include/hnh_attn_v2.h); set_score accepts the union of the two tables
+    SCORE_V2 = {"gatv2": 2}  # HNH_GAT_SCORE_GATV2 (include/hnh_attn_v2.h); set_score accepts the union of the tables
+    SCORE_QKV = {"transformer": 3}  # HNH_GAT_SCORE_TRANSFORMER (include/hnh_attn_qkv.h)
 
     ACTIVATION = {"relu": 0, "elu": 1, "identity": 2}  # HNH_GAT_ACT_RELU / _ELU / _IDENTITY
 
@@ -808,9 +812,12 @@ class GAT:
         set_attention_vectors, include/hnh_attn_additive.h; attention "softmax" on 15d_fusion2 with c = 1 and heads of at most 256
         features only, forwardPass / backwardPass raise HnhError elsewhere), or "gatv2" (Brody, Alon and Yahav's dynamic attention,
         e_ij = sum_c a_c LeakyReLU(A_ic + A_jc) with ONE vector per head, the a1 of set_attention_vectors, include/hnh_attn_v2.h; supported
-        where "additive" is, without attention dropout).  With "additive" and "gatv2" there is one backward implementation: set_backward
-        is not consulted.  A change invalidates the stored forward pass."""
-        table = dict(self.SCORE, **self.SCORE_V2)
+        where "additive" is, without attention dropout), or "transformer" (scaled dot-product attention with separate projections,
+        s_ij = <Q_i, K_j> / sqrt(f) with Q = X W_q, K = X W_k and the aggregate over V = X W of set_weight, include/hnh_attn_qkv.h;
+        set_query_weight / set_key_weight, zero until set, which is a stationary point: initialise them; supported where "gatv2" is).  With
+        "additive", "gatv2" and "transformer" there is one backward implementation: set_backward is not consulted.  A change invalidates
+        the stored forward pass."""
+        table = dict(self.SCORE, **self.SCORE_V2, **self.SCORE_QKV)
         if mode not in table:
             raise ValueError("score must be one of %s, not %r" % (sorted(table), mode))
         _check(lib().hnh_gat_set_score(self.h, table[mode]), "gat_set_score")
@@ -919,6 +926,40 @@ class GAT:
         w = np.ascontiguousarray(w, dtype=np.float64)
         assert w.shape == self.weight_shape(layer, head)
         _check(lib().hnh_gat_set_weight(self.h, layer, head, w.ctypes.data), "gat_set_weight")
+
+    # ---- the transformer score's query and key weights (include/hnh_attn_qkv.h): which = 0 is W_q, 1 is W_k
+    def _set_qk(self, layer, head, which, w):
+        w = np.ascontiguousarray(w, dtype=np.float64)
+        if w.shape != self.weight_shape(layer, head):
+            raise ValueError("the weight of layer %d, head %d is %r, not %r" % (layer, head, self.weight_shape(layer, head), w.shape))
+        _check(lib().hnh_gat_set_qk_weight(self.h, int(layer), int(head), which, w.ctypes.data), "gat_set_qk_weight")
+
+    def _get_qk(self, fn, name, layer, head, which):
+        out = np.empty(self.weight_shape(layer, head))
+        _check(fn(self.h, int(layer), int(head), which, out.ctypes.data), name)
+        return out
+
+    def set_query_weight(self, layer: int, head: int, w: np.ndarray):
+        """W_q of (layer, head) for score "transformer": the shape of set_weight's, zero until set.  Invalidates the stored forward pass."""
+        self._set_qk(layer, head, 0, w)
+
+    def set_key_weight(self, layer: int, head: int, w: np.ndarray):
+        """W_k of (layer, head) for score "transformer": the shape of set_weight's, zero until set.  Invalidates the stored forward pass."""
+        self._set_qk(layer, head, 1, w)
+
+    def get_query_weight(self, layer: int, head: int) -> np.ndarray:
+        return self._get_qk(lib().hnh_gat_get_qk_weight, "gat_get_qk_weight", layer, head, 0)
+
+    def get_key_weight(self, layer: int, head: int) -> np.ndarray:
+        return self._get_qk(lib().hnh_gat_get_qk_weight, "gat_get_qk_weight", layer, head, 1)
+
+    def query_weight_grad(self, layer: int, head: int) -> np.ndarray:
+        """dL/dW_q of (layer, head) after backwardPass with score "transformer", summed over every rank."""
+        return self._get_qk(lib().hnh_gat_get_qk_weight_grad, "gat_get_qk_weight_grad", layer, head, 0)
+
+    def key_weight_grad(self, layer: int, head: int) -> np.ndarray:
+        """dL/dW_k of (layer, head) after backwardPass with score "transformer", summed over every rank."""
+        return self._get_qk(lib().hnh_gat_get_qk_weight_grad, "gat_get_qk_weight_grad", layer, head, 1)
 
     def buffer_shape(self, index: int):
         o = (C.c_int64 * 2)()

@@ -12,6 +12,7 @@
 #include "hnh_attn_grad.h"
 #include "hnh_attn_coef.h"
 #include "hnh_attn_v2.h"
+#include "hnh_attn_qkv.h"
 #include "hnh_gat_skip.h"
 #include "hnh_grad.h"
 #include "hnh_kernels.h"
@@ -67,6 +68,8 @@ struct Backend {
     HNH_FN(hnh_xent_rows_f64_workspace) HNH_FN(hnh_xent_rows_f64) HNH_FN(hnh_optim_step_f64)
     // OPTIONAL group (include/hnh_attn_v2.h), bound the same way: only the GAT's gatv2 score needs it
     HNH_FN(hnh_attn_v2_fwd_csr_p) HNH_FN(hnh_attn_v2_row_csr_p) HNH_FN(hnh_attn_v2_col_csr_p) HNH_FN(hnh_attn_v2_finish_f64)
+    // OPTIONAL group (include/hnh_attn_qkv.h), bound the same way: only the GAT's transformer score needs it
+    HNH_FN(hnh_attn_qkv_fwd_csr_p) HNH_FN(hnh_attn_qkv_row_csr_p) HNH_FN(hnh_attn_qkv_col_csr_p)
     // OPTIONAL group (include/hnh_attn_coef.h), bound the same way: only GAT::attention_coefficients needs it
     HNH_FN(hnh_attn_coef_csr_p) HNH_FN(hnh_attn_coef_scores_f64)
     // OPTIONAL group (include/hnh_gat_skip.h), bound the same way: only a GAT layer with a bias or a skip connection needs it

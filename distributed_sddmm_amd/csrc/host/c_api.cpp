@@ -777,6 +777,29 @@ int hnh_gat_set_backward(hnh_gat* g, int mode) {
 int hnh_gat_set_score(hnh_gat* g, int mode) {
     return guarded(g->w, [&] { g->g->set_score(mode); });
 }
+int hnh_gat_set_qk_weight(hnh_gat* g, int layer, int head, int which, const double* host) {
+    return guarded(g->w, [&] { g->g->set_qk_weight(layer, head, which, host); });
+}
+int hnh_gat_get_qk_weight(hnh_gat* g, int layer, int head, int which, double* host) {
+    return guarded(g->w, [&] { g->g->get_qk_weight(layer, head, which, host); });
+}
+int hnh_gat_get_qk_weight_grad(hnh_gat* g, int layer, int head, int which, double* host) {
+    return guarded(g->w, [&] {
+        GAT& gat = *g->g;
+        const GATLayer& l = gat.layers.at(layer);
+        if (head < 0 || head >= l.num_heads) throw hnh::Error("Error, GAT head index out of range!");
+        if (which != 0 && which != 1) throw hnh::Error("Error, GAT query/key weight selector " + std::to_string(which) + " is neither 0 (query) nor 1 (key)!");
+        if (!host) throw hnh::Error("Error, hnh_gat_get_qk_weight_grad: null pointer!");
+        const std::vector<DenseMatrix>& grads = gat.qk_weight_grads[which];
+        if (grads.size() != gat.layers.size() || grads[(size_t)layer].size() == 0)
+            throw hnh::Error("Error, no GAT query/key weight gradient yet: call hnh_gat_backward with score transformer first!");
+        const DenseMatrix& dW = grads[(size_t)layer];  // input_features x (heads * features_per_head)
+        std::vector<double> all((size_t)dW.size());
+        dW.copy_to_host(all.data());
+        const int64_t k = dW.rows(), ld = dW.cols(), f = l.features_per_head;
+        for (int64_t r = 0; r < k; r++) std::memcpy(host + r * f, all.data() + r * ld + (int64_t)head * f, sizeof(double) * (size_t)f);
+    });
+}
 int hnh_gat_set_activation(hnh_gat* g, int layer, int mode) {
     return guarded(g->w, [&] { g->g->set_activation(layer, mode); });
 }

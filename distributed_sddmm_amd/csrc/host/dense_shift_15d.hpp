@@ -356,6 +356,23 @@ public:
         return true;
     }
 
+    // One pass of the query/key/value attention (include/hnh_attn_qkv.h): pass 0 = the forward pass over S and 1 = the backward row pass
+    // over S (`moving` = the packed [K | V]), 2 = the backward column pass over S^T (`moving` = the packed [Q | dZ | lse delta]).  Everything
+    // as for attnV2_pass: the schedule's R must be the MOVING operand's packed width, the forward pass makes its first and its closing call
+    // also for an absent block, `finish_flags` go to the closing call alone.  Returns false, having done nothing, where a rank's own
+    // launches do not see all of a row's nonzeros.  Not a virtual of Distributed_Sparse, for fusedSoftmax_out's reason.
+    bool attnQKV_pass(int pass, DenseMatrix& moving, const hnh_attn_qkv& args, int64_t out_rows, bool overwrite, unsigned finish_flags = 0u) {
+        if (fusionApproach != 2 || c != 1) return false;
+        if (pass < 0 || pass > 2) hnh::fatal("Error, attnQKV_pass: unknown pass!");
+        if (moving.cols() != R) hnh::fatal("Error, attnQKV_pass: the schedule's R must be the moving operand's width!");
+        attn_walk(pass == 2 ? ST.get() : S.get(), moving, args, overwrite, pass == 0,
+                  "Error, the kernel implementation has no transformer attention pass (KernelImplementation::attn_qkv_local)!",
+                  [&](SpmatLocal& choice, int block_id, const hnh_attn_qkv& a, unsigned flags, bool finish) {
+                      return kernel->attn_qkv_local(choice, block_id, a, pass, flags | (finish ? finish_flags : 0u), out_rows, finish);
+                  });
+        return true;
+    }
+
     // The export of the attention coefficients (include/hnh_attn_coef.h) over S: `moving` is the gathered operand (the head's product A for
     // the scores dot and gatv2, the packed pair [t | id] for additive) and, as for attnV2_pass, the schedule's R must be its width.  The
     // blocks are walked in attn_walk's order (the own block, then the fetched blocks by window or adaptive group, or the ring); block i

@@ -63,6 +63,18 @@
 // attn_grads keeps its (H f) x 2 shape: column 0 = da, column 1 = zeros.  Supported where score ADDITIVE is, without attention dropout; one
 // backward implementation.
 //
+// HNH_GAT_SCORE_TRANSFORMER (an addition; include/hnh_attn_qkv.h) is scaled dot-product attention with separate projections (TransformerConv /
+// UniMP, the graph transformers): per (layer, head) W_q and W_k (input_features x f, zero until set) next to the head's weight, which is W_v:
+//     Q = X W_q,  K = X W_k,  V = X W_v,  s_ij = <Q_i, K_j> / sqrt(f)  (no LeakyReLU),  then the neighbourhood softmax as above over V.
+// Forward: the head's product stage gives V; the attention stage on the compute stream makes Q and K (two more hnh_gemm_f64), packs
+// [K | V] with hnh_attn_grad_pack_f64 (no scalars) and runs one pass that gathers a packed row per nonzero; the schedule runs at the packed
+// width.  Backward, with dZ and delta as above and g_ij = p_ij (<dZ_i, V_j> - delta_i) / sqrt(f):
+//     dQ_i = sum_j g_ij K_j  (row pass over S, gathering [K | V]),  dK_j = sum_i g_ij Q_i,  dV_j = sum_i p_ij dZ_i  (column pass over S^T,
+//     gathering the packed [Q | dZ | lse delta]),  dW_v = X^T dV (weight_grads),  dW_q = X^T dQ,  dW_k = X^T dK (qk_weight_grads, summed over
+//     the world like dW),  dX = dV W_v^T + dQ W_q^T + dK W_k^T in this order.
+// W_q = W_k = 0 is a stationary point of both (uniform attention, dQ = dK = 0): callers initialise them.  Supported where score GATV2 is,
+// without attention dropout; one backward implementation; attention_coefficients refuses this score.
+//
 // Dropout (an addition; set_dropout(attention_p, feature_p, seed), both rates 0 by default, which launches exactly the kernels above at
 // their widths).  The masks are never stored: every pass recomputes them from Philox-4x32-10 keyed by (seed, layer, head, global row,
 // global column) (include/hnh_attn_dropout.h), so they do not depend on the rank count, windows, panels or hub-row segments, and the
@@ -153,6 +165,7 @@ public:
         bias_on_.assign(layers.size(), 0);
         bias_.assign(layers.size(), DenseMatrix());
         w_res_.assign(layers.size(), std::vector<DenseMatrix>());
+        for (auto& w : w_qk_) w.assign(layers.size(), std::vector<DenseMatrix>());
         d_ops->setRValue(layers[0].input_features);
         buffers.push_back(d_ops->like_B_matrix(0.0));
         for (size_t i = 0; i < layers.size(); i++) {
@@ -185,13 +198,35 @@ public:
         attention_ = mode;
     }
 
-    // HNH_GAT_SCORE_DOT | HNH_GAT_SCORE_ADDITIVE | HNH_GAT_SCORE_GATV2 (include/hnh_dist.h); a change invalidates the stored forward pass
+    // HNH_GAT_SCORE_DOT | HNH_GAT_SCORE_ADDITIVE | HNH_GAT_SCORE_GATV2 | HNH_GAT_SCORE_TRANSFORMER (include/hnh_dist.h); a change invalidates
+    // the stored forward pass, and one away from TRANSFORMER drops qk_weight_grads
     int score() const { return score_; }
     void set_score(int mode) {
-        if (mode != HNH_GAT_SCORE_DOT && mode != HNH_GAT_SCORE_ADDITIVE && mode != HNH_GAT_SCORE_GATV2)
+        if (mode != HNH_GAT_SCORE_DOT && mode != HNH_GAT_SCORE_ADDITIVE && mode != HNH_GAT_SCORE_GATV2 && mode != HNH_GAT_SCORE_TRANSFORMER)
             throw hnh::Error("Error, unknown GAT score " + std::to_string(mode) + " (dot = 0, additive = 1, gatv2 = 2)!");
-        if (mode != score_) invalidate_forward();
+        if (mode != score_) {
+            invalidate_forward();
+            // (leaving score TRANSFORMER: no later backward pass refreshes dW_q and dW_k, so their getter refuses rather than hand out old ones)
+            if (score_ == HNH_GAT_SCORE_TRANSFORMER)
+                for (auto& gq : qk_weight_grads) gq.clear();
+        }
         score_ = mode;
+    }
+
+    // The transformer score's W_q (which = 0) and W_k (which = 1) of (layer i, head h): HOST matrices, row-major input_features x
+    // features_per_head like the head's weight, zero until set, allocated on first use.  Setting one invalidates the stored forward pass.
+    void set_qk_weight(int i, int h, int which, const double* host) {
+        check_qk(i, h, which);
+        if (host == nullptr) throw hnh::Error("Error, GAT set_qk_weight: null pointer!");
+        ensure_qk_weights(i);
+        w_qk_[which][(size_t)i][(size_t)h].copy_from_host(host);
+        invalidate_forward();
+    }
+    void get_qk_weight(int i, int h, int which, double* host) {
+        check_qk(i, h, which);
+        if (host == nullptr) throw hnh::Error("Error, GAT get_qk_weight: null pointer!");
+        ensure_qk_weights(i);
+        w_qk_[which][(size_t)i][(size_t)h].copy_to_host(host);
     }
 
     // HNH_GAT_ACT_RELU | HNH_GAT_ACT_ELU | HNH_GAT_ACT_IDENTITY of layer i's output (include/hnh_dist.h); a change invalidates the stored
@@ -394,6 +429,9 @@ public:
             input_grads.assign((size_t)L, DenseMatrix());
         }
         if (learns_vectors() && (int)attn_grads.size() != L) attn_grads.assign((size_t)L, DenseMatrix());
+        if (score_ == HNH_GAT_SCORE_TRANSFORMER)
+            for (auto& gq : qk_weight_grads)
+                if ((int)gq.size() != L) gq.assign((size_t)L, DenseMatrix());
         if ((int)bias_grads.size() != L) {
             bias_grads.assign((size_t)L, DenseMatrix());
             res_weight_grads.assign((size_t)L, DenseMatrix());
@@ -418,6 +456,8 @@ public:
     void attention_coefficients(int i, int h, VectorXd& out, bool dropped) {
         const std::string what = "attention_coefficients";
         check_layer_head(i, h);
+        if (score_ == HNH_GAT_SCORE_TRANSFORMER)
+            throw hnh::Error("Error, GAT " + what + " does not support score transformer: the export has no query/key/value pass (include/hnh_attn_coef.h)");
         auto* ds = dynamic_cast<Sparse15D_Dense_Shift*>(d_ops);
         if (ds != nullptr) {
             SpmatLocal* s = ds->fusionApproach == 1 ? ds->ST.get() : ds->S.get();
@@ -623,6 +663,9 @@ public:
     // bias_grads[i] ((num_heads * features_per_head) x 1, a layer with a bias) and res_weight_grads[i] (input_features x (num_heads *
     // features_per_head), residual projection) of layer i, the same on every rank; empty for a layer without
     std::vector<DenseMatrix> bias_grads, res_weight_grads;
+    // score TRANSFORMER: qk_weight_grads[0][i] = dW_q and [1][i] = dW_k of layer i (input_features x (num_heads * features_per_head), column
+    // block h belongs to head h, like weight_grads), the same on every rank
+    std::vector<DenseMatrix> qk_weight_grads[2];
 
 private:
     hnh::World* world_ = nullptr;
@@ -643,6 +686,8 @@ private:
     std::vector<DenseMatrix> bias_;
     std::vector<std::vector<DenseMatrix>> w_res_;
     DenseMatrix res_product_;
+    // score TRANSFORMER: W_q ([0]) and W_k ([1]) per (layer, head), input_features x f each (kept here, not in GATLayer, for act_'s reason)
+    std::vector<std::vector<DenseMatrix>> w_qk_[2];
     // training (include/hnh_train.h): this rank's labels on the device (-1: not in the loss) with the world's labelled count; the host's
     // copy of all labels and of the training mask (loss / evaluate build other sets from them); the optimizer and its moments
     struct LabelSet {
@@ -658,7 +703,7 @@ private:
     hnh_optim optim_ = {};
     int64_t optim_steps_ = 0;
     // Every learned tensor of the model is one row of optimizer_step's table (learned_parameters()); its moments live under its key.
-    enum ParamKind { PARAM_W, PARAM_A1, PARAM_A2, PARAM_BIAS, PARAM_W_RES };
+    enum ParamKind { PARAM_W, PARAM_A1, PARAM_A2, PARAM_BIAS, PARAM_W_RES, PARAM_W_Q, PARAM_W_K };
     typedef std::tuple<int, int, int> ParamKey;            // (kind, layer, head; head 0 for a tensor of the whole layer)
     typedef std::pair<DenseMatrix, DenseMatrix> Moments;   // (first moment: Adam only, SGD keeps none; second moment, or SGD's momentum buffer)
     struct Learned {
@@ -672,7 +717,8 @@ private:
     std::map<ParamKey, Moments> moments_;
 
     // The table's rows in order: per layer W_0 .. W_{H-1}, then a1, then a2 (score ADDITIVE; GATV2 learns a1 alone); after all layers, per
-    // layer the enabled bias, then W_res_0 .. W_res_{H-1} of a projection (include/hnh_gat_skip.h).  Weight decay applies to all alike.
+    // layer the enabled bias, then W_res_0 .. W_res_{H-1} of a projection (include/hnh_gat_skip.h), then with score TRANSFORMER W_q_0 ..
+    // W_q_{H-1} and W_k_0 .. W_k_{H-1} (behind every other entry of the layer).  Weight decay applies to all alike.
     std::vector<Learned> learned_parameters() {
         std::vector<Learned> all;
         const size_t n = layers.size();
@@ -705,10 +751,16 @@ private:
             if (bias_on_[i])
                 add(PARAM_BIAS, i, 0, bias_[i].data(), 1, hf, 1, held(bias_grads, i, hf, 1), 0,
                     "Error, GAT optimizer_step needs the bias gradient of a backwardPass since set_bias!");
-            if (res_mode_[i] != HNH_GAT_RESIDUAL_PROJECTION) continue;
-            for (int h = 0; h < L.num_heads; h++)
-                add(PARAM_W_RES, i, h, w_res_[i][(size_t)h].data(), f, k, f, held(res_weight_grads, i, k, hf), (int64_t)h * f,
-                    "Error, GAT optimizer_step needs the residual-weight gradient of a backwardPass since set_residual!");
+            if (res_mode_[i] == HNH_GAT_RESIDUAL_PROJECTION)
+                for (int h = 0; h < L.num_heads; h++)
+                    add(PARAM_W_RES, i, h, w_res_[i][(size_t)h].data(), f, k, f, held(res_weight_grads, i, k, hf), (int64_t)h * f,
+                        "Error, GAT optimizer_step needs the residual-weight gradient of a backwardPass since set_residual!");
+            if (score_ != HNH_GAT_SCORE_TRANSFORMER) continue;
+            ensure_qk_weights((int)i);
+            for (int which = 0; which < 2; which++)
+                for (int h = 0; h < L.num_heads; h++)
+                    add(which == 0 ? PARAM_W_Q : PARAM_W_K, i, h, w_qk_[which][i][(size_t)h].data(), f, k, f, held(qk_weight_grads[which], i, k, hf),
+                        (int64_t)h * f, "Error, GAT optimizer_step needs the query and key weight gradients of a backwardPass with score transformer!");
         }
         return all;
     }
@@ -731,6 +783,19 @@ private:
         check_layer(i);
         if (h < 0 || h >= layers[(size_t)i].num_heads)
             throw hnh::Error("Error, GAT head index " + std::to_string(h) + " out of range: layer " + std::to_string(i) + " has " + std::to_string(layers[(size_t)i].num_heads) + " heads!");
+    }
+    void check_qk(int i, int h, int which) const {
+        check_layer_head(i, h);
+        if (which != 0 && which != 1) throw hnh::Error("Error, GAT query/key weight selector " + std::to_string(which) + " is neither 0 (query) nor 1 (key)!");
+    }
+    void ensure_qk_weights(int i) {
+        const GATLayer& L = layers[(size_t)i];
+        for (auto& all : w_qk_) {
+            std::vector<DenseMatrix>& w = all[(size_t)i];
+            if (w.size() == (size_t)L.num_heads) continue;
+            w.clear();
+            for (int h = 0; h < L.num_heads; h++) w.push_back(DenseMatrix::Constant(L.wMats[(size_t)h].rows(), L.wMats[(size_t)h].cols(), 0.0));
+        }
     }
     int label_classes() const {
         const GATLayer& L = layers.back();
@@ -859,7 +924,7 @@ private:
     // workspace of every X^T D product of gemm_tn, and SC_PACKED, the packed P = [A | dZ | lse delta] of the fused and the gatv2 backward.
     enum ScratchRole { SC_DA_ALL, SC_WT, SC_A, SC_DZ, SC_DA_ROW, SC_T1, SC_T2, SC_TN_WORK, SC_DELTA, SC_PACKED, SC_ADD_M, SC_ADD_Q, SC_ADD_D, SC_ADD_DAGG,
                        SC_ADD_TN_WORK, SC_XENT_WORK, SC_V2_R, SC_V2_C, SC_V2_DAGG, SC_V2_WORK, SC_COEF_A, SC_COEF_S, SC_COEF_T, SC_RES_PRODUCT, SC_DZ_ALL,
-                       SC_COLSUM_WORK, SC_DX_RES };
+                       SC_COLSUM_WORK, SC_DX_RES, SC_QKV_Q, SC_QKV_K, SC_QKV_KV, SC_QKV_P, SC_QKV_DQ, SC_QKV_DK, SC_QKV_DX };
     std::map<std::tuple<int, int64_t, int64_t>, DenseMatrix> scratch_;
 
     // m at rows x cols: allocated anew (on the compute stream) unless it has that shape already
@@ -918,7 +983,9 @@ private:
         if (!(attn_p_ > 0.0) && !(feat_p_ > 0.0)) return;
         if (attn_p_ > 0.0 && score_ != HNH_GAT_SCORE_ADDITIVE)
             throw hnh::Error(std::string("Error, GAT attention dropout supports score additive only, not score ") +
-                             (score_ == HNH_GAT_SCORE_GATV2 ? "gatv2: the gatv2 passes have no mask " : "dot: the dot-product passes have no mask ") +
+                             (score_ == HNH_GAT_SCORE_GATV2         ? "gatv2: the gatv2 passes have no mask "
+                              : score_ == HNH_GAT_SCORE_TRANSFORMER ? "transformer: the query/key/value passes have no mask "
+                                                                    : "dot: the dot-product passes have no mask ") +
                              "(include/hnh_attn_dropout.h)");
         if (d_ops->M > 4294967296LL || d_ops->N > 4294967296LL || layers.size() > 65536)
             throw hnh::Error("Error, GAT dropout needs row ids below 2^32 and at most 65536 layers (the generator's counter words)!");
@@ -1068,6 +1135,7 @@ private:
     void check_backward_supported() {
         if (score_ == HNH_GAT_SCORE_ADDITIVE) check_additive_supported();
         else if (score_ == HNH_GAT_SCORE_GATV2) check_gatv2_supported();
+        else if (score_ == HNH_GAT_SCORE_TRANSFORMER) check_transformer_supported();
         else if (backward_ == HNH_GAT_BACKWARD_FUSED) check_fused_backward_supported();
         auto* ds = dynamic_cast<Sparse15D_Dense_Shift*>(d_ops);
         if (ds == nullptr || ds->r_split)
@@ -1110,6 +1178,19 @@ private:
                          HNH_GAT_KERNEL(hnh_attn_v2_finish_f64)});
         require_kernels("score gatv2", "include/hnh_attn_grad.h", {HNH_GAT_KERNEL(hnh_attn_grad_pack_f64)});
     }
+    // The transformer score: no attention dropout (its passes have no mask); its kernel group and the pack kernel of the fused backward,
+    // which builds all of its gathered operands.
+    void check_transformer_supported() {
+        require_softmax("score transformer", "", "include/hnh_attn_qkv.h");
+        require_own_rows("score transformer");
+        require_head_width("score transformer", HNH_ATTN_QKV_MAX_F, "include/hnh_attn_qkv.h");
+        if (attn_p_ > 0.0)
+            throw hnh::Error("Error, GAT score transformer does not support attention dropout (p = " + std::to_string(attn_p_) +
+                             "): its passes have no mask (include/hnh_attn_qkv.h)");
+        require_kernels("score transformer", "include/hnh_attn_qkv.h",
+                        {HNH_GAT_KERNEL(hnh_attn_qkv_fwd_csr_p), HNH_GAT_KERNEL(hnh_attn_qkv_row_csr_p), HNH_GAT_KERNEL(hnh_attn_qkv_col_csr_p)});
+        require_kernels("score transformer", "include/hnh_attn_grad.h", {HNH_GAT_KERNEL(hnh_attn_grad_pack_f64)});
+    }
     // Softmax attention with score dot: a row's softmax needs all of the row's nonzeros summed by this rank's own launches.
     void check_softmax_supported() {
         require_own_rows("softmax attention");
@@ -1137,6 +1218,7 @@ private:
         if (op != OP_FORWARD) return;  // (evaluate's forwardPass checks the score)
         if (score_ == HNH_GAT_SCORE_ADDITIVE) check_additive_supported();
         else if (score_ == HNH_GAT_SCORE_GATV2) check_gatv2_supported();
+        else if (score_ == HNH_GAT_SCORE_TRANSFORMER) check_transformer_supported();
         else if (attention_ == HNH_GAT_ATTENTION_SOFTMAX) check_softmax_supported();
     }
 
@@ -1177,6 +1259,9 @@ private:
         if (learns_vectors() && score_ == HNH_GAT_SCORE_GATV2) shaped(attn_grads[(size_t)i], hf, 2).setZero();  // (column 1 stays zero; column 0 is written head by head)
         else if (learns_vectors()) shaped(attn_grads[(size_t)i], hf, 2);
         DenseMatrix* dZ_all = has_addend(i) ? &scratch(SC_DZ_ALL, rows, hf) : nullptr;
+        const bool qkv = score_ == HNH_GAT_SCORE_TRANSFORMER;
+        DenseMatrix* dQ_all = qkv ? &scratch(SC_QKV_DQ, rows, hf) : nullptr;
+        DenseMatrix* dK_all = qkv ? &scratch(SC_QKV_DK, rows, hf) : nullptr;
         d_ops->setRValue(f);
         for (int h = 0; h < H; h++) {
             DenseMatrix& Wh = layers[(size_t)i].wMats[(size_t)h];
@@ -1186,6 +1271,7 @@ private:
             head_dz(i, h, G, dZ, dZ_all);
             if (score_ == HNH_GAT_SCORE_ADDITIVE) backward_head_additive(i, h, A, dZ, dA_all);
             else if (score_ == HNH_GAT_SCORE_GATV2) backward_head_gatv2(i, h, A, dZ, dA_all);
+            else if (qkv) backward_head_transformer(i, h, A, dZ, dA_all, *dQ_all, *dK_all);
             else if (backward_ == HNH_GAT_BACKWARD_FUSED) backward_head_fused(i, h, A, dZ, dA_all);
             else backward_head_unfused(i, h, A, dZ, dA_all);
             HNH_GAT_CALL(hnh_transpose_into_f64, Wt.data(), k, (int64_t)h * f, Wh.data(), k, f, S0);
@@ -1195,6 +1281,17 @@ private:
         // dX = dA_all [W_1^T; ..; W_H^T]
         DenseMatrix& dX = shaped(input_grads[(size_t)i], rows, k);
         HNH_GAT_CALL(hnh_gemm_f64, rows, k, hf, dA_all.data(), Wt.data(), dX.data(), S0);
+        if (qkv) {  // dW_q = X^T dQ_all, dW_k = X^T dK_all; dX += dQ_all W_q^T, then dK_all W_k^T (Wt, free by now, takes the transposes)
+            DenseMatrix* side[2] = {dQ_all, dK_all};
+            DenseMatrix& dXs = scratch(SC_QKV_DX, rows, k);
+            for (int which = 0; which < 2; which++) {
+                world_grad_tn(qk_weight_grads[which][(size_t)i], X, *side[which]);
+                for (int h = 0; h < H; h++)
+                    HNH_GAT_CALL(hnh_transpose_into_f64, Wt.data(), k, (int64_t)h * f, w_qk_[which][(size_t)i].at((size_t)h).data(), k, f, S0);
+                HNH_GAT_CALL(hnh_gemm_f64, rows, k, hf, side[which]->data(), Wt.data(), dXs.data(), S0);
+                HNH_GAT_CALL(hnh_axpy_f64, dX.data(), dXs.data(), 1.0, dX.size(), S0);
+            }
+        }
         if (dZ_all != nullptr) backward_skip(i, X, *dZ_all, Wt, dX);
         if (feat_p_ > 0.0) feature_mask(i, dX, dX);  // dL/dX = c_q mask o dL/dXd
     }
@@ -1419,6 +1516,69 @@ private:
                      attn_grads[(size_t)i].data() + (int64_t)h * f * 2, 2, rows, f, work.data(), HNH_ATTN_V2_FINISH_WORK(f), S0);
     }
 
+    // The transformer score's operands of (layer i, head h) on the compute stream: Q = X W_q and K = X W_k into their scratch
+    struct QK {
+        DenseMatrix &Q, &K;
+    };
+    QK head_qk(int i, int h) {
+        DenseMatrix& X = layer_input(i);
+        const int f = layers[(size_t)i].features_per_head;
+        ensure_qk_weights(i);
+        QK r = {scratch(SC_QKV_Q, X.rows(), f), scratch(SC_QKV_K, X.rows(), f)};
+        HNH_GAT_CALL(hnh_gemm_f64, X.rows(), f, X.cols(), X.data(), w_qk_[0][(size_t)i][(size_t)h].data(), r.Q.data(), HNH_STREAM_COMPUTE);
+        HNH_GAT_CALL(hnh_gemm_f64, X.rows(), f, X.cols(), X.data(), w_qk_[1][(size_t)i][(size_t)h].data(), r.K.data(), HNH_STREAM_COMPUTE);
+        return r;
+    }
+    // [K (0) | V (0)], the gathered operand of the forward and the row pass: the pack of the fused backward without scalars
+    DenseMatrix& pack_kv(const DenseMatrix& K, const DenseMatrix& V) {
+        const int f = (int)K.cols(), pw = HNH_ATTN_GRAD_PACKED_WIDTH(f, 0);
+        DenseMatrix& KV = scratch(SC_QKV_KV, K.rows(), pw);
+        HNH_GAT_CALL(hnh_attn_grad_pack_f64, KV.data(), pw, K.data(), f, V.data(), f, nullptr, nullptr, K.rows(), f, HNH_STREAM_COMPUTE);
+        return KV;
+    }
+    // score TRANSFORMER (include/hnh_attn_qkv.h): Q, K and both packs, the row pass (dQ into its column block of dQ_all) and the column
+    // pass (dK into dK_all, dV into dA_all: V = X W_h, so the layer's dW and dX take it as every other score's dA)
+    void backward_head_transformer(int i, int h, DenseMatrix& V, DenseMatrix& dZ, DenseMatrix& dA_all, DenseMatrix& dQ_all, DenseMatrix& dK_all) {
+        const int S0 = HNH_STREAM_COMPUTE;
+        const int f = layers[(size_t)i].features_per_head;
+        const int64_t rows = V.rows(), hf = dA_all.cols(), at = (int64_t)h * f;
+        auto* ds = dynamic_cast<Sparse15D_Dense_Shift*>(d_ops);
+        const QK qk = head_qk(i, h);
+        DenseMatrix& KV = pack_kv(qk.K, V);
+        const int pw = HNH_ATTN_GRAD_PACKED_WIDTH(f, 1);
+        DenseMatrix& P = scratch(SC_QKV_P, rows, pw);
+        double* lse = lse_.at((size_t)i).at((size_t)h).data();
+        DenseMatrix& dl = head_delta(i, h, dZ);
+        HNH_GAT_CALL(hnh_attn_grad_pack_f64, P.data(), pw, qk.Q.data(), f, dZ.data(), f, lse, dl.data(), rows, f, S0);
+        hnh_attn_qkv g = {};
+        g.X = qk.Q.data();
+        g.ld_x = f;
+        g.dZ = dZ.data();
+        g.ld_dz = f;
+        g.lse = lse;
+        g.delta = dl.data();
+        g.Out = dQ_all.data() + at;
+        g.ld_out = hf;
+        g.f = f;
+        g.scale = 1.0 / std::sqrt((double)f);
+        bool ok = false;
+        if (ds != nullptr) {  // the moving operand is [K | V], then P
+            ScheduleWidth width(d_ops, (int)KV.cols(), f);
+            ok = ds->attnQKV_pass(1, KV, g, rows, true);  // row side: dQ
+            if (ok) {
+                d_ops->setRValue(pw);
+                g.X = qk.K.data();
+                g.X2 = V.data();
+                g.ld_x2 = f;
+                g.Out = dK_all.data() + at;
+                g.Out2 = dA_all.data() + at;
+                g.ld_out2 = hf;
+                ok = ds->attnQKV_pass(2, P, g, rows, true);  // column side: dK, dV
+            }
+        }
+        require_own_rows("score transformer", !ok);
+    }
+
     DenseMatrix product[2];  // X * W_j of the head in flight and of the next one
     void* ev_input = nullptr;
     void* ev_gemm[2] = {nullptr, nullptr};
@@ -1527,6 +1687,32 @@ private:
             g.a = attn_vector(i, j, 0);
             s.fill(g);
             require_own_rows("score gatv2", ds == nullptr || !ds->attnV2_pass(0, A, g, A.rows(), true, s.flags));
+            return;
+        }
+        if (score_ == HNH_GAT_SCORE_TRANSFORMER) {
+            // A is V; Q and K are made here, on the compute stream, and one pass gathers the packed [K | V] with the softmax pass's row
+            // state (include/hnh_attn_qkv.h): the schedule runs at the packed width
+            const SoftmaxHead s = softmax_head(i, j, A.rows(), f + (f & 1));
+            const QK qk = head_qk(i, j);
+            DenseMatrix& KV = pack_kv(qk.K, A);
+            hnh_attn_qkv g = {};
+            g.X = qk.Q.data();
+            g.ld_x = f;
+            g.lse = s.lse;
+            g.Out = const_cast<double*>(s.H.data());
+            g.ld_out = s.H.cols();
+            g.row_max = s.row_max;
+            g.row_sum = s.row_sum;
+            g.relu_dst = s.dst;
+            g.relu_ld = s.ld_dst;
+            g.f = f;
+            g.scale = 1.0 / std::sqrt((double)f);
+            bool ok = false;
+            if (ds != nullptr) {
+                ScheduleWidth width(d_ops, (int)KV.cols(), f);
+                ok = ds->attnQKV_pass(0, KV, g, A.rows(), true, s.flags);
+            }
+            require_own_rows("score transformer", !ok);
             return;
         }
         if (attention_ == HNH_GAT_ATTENTION_SOFTMAX) {

@@ -258,6 +258,28 @@ bool StandardKernel::attn_v2_block(SpmatLocal& S, int block, const hnh_attn_v2& 
     return true;
 }
 
+bool KernelImplementation::attn_qkv_local(SpmatLocal& S, int block, const hnh_attn_qkv& args, int pass, unsigned flags, int64_t rows, bool finish) {
+    StandardKernel* k = dynamic_cast<StandardKernel*>(this);
+    return k != nullptr && k->attn_qkv_block(S, block, args, pass, flags, rows, finish);
+}
+
+// The three sparse passes of the query/key/value attention (include/hnh_attn_qkv.h), next to attn_v2_block: same block and window handling;
+// the gathered width is the packed operand's of the pass.
+bool StandardKernel::attn_qkv_block(SpmatLocal& S, int block, const hnh_attn_qkv& args, int pass, unsigned flags, int64_t rows, bool finish) {
+    hnh::World* w = S.world;
+    auto fn = pass == 0 ? w->be->hnh_attn_qkv_fwd_csr_p : (pass == 1 ? w->be->hnh_attn_qkv_row_csr_p : w->be->hnh_attn_qkv_col_csr_p);
+    const char* name = pass == 0 ? "hnh_attn_qkv_fwd_csr_p" : (pass == 1 ? "hnh_attn_qkv_row_csr_p" : "hnh_attn_qkv_col_csr_p");
+    if (fn == nullptr)
+        throw hnh::Error(std::string("Error, the transformer attention score needs the kernel ") + name + ", which the kernel library " + w->be->path +
+                         " does not export (include/hnh_attn_qkv.h)");
+    const unsigned f = flags | ((pass == 0 && finish) ? HNH_ATTN_FINISH : 0u);
+    const char* finish_text = (pass == 0 && finish) ? "Error, the transformer forward finish belongs to the block's last window!" : nullptr;
+    attn_block_call(S, block, rows, "the transformer attention pass", finish_text, HNH_ATTN_GRAD_PACKED_WIDTH(args.f, pass == 2 ? 1 : 0), profile,
+                    [&](const hnh_csr_block& d, const hnh_csr_window* win) { w->check(fn(w->ctx, &d, &args, f, win, HNH_STREAM_COMPUTE), name); },
+                    [&] { begin(w); }, [&](long launches) { end(w, launches); });
+    return true;
+}
+
 bool KernelImplementation::attn_coef_local(SpmatLocal& S, int block, const hnh_attn_coef& args, int64_t rows, const hnh_attn_drop* drop) {
     StandardKernel* k = dynamic_cast<StandardKernel*>(this);
     return k != nullptr && k->attn_coef_block(S, block, args, rows, drop);

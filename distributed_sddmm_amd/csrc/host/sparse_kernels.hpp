@@ -92,6 +92,12 @@ public:
     // when the implementation has no such pass.  NOT virtual, for softmax_local's reason.
     bool attn_v2_local(SpmatLocal& S, int block, const hnh_attn_v2& args, int pass, unsigned flags, int64_t rows, bool finish);
 
+    // One pass of the query/key/value attention (include/hnh_attn_qkv.h, the GAT's score "transformer") on one block, or the selected
+    // window(s) of it: pass 0 = forward over a block of S, 1 = backward row pass over a block of S (both gather the packed [K | V]), 2 =
+    // backward column pass over a block of S^T (gathers the packed [Q | dZ | lse delta]).  `args`, `rows` and `finish` as for attn_v2_local.
+    // Returns false, having done nothing, when the implementation has no such pass.  NOT virtual, for softmax_local's reason.
+    bool attn_qkv_local(SpmatLocal& S, int block, const hnh_attn_qkv& args, int pass, unsigned flags, int64_t rows, bool finish);
+
     // The export of the attention coefficients (include/hnh_attn_coef.h) on one block of S, or the selected window(s) of it: every nonzero
     // of the call gets its coefficient in the block's value slice, which the schedule has lent from the caller's vector (CSRLocal::sddmm_dst)
     // as for an SDDMM; without a lent slice the block's own value array takes them.  An absent or empty block has nothing to store.  `rows`
@@ -183,6 +189,8 @@ public:
                              const hnh_attn_drop* drop);
     // KernelImplementation::attn_v2_local's pass (non-virtual: see there)
     bool attn_v2_block(SpmatLocal& S, int block, const hnh_attn_v2& args, int pass, unsigned flags, int64_t rows, bool finish);
+    // KernelImplementation::attn_qkv_local's pass (non-virtual: see there)
+    bool attn_qkv_block(SpmatLocal& S, int block, const hnh_attn_qkv& args, int pass, unsigned flags, int64_t rows, bool finish);
     // KernelImplementation::attn_coef_local's pass (non-virtual: see there)
     bool attn_coef_block(SpmatLocal& S, int block, const hnh_attn_coef& args, int64_t rows, const hnh_attn_drop* drop);
     ~StandardKernel() override;

@@ -265,11 +265,22 @@ int hnh_gat_set_backward(hnh_gat* g, int mode);
  * inside the contraction and none outside (include/hnh_attn_v2.h; shared weights: the same A scores and is aggregated), forward and backward;
  * attention SOFTMAX on 15d_fusion2 with c = 1, heads of at most 256 features and no attention dropout only, refused elsewhere like ADDITIVE, and
  * like it with one backward implementation.  The head's vector is a1 of hnh_gat_set_attn_vectors (a2 is kept and not used); after
- * hnh_gat_backward hnh_gat_get_attn_grads returns its gradient as da1 and zeros as da2. */
+ * hnh_gat_backward hnh_gat_get_attn_grads returns its gradient as da1 and zeros as da2.
+ * TRANSFORMER (TransformerConv / UniMP: scaled dot-product attention with separate projections): s_ij = <Q_i, K_j> / sqrt(f) with Q = X W_q,
+ * K = X W_k and the aggregate over V = X W_v, W_v being the head's weight of hnh_gat_set_weight (include/hnh_attn_qkv.h), forward and backward;
+ * supported where GATV2 is and refused elsewhere like it, with one backward implementation; hnh_gat_attention_coefficients refuses it.  W_q and
+ * W_k (hnh_gat_weight_shape each, per layer and head; which = 0: query, 1: key) are zero until set, which is a stationary point (uniform
+ * attention, zero gradients of both): callers initialise them.  Setting one invalidates the forward pass; after hnh_gat_backward with this score
+ * their gradients (summed over all ranks) can be read, and hnh_gat_optimizer_step updates them with the other parameters; hnh_gat_set_score
+ * to another score drops them, and hnh_gat_get_qk_weight_grad refuses until the next hnh_gat_backward with this score. */
 #define HNH_GAT_SCORE_DOT 0
 #define HNH_GAT_SCORE_ADDITIVE 1
 #define HNH_GAT_SCORE_GATV2 2
+#define HNH_GAT_SCORE_TRANSFORMER 3
 int hnh_gat_set_score(hnh_gat* g, int mode);
+int hnh_gat_set_qk_weight(hnh_gat* g, int layer, int head, int which, const double* host);
+int hnh_gat_get_qk_weight(hnh_gat* g, int layer, int head, int which, double* host);
+int hnh_gat_get_qk_weight_grad(hnh_gat* g, int layer, int head, int which, double* host);
 /* Output activation of a layer (an addition).  RELU (the default of hnh_gat_create on every layer): out = max(o, 0), everything above.  ELU:
  * out = o for o > 0 and expm1(o) otherwise.  IDENTITY: out = o.  The backward pass works from the stored output alone (include/hnh_grad.h,
  * hnh_act_grad_cols_f64).  A non-ReLU layer is supported with attention SOFTMAX, score DOT or ADDITIVE, any dropout rates, on 15d_fusion2

@@ -285,6 +285,16 @@ class AttnQKV(C.Structure):
                 ("relu_dst", _vp), ("relu_ld", _i64), ("values", _vp), ("f", _i32), ("scale", _dbl)]
 
 
+# include/hnh_attn_edge.h: a per-edge bias on the logits of the query/key/value attention (GAT.set_edge_bias); an eleventh OPTIONAL group bound
+# only for the product library.  The three passes of QKV_SIGNATURES with `const double* bias` behind the arguments: bias[e] belongs to entry e
+# of the block's CSR order.
+EDGE_SIGNATURES = {
+    "hnh_attn_qkv_bias_fwd_csr_p": (_i32, [_vp, _vp, _vp, _vp, C.c_uint, _vp, _i32]),
+    "hnh_attn_qkv_bias_row_csr_p": (_i32, [_vp, _vp, _vp, _vp, C.c_uint, _vp, _i32]),
+    "hnh_attn_qkv_bias_col_csr_p": (_i32, [_vp, _vp, _vp, _vp, C.c_uint, _vp, _i32]),
+}
+
+
 # include/hnh_attn_coef.h: export of the GAT's per-edge attention coefficients in every score mode; an eighth OPTIONAL group bound only for the
 # product library
 ATTN_COEF_SIGNATURES = {
@@ -377,7 +387,7 @@ def load(path: str | None = None) -> C.CDLL:
         for name, (res, args) in list(GRAD_SIGNATURES.items()) + list(ATTN_SIGNATURES.items()) + list(ATTN_GRAD_SIGNATURES.items()) + \
                 list(ATTN_ADD_SIGNATURES.items()) + list(ATTN_DROP_SIGNATURES.items()) + list(TRAIN_SIGNATURES.items()) + \
                 list(V2_SIGNATURES.items()) + list(ATTN_COEF_SIGNATURES.items()) + list(SKIP_SIGNATURES.items()) + \
-                list(QKV_SIGNATURES.items()):
+                list(QKV_SIGNATURES.items()) + list(EDGE_SIGNATURES.items()):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
     if path is None:

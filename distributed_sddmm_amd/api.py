@@ -138,6 +138,7 @@ SIGNATURES = {
     "hnh_gat_set_qk_weight": (_i32, [_vp, _i32, _i32, _i32, _vp]),
     "hnh_gat_get_qk_weight": (_i32, [_vp, _i32, _i32, _i32, _vp]),
     "hnh_gat_get_qk_weight_grad": (_i32, [_vp, _i32, _i32, _i32, _vp]),
+    "hnh_gat_set_edge_bias": (_i32, [_vp, _i32, _vp, _vp]),
     "hnh_gat_set_activation": (_i32, [_vp, _i32, _i32]),
     "hnh_gat_set_attn_vectors": (_i32, [_vp, _i32, _i32, _vp, _vp]),
     "hnh_gat_set_residual": (_i32, [_vp, _i32, _i32]),
@@ -726,6 +727,7 @@ class GAT:
 
     SCORE_V2 = {"gatv2": 2}  # HNH_GAT_SCORE_GATV2 (include/hnh_attn_v2.h); set_score accepts the union of the tables
     SCORE_QKV = {"transformer": 3}  # HNH_GAT_SCORE_TRANSFORMER (include/hnh_attn_qkv.h)
+    EDGE_BIAS_ROW_MAX = 1e6  # edge_bias_from: the largest bias of a row of several edges lies within +-this (include/hnh_attn_edge.h, Magnitudes)
 
     ACTIVATION = {"relu": 0, "elu": 1, "identity": 2}  # HNH_GAT_ACT_RELU / _ELU / _IDENTITY
 
@@ -960,6 +962,55 @@ class GAT:
     def key_weight_grad(self, layer: int, head: int) -> np.ndarray:
         """dL/dW_k of (layer, head) after backwardPass with score "transformer", summed over every rank."""
         return self._get_qk(lib().hnh_gat_get_qk_weight_grad, "gat_get_qk_weight_grad", layer, head, 1)
+
+    # ---- the per-edge bias of the transformer score's logits (include/hnh_attn_edge.h)
+    def set_edge_bias(self, layer: int, bias_s: Vec | None, bias_st: Vec | None):
+        """A per-edge bias on layer `layer`'s logits with score "transformer": s_ij = <Q_i, K_j> / sqrt(f) + b_ij, one finite value per nonzero
+        of S on this rank, shared by the layer's heads and not learned (b = log w: the weighted neighbourhood softmax; a distance or relation
+        bias; -1e300 removes an edge from every row that keeps one of moderate bias; -inf is not supported; a row's largest bias should stay
+        within +-EDGE_BIAS_ROW_MAX, and a row of several edges that are all switched off is not supported: include/hnh_attn_edge.h, which
+        this call does not check and edge_bias_from does).  bias_s is in the like_S_values layout and
+        bias_st holds the same values in the like_ST_values layout (edge_bias_from builds both from one function); both are copied.  Both
+        None clears the bias: the layer launches what it launched before.  HnhError for one None, a wrong length or a layer out of range,
+        which leave the object as it was.  Invalidates the stored forward pass; any other score refuses a layer with an edge bias when a pass
+        is asked for."""
+        _check(lib().hnh_gat_set_edge_bias(self.h, int(layer), bias_s.h if bias_s is not None else None, bias_st.h if bias_st is not None else None),
+               "gat_set_edge_bias")
+
+    def edge_bias_from(self, fn, layer: int | None = None):
+        """set_edge_bias from one function: fn(rows, cols) -> float64 array gives the bias of the nonzeros at the global coordinates (rows, cols)
+        of S; it is evaluated on op.S_coordinates() and on op.ST_coordinates() (swapped back to the coordinates of S), uploaded in both layouts and
+        set on `layer`, or on every layer when None.  A function of the coordinates alone gives the two layouts the same values, which is what
+        the backward pass needs.  ValueError for a value that is not finite, and for a row of two or more entries whose largest bias lies
+        beyond +-EDGE_BIAS_ROW_MAX (such as a row whose every edge is switched off with -1e300): the backward pass recomputes the
+        coefficients from the row's lse, which is as large as that bias, and would lose them (include/hnh_attn_edge.h); a single edge may
+        carry any finite value.  Collective, like S_coordinates."""
+        made = []
+        try:
+            for transposed, like in ((False, self.op.like_S_values), (True, self.op.like_ST_values)):
+                if transposed:  # (an entry (j, i) of S^T is the nonzero (i, j) of S)
+                    cols, rows = self.op.ST_coordinates()
+                else:
+                    rows, cols = self.op.S_coordinates()
+                vals = np.ascontiguousarray(np.broadcast_to(np.asarray(fn(rows, cols), dtype=np.float64), rows.shape))
+                if not np.all(np.isfinite(vals)):
+                    raise ValueError("an edge bias must be finite (use a very negative value such as -1e300 to switch an edge off)")
+                if not transposed and len(rows):  # (15d_fusion2 with c = 1, the only schedule that runs a bias, keeps whole rows of S on a rank)
+                    ids, inv, deg = np.unique(rows, return_inverse=True, return_counts=True)
+                    top = np.full(len(ids), -np.inf)
+                    np.maximum.at(top, inv, vals)
+                    bad = np.flatnonzero((deg >= 2) & (np.abs(top) > self.EDGE_BIAS_ROW_MAX))
+                    if len(bad):
+                        raise ValueError("the largest edge bias of row %d is %g: a row of several edges needs one within +-%g (a row whose every "
+                                         "edge is switched off is not supported)" % (ids[bad[0]], top[bad[0]], self.EDGE_BIAS_ROW_MAX))
+                v = like(0.0)
+                made.append(v)
+                v.upload(vals)
+            for i in (range(len(self.layers)) if layer is None else [int(layer)]):
+                self.set_edge_bias(i, made[0], made[1])
+        finally:
+            for v in made:
+                v.free()
 
     def buffer_shape(self, index: int):
         o = (C.c_int64 * 2)()

@@ -13,6 +13,7 @@
 //                                  acc += g Q_i (dK) and acc2 += p dZ_i (dV): two accumulators per row, stored to two outputs
 // Every gathered row has two halves, so U is that of attn_grad_process's column pass: U nonzeros per batch in one of two register buffers
 // (the next batch's gathers fly while this one is computed), at most 16 gathered doubles per lane and batch (f = 256: U = 2).
+// The BIAS instances (include/hnh_attn_edge.h) are the same three passes with a per-nonzero addend on the score: see attn_qkv_process.
 #pragma once
 
 namespace {
@@ -35,9 +36,18 @@ struct AqArgs {  // hnh_attn_qkv as the kernels take it
     double scale;
 };
 
-template <int PASS, int LPR, int VEC, int W, bool EXACT>
-__device__ __forceinline__ void attn_qkv_process(int64_t row, int beg, int end, const int32_t* __restrict__ colidx, const AqArgs& a, unsigned flags,
-                                                 int lig, double* part_row) {
+// ... and with the per-edge bias of include/hnh_attn_edge.h: a type of its own, so that the plain instances' kernel arguments stay as they are
+struct AqBiasArgs : AqArgs {
+    const double* bias;  // bias[e] of nonzero e, in the block's numbering (where values[e] goes)
+};
+
+// BIAS (include/hnh_attn_edge.h): s_e = scale <Q_i, K_j> + bias[e].  The lane that owns nonzero e's score after the butterfly loads bias[e]
+// with the batch's column indices, ahead of the gathers, into the batch's buffer (one vector load of 8 bytes per lane: the lanes of a group
+// read U consecutive doubles of one line; it works at every LPR, where loads through the scalar cache would need a wave-uniform row), and
+// adds it before the online-softmax step (forward) or to the exponent scale qk - lse before the exp (row and column pass).
+template <int PASS, int LPR, int VEC, int W, bool EXACT, bool BIAS = false>
+__device__ __forceinline__ void attn_qkv_process(int64_t row, int beg, int end, const int32_t* __restrict__ colidx,
+                                                 const std::conditional_t<BIAS, AqBiasArgs, AqArgs>& a, unsigned flags, int lig, double* part_row) {
     constexpr int U = AgUnroll<1, LPR, VEC, W>::value;  // (two halves per gathered row in every pass)
     constexpr int NR = PASS == 0 ? U : 2 * U;           // reductions of a batch's butterfly
     constexpr int SUB = LPR / NR;                       // lanes that end up holding the same reduced value
@@ -96,6 +106,7 @@ __device__ __forceinline__ void attn_qkv_process(int64_t row, int beg, int end, 
     struct Batch {
         double y[U][2][VEC][W];
         double sc[PASS == 2 ? U : 1][2];  // column pass: lse and delta of the gathered rows
+        double bias[BIAS ? 1 : 0];        // BIAS: bias[e + umine], the nonzero whose score this lane holds after the butterfly
     };
 
     auto load_idx = [&](auto full, int e, int (&c)[U]) {
@@ -108,6 +119,13 @@ __device__ __forceinline__ void attn_qkv_process(int64_t row, int beg, int end, 
             const int cv = (FULL || my < end) ? colidx[my] : -1;
 #pragma unroll
             for (int u = 0; u < U; u++) c[u] = __shfl(cv, u, LPR);
+        }
+    };
+    auto load_bias = [&](auto full, int e, Batch& b) {
+        constexpr bool FULL = decltype(full)::value;
+        if constexpr (BIAS) {
+            const int mine = e + (lig / SUB) % U;
+            b.bias[0] = (FULL || mine < end) ? a.bias[mine] : 0.0;
         }
     };
     auto gather = [&](auto full, const int (&c)[U], Batch& b) {
@@ -162,7 +180,9 @@ __device__ __forceinline__ void attn_qkv_process(int64_t row, int beg, int end, 
         const bool have = FULL || e + umine < end;
         if constexpr (PASS == 0) {
             // the online-softmax step of kFusedSoftmax (process_row), nonzero by nonzero in row order
-            const double s = have ? scale * r : -__builtin_inf();
+            double sb = scale * r;
+            if constexpr (BIAS) sb += b.bias[0];
+            const double s = have ? sb : -__builtin_inf();
             if (a.values != nullptr && have && lig % SUB == 0) a.values[e + umine] = s;
             double run = m_run, mprev = m_run, mcur = m_run;
 #pragma unroll
@@ -206,7 +226,12 @@ __device__ __forceinline__ void attn_qkv_process(int64_t row, int beg, int end, 
                         dl = b.sc[u][1];
                     }
             }
-            double wp = exp(scale * qk - l);
+            // BIAS: exp((scale qk - lse) + bias).  The parent's expression first, so that a zero bias leaves the plain pass's bits; the bias
+            // behind it, so that an edge at -1e300 gives exp(-1e300) = 0 next to a moderate lse and exp(0) = 1 alone in its row, whose lse
+            // the forward pass stored as -1e300 (never lse - bias: in that row it would be 0 and p the unbiased exp(scale qk)).
+            double ex = scale * qk - l;
+            if constexpr (BIAS) ex += b.bias[0];
+            double wp = exp(ex);
             double wg = scale * (wp * (da - dl));
             if (!have) {
                 wp = 0.0;
@@ -245,11 +270,13 @@ __device__ __forceinline__ void attn_qkv_process(int64_t row, int beg, int end, 
     if (e + U <= end) {
         int c0[U], c1[U];
         load_idx(kFull, e, c0);
+        load_bias(kFull, e, ba);
         gather(kFull, c0, ba);
         for (;;) {
             const bool more = e + 2 * U <= end;
             if (more) {  // the next batch's gathers fly while this one is computed
                 load_idx(kFull, e + U, c1);
+                load_bias(kFull, e + U, bb);
                 gather(kFull, c1, bb);
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -260,6 +287,7 @@ __device__ __forceinline__ void attn_qkv_process(int64_t row, int beg, int end, 
             const bool more2 = e + 2 * U <= end;
             if (more2) {
                 load_idx(kFull, e + U, c0);
+                load_bias(kFull, e + U, ba);
                 gather(kFull, c0, ba);
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -272,6 +300,7 @@ __device__ __forceinline__ void attn_qkv_process(int64_t row, int beg, int end, 
     if (e < end) {  // fewer than U nonzeros left: one masked batch
         int c0[U];
         load_idx(kMasked, e, c0);
+        load_bias(kMasked, e, ba);
         gather(kMasked, c0, ba);
         compute(kMasked, e, ba);
     }
@@ -330,21 +359,24 @@ __device__ __forceinline__ void attn_qkv_process(int64_t row, int beg, int end, 
 }
 
 // the instance's name for the shells of hnh_attn_dispatch.hpp (attn_rows_kernel, attn_segments_kernel)
-template <int PASS, int LPR, int VEC, int W, bool EXACT>
+template <int PASS, int LPR, int VEC, int W, bool EXACT, bool BIAS = false>
 struct AqPass {
-    using Args = AqArgs;
+    using Args = std::conditional_t<BIAS, AqBiasArgs, AqArgs>;
     static constexpr int lpr = LPR;
-    static __device__ __forceinline__ void run(int64_t row, int beg, int end, const int32_t* __restrict__ colidx, const AqArgs& a, unsigned flags, int lig,
+    static __device__ __forceinline__ void run(int64_t row, int beg, int end, const int32_t* __restrict__ colidx, const Args& a, unsigned flags, int lig,
                                                double* part_row) {
-        attn_qkv_process<PASS, LPR, VEC, W, EXACT>(row, beg, end, colidx, a, flags, lig, part_row);
+        attn_qkv_process<PASS, LPR, VEC, W, EXACT, BIAS>(row, beg, end, colidx, a, flags, lig, part_row);
     }
 };
 
-template <int PASS>
+// BIAS: the entry points of include/hnh_attn_edge.h, with `bias` in the block's numbering
+template <int PASS, bool BIAS = false>
 int attn_qkv_dispatch(hnh_ctx* ctx, const hnh_csr_block* b, const hnh_attn_qkv* g, unsigned flags, const hnh_csr_window* win, int stream,
-                      const char* who) {
+                      const char* who, const double* bias = nullptr) {
     HNH_ENTER(ctx, stream);
     if (int rc = attn_dispatch_head(ctx, b, g != nullptr, g ? g->f : 0, HNH_ATTN_QKV_MAX_F, "HNH_ATTN_QKV_MAX_F", PASS == 0, flags, win, who)) return rc;
+    // (behind the head: the parents' refusals, the width limit among them, come first and with their codes)
+    if (BIAS && b->rowptr != nullptr && bias == nullptr) return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": null bias");
     const bool finish = PASS == 0 && (flags & HNH_ATTN_FINISH) != 0;
     if (b->rows == 0) return HNH_OK;
     const int f = g->f, fp = f + (f & 1);
@@ -352,7 +384,8 @@ int attn_qkv_dispatch(hnh_ctx* ctx, const hnh_csr_block* b, const hnh_attn_qkv* 
     if (PASS == 2 && (!g->Out2 || g->ld_out2 < f || g->Out2 == g->Out)) return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": bad second output");
     if (PASS == 0 && (!g->row_max || !g->row_sum || !g->lse || !g->relu_dst || g->relu_ld < f))
         return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": bad row state");
-    AqArgs a;
+    std::conditional_t<BIAS, AqBiasArgs, AqArgs> a;
+    if constexpr (BIAS) a.bias = bias;
     a.X = g->X; a.X2 = g->X2; a.dZ = g->dZ; a.delta = g->delta; a.Y = g->Y; a.lse = g->lse; a.Out = g->Out; a.Out2 = g->Out2;
     a.row_max = g->row_max; a.row_sum = g->row_sum; a.relu_dst = g->relu_dst; a.values = PASS == 0 ? g->values : nullptr;
     a.ld_x = g->ld_x; a.ld_x2 = g->ld_x2; a.ld_dz = g->ld_dz; a.ld_y = g->ld_y; a.ld_out = g->ld_out; a.ld_out2 = g->ld_out2; a.relu_ld = g->relu_ld;
@@ -393,7 +426,7 @@ int attn_qkv_dispatch(hnh_ctx* ctx, const hnh_csr_block* b, const hnh_attn_qkv* 
 
     auto launch = [&](const LongCtl& lc, const int32_t* beg_ptr, const int32_t* end_ptr, unsigned fl, bool run_long) {
         return attn_launch_shape(f, w2, [&](auto l, auto v, auto w, auto ex) {
-            return attn_launch<AqPass<PASS, decltype(l)::value, decltype(v)::value, decltype(w)::value, decltype(ex)::value>, PASS == 0, false>(
+            return attn_launch<AqPass<PASS, decltype(l)::value, decltype(v)::value, decltype(w)::value, decltype(ex)::value, BIAS>, PASS == 0, false>(
                 ctx, st, lc, b->rows, b->rowptr, beg_ptr, end_ptr, b->col_idx, a, fl, run_long, pitch, sums);
         });
     };
@@ -414,6 +447,22 @@ int hnh_attn_qkv_row_csr_p(hnh_ctx* ctx, const hnh_csr_block* b, const hnh_attn_
 
 int hnh_attn_qkv_col_csr_p(hnh_ctx* ctx, const hnh_csr_block* b, const hnh_attn_qkv* args, unsigned flags, const hnh_csr_window* window, int stream) {
     return attn_qkv_dispatch<2>(ctx, b, args, flags, window, stream, "hnh_attn_qkv_col_csr_p");
+}
+
+// ---- the per-edge bias (include/hnh_attn_edge.h)
+int hnh_attn_qkv_bias_fwd_csr_p(hnh_ctx* ctx, const hnh_csr_block* b, const hnh_attn_qkv* args, const double* bias, unsigned flags,
+                                const hnh_csr_window* window, int stream) {
+    return attn_qkv_dispatch<0, true>(ctx, b, args, flags, window, stream, "hnh_attn_qkv_bias_fwd_csr_p", bias);
+}
+
+int hnh_attn_qkv_bias_row_csr_p(hnh_ctx* ctx, const hnh_csr_block* b, const hnh_attn_qkv* args, const double* bias, unsigned flags,
+                                const hnh_csr_window* window, int stream) {
+    return attn_qkv_dispatch<1, true>(ctx, b, args, flags, window, stream, "hnh_attn_qkv_bias_row_csr_p", bias);
+}
+
+int hnh_attn_qkv_bias_col_csr_p(hnh_ctx* ctx, const hnh_csr_block* b, const hnh_attn_qkv* args, const double* bias, unsigned flags,
+                                const hnh_csr_window* window, int stream) {
+    return attn_qkv_dispatch<2, true>(ctx, b, args, flags, window, stream, "hnh_attn_qkv_bias_col_csr_p", bias);
 }
 
 }  // extern "C"

@@ -33,6 +33,7 @@
 #include "hnh_attn_dropout.h"
 #include "hnh_attn_v2.h"
 #include "hnh_attn_qkv.h"
+#include "hnh_attn_edge.h"
 #include "hnh_gat_skip.h"
 
 namespace {
@@ -2849,5 +2850,6 @@ int hnh_rowdot_cols_f64(hnh_ctx* ctx, double* out, const double* dZ, int64_t ld_
 // ---------------------------------------------------------------- export of the attention coefficients (include/hnh_attn_coef.h)
 #include "hnh_attn_coef_kernels.hpp"
 
-// ---------------------------------------------------------------- query/key/value attention scores (include/hnh_attn_qkv.h)
+// ---------------------------------------------------------------- query/key/value attention scores (include/hnh_attn_qkv.h), with a per-edge
+// bias (include/hnh_attn_edge.h)
 #include "hnh_attn_qkv_kernels.hpp"

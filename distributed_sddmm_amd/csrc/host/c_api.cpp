@@ -800,6 +800,9 @@ int hnh_gat_get_qk_weight_grad(hnh_gat* g, int layer, int head, int which, doubl
         for (int64_t r = 0; r < k; r++) std::memcpy(host + r * f, all.data() + r * ld + (int64_t)head * f, sizeof(double) * (size_t)f);
     });
 }
+int hnh_gat_set_edge_bias(hnh_gat* g, int layer, const hnh_vec* s, const hnh_vec* st) {
+    return guarded(g->w, [&] { g->g->set_edge_bias(layer, s ? &s->v : nullptr, st ? &st->v : nullptr); });
+}
 int hnh_gat_set_activation(hnh_gat* g, int layer, int mode) {
     return guarded(g->w, [&] { g->g->set_activation(layer, mode); });
 }

@@ -361,14 +361,39 @@ public:
     // as for attnV2_pass: the schedule's R must be the MOVING operand's packed width, the forward pass makes its first and its closing call
     // also for an absent block, `finish_flags` go to the closing call alone.  Returns false, having done nothing, where a rank's own
     // launches do not see all of a row's nonzeros.  Not a virtual of Distributed_Sparse, for fusedSoftmax_out's reason.
-    bool attnQKV_pass(int pass, DenseMatrix& moving, const hnh_attn_qkv& args, int64_t out_rows, bool overwrite, unsigned finish_flags = 0u) {
+    // `bias` (include/hnh_attn_edge.h): one value per nonzero in the like_S_values layout (passes 0 and 1) or the like_ST_values layout (pass
+    // 2); block i is lent its slice bias->data() + blockStarts[i] (CSRLocal::spmm_values: a value array that the pass reads in place), as
+    // attnCoef_pass lends its destination, and the slices are reclaimed before the pass returns.
+    bool attnQKV_pass(int pass, DenseMatrix& moving, const hnh_attn_qkv& args, int64_t out_rows, bool overwrite, unsigned finish_flags = 0u,
+                      const VectorXd* bias = nullptr) {
         if (fusionApproach != 2 || c != 1) return false;
         if (pass < 0 || pass > 2) hnh::fatal("Error, attnQKV_pass: unknown pass!");
         if (moving.cols() != R) hnh::fatal("Error, attnQKV_pass: the schedule's R must be the moving operand's width!");
-        attn_walk(pass == 2 ? ST.get() : S.get(), moving, args, overwrite, pass == 0,
-                  "Error, the kernel implementation has no transformer attention pass (KernelImplementation::attn_qkv_local)!",
+        SpmatLocal* s = pass == 2 ? ST.get() : S.get();
+        const char* missing = "Error, the kernel implementation has no transformer attention pass (KernelImplementation::attn_qkv_local)!";
+        if (bias == nullptr) {
+            attn_walk(s, moving, args, overwrite, pass == 0, missing,
+                      [&](SpmatLocal& choice, int block_id, const hnh_attn_qkv& a, unsigned flags, bool finish) {
+                          return kernel->attn_qkv_local(choice, block_id, a, pass, flags | (finish ? finish_flags : 0u), out_rows, finish);
+                      });
+            return true;
+        }
+        if (!s->blockStarts.empty() && (uint64_t)bias->size() < s->blockStarts.back()) hnh::fatal("Error, sparse value vector has the wrong length!");
+        for (size_t i = 0; i + 1 < s->blockStarts.size(); i++) {
+            CSRLocal* blk = s->csr_blocks[i];
+            if (blk == nullptr) continue;
+            if (blk->shifting) hnh::fatal("Error, attnQKV_pass: a travelling block cannot borrow a value slice!");
+            blk->spmm_values = bias->data() + s->blockStarts[i];
+        }
+        struct Reclaim {
+            SpmatLocal* s;
+            ~Reclaim() { s->reclaimValueArrays(); }
+        } reclaim{s};
+        attn_walk(s, moving, args, overwrite, pass == 0, missing,
                   [&](SpmatLocal& choice, int block_id, const hnh_attn_qkv& a, unsigned flags, bool finish) {
-                      return kernel->attn_qkv_local(choice, block_id, a, pass, flags | (finish ? finish_flags : 0u), out_rows, finish);
+                      const CSRLocal* blk = choice.csr_blocks[block_id];
+                      return kernel->attn_qkv_local(choice, block_id, a, pass, flags | (finish ? finish_flags : 0u), out_rows, finish,
+                                                    blk ? blk->spmm_values : nullptr);
                   });
         return true;
     }

@@ -164,6 +164,8 @@ public:
         res_mode_.assign(layers.size(), HNH_GAT_RESIDUAL_NONE);
         bias_on_.assign(layers.size(), 0);
         bias_.assign(layers.size(), DenseMatrix());
+        edge_bias_on_.assign(layers.size(), 0);
+        for (auto& e : edge_bias_) e.assign(layers.size(), VectorXd());
         w_res_.assign(layers.size(), std::vector<DenseMatrix>());
         for (auto& w : w_qk_) w.assign(layers.size(), std::vector<DenseMatrix>());
         d_ops->setRValue(layers[0].input_features);
@@ -300,6 +302,50 @@ public:
         if (host == nullptr) throw hnh::Error("Error, GAT get_bias: null pointer!");
         if (!bias_on_[(size_t)i]) throw hnh::Error("Error, GAT layer " + std::to_string(i) + " has no bias: set_bias first!");
         bias_[(size_t)i].copy_to_host(host);
+    }
+
+    // The per-edge bias of layer i's logits (include/hnh_attn_edge.h; score TRANSFORMER only, checked by forwardPass): one finite value per
+    // nonzero of S on this rank, shared by the layer's heads and not learned, given TWICE: `s` in the like_S_values layout (the forward and
+    // the backward row pass) and `st` in the like_ST_values layout (the backward column pass over S^T).  The caller keeps the two in
+    // agreement: entry e of S and the entry of S^T that is the same nonzero carry the same value (S_coordinates / ST_coordinates name
+    // them; two copies of a repeated pair may differ).  Both are copied, device to device; both null clears the bias, and the layer then
+    // launches what it launched before.  A very negative value (-1e300) removes an edge from every row that keeps an edge of moderate
+    // bias; a row's largest bias should stay within +-1e6, and a row of several edges that are ALL switched off is not supported (the
+    // backward pass cannot recover 1 / degree from an lse of -1e300: include/hnh_attn_edge.h); -inf is not supported.  A change
+    // invalidates the stored forward pass; a refused call leaves the object as it was.
+    bool has_edge_bias(int i) const {
+        check_layer(i);
+        return edge_bias_on_[(size_t)i] != 0;
+    }
+    void set_edge_bias(int i, const VectorXd* s, const VectorXd* st) {
+        check_layer(i);
+        if (s == nullptr && st == nullptr) {
+            if (edge_bias_on_[(size_t)i]) invalidate_forward();
+            edge_bias_on_[(size_t)i] = 0;
+            for (auto& e : edge_bias_) e[(size_t)i] = VectorXd();
+            return;
+        }
+        if (s == nullptr || st == nullptr)
+            throw hnh::Error(std::string("Error, GAT set_edge_bias needs the bias in both orders: the ") + (s == nullptr ? "like_S_values" : "like_ST_values") +
+                             " vector is null (both null clears the bias)!");
+        if (edge_len_[0] < 0) {  // (the schedule says its layouts' lengths through the vectors it makes: asked once per object)
+            edge_len_[0] = d_ops->like_S_values(0.0).size();
+            edge_len_[1] = d_ops->like_ST_values(0.0).size();
+        }
+        const int64_t want[2] = {edge_len_[0], edge_len_[1]};
+        const VectorXd* in[2] = {s, st};
+        for (int k = 0; k < 2; k++)
+            if (in[k]->size() != want[k])
+                throw hnh::Error(std::string("Error, GAT set_edge_bias needs a vector of ") + (k == 0 ? "like_S_values" : "like_ST_values") + " length: " +
+                                 std::to_string(want[k]) + " entries, not " + std::to_string(in[k]->size()) + "!");
+        hnh::World* w = d_ops->world;
+        for (int k = 0; k < 2; k++) {
+            VectorXd& mine = edge_bias_[k][(size_t)i];
+            if (mine.size() != want[k]) mine = VectorXd(want[k]);
+            if (want[k] > 0) w->copy(mine.data(), in[k]->data(), sizeof(double) * (size_t)want[k], HNH_COPY_D2D, HNH_STREAM_COMPUTE);
+        }
+        edge_bias_on_[(size_t)i] = 1;
+        invalidate_forward();
     }
 
     // Dropout (include/hnh_attn_dropout.h): rates in [0, 1) on the attention coefficients (score ADDITIVE only; checked by forwardPass)
@@ -686,6 +732,11 @@ private:
     std::vector<DenseMatrix> bias_;
     std::vector<std::vector<DenseMatrix>> w_res_;
     DenseMatrix res_product_;
+    // the per-edge bias (include/hnh_attn_edge.h) of every layer: [0] in S's order, [1] in S^T's, with its enabled bit (kept here, not in
+    // GATLayer, for act_'s reason)
+    std::vector<char> edge_bias_on_;
+    std::vector<VectorXd> edge_bias_[2];
+    int64_t edge_len_[2] = {-1, -1};  // the lengths of like_S_values / like_ST_values, once set_edge_bias has asked for them
     // score TRANSFORMER: W_q ([0]) and W_k ([1]) per (layer, head), input_features x f each (kept here, not in GATLayer, for act_'s reason)
     std::vector<std::vector<DenseMatrix>> w_qk_[2];
     // training (include/hnh_train.h): this rank's labels on the device (-1: not in the loss) with the world's labelled count; the host's
@@ -1191,6 +1242,23 @@ private:
                         {HNH_GAT_KERNEL(hnh_attn_qkv_fwd_csr_p), HNH_GAT_KERNEL(hnh_attn_qkv_row_csr_p), HNH_GAT_KERNEL(hnh_attn_qkv_col_csr_p)});
         require_kernels("score transformer", "include/hnh_attn_grad.h", {HNH_GAT_KERNEL(hnh_attn_grad_pack_f64)});
     }
+    // A layer with an edge bias: the transformer score's passes alone take one (its own conditions are check_transformer_supported's, which
+    // follows); the kernel group.
+    void check_edge_bias_supported() {
+        for (size_t i = 0; i < layers.size(); i++) {
+            if (!edge_bias_on_[i]) continue;
+            const std::string what = "edge bias of layer " + std::to_string(i);
+            if (score_ != HNH_GAT_SCORE_TRANSFORMER)
+                throw hnh::Error("Error, GAT " + what + " supports score transformer only, not score " + score_name(score_) +
+                                 ": its passes have no bias operand (include/hnh_attn_edge.h)");
+            require_kernels("edge bias", "include/hnh_attn_edge.h",
+                            {HNH_GAT_KERNEL(hnh_attn_qkv_bias_fwd_csr_p), HNH_GAT_KERNEL(hnh_attn_qkv_bias_row_csr_p),
+                             HNH_GAT_KERNEL(hnh_attn_qkv_bias_col_csr_p)});
+        }
+    }
+    static const char* score_name(int score) {
+        return score == HNH_GAT_SCORE_DOT ? "dot" : score == HNH_GAT_SCORE_ADDITIVE ? "additive" : score == HNH_GAT_SCORE_GATV2 ? "gatv2" : "transformer";
+    }
     // Softmax attention with score dot: a row's softmax needs all of the row's nonzeros summed by this rank's own launches.
     void check_softmax_supported() {
         require_own_rows("softmax attention");
@@ -1205,7 +1273,7 @@ private:
         require_kernels("softmax attention", "include/hnh_attention.h", {HNH_GAT_KERNEL(hnh_attn_softmax_csr_p)});
     }
     // What an entry point refuses, in one order: the training state (labels, optimizer, training kernels, output width, whole rows), then
-    // dropout, the activations, bias and skip connections, then the backward pass's conditions or, for a forward pass, the score's own.  The
+    // dropout, the activations, bias and skip connections, the edge bias, then the backward pass's conditions or, for a forward pass, the score's own.  The
     // stored forward pass and the shapes of the arguments are the entry point's own checks, afterwards.
     enum Op { OP_FORWARD, OP_BACKWARD, OP_TRAIN_STEP, OP_EVALUATE, OP_LOSS };
     void check_supported(Op op) {
@@ -1214,6 +1282,7 @@ private:
         check_dropout_supported();
         check_activation_supported();
         check_skip_supported();
+        check_edge_bias_supported();
         if (op == OP_BACKWARD || op == OP_TRAIN_STEP) check_backward_supported();
         if (op != OP_FORWARD) return;  // (evaluate's forwardPass checks the score)
         if (score_ == HNH_GAT_SCORE_ADDITIVE) check_additive_supported();
@@ -1564,7 +1633,8 @@ private:
         bool ok = false;
         if (ds != nullptr) {  // the moving operand is [K | V], then P
             ScheduleWidth width(d_ops, (int)KV.cols(), f);
-            ok = ds->attnQKV_pass(1, KV, g, rows, true);  // row side: dQ
+            const bool biased = edge_bias_on_[(size_t)i] != 0;
+            ok = ds->attnQKV_pass(1, KV, g, rows, true, 0u, biased ? &edge_bias_[0][(size_t)i] : nullptr);  // row side: dQ
             if (ok) {
                 d_ops->setRValue(pw);
                 g.X = qk.K.data();
@@ -1573,7 +1643,7 @@ private:
                 g.Out = dK_all.data() + at;
                 g.Out2 = dA_all.data() + at;
                 g.ld_out2 = hf;
-                ok = ds->attnQKV_pass(2, P, g, rows, true);  // column side: dK, dV
+                ok = ds->attnQKV_pass(2, P, g, rows, true, 0u, biased ? &edge_bias_[1][(size_t)i] : nullptr);  // column side: dK, dV
             }
         }
         require_own_rows("score transformer", !ok);
@@ -1710,7 +1780,7 @@ private:
             bool ok = false;
             if (ds != nullptr) {
                 ScheduleWidth width(d_ops, (int)KV.cols(), f);
-                ok = ds->attnQKV_pass(0, KV, g, A.rows(), true, s.flags);
+                ok = ds->attnQKV_pass(0, KV, g, A.rows(), true, s.flags, edge_bias_on_[(size_t)i] ? &edge_bias_[0][(size_t)i] : nullptr);
             }
             require_own_rows("score transformer", !ok);
             return;

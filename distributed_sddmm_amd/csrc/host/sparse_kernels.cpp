@@ -1,3 +1,4 @@
+#include <functional>
 #include "sparse_kernels.hpp"
 
 // SDDMM of operands up to this many columns goes through the nonzero-balanced COO kernel (StandardKernel::sddmm_local)
@@ -264,20 +265,43 @@ bool KernelImplementation::attn_qkv_local(SpmatLocal& S, int block, const hnh_at
 }
 
 // The three sparse passes of the query/key/value attention (include/hnh_attn_qkv.h), next to attn_v2_block: same block and window handling;
-// the gathered width is the packed operand's of the pass.
-bool StandardKernel::attn_qkv_block(SpmatLocal& S, int block, const hnh_attn_qkv& args, int pass, unsigned flags, int64_t rows, bool finish) {
+// the gathered width is the packed operand's of the pass.  `biased`: the entry points of include/hnh_attn_edge.h, which take the block's
+// slice of the bias vector behind the arguments; both overloads of attn_qkv_block are this one function.
+static bool attn_qkv_call(StandardKernel& k, SpmatLocal& S, int block, const hnh_attn_qkv& args, int pass, unsigned flags, int64_t rows, bool finish,
+                          bool biased, const double* bias, const std::function<void()>& begin, const std::function<void(long)>& end) {
     hnh::World* w = S.world;
-    auto fn = pass == 0 ? w->be->hnh_attn_qkv_fwd_csr_p : (pass == 1 ? w->be->hnh_attn_qkv_row_csr_p : w->be->hnh_attn_qkv_col_csr_p);
-    const char* name = pass == 0 ? "hnh_attn_qkv_fwd_csr_p" : (pass == 1 ? "hnh_attn_qkv_row_csr_p" : "hnh_attn_qkv_col_csr_p");
-    if (fn == nullptr)
-        throw hnh::Error(std::string("Error, the transformer attention score needs the kernel ") + name + ", which the kernel library " + w->be->path +
-                         " does not export (include/hnh_attn_qkv.h)");
+    const hnh::Backend* be = w->be;
+    auto plain = pass == 0 ? be->hnh_attn_qkv_fwd_csr_p : (pass == 1 ? be->hnh_attn_qkv_row_csr_p : be->hnh_attn_qkv_col_csr_p);
+    auto with_bias = pass == 0 ? be->hnh_attn_qkv_bias_fwd_csr_p : (pass == 1 ? be->hnh_attn_qkv_bias_row_csr_p : be->hnh_attn_qkv_bias_col_csr_p);
+    const std::string name = std::string(biased ? "hnh_attn_qkv_bias_" : "hnh_attn_qkv_") + (pass == 0 ? "fwd" : (pass == 1 ? "row" : "col")) + "_csr_p";
+    if (biased ? with_bias == nullptr : plain == nullptr)
+        throw hnh::Error(std::string("Error, the transformer attention score") + (biased ? " with an edge bias" : "") + " needs the kernel " + name +
+                         ", which the kernel library " + be->path + " does not export (" + (biased ? "include/hnh_attn_edge.h" : "include/hnh_attn_qkv.h") + ")");
     const unsigned f = flags | ((pass == 0 && finish) ? HNH_ATTN_FINISH : 0u);
     const char* finish_text = (pass == 0 && finish) ? "Error, the transformer forward finish belongs to the block's last window!" : nullptr;
-    attn_block_call(S, block, rows, "the transformer attention pass", finish_text, HNH_ATTN_GRAD_PACKED_WIDTH(args.f, pass == 2 ? 1 : 0), profile,
-                    [&](const hnh_csr_block& d, const hnh_csr_window* win) { w->check(fn(w->ctx, &d, &args, f, win, HNH_STREAM_COMPUTE), name); },
-                    [&] { begin(w); }, [&](long launches) { end(w, launches); });
+    attn_block_call(S, block, rows, biased ? "the transformer attention pass with an edge bias" : "the transformer attention pass", finish_text,
+                    HNH_ATTN_GRAD_PACKED_WIDTH(args.f, pass == 2 ? 1 : 0), k.profile,
+                    [&](const hnh_csr_block& d, const hnh_csr_window* win) {
+                        w->check(biased ? with_bias(w->ctx, &d, &args, bias, f, win, HNH_STREAM_COMPUTE) : plain(w->ctx, &d, &args, f, win, HNH_STREAM_COMPUTE),
+                                 name.c_str());
+                    },
+                    begin, end);
     return true;
+}
+
+bool StandardKernel::attn_qkv_block(SpmatLocal& S, int block, const hnh_attn_qkv& args, int pass, unsigned flags, int64_t rows, bool finish) {
+    return attn_qkv_call(*this, S, block, args, pass, flags, rows, finish, false, nullptr, [&] { begin(S.world); }, [&](long n) { end(S.world, n); });
+}
+
+bool KernelImplementation::attn_qkv_local(SpmatLocal& S, int block, const hnh_attn_qkv& args, int pass, unsigned flags, int64_t rows, bool finish,
+                                          const double* bias) {
+    StandardKernel* k = dynamic_cast<StandardKernel*>(this);
+    return k != nullptr && k->attn_qkv_block(S, block, args, pass, flags, rows, finish, bias);
+}
+
+bool StandardKernel::attn_qkv_block(SpmatLocal& S, int block, const hnh_attn_qkv& args, int pass, unsigned flags, int64_t rows, bool finish,
+                                    const double* bias) {
+    return attn_qkv_call(*this, S, block, args, pass, flags, rows, finish, true, bias, [&] { begin(S.world); }, [&](long n) { end(S.world, n); });
 }
 
 bool KernelImplementation::attn_coef_local(SpmatLocal& S, int block, const hnh_attn_coef& args, int64_t rows, const hnh_attn_drop* drop) {

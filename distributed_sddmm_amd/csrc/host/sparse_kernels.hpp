@@ -97,6 +97,10 @@ public:
     // backward column pass over a block of S^T (gathers the packed [Q | dZ | lse delta]).  `args`, `rows` and `finish` as for attn_v2_local.
     // Returns false, having done nothing, when the implementation has no such pass.  NOT virtual, for softmax_local's reason.
     bool attn_qkv_local(SpmatLocal& S, int block, const hnh_attn_qkv& args, int pass, unsigned flags, int64_t rows, bool finish);
+    // ... with a per-edge bias (include/hnh_attn_edge.h): `bias` is the block's slice, entry e of the block's CSR order at bias[e] (of S
+    // for passes 0 and 1, of S^T for pass 2); it may be null only for an absent or empty block.  An overload, not a default argument: the
+    // earlier symbol stays.
+    bool attn_qkv_local(SpmatLocal& S, int block, const hnh_attn_qkv& args, int pass, unsigned flags, int64_t rows, bool finish, const double* bias);
 
     // The export of the attention coefficients (include/hnh_attn_coef.h) on one block of S, or the selected window(s) of it: every nonzero
     // of the call gets its coefficient in the block's value slice, which the schedule has lent from the caller's vector (CSRLocal::sddmm_dst)
@@ -191,6 +195,7 @@ public:
     bool attn_v2_block(SpmatLocal& S, int block, const hnh_attn_v2& args, int pass, unsigned flags, int64_t rows, bool finish);
     // KernelImplementation::attn_qkv_local's pass (non-virtual: see there)
     bool attn_qkv_block(SpmatLocal& S, int block, const hnh_attn_qkv& args, int pass, unsigned flags, int64_t rows, bool finish);
+    bool attn_qkv_block(SpmatLocal& S, int block, const hnh_attn_qkv& args, int pass, unsigned flags, int64_t rows, bool finish, const double* bias);
     // KernelImplementation::attn_coef_local's pass (non-virtual: see there)
     bool attn_coef_block(SpmatLocal& S, int block, const hnh_attn_coef& args, int64_t rows, const hnh_attn_drop* drop);
     ~StandardKernel() override;

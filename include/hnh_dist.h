@@ -281,6 +281,16 @@ int hnh_gat_set_score(hnh_gat* g, int mode);
 int hnh_gat_set_qk_weight(hnh_gat* g, int layer, int head, int which, const double* host);
 int hnh_gat_get_qk_weight(hnh_gat* g, int layer, int head, int which, double* host);
 int hnh_gat_get_qk_weight_grad(hnh_gat* g, int layer, int head, int which, double* host);
+/* A per-edge bias on the logits of a layer with score TRANSFORMER (an addition; include/hnh_attn_edge.h): s_ij = <Q_i, K_j> / sqrt(f) + b_ij with
+ * one finite value per nonzero of S on this rank, shared by the layer's heads and not learned (b = log w is the weighted neighbourhood softmax;
+ * a distance or relation bias; -1e300 removes an edge from every row that keeps one of moderate bias; a row's largest bias should stay within
+ * +-1e6, and a row of several edges ALL switched off is not supported: include/hnh_attn_edge.h; -inf is not supported).  It is given in both orders:
+ * `s` in hnh_vec_like's S layout and `st` in its S^T layout (a probe SDDMM of row or column numbers names every entry's coordinates); the
+ * caller keeps them in agreement, and two copies of a repeated pair may carry different values.  Both are copied; both NULL clears the bias and the
+ * layer launches what it launched before.  One NULL, a wrong length or a layer out of range is refused and leaves the object as it was.  Invalidates
+ * the forward pass.  Any other score refuses a layer with an edge bias by name when a pass is asked for; the bias is no parameter:
+ * hnh_gat_optimizer_step does not touch it. */
+int hnh_gat_set_edge_bias(hnh_gat* g, int layer, const hnh_vec* s, const hnh_vec* st);
 /* Output activation of a layer (an addition).  RELU (the default of hnh_gat_create on every layer): out = max(o, 0), everything above.  ELU:
  * out = o for o > 0 and expm1(o) otherwise.  IDENTITY: out = o.  The backward pass works from the stored output alone (include/hnh_grad.h,
  * hnh_act_grad_cols_f64).  A non-ReLU layer is supported with attention SOFTMAX, score DOT or ADDITIVE, any dropout rates, on 15d_fusion2

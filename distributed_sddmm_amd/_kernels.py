@@ -295,6 +295,14 @@ EDGE_SIGNATURES = {
 }
 
 
+# include/hnh_attn_edge_grad.h: the gradient of that bias (GAT.set_edge_bias_learned); a twelfth OPTIONAL group bound only for the product
+# library.  The two backward passes of EDGE_SIGNATURES with `double* dbias, int accumulate` behind the bias: dbias[e] is addressed like bias[e].
+EDGE_GRAD_SIGNATURES = {
+    "hnh_attn_qkv_bias_grad_row_csr_p": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, C.c_uint, _vp, _i32]),
+    "hnh_attn_qkv_bias_grad_col_csr_p": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, C.c_uint, _vp, _i32]),
+}
+
+
 # include/hnh_attn_coef.h: export of the GAT's per-edge attention coefficients in every score mode; an eighth OPTIONAL group bound only for the
 # product library
 ATTN_COEF_SIGNATURES = {
@@ -387,7 +395,7 @@ def load(path: str | None = None) -> C.CDLL:
         for name, (res, args) in list(GRAD_SIGNATURES.items()) + list(ATTN_SIGNATURES.items()) + list(ATTN_GRAD_SIGNATURES.items()) + \
                 list(ATTN_ADD_SIGNATURES.items()) + list(ATTN_DROP_SIGNATURES.items()) + list(TRAIN_SIGNATURES.items()) + \
                 list(V2_SIGNATURES.items()) + list(ATTN_COEF_SIGNATURES.items()) + list(SKIP_SIGNATURES.items()) + \
-                list(QKV_SIGNATURES.items()) + list(EDGE_SIGNATURES.items()):
+                list(QKV_SIGNATURES.items()) + list(EDGE_SIGNATURES.items()) + list(EDGE_GRAD_SIGNATURES.items()):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
     if path is None:

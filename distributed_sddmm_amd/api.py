@@ -139,6 +139,9 @@ SIGNATURES = {
     "hnh_gat_get_qk_weight": (_i32, [_vp, _i32, _i32, _i32, _vp]),
     "hnh_gat_get_qk_weight_grad": (_i32, [_vp, _i32, _i32, _i32, _vp]),
     "hnh_gat_set_edge_bias": (_i32, [_vp, _i32, _vp, _vp]),
+    "hnh_gat_set_edge_bias_learned": (_i32, [_vp, _i32, _i32]),
+    "hnh_gat_get_edge_bias": (_i32, [_vp, _i32, _i32, _vp]),
+    "hnh_gat_get_edge_bias_grad": (_i32, [_vp, _i32, _i32, _vp]),
     "hnh_gat_set_activation": (_i32, [_vp, _i32, _i32]),
     "hnh_gat_set_attn_vectors": (_i32, [_vp, _i32, _i32, _vp, _vp]),
     "hnh_gat_set_residual": (_i32, [_vp, _i32, _i32]),
@@ -1012,6 +1015,37 @@ class GAT:
             for v in made:
                 v.free()
 
+    # ---- a learned edge bias (include/hnh_attn_edge_grad.h)
+    def set_edge_bias_learned(self, layer: int, on: bool = True):
+        """Makes layer `layer`'s edge bias a parameter (or, with on=False, a constant again): backwardPass then also computes
+        dL/db_e = sum_h p_e (<dZ_i, V_j> - delta_i) per nonzero, and optimizer_step / train_step update the bias from it with the other
+        parameters' hyper-parameters but never with weight decay, so an entry at -1e300 keeps gradient 0 and stays -1e300 to the bit.  Both
+        copies of the bias (like_S_values and like_ST_values order) are parameters, each updated from its own pass's gradient; every rank
+        holds its own nonzeros' bias and nothing is all-reduced.  HnhError unless the layer has an edge bias; clearing the bias clears the
+        switch."""
+        _check(lib().hnh_gat_set_edge_bias_learned(self.h, int(layer), 1 if on else 0), "gat_set_edge_bias_learned")
+
+    def _edge_vectors(self, fn, name, layer):
+        out = []
+        for which, like in ((0, self.op.like_S_values), (1, self.op.like_ST_values)):
+            v = like(0.0)
+            try:
+                _check(fn(self.h, int(layer), which, v.h), name)
+                out.append(v.download())
+            finally:
+                v.free()
+        return tuple(out)
+
+    def get_edge_bias(self, layer: int):
+        """(bias_s, bias_st): layer `layer`'s edge bias as it stands on this rank, in the like_S_values and the like_ST_values layout."""
+        return self._edge_vectors(lib().hnh_gat_get_edge_bias, "gat_get_edge_bias", layer)
+
+    def edge_bias_grad(self, layer: int):
+        """(dbias_s, dbias_st): dL/db of layer `layer`'s learned edge bias after backwardPass, per nonzero of S on this rank in the
+        like_S_values layout (from the backward row pass) and in the like_ST_values layout (from the column pass); not summed over ranks,
+        which hold different nonzeros.  HnhError before a backward pass with the bias learned."""
+        return self._edge_vectors(lib().hnh_gat_get_edge_bias_grad, "gat_get_edge_bias_grad", layer)
+
     def buffer_shape(self, index: int):
         o = (C.c_int64 * 2)()
         _check(lib().hnh_gat_buffer_shape(self.h, index, o), "gat_buffer_shape")
@@ -1109,7 +1143,7 @@ class GAT:
     def set_optimizer(self, kind: str, lr: float, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8, momentum: float = 0.0,
                       weight_decay: float = 0.0):
         """"adam" or "sgd" (with momentum) over every W, a1, a2 with score "additive", and every enabled bias and residual weight; weight
-        decay is added to the gradient of each of them.
+        decay is added to the gradient of each of them.  A learned edge bias (set_edge_bias_learned) is updated too, but never decayed.
         (Re)allocates zeroed moments and resets the step count."""
         if kind not in self.OPTIMIZER:
             raise ValueError("optimizer must be one of %s, not %r" % (sorted(self.OPTIMIZER), kind))

@@ -13,7 +13,8 @@
 //                                  acc += g Q_i (dK) and acc2 += p dZ_i (dV): two accumulators per row, stored to two outputs
 // Every gathered row has two halves, so U is that of attn_grad_process's column pass: U nonzeros per batch in one of two register buffers
 // (the next batch's gathers fly while this one is computed), at most 16 gathered doubles per lane and batch (f = 256: U = 2).
-// The BIAS instances (include/hnh_attn_edge.h) are the same three passes with a per-nonzero addend on the score: see attn_qkv_process.
+// The BIAS instances (include/hnh_attn_edge.h) are the same three passes with a per-nonzero addend on the score, and the DBIAS instances
+// (include/hnh_attn_edge_grad.h) the two biased backward passes with one more store per nonzero, dL/db_e: see attn_qkv_process.
 #pragma once
 
 namespace {
@@ -41,13 +42,26 @@ struct AqBiasArgs : AqArgs {
     const double* bias;  // bias[e] of nonzero e, in the block's numbering (where values[e] goes)
 };
 
+// ... and with the bias's gradient of include/hnh_attn_edge_grad.h, again a type of its own: the BIAS instances' arguments stay as they are
+struct AqBiasGradArgs : AqBiasArgs {
+    double* dbias;   // dbias[e] of nonzero e, addressed like bias[e]
+    int accumulate;  // 0: dbias[e] = p_e (<dZ_i, V_j> - delta_i); otherwise dbias[e] += that (an earlier head's value)
+};
+
+template <bool BIAS, bool DBIAS>
+using AqArgsOf = std::conditional_t<DBIAS, AqBiasGradArgs, std::conditional_t<BIAS, AqBiasArgs, AqArgs>>;
+
 // BIAS (include/hnh_attn_edge.h): s_e = scale <Q_i, K_j> + bias[e].  The lane that owns nonzero e's score after the butterfly loads bias[e]
 // with the batch's column indices, ahead of the gathers, into the batch's buffer (one vector load of 8 bytes per lane: the lanes of a group
 // read U consecutive doubles of one line; it works at every LPR, where loads through the scalar cache would need a wave-uniform row), and
 // adds it before the online-softmax step (forward) or to the exponent scale qk - lse before the exp (row and column pass).
-template <int PASS, int LPR, int VEC, int W, bool EXACT, bool BIAS = false>
-__device__ __forceinline__ void attn_qkv_process(int64_t row, int beg, int end, const int32_t* __restrict__ colidx,
-                                                 const std::conditional_t<BIAS, AqBiasArgs, AqArgs>& a, unsigned flags, int lig, double* part_row) {
+// DBIAS (include/hnh_attn_edge_grad.h; backward passes with BIAS): after the butterfly every lane of a nonzero's SUB lanes, in both halves of
+// the group, holds wp (da - dl) = dL/db_e of this head; one of them (the first of the lower half, as the forward pass stores values[e])
+// stores it to dbias[e], or adds it to what is there.  Every nonzero belongs to one (launch, segment): no partial rows, no atomics.
+template <int PASS, int LPR, int VEC, int W, bool EXACT, bool BIAS = false, bool DBIAS = false>
+__device__ __forceinline__ void attn_qkv_process(int64_t row, int beg, int end, const int32_t* __restrict__ colidx, const AqArgsOf<BIAS, DBIAS>& a,
+                                                 unsigned flags, int lig, double* part_row) {
+    static_assert(!DBIAS || (BIAS && PASS != 0), "the bias's gradient belongs to the biased backward passes");
     constexpr int U = AgUnroll<1, LPR, VEC, W>::value;  // (two halves per gathered row in every pass)
     constexpr int NR = PASS == 0 ? U : 2 * U;           // reductions of a batch's butterfly
     constexpr int SUB = LPR / NR;                       // lanes that end up holding the same reduced value
@@ -233,6 +247,16 @@ __device__ __forceinline__ void attn_qkv_process(int64_t row, int beg, int end, 
             if constexpr (BIAS) ex += b.bias[0];
             double wp = exp(ex);
             double wg = scale * (wp * (da - dl));
+            if constexpr (DBIAS) {
+                if (have && lower && lig % SUB == 0) {
+                    double* const d = a.dbias + (e + umine);
+                    double gb = wp * (da - dl);
+                    // (load, add, store: the product is rounded before the sum and never contracted into it, so that accumulating onto a
+                    // vector is that vector plus the overwriting call's result to the bit)
+                    asm volatile("" : "+v"(gb));
+                    *d = a.accumulate ? *d + gb : gb;
+                }
+            }
             if (!have) {
                 wp = 0.0;
                 wg = 0.0;
@@ -359,24 +383,26 @@ __device__ __forceinline__ void attn_qkv_process(int64_t row, int beg, int end, 
 }
 
 // the instance's name for the shells of hnh_attn_dispatch.hpp (attn_rows_kernel, attn_segments_kernel)
-template <int PASS, int LPR, int VEC, int W, bool EXACT, bool BIAS = false>
+template <int PASS, int LPR, int VEC, int W, bool EXACT, bool BIAS = false, bool DBIAS = false>
 struct AqPass {
-    using Args = std::conditional_t<BIAS, AqBiasArgs, AqArgs>;
+    using Args = AqArgsOf<BIAS, DBIAS>;
     static constexpr int lpr = LPR;
     static __device__ __forceinline__ void run(int64_t row, int beg, int end, const int32_t* __restrict__ colidx, const Args& a, unsigned flags, int lig,
                                                double* part_row) {
-        attn_qkv_process<PASS, LPR, VEC, W, EXACT, BIAS>(row, beg, end, colidx, a, flags, lig, part_row);
+        attn_qkv_process<PASS, LPR, VEC, W, EXACT, BIAS, DBIAS>(row, beg, end, colidx, a, flags, lig, part_row);
     }
 };
 
-// BIAS: the entry points of include/hnh_attn_edge.h, with `bias` in the block's numbering
-template <int PASS, bool BIAS = false>
+// BIAS: the entry points of include/hnh_attn_edge.h, with `bias` in the block's numbering; DBIAS: those of include/hnh_attn_edge_grad.h, with
+// `dbias` in the same numbering
+template <int PASS, bool BIAS = false, bool DBIAS = false>
 int attn_qkv_dispatch(hnh_ctx* ctx, const hnh_csr_block* b, const hnh_attn_qkv* g, unsigned flags, const hnh_csr_window* win, int stream,
-                      const char* who, const double* bias = nullptr) {
+                      const char* who, const double* bias = nullptr, double* dbias = nullptr, int accumulate = 0) {
     HNH_ENTER(ctx, stream);
     if (int rc = attn_dispatch_head(ctx, b, g != nullptr, g ? g->f : 0, HNH_ATTN_QKV_MAX_F, "HNH_ATTN_QKV_MAX_F", PASS == 0, flags, win, who)) return rc;
     // (behind the head: the parents' refusals, the width limit among them, come first and with their codes)
     if (BIAS && b->rowptr != nullptr && bias == nullptr) return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": null bias");
+    if (DBIAS && b->rowptr != nullptr && dbias == nullptr) return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": null dbias");
     const bool finish = PASS == 0 && (flags & HNH_ATTN_FINISH) != 0;
     if (b->rows == 0) return HNH_OK;
     const int f = g->f, fp = f + (f & 1);
@@ -384,8 +410,12 @@ int attn_qkv_dispatch(hnh_ctx* ctx, const hnh_csr_block* b, const hnh_attn_qkv* 
     if (PASS == 2 && (!g->Out2 || g->ld_out2 < f || g->Out2 == g->Out)) return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": bad second output");
     if (PASS == 0 && (!g->row_max || !g->row_sum || !g->lse || !g->relu_dst || g->relu_ld < f))
         return hnh::fail(ctx, HNH_ERR_INVALID, std::string(who) + ": bad row state");
-    std::conditional_t<BIAS, AqBiasArgs, AqArgs> a;
+    AqArgsOf<BIAS, DBIAS> a;
     if constexpr (BIAS) a.bias = bias;
+    if constexpr (DBIAS) {
+        a.dbias = dbias;
+        a.accumulate = accumulate != 0;
+    }
     a.X = g->X; a.X2 = g->X2; a.dZ = g->dZ; a.delta = g->delta; a.Y = g->Y; a.lse = g->lse; a.Out = g->Out; a.Out2 = g->Out2;
     a.row_max = g->row_max; a.row_sum = g->row_sum; a.relu_dst = g->relu_dst; a.values = PASS == 0 ? g->values : nullptr;
     a.ld_x = g->ld_x; a.ld_x2 = g->ld_x2; a.ld_dz = g->ld_dz; a.ld_y = g->ld_y; a.ld_out = g->ld_out; a.ld_out2 = g->ld_out2; a.relu_ld = g->relu_ld;
@@ -426,7 +456,7 @@ int attn_qkv_dispatch(hnh_ctx* ctx, const hnh_csr_block* b, const hnh_attn_qkv* 
 
     auto launch = [&](const LongCtl& lc, const int32_t* beg_ptr, const int32_t* end_ptr, unsigned fl, bool run_long) {
         return attn_launch_shape(f, w2, [&](auto l, auto v, auto w, auto ex) {
-            return attn_launch<AqPass<PASS, decltype(l)::value, decltype(v)::value, decltype(w)::value, decltype(ex)::value, BIAS>, PASS == 0, false>(
+            return attn_launch<AqPass<PASS, decltype(l)::value, decltype(v)::value, decltype(w)::value, decltype(ex)::value, BIAS, DBIAS>, PASS == 0, false>(
                 ctx, st, lc, b->rows, b->rowptr, beg_ptr, end_ptr, b->col_idx, a, fl, run_long, pitch, sums);
         });
     };
@@ -463,6 +493,17 @@ int hnh_attn_qkv_bias_row_csr_p(hnh_ctx* ctx, const hnh_csr_block* b, const hnh_
 int hnh_attn_qkv_bias_col_csr_p(hnh_ctx* ctx, const hnh_csr_block* b, const hnh_attn_qkv* args, const double* bias, unsigned flags,
                                 const hnh_csr_window* window, int stream) {
     return attn_qkv_dispatch<2, true>(ctx, b, args, flags, window, stream, "hnh_attn_qkv_bias_col_csr_p", bias);
+}
+
+// ---- the per-edge bias's gradient (include/hnh_attn_edge_grad.h)
+int hnh_attn_qkv_bias_grad_row_csr_p(hnh_ctx* ctx, const hnh_csr_block* b, const hnh_attn_qkv* args, const double* bias, double* dbias, int accumulate,
+                                     unsigned flags, const hnh_csr_window* window, int stream) {
+    return attn_qkv_dispatch<1, true, true>(ctx, b, args, flags, window, stream, "hnh_attn_qkv_bias_grad_row_csr_p", bias, dbias, accumulate);
+}
+
+int hnh_attn_qkv_bias_grad_col_csr_p(hnh_ctx* ctx, const hnh_csr_block* b, const hnh_attn_qkv* args, const double* bias, double* dbias, int accumulate,
+                                     unsigned flags, const hnh_csr_window* window, int stream) {
+    return attn_qkv_dispatch<2, true, true>(ctx, b, args, flags, window, stream, "hnh_attn_qkv_bias_grad_col_csr_p", bias, dbias, accumulate);
 }
 
 }  // extern "C"

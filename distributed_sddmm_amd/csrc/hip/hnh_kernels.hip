@@ -34,6 +34,7 @@
 #include "hnh_attn_v2.h"
 #include "hnh_attn_qkv.h"
 #include "hnh_attn_edge.h"
+#include "hnh_attn_edge_grad.h"
 #include "hnh_gat_skip.h"
 
 namespace {
@@ -2851,5 +2852,5 @@ int hnh_rowdot_cols_f64(hnh_ctx* ctx, double* out, const double* dZ, int64_t ld_
 #include "hnh_attn_coef_kernels.hpp"
 
 // ---------------------------------------------------------------- query/key/value attention scores (include/hnh_attn_qkv.h), with a per-edge
-// bias (include/hnh_attn_edge.h)
+// bias (include/hnh_attn_edge.h) and its gradient (include/hnh_attn_edge_grad.h)
 #include "hnh_attn_qkv_kernels.hpp"

@@ -14,6 +14,7 @@
 #include "hnh_attn_v2.h"
 #include "hnh_attn_qkv.h"
 #include "hnh_attn_edge.h"
+#include "hnh_attn_edge_grad.h"
 #include "hnh_gat_skip.h"
 #include "hnh_grad.h"
 #include "hnh_kernels.h"
@@ -73,6 +74,8 @@ struct Backend {
     HNH_FN(hnh_attn_qkv_fwd_csr_p) HNH_FN(hnh_attn_qkv_row_csr_p) HNH_FN(hnh_attn_qkv_col_csr_p)
     // OPTIONAL group (include/hnh_attn_edge.h), bound the same way: only a GAT layer with an edge bias needs it
     HNH_FN(hnh_attn_qkv_bias_fwd_csr_p) HNH_FN(hnh_attn_qkv_bias_row_csr_p) HNH_FN(hnh_attn_qkv_bias_col_csr_p)
+    // OPTIONAL group (include/hnh_attn_edge_grad.h), bound the same way: only a GAT layer whose edge bias is learned needs it
+    HNH_FN(hnh_attn_qkv_bias_grad_row_csr_p) HNH_FN(hnh_attn_qkv_bias_grad_col_csr_p)
     // OPTIONAL group (include/hnh_attn_coef.h), bound the same way: only GAT::attention_coefficients needs it
     HNH_FN(hnh_attn_coef_csr_p) HNH_FN(hnh_attn_coef_scores_f64)
     // OPTIONAL group (include/hnh_gat_skip.h), bound the same way: only a GAT layer with a bias or a skip connection needs it

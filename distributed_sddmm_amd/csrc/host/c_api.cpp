@@ -803,6 +803,21 @@ int hnh_gat_get_qk_weight_grad(hnh_gat* g, int layer, int head, int which, doubl
 int hnh_gat_set_edge_bias(hnh_gat* g, int layer, const hnh_vec* s, const hnh_vec* st) {
     return guarded(g->w, [&] { g->g->set_edge_bias(layer, s ? &s->v : nullptr, st ? &st->v : nullptr); });
 }
+int hnh_gat_set_edge_bias_learned(hnh_gat* g, int layer, int on) {
+    return guarded(g->w, [&] { g->g->set_edge_bias_learned(layer, on != 0); });
+}
+int hnh_gat_get_edge_bias(hnh_gat* g, int layer, int which, hnh_vec* out) {
+    return guarded(g->w, [&] {
+        if (!out) throw hnh::Error("Error, hnh_gat_get_edge_bias: null pointer!");
+        g->g->get_edge_bias(layer, which, out->v);
+    });
+}
+int hnh_gat_get_edge_bias_grad(hnh_gat* g, int layer, int which, hnh_vec* out) {
+    return guarded(g->w, [&] {
+        if (!out) throw hnh::Error("Error, hnh_gat_get_edge_bias_grad: null pointer!");
+        g->g->edge_bias_grad(layer, which, out->v);
+    });
+}
 int hnh_gat_set_activation(hnh_gat* g, int layer, int mode) {
     return guarded(g->w, [&] { g->g->set_activation(layer, mode); });
 }

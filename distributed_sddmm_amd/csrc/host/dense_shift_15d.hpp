@@ -364,13 +364,17 @@ public:
     // `bias` (include/hnh_attn_edge.h): one value per nonzero in the like_S_values layout (passes 0 and 1) or the like_ST_values layout (pass
     // 2); block i is lent its slice bias->data() + blockStarts[i] (CSRLocal::spmm_values: a value array that the pass reads in place), as
     // attnCoef_pass lends its destination, and the slices are reclaimed before the pass returns.
+    // `dbias` (include/hnh_attn_edge_grad.h; passes 1 and 2 with a bias): the bias's gradient in the bias's layout, sliced per block in the
+    // same way (CSRLocal::sddmm_dst: a value array that the pass writes in place); every nonzero's entry is overwritten or, with
+    // `accumulate`, added to, and entries of absent blocks are not touched.
     bool attnQKV_pass(int pass, DenseMatrix& moving, const hnh_attn_qkv& args, int64_t out_rows, bool overwrite, unsigned finish_flags = 0u,
-                      const VectorXd* bias = nullptr) {
+                      const VectorXd* bias = nullptr, VectorXd* dbias = nullptr, bool accumulate = false) {
         if (fusionApproach != 2 || c != 1) return false;
         if (pass < 0 || pass > 2) hnh::fatal("Error, attnQKV_pass: unknown pass!");
         if (moving.cols() != R) hnh::fatal("Error, attnQKV_pass: the schedule's R must be the moving operand's width!");
         SpmatLocal* s = pass == 2 ? ST.get() : S.get();
         const char* missing = "Error, the kernel implementation has no transformer attention pass (KernelImplementation::attn_qkv_local)!";
+        if (dbias != nullptr && (bias == nullptr || pass == 0)) hnh::fatal("Error, attnQKV_pass: the bias's gradient belongs to a backward pass with a bias!");
         if (bias == nullptr) {
             attn_walk(s, moving, args, overwrite, pass == 0, missing,
                       [&](SpmatLocal& choice, int block_id, const hnh_attn_qkv& a, unsigned flags, bool finish) {
@@ -379,11 +383,14 @@ public:
             return true;
         }
         if (!s->blockStarts.empty() && (uint64_t)bias->size() < s->blockStarts.back()) hnh::fatal("Error, sparse value vector has the wrong length!");
+        if (dbias != nullptr && !s->blockStarts.empty() && (uint64_t)dbias->size() < s->blockStarts.back())
+            hnh::fatal("Error, sparse value vector has the wrong length!");
         for (size_t i = 0; i + 1 < s->blockStarts.size(); i++) {
             CSRLocal* blk = s->csr_blocks[i];
             if (blk == nullptr) continue;
             if (blk->shifting) hnh::fatal("Error, attnQKV_pass: a travelling block cannot borrow a value slice!");
             blk->spmm_values = bias->data() + s->blockStarts[i];
+            if (dbias != nullptr) blk->sddmm_dst = dbias->data() + s->blockStarts[i];
         }
         struct Reclaim {
             SpmatLocal* s;
@@ -392,6 +399,9 @@ public:
         attn_walk(s, moving, args, overwrite, pass == 0, missing,
                   [&](SpmatLocal& choice, int block_id, const hnh_attn_qkv& a, unsigned flags, bool finish) {
                       const CSRLocal* blk = choice.csr_blocks[block_id];
+                      if (dbias != nullptr)
+                          return kernel->attn_qkv_local(choice, block_id, a, pass, flags, out_rows, finish, blk ? blk->spmm_values : nullptr,
+                                                        blk ? blk->sddmm_dst : nullptr, accumulate);
                       return kernel->attn_qkv_local(choice, block_id, a, pass, flags | (finish ? finish_flags : 0u), out_rows, finish,
                                                     blk ? blk->spmm_values : nullptr);
                   });

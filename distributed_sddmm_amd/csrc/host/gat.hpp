@@ -166,6 +166,9 @@ public:
         bias_.assign(layers.size(), DenseMatrix());
         edge_bias_on_.assign(layers.size(), 0);
         for (auto& e : edge_bias_) e.assign(layers.size(), VectorXd());
+        edge_bias_learned_.assign(layers.size(), 0);
+        dbias_held_.assign(layers.size(), 0);
+        for (auto& e : dbias_) e.assign(layers.size(), VectorXd());
         w_res_.assign(layers.size(), std::vector<DenseMatrix>());
         for (auto& w : w_qk_) w.assign(layers.size(), std::vector<DenseMatrix>());
         d_ops->setRValue(layers[0].input_features);
@@ -209,8 +212,10 @@ public:
         if (mode != score_) {
             invalidate_forward();
             // (leaving score TRANSFORMER: no later backward pass refreshes dW_q and dW_k, so their getter refuses rather than hand out old ones)
-            if (score_ == HNH_GAT_SCORE_TRANSFORMER)
+            if (score_ == HNH_GAT_SCORE_TRANSFORMER) {
                 for (auto& gq : qk_weight_grads) gq.clear();
+                for (size_t l = 0; l < layers.size(); l++) drop_edge_bias_grad((int)l);
+            }
         }
         score_ = mode;
     }
@@ -323,6 +328,8 @@ public:
             if (edge_bias_on_[(size_t)i]) invalidate_forward();
             edge_bias_on_[(size_t)i] = 0;
             for (auto& e : edge_bias_) e[(size_t)i] = VectorXd();
+            edge_bias_learned_[(size_t)i] = 0;  // (no bias, nothing to learn: the switch goes with it)
+            drop_edge_bias_grad(i);
             return;
         }
         if (s == nullptr || st == nullptr)
@@ -346,6 +353,44 @@ public:
         }
         edge_bias_on_[(size_t)i] = 1;
         invalidate_forward();
+    }
+
+    // A LEARNED edge bias (include/hnh_attn_edge_grad.h): the layer's bias becomes a parameter.  backwardPass then also computes
+    //     dL/db_e = sum_h p_e^h (<dZ_i^h, V_j^h> - delta_i^h)        (heads added in the order h = 0 .. H-1)
+    // with the two backward passes' grad entry points (accumulate = (h > 0)): the row pass writes it in S's order, the column pass in
+    // S^T's, and optimizer_step updates each copy of the bias from the gradient of its own pass (the two copies are both parameters, as
+    // ALS keeps ground_truth and ground_truth_transpose; both passes compute the same expression from the same operands, so the copies
+    // agree to rounding, and two entries that start equal and get equal gradients stay equal).  Every rank holds the bias of its own
+    // nonzeros only: the gradient needs no all-reduce.  THE BIAS IS NEVER DECAYED: optimizer_step updates these tensors in a call of
+    // their own with weight_decay = 0 (same step count, same hyper-parameters otherwise), so an entry at -1e300 (a switched-off edge),
+    // whose p_e and hence gradient are exactly 0 in every head and whose moments therefore stay 0, stays -1e300 to the bit under Adam
+    // (eps > 0) and SGD; decay would multiply it.  Refused by name unless the layer has an edge bias; clearing the bias clears the
+    // switch.  The forward pass does not depend on the switch, so the stored pass stays valid; switching it off drops the gradient.
+    bool edge_bias_learned(int i) const {
+        check_layer(i);
+        return edge_bias_learned_[(size_t)i] != 0;
+    }
+    void set_edge_bias_learned(int i, bool on) {
+        check_layer(i);
+        if (on && !edge_bias_on_[(size_t)i])
+            throw hnh::Error("Error, GAT set_edge_bias_learned: layer " + std::to_string(i) + " has no edge bias to learn (set_edge_bias first)!");
+        edge_bias_learned_[(size_t)i] = on ? 1 : 0;
+        if (!on) drop_edge_bias_grad(i);
+    }
+    // The bias of layer i as it stands (which = 0: S's order, like_S_values; 1: S^T's order, like_ST_values), device to device into `out`
+    void get_edge_bias(int i, int which, VectorXd& out) {
+        check_edge_which(i, which);
+        if (!edge_bias_on_[(size_t)i]) throw hnh::Error("Error, GAT get_edge_bias: layer " + std::to_string(i) + " has no edge bias!");
+        copy_edge_vector(edge_bias_[which][(size_t)i], out, "get_edge_bias");
+    }
+    // dL/db of layer i from the last backwardPass, in the same two orders.  Refuses before a backward pass with the layer's bias learned,
+    // and after whatever dropped it: the switch or the bias cleared, a score other than TRANSFORMER set.
+    void edge_bias_grad(int i, int which, VectorXd& out) {
+        check_edge_which(i, which);
+        if (!edge_bias_learned_[(size_t)i] || !dbias_held_[(size_t)i])
+            throw hnh::Error("Error, no GAT edge-bias gradient of layer " + std::to_string(i) +
+                             " yet: call backwardPass with set_edge_bias_learned on this layer first!");
+        copy_edge_vector(dbias_[which][(size_t)i], out, "edge_bias_grad");
     }
 
     // Dropout (include/hnh_attn_dropout.h): rates in [0, 1) on the attention coefficients (score ADDITIVE only; checked by forwardPass)
@@ -629,16 +674,23 @@ public:
         const std::vector<Learned> learned = learned_parameters();
         for (const Learned& t : learned)
             if (t.g == nullptr) throw hnh::Error(t.refusal);
-        std::vector<hnh_optim_tensor> table;
+        // the learned edge biases (PARAM_EDGE_BIAS_S / _ST) in a table and a call of their own: they are never decayed
+        std::vector<hnh_optim_tensor> table, undecayed;
         for (const Learned& t : learned) {
+            if (t.rows == 0) continue;  // (a rank without nonzeros holds none of a layer's bias)
             const Moments& m = ensure_moments(t);
-            table.push_back({t.p, t.ld_p, t.g, t.ld_g, m.first.data(), m.second.data(), t.rows, t.cols});
+            const bool edge = std::get<0>(t.key) == PARAM_EDGE_BIAS_S || std::get<0>(t.key) == PARAM_EDGE_BIAS_ST;
+            (edge ? undecayed : table).push_back({t.p, t.ld_p, t.g, t.ld_g, m.first.data(), m.second.data(), t.rows, t.cols});
         }
         optim_steps_++;
         hnh_optim hy = optim_;
         hy.bias1 = 1.0 - std::pow(hy.beta1, (double)optim_steps_);
         hy.bias2 = 1.0 - std::pow(hy.beta2, (double)optim_steps_);
         HNH_GAT_CALL(hnh_optim_step_f64, table.data(), (int)table.size(), &hy, HNH_STREAM_COMPUTE);
+        if (!undecayed.empty()) {
+            hy.weight_decay = 0.0;
+            HNH_GAT_CALL(hnh_optim_step_f64, undecayed.data(), (int)undecayed.size(), &hy, HNH_STREAM_COMPUTE);
+        }
         grads_fresh_ = false;
         invalidate_forward();
     }
@@ -737,6 +789,23 @@ private:
     std::vector<char> edge_bias_on_;
     std::vector<VectorXd> edge_bias_[2];
     int64_t edge_len_[2] = {-1, -1};  // the lengths of like_S_values / like_ST_values, once set_edge_bias has asked for them
+    // a learned edge bias (include/hnh_attn_edge_grad.h): the switch per layer, dL/db in both orders ([0]: S's, from the row pass; [1]:
+    // S^T's, from the column pass) and whether a backward pass has filled them since they were last dropped
+    std::vector<char> edge_bias_learned_, dbias_held_;
+    std::vector<VectorXd> dbias_[2];
+    void drop_edge_bias_grad(int i) {
+        dbias_held_[(size_t)i] = 0;
+        for (auto& e : dbias_) e[(size_t)i] = VectorXd();
+    }
+    void check_edge_which(int i, int which) const {
+        check_layer(i);
+        if (which != 0 && which != 1) throw hnh::Error("Error, GAT edge-bias order selector " + std::to_string(which) + " is neither 0 (S) nor 1 (S^T)!");
+    }
+    void copy_edge_vector(const VectorXd& from, VectorXd& out, const char* who) {
+        if (out.size() != from.size())
+            throw hnh::Error(std::string("Error, GAT ") + who + " needs a vector of " + std::to_string(from.size()) + " entries, not " + std::to_string(out.size()) + "!");
+        if (from.size() > 0) d_ops->world->copy(out.data(), from.data(), sizeof(double) * (size_t)from.size(), HNH_COPY_D2D, HNH_STREAM_COMPUTE);
+    }
     // score TRANSFORMER: W_q ([0]) and W_k ([1]) per (layer, head), input_features x f each (kept here, not in GATLayer, for act_'s reason)
     std::vector<std::vector<DenseMatrix>> w_qk_[2];
     // training (include/hnh_train.h): this rank's labels on the device (-1: not in the loss) with the world's labelled count; the host's
@@ -754,7 +823,7 @@ private:
     hnh_optim optim_ = {};
     int64_t optim_steps_ = 0;
     // Every learned tensor of the model is one row of optimizer_step's table (learned_parameters()); its moments live under its key.
-    enum ParamKind { PARAM_W, PARAM_A1, PARAM_A2, PARAM_BIAS, PARAM_W_RES, PARAM_W_Q, PARAM_W_K };
+    enum ParamKind { PARAM_W, PARAM_A1, PARAM_A2, PARAM_BIAS, PARAM_W_RES, PARAM_W_Q, PARAM_W_K, PARAM_EDGE_BIAS_S, PARAM_EDGE_BIAS_ST };
     typedef std::tuple<int, int, int> ParamKey;            // (kind, layer, head; head 0 for a tensor of the whole layer)
     typedef std::pair<DenseMatrix, DenseMatrix> Moments;   // (first moment: Adam only, SGD keeps none; second moment, or SGD's momentum buffer)
     struct Learned {
@@ -769,7 +838,8 @@ private:
 
     // The table's rows in order: per layer W_0 .. W_{H-1}, then a1, then a2 (score ADDITIVE; GATV2 learns a1 alone); after all layers, per
     // layer the enabled bias, then W_res_0 .. W_res_{H-1} of a projection (include/hnh_gat_skip.h), then with score TRANSFORMER W_q_0 ..
-    // W_q_{H-1} and W_k_0 .. W_k_{H-1} (behind every other entry of the layer).  Weight decay applies to all alike.
+    // W_q_{H-1} and W_k_0 .. W_k_{H-1}, then a learned edge bias in S's and in S^T's order (one nnz x 1 tensor each, behind every other
+    // entry of the layer).  Weight decay applies to all alike but the edge bias, which optimizer_step never decays.
     std::vector<Learned> learned_parameters() {
         std::vector<Learned> all;
         const size_t n = layers.size();
@@ -812,6 +882,14 @@ private:
                 for (int h = 0; h < L.num_heads; h++)
                     add(which == 0 ? PARAM_W_Q : PARAM_W_K, i, h, w_qk_[which][i][(size_t)h].data(), f, k, f, held(qk_weight_grads[which], i, k, hf),
                         (int64_t)h * f, "Error, GAT optimizer_step needs the query and key weight gradients of a backwardPass with score transformer!");
+            if (!edge_bias_learned_[i]) continue;
+            for (int which = 0; which < 2; which++) {
+                VectorXd& b = edge_bias_[which][i];
+                const VectorXd& g = dbias_[which][i];
+                const bool held = dbias_held_[i] && g.size() == b.size();
+                all.push_back({ParamKey(which == 0 ? PARAM_EDGE_BIAS_S : PARAM_EDGE_BIAS_ST, (int)i, 0), b.data(), 1, held ? g.data() : nullptr, 1,
+                               (int64_t)b.size(), 1, "Error, GAT optimizer_step needs the edge-bias gradient of a backwardPass since set_edge_bias_learned!"});
+            }
         }
         return all;
     }
@@ -1244,13 +1322,18 @@ private:
     }
     // A layer with an edge bias: the transformer score's passes alone take one (its own conditions are check_transformer_supported's, which
     // follows); the kernel group.
-    void check_edge_bias_supported() {
+    // A layer whose bias is learned needs the gradient's group as well wherever a backward pass runs, asked for first: it is what the
+    // layer's backward pass launches.
+    void check_edge_bias_supported(bool backward) {
         for (size_t i = 0; i < layers.size(); i++) {
             if (!edge_bias_on_[i]) continue;
             const std::string what = "edge bias of layer " + std::to_string(i);
             if (score_ != HNH_GAT_SCORE_TRANSFORMER)
                 throw hnh::Error("Error, GAT " + what + " supports score transformer only, not score " + score_name(score_) +
                                  ": its passes have no bias operand (include/hnh_attn_edge.h)");
+            if (backward && edge_bias_learned_[i])
+                require_kernels("learned edge bias", "include/hnh_attn_edge_grad.h",
+                                {HNH_GAT_KERNEL(hnh_attn_qkv_bias_grad_row_csr_p), HNH_GAT_KERNEL(hnh_attn_qkv_bias_grad_col_csr_p)});
             require_kernels("edge bias", "include/hnh_attn_edge.h",
                             {HNH_GAT_KERNEL(hnh_attn_qkv_bias_fwd_csr_p), HNH_GAT_KERNEL(hnh_attn_qkv_bias_row_csr_p),
                              HNH_GAT_KERNEL(hnh_attn_qkv_bias_col_csr_p)});
@@ -1282,7 +1365,7 @@ private:
         check_dropout_supported();
         check_activation_supported();
         check_skip_supported();
-        check_edge_bias_supported();
+        check_edge_bias_supported(op == OP_BACKWARD || op == OP_TRAIN_STEP);
         if (op == OP_BACKWARD || op == OP_TRAIN_STEP) check_backward_supported();
         if (op != OP_FORWARD) return;  // (evaluate's forwardPass checks the score)
         if (score_ == HNH_GAT_SCORE_ADDITIVE) check_additive_supported();
@@ -1633,8 +1716,15 @@ private:
         bool ok = false;
         if (ds != nullptr) {  // the moving operand is [K | V], then P
             ScheduleWidth width(d_ops, (int)KV.cols(), f);
-            const bool biased = edge_bias_on_[(size_t)i] != 0;
-            ok = ds->attnQKV_pass(1, KV, g, rows, true, 0u, biased ? &edge_bias_[0][(size_t)i] : nullptr);  // row side: dQ
+            const bool biased = edge_bias_on_[(size_t)i] != 0, learned = biased && edge_bias_learned_[(size_t)i] != 0;
+            VectorXd* db[2] = {nullptr, nullptr};  // a learned bias: dL/db in S's and S^T's order, head h added to the heads before it
+            if (learned)
+                for (int k = 0; k < 2; k++) {
+                    VectorXd& d = dbias_[k][(size_t)i];
+                    if (d.size() != edge_bias_[k][(size_t)i].size()) d = VectorXd(edge_bias_[k][(size_t)i].size());
+                    db[k] = &d;
+                }
+            ok = ds->attnQKV_pass(1, KV, g, rows, true, 0u, biased ? &edge_bias_[0][(size_t)i] : nullptr, db[0], h > 0);  // row side: dQ
             if (ok) {
                 d_ops->setRValue(pw);
                 g.X = qk.K.data();
@@ -1643,7 +1733,8 @@ private:
                 g.Out = dK_all.data() + at;
                 g.Out2 = dA_all.data() + at;
                 g.ld_out2 = hf;
-                ok = ds->attnQKV_pass(2, P, g, rows, true, 0u, biased ? &edge_bias_[1][(size_t)i] : nullptr);  // column side: dK, dV
+                ok = ds->attnQKV_pass(2, P, g, rows, true, 0u, biased ? &edge_bias_[1][(size_t)i] : nullptr, db[1], h > 0);  // column side: dK, dV
+                if (ok && learned && h + 1 == layers[(size_t)i].num_heads) dbias_held_[(size_t)i] = 1;
             }
         }
         require_own_rows("score transformer", !ok);

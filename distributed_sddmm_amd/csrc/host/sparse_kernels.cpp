@@ -266,13 +266,30 @@ bool KernelImplementation::attn_qkv_local(SpmatLocal& S, int block, const hnh_at
 
 // The three sparse passes of the query/key/value attention (include/hnh_attn_qkv.h), next to attn_v2_block: same block and window handling;
 // the gathered width is the packed operand's of the pass.  `biased`: the entry points of include/hnh_attn_edge.h, which take the block's
-// slice of the bias vector behind the arguments; both overloads of attn_qkv_block are this one function.
+// slice of the bias vector behind the arguments; `graded`: those of include/hnh_attn_edge_grad.h (the backward passes alone), which also
+// take the block's slice of the bias's gradient and `accumulate`; every overload of attn_qkv_block is this one function.
 static bool attn_qkv_call(StandardKernel& k, SpmatLocal& S, int block, const hnh_attn_qkv& args, int pass, unsigned flags, int64_t rows, bool finish,
-                          bool biased, const double* bias, const std::function<void()>& begin, const std::function<void(long)>& end) {
+                          bool biased, const double* bias, const std::function<void()>& begin, const std::function<void(long)>& end,
+                          bool graded = false, double* dbias = nullptr, bool accumulate = false) {
     hnh::World* w = S.world;
     const hnh::Backend* be = w->be;
     auto plain = pass == 0 ? be->hnh_attn_qkv_fwd_csr_p : (pass == 1 ? be->hnh_attn_qkv_row_csr_p : be->hnh_attn_qkv_col_csr_p);
     auto with_bias = pass == 0 ? be->hnh_attn_qkv_bias_fwd_csr_p : (pass == 1 ? be->hnh_attn_qkv_bias_row_csr_p : be->hnh_attn_qkv_bias_col_csr_p);
+    if (graded) {
+        if (pass != 1 && pass != 2) hnh::fatal("Error, the edge bias's gradient belongs to the backward passes!");
+        auto with_grad = pass == 1 ? be->hnh_attn_qkv_bias_grad_row_csr_p : be->hnh_attn_qkv_bias_grad_col_csr_p;
+        const char* gname = pass == 1 ? "hnh_attn_qkv_bias_grad_row_csr_p" : "hnh_attn_qkv_bias_grad_col_csr_p";
+        if (with_grad == nullptr)
+            throw hnh::Error(std::string("Error, the transformer attention score with a learned edge bias needs the kernel ") + gname +
+                             ", which the kernel library " + be->path + " does not export (include/hnh_attn_edge_grad.h)");
+        attn_block_call(S, block, rows, "the transformer attention pass with a learned edge bias", nullptr, HNH_ATTN_GRAD_PACKED_WIDTH(args.f, pass == 2 ? 1 : 0),
+                        k.profile,
+                        [&](const hnh_csr_block& d, const hnh_csr_window* win) {
+                            w->check(with_grad(w->ctx, &d, &args, bias, dbias, accumulate ? 1 : 0, flags, win, HNH_STREAM_COMPUTE), gname);
+                        },
+                        begin, end);
+        return true;
+    }
     const std::string name = std::string(biased ? "hnh_attn_qkv_bias_" : "hnh_attn_qkv_") + (pass == 0 ? "fwd" : (pass == 1 ? "row" : "col")) + "_csr_p";
     if (biased ? with_bias == nullptr : plain == nullptr)
         throw hnh::Error(std::string("Error, the transformer attention score") + (biased ? " with an edge bias" : "") + " needs the kernel " + name +
@@ -302,6 +319,18 @@ bool KernelImplementation::attn_qkv_local(SpmatLocal& S, int block, const hnh_at
 bool StandardKernel::attn_qkv_block(SpmatLocal& S, int block, const hnh_attn_qkv& args, int pass, unsigned flags, int64_t rows, bool finish,
                                     const double* bias) {
     return attn_qkv_call(*this, S, block, args, pass, flags, rows, finish, true, bias, [&] { begin(S.world); }, [&](long n) { end(S.world, n); });
+}
+
+bool KernelImplementation::attn_qkv_local(SpmatLocal& S, int block, const hnh_attn_qkv& args, int pass, unsigned flags, int64_t rows, bool finish,
+                                          const double* bias, double* dbias, bool accumulate) {
+    StandardKernel* k = dynamic_cast<StandardKernel*>(this);
+    return k != nullptr && k->attn_qkv_block(S, block, args, pass, flags, rows, finish, bias, dbias, accumulate);
+}
+
+bool StandardKernel::attn_qkv_block(SpmatLocal& S, int block, const hnh_attn_qkv& args, int pass, unsigned flags, int64_t rows, bool finish,
+                                    const double* bias, double* dbias, bool accumulate) {
+    return attn_qkv_call(*this, S, block, args, pass, flags, rows, finish, true, bias, [&] { begin(S.world); }, [&](long n) { end(S.world, n); }, true, dbias,
+                         accumulate);
 }
 
 bool KernelImplementation::attn_coef_local(SpmatLocal& S, int block, const hnh_attn_coef& args, int64_t rows, const hnh_attn_drop* drop) {

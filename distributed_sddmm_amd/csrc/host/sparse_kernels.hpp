@@ -101,6 +101,10 @@ public:
     // for passes 0 and 1, of S^T for pass 2); it may be null only for an absent or empty block.  An overload, not a default argument: the
     // earlier symbol stays.
     bool attn_qkv_local(SpmatLocal& S, int block, const hnh_attn_qkv& args, int pass, unsigned flags, int64_t rows, bool finish, const double* bias);
+    // ... and with the bias's gradient (include/hnh_attn_edge_grad.h; passes 1 and 2 alone): `dbias` is the block's slice like `bias`,
+    // dbias[e] = or, with `accumulate`, += dL/db_e of this head.  Another overload: the earlier symbols stay.
+    bool attn_qkv_local(SpmatLocal& S, int block, const hnh_attn_qkv& args, int pass, unsigned flags, int64_t rows, bool finish, const double* bias,
+                        double* dbias, bool accumulate);
 
     // The export of the attention coefficients (include/hnh_attn_coef.h) on one block of S, or the selected window(s) of it: every nonzero
     // of the call gets its coefficient in the block's value slice, which the schedule has lent from the caller's vector (CSRLocal::sddmm_dst)
@@ -196,6 +200,8 @@ public:
     // KernelImplementation::attn_qkv_local's pass (non-virtual: see there)
     bool attn_qkv_block(SpmatLocal& S, int block, const hnh_attn_qkv& args, int pass, unsigned flags, int64_t rows, bool finish);
     bool attn_qkv_block(SpmatLocal& S, int block, const hnh_attn_qkv& args, int pass, unsigned flags, int64_t rows, bool finish, const double* bias);
+    bool attn_qkv_block(SpmatLocal& S, int block, const hnh_attn_qkv& args, int pass, unsigned flags, int64_t rows, bool finish, const double* bias,
+                        double* dbias, bool accumulate);
     // KernelImplementation::attn_coef_local's pass (non-virtual: see there)
     bool attn_coef_block(SpmatLocal& S, int block, const hnh_attn_coef& args, int64_t rows, const hnh_attn_drop* drop);
     ~StandardKernel() override;

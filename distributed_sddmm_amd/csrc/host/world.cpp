@@ -131,6 +131,7 @@ Backend* load_backend(const char* path_c) {
     HNH_BIND_OPTIONAL(hnh_attn_v2_finish_f64)
     HNH_BIND_OPTIONAL(hnh_attn_qkv_fwd_csr_p) HNH_BIND_OPTIONAL(hnh_attn_qkv_row_csr_p) HNH_BIND_OPTIONAL(hnh_attn_qkv_col_csr_p)
     HNH_BIND_OPTIONAL(hnh_attn_qkv_bias_fwd_csr_p) HNH_BIND_OPTIONAL(hnh_attn_qkv_bias_row_csr_p) HNH_BIND_OPTIONAL(hnh_attn_qkv_bias_col_csr_p)
+    HNH_BIND_OPTIONAL(hnh_attn_qkv_bias_grad_row_csr_p) HNH_BIND_OPTIONAL(hnh_attn_qkv_bias_grad_col_csr_p)
     HNH_BIND_OPTIONAL(hnh_attn_coef_csr_p) HNH_BIND_OPTIONAL(hnh_attn_coef_scores_f64)
     HNH_BIND_OPTIONAL(hnh_skip_addend_cols_f64) HNH_BIND_OPTIONAL(hnh_skip_grad_cols_f64) HNH_BIND_OPTIONAL(hnh_colsum_f64_workspace)
     HNH_BIND_OPTIONAL(hnh_colsum_f64)

@@ -10,8 +10,8 @@
  * pair (i, j): two copies of a repeated pair may carry different values.  With the definitions of hnh_attn_qkv.h,
  *     s_e = scale <Q_i, K_j> + b_e     lse_i = log sum_e exp(s_e)     p_e = exp(s_e - lse_i)     o_i = sum_e p_e V_j                (forward)
  *     delta_i, g_e = scale p_e (<dZ_i, V_j> - delta_i), dQ, dK, dV as there, with p_e from the biased s_e                          (backward)
- * so b_e = log w_e gives the weighted neighbourhood softmax p_e ~ w_e exp(scale <Q_i, K_j>), and the bias is not differentiated: nothing
- * here returns dL/db_e (it would be g_e / scale).
+ * so b_e = log w_e gives the weighted neighbourhood softmax p_e ~ w_e exp(scale <Q_i, K_j>).  The entry points of this header treat the
+ * bias as a constant; dL/db_e = g_e / scale is returned by the backward passes' twins of include/hnh_attn_edge_grad.h, a group of its own.
  *
  * Addressing: bias is addressed exactly as hnh_sddmm_csr_ps addresses `values`: bias[e], e in the BLOCK's numbering, whatever window,
  * group of windows, Infinity-Cache panel or hub-row segment the nonzero is visited in; it may be a slice of a caller's longer vector.  The

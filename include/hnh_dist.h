@@ -288,9 +288,22 @@ int hnh_gat_get_qk_weight_grad(hnh_gat* g, int layer, int head, int which, doubl
  * `s` in hnh_vec_like's S layout and `st` in its S^T layout (a probe SDDMM of row or column numbers names every entry's coordinates); the
  * caller keeps them in agreement, and two copies of a repeated pair may carry different values.  Both are copied; both NULL clears the bias and the
  * layer launches what it launched before.  One NULL, a wrong length or a layer out of range is refused and leaves the object as it was.  Invalidates
- * the forward pass.  Any other score refuses a layer with an edge bias by name when a pass is asked for; the bias is no parameter:
- * hnh_gat_optimizer_step does not touch it. */
+ * the forward pass.  Any other score refuses a layer with an edge bias by name when a pass is asked for; the bias is no parameter
+ * (hnh_gat_optimizer_step does not touch it) unless hnh_gat_set_edge_bias_learned says so. */
 int hnh_gat_set_edge_bias(hnh_gat* g, int layer, const hnh_vec* s, const hnh_vec* st);
+/* A LEARNED edge bias (an addition; include/hnh_attn_edge_grad.h).  on != 0 makes the layer's bias a parameter: hnh_gat_backward also computes
+ * dL/db_e = sum over the layer's heads of p_e (<dZ_i, V_j> - delta_i), heads added in the order 0 .. H-1, in S's order (from the backward row pass)
+ * and in S^T's order (from the column pass), and hnh_gat_optimizer_step / hnh_gat_train_step update each copy of the bias from the gradient of its
+ * own pass, with the other parameters' step count and hyper-parameters but NEVER with weight decay: an entry at -1e300 has gradient 0 and moments
+ * 0 and stays -1e300 to the bit.  Every rank holds the bias of its own nonzeros: nothing is all-reduced.  Refused by name unless the layer has an
+ * edge bias; clearing the bias clears the switch; switching off, clearing, or leaving score TRANSFORMER drops the gradient.  A layer whose bias is
+ * not learned launches what it launched before.  hnh_gat_get_edge_bias copies the bias as it stands and hnh_gat_get_edge_bias_grad the gradient of
+ * the last hnh_gat_backward into `out` (which = 0: S's order, a vector of hnh_vec_like's S layout; 1: S^T's); the gradient getter refuses before a
+ * backward pass with the switch on and after anything that dropped the gradient.  A kernel library without the group: hnh_gat_backward and
+ * hnh_gat_train_step name the missing symbol before anything is launched. */
+int hnh_gat_set_edge_bias_learned(hnh_gat* g, int layer, int on);
+int hnh_gat_get_edge_bias(hnh_gat* g, int layer, int which, hnh_vec* out);
+int hnh_gat_get_edge_bias_grad(hnh_gat* g, int layer, int which, hnh_vec* out);
 /* Output activation of a layer (an addition).  RELU (the default of hnh_gat_create on every layer): out = max(o, 0), everything above.  ELU:
  * out = o for o > 0 and expm1(o) otherwise.  IDENTITY: out = o.  The backward pass works from the stored output alone (include/hnh_grad.h,
  * hnh_act_grad_cols_f64).  A non-ReLU layer is supported with attention SOFTMAX, score DOT or ADDITIVE, any dropout rates, on 15d_fusion2

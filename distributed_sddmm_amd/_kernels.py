@@ -325,6 +325,16 @@ SKIP_SIGNATURES = {
 ATTN_ADDEND = 0x40  # HNH_ATTN_ADDEND: the finishing call adds what waits in relu_dst before the activation
 
 
+# include/hnh_gat_norm.h: layer normalisation of the GAT layers (two dense row passes and the backward pass's workspace size); a further
+# OPTIONAL group bound only for the product library
+NORM_SIGNATURES = {
+    "hnh_layernorm_fwd_f64": (_i32, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _dbl, _i32, _i32]),
+    "hnh_layernorm_bwd_workspace": (_i64, [_i64, _i64]),
+    "hnh_layernorm_bwd_f64": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _i32]),
+}
+NORM_MAX_COLS = 4096  # HNH_NORM_MAX_COLS
+
+
 class AttnCoef(C.Structure):
     """struct hnh_attn_coef"""
     _fields_ = [("X", _vp), ("ld_x", _i64), ("a", _vp), ("s", _vp), ("lse", _vp), ("Y", _vp), ("ld_y", _i64), ("f", _i32), ("score", _i32),
@@ -395,7 +405,8 @@ def load(path: str | None = None) -> C.CDLL:
         for name, (res, args) in list(GRAD_SIGNATURES.items()) + list(ATTN_SIGNATURES.items()) + list(ATTN_GRAD_SIGNATURES.items()) + \
                 list(ATTN_ADD_SIGNATURES.items()) + list(ATTN_DROP_SIGNATURES.items()) + list(TRAIN_SIGNATURES.items()) + \
                 list(V2_SIGNATURES.items()) + list(ATTN_COEF_SIGNATURES.items()) + list(SKIP_SIGNATURES.items()) + \
-                list(QKV_SIGNATURES.items()) + list(EDGE_SIGNATURES.items()) + list(EDGE_GRAD_SIGNATURES.items()):
+                list(QKV_SIGNATURES.items()) + list(EDGE_SIGNATURES.items()) + list(EDGE_GRAD_SIGNATURES.items()) + \
+                list(NORM_SIGNATURES.items()):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
     if path is None:

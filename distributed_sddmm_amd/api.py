@@ -151,6 +151,10 @@ SIGNATURES = {
     "hnh_gat_set_bias": (_i32, [_vp, _i32, _vp]),
     "hnh_gat_get_bias": (_i32, [_vp, _i32, _vp]),
     "hnh_gat_get_bias_grad": (_i32, [_vp, _i32, _vp]),
+    "hnh_gat_set_norm": (_i32, [_vp, _i32, _i32, C.c_double]),
+    "hnh_gat_set_norm_weights": (_i32, [_vp, _i32, _vp, _vp, C.c_int64]),
+    "hnh_gat_get_norm_weights": (_i32, [_vp, _i32, _vp, _vp, C.c_int64]),
+    "hnh_gat_get_norm_grad": (_i32, [_vp, _i32, _vp, _vp, C.c_int64]),
     "hnh_gat_get_attn_grads": (_i32, [_vp, _i32, _i32, _vp, _vp]),
     "hnh_gat_set_dropout": (_i32, [_vp, _dbl, _dbl, C.c_uint64]),
     "hnh_gat_set_dropout_seed": (_i32, [_vp, C.c_uint64]),
@@ -736,13 +740,21 @@ class GAT:
 
     RESIDUAL = {"none": 0, "identity": 1, "projection": 2}  # HNH_GAT_RESIDUAL_NONE / _IDENTITY / _PROJECTION
 
+    NORM = {"none": 0, "layer": 1}  # HNH_GAT_NORM_NONE / _LAYER
+
     HEADS = {"mean": 0, "concat": 1}  # HNH_GAT_HEADS_MEAN / _CONCAT
 
     OPTIMIZER = {"adam": 0, "sgd": 1}  # HNH_GAT_OPTIMIZER_ADAM / _SGD
 
     def __init__(self, op: DistributedSparse, layers, leaky_relu_alpha: float = 0.2, attention: str = "none", backward: str = "unfused",
-                 score: str = "dot", dropout=(0.0, 0.0), seed: int = 0, activation="relu", residual="none", bias=False):
+                 score: str = "dot", dropout=(0.0, 0.0), seed: int = 0, activation="relu", residual="none", bias=False, norm="none"):
         self.op, self.layers = op, [tuple(l) for l in layers]
+        norms = [norm] * len(self.layers) if isinstance(norm, str) else list(norm)
+        if len(norms) != len(self.layers):
+            raise ValueError("norm is one name or one name per layer: %d layers, not %d names" % (len(self.layers), len(norms)))
+        for n in norms:
+            if n not in self.NORM:
+                raise ValueError("norm must be one of %s, not %r" % (sorted(self.NORM), n))
         ress = [residual] * len(self.layers) if isinstance(residual, str) else list(residual)
         if len(ress) != len(self.layers):
             raise ValueError("residual is one name or one name per layer: %d layers, not %d names" % (len(self.layers), len(ress)))
@@ -779,6 +791,9 @@ class GAT:
             for i, b in enumerate(biases):
                 if b:
                     self.set_bias(i, np.zeros(self.layers[i][1] * self.layers[i][2]))
+            for i, n in enumerate(norms):
+                if n != "none":
+                    self.set_norm(i, n)
         except BaseException:
             self.free()
             raise
@@ -904,6 +919,49 @@ class GAT:
         out = np.empty(self._width(layer))
         _check(lib().hnh_gat_get_bias_grad(self.h, layer, out.ctypes.data), "gat_get_bias_grad")
         return out
+
+    # ---- layer normalisation (include/hnh_gat_norm.h)
+    def set_norm(self, layer: int, mode: str, eps: float = 1e-5):
+        """"none" (the default on every layer) or "layer": out = act(gamma * xh + beta) with xh = (z - mean(z)) / sqrt(var(z) + eps) over the
+        WHOLE row z = o + r + b (all heads side by side; the biased variance), the post-norm block of the transformer and LayerNorm-then-
+        activation of TransformerConv / UniMP.  gamma = 1 and beta = 0 until set_norm_weights; both are learned (norm_grad, optimizer_step,
+        train_step) and never decayed.  A normalised layer keeps one more matrix of the layer output's size between the passes.  Needs
+        attention "softmax" (every score, both backward modes, any dropout the score allows, bias and both residuals) on 15d_fusion2 with
+        c = 1 and heads * features_per_head <= 4096: forwardPass / backwardPass / train_step / evaluate raise HnhError elsewhere, before
+        anything is launched.  A change invalidates the stored forward pass."""
+        if mode not in self.NORM:
+            raise ValueError("norm must be one of %s, not %r" % (sorted(self.NORM), mode))
+        eps = float(eps)
+        if not (eps > 0.0 and np.isfinite(eps)):
+            raise ValueError("the norm's eps must be positive and finite, not %r" % (eps,))
+        _check(lib().hnh_gat_set_norm(self.h, self._layer(layer), self.NORM[mode], eps), "gat_set_norm")
+
+    def _norm_pair(self, layer, gamma, beta, what):
+        gamma = np.ascontiguousarray(gamma, dtype=np.float64)
+        beta = np.ascontiguousarray(beta, dtype=np.float64)
+        if gamma.shape != (self._width(layer),) or beta.shape != (self._width(layer),):
+            raise ValueError("%s of layer %d have %d entries each, not shapes %r and %r" % (what, layer, self._width(layer), gamma.shape, beta.shape))
+        return gamma, beta
+
+    def set_norm_weights(self, layer: int, gamma, beta):
+        """gamma and beta of the layer's norm (heads * features_per_head entries each).  Invalidates the stored forward pass like set_weight."""
+        layer = self._layer(layer)
+        gamma, beta = self._norm_pair(layer, gamma, beta, "gamma and beta")
+        _check(lib().hnh_gat_set_norm_weights(self.h, layer, gamma.ctypes.data, beta.ctypes.data, gamma.size), "gat_set_norm_weights")
+
+    def get_norm_weights(self, layer: int):
+        """(gamma, beta) of the layer's norm as they stand: (ones, zeros) until set or trained."""
+        layer = self._layer(layer)
+        gamma, beta = np.empty(self._width(layer)), np.empty(self._width(layer))
+        _check(lib().hnh_gat_get_norm_weights(self.h, layer, gamma.ctypes.data, beta.ctypes.data, gamma.size), "gat_get_norm_weights")
+        return gamma, beta
+
+    def norm_grad(self, layer: int):
+        """(dL/dgamma, dL/dbeta) of the layer after backwardPass with the layer normalised, summed over every rank."""
+        layer = self._layer(layer)
+        dgamma, dbeta = np.empty(self._width(layer)), np.empty(self._width(layer))
+        _check(lib().hnh_gat_get_norm_grad(self.h, layer, dgamma.ctypes.data, dbeta.ctypes.data, dgamma.size), "gat_get_norm_grad")
+        return dgamma, dbeta
 
     def set_attention_vectors(self, layer: int, head: int, a1: np.ndarray, a2: np.ndarray):
         """The additive score's vectors of (layer, head): features_per_head entries each, zero until set.  Score "gatv2" uses a1 as the

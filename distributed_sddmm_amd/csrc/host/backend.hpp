@@ -16,6 +16,7 @@
 #include "hnh_attn_edge.h"
 #include "hnh_attn_edge_grad.h"
 #include "hnh_gat_skip.h"
+#include "hnh_gat_norm.h"
 #include "hnh_grad.h"
 #include "hnh_kernels.h"
 #include "hnh_train.h"
@@ -81,6 +82,8 @@ struct Backend {
     // OPTIONAL group (include/hnh_gat_skip.h), bound the same way: only a GAT layer with a bias or a skip connection needs it
     // (its presence also says that the library knows the HNH_ATTN_ADDEND flag)
     HNH_FN(hnh_skip_addend_cols_f64) HNH_FN(hnh_skip_grad_cols_f64) HNH_FN(hnh_colsum_f64_workspace) HNH_FN(hnh_colsum_f64)
+    // OPTIONAL group (include/hnh_gat_norm.h), bound the same way: only a normalised GAT layer needs it
+    HNH_FN(hnh_layernorm_fwd_f64) HNH_FN(hnh_layernorm_bwd_workspace) HNH_FN(hnh_layernorm_bwd_f64)
 #ifdef HNH_MEASUREMENT_AIDS
     HNH_FN(hnh_stream_delay_us) HNH_FN(hnh_stream_paced_copy) HNH_FN(hnh_stream_pace_begin) HNH_FN(hnh_stream_pace_end)
 #endif

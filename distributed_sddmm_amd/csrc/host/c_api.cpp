@@ -856,6 +856,18 @@ int hnh_gat_get_bias_grad(hnh_gat* g, int layer, double* host) {
         gat.bias_grads[(size_t)layer].copy_to_host(host);
     });
 }
+int hnh_gat_set_norm(hnh_gat* g, int layer, int mode, double eps) {
+    return guarded(g->w, [&] { g->g->set_norm(layer, mode, eps); });
+}
+int hnh_gat_set_norm_weights(hnh_gat* g, int layer, const double* gamma_host, const double* beta_host, int64_t n) {
+    return guarded(g->w, [&] { g->g->set_norm_weights(layer, gamma_host, beta_host, n); });
+}
+int hnh_gat_get_norm_weights(hnh_gat* g, int layer, double* gamma_host, double* beta_host, int64_t n) {
+    return guarded(g->w, [&] { g->g->get_norm_weights(layer, gamma_host, beta_host, n); });
+}
+int hnh_gat_get_norm_grad(hnh_gat* g, int layer, double* dgamma_host, double* dbeta_host, int64_t n) {
+    return guarded(g->w, [&] { g->g->get_norm_grad(layer, dgamma_host, dbeta_host, n); });
+}
 int hnh_gat_set_attn_vectors(hnh_gat* g, int layer, int head, const double* a1_host, const double* a2_host) {
     return guarded(g->w, [&] {
         if (layer < 0 || layer >= (int)g->g->layers.size()) throw hnh::Error("Error, GAT layer index out of range!");

@@ -125,6 +125,26 @@
 // mask.  Neither a pre-activation nor an addend is kept between the passes.  Supported with attention softmax (every score, both backward
 // modes, any dropout the score allows, any activation) on 15d_fusion2 with c = 1; everything else raises before anything is launched
 // (check_skip_supported).  optimizer_step appends every enabled bias and W_res to its table; weight decay applies to them as to W.
+//
+// Layer normalisation (an addition; include/hnh_gat_norm.h; set_norm(layer, mode, eps), set_norm_weights(layer, gamma, beta), off on every
+// layer by default, which launches exactly the kernels above).  out = phi_l(gamma o xh + beta) with xh the WHOLE row z = o + r + b (all heads
+// side by side, C = H f columns) normalised: mu = mean_c z, var = mean_c (z - mu)^2 (biased, two-pass), xh = (z - mu) / sqrt(var + eps); gamma = 1
+// and beta = 0 until set, both learned.  Forward: a normalised layer l keeps pre_[l] (rows x H f: ONE MORE MATRIX OF THE LAYER OUTPUT'S SIZE, the
+// feature's memory cost) and norm_stats_[l] (rows x 2: mu, 1 / sigma).  The heads' addend (head_addend) and the finishing launch of every
+// score's forward pass target pre_[l] with the identity activation flag where they target buffers[l + 1] otherwise (head_target / head_act), and
+// after the layer's last head one hnh_layernorm_fwd_f64 on the compute stream writes buffers[l + 1], which everything downstream reads as
+// before (the next layer, the loss, evaluate, the coefficient export, copies to the host).  Order: the argument of the addend above carries
+// over to pre_[l] word for word: ev_gemm of the head's stage orders the addend before the finish; the two streams write disjoint column blocks;
+// and every earlier reader of pre_[l] (the previous pass's normalisation and backward pass) runs on the compute stream before the layer's
+// ev_input mark, which the auxiliary stream awaits before its first write; pre_[l] is allocated before that mark, like the product buffers.
+// Backward: backward_layer(i, G) first runs hnh_layernorm_bwd_f64 from G, pre_[i] and the stats into a scratch G' (dz of the formulas in the
+// header; y is recomputed), sums norm_grads_[i] = [dgamma; dbeta] over the world as db is summed, and then runs the layer code above with G' in
+// G's place, pre_[i] in the stored output's place and the identity in the activation's place: head_dz / hnh_skip_grad_cols_f64 /
+// hnh_act_grad_cols_f64 do for it what they do for an identity layer, and nothing in the scores' backward passes changes.  Supported where the
+// activations are (attention softmax, every score, both backward modes, any dropout the score allows, bias and both residuals) on 15d_fusion2
+// with c = 1 and rows of at most HNH_NORM_MAX_COLS values; everything else raises before anything is launched, naming the layer
+// (check_norm_supported).  optimizer_step appends gamma and beta of every normalised layer behind the layer's other entries; like the edge
+// bias they are NEVER decayed (decay would pull gamma to 0).  dgamma and dbeta are identical on every rank, so the two stay equal bit for bit.
 #pragma once
 #include "dense_shift_15d.hpp"
 #include "distributed_sparse.hpp"
@@ -162,6 +182,10 @@ public:
         layers = l_input;
         act_.assign(layers.size(), HNH_GAT_ACT_RELU);
         res_mode_.assign(layers.size(), HNH_GAT_RESIDUAL_NONE);
+        norm_.assign(layers.size(), HNH_GAT_NORM_NONE);
+        norm_eps_.assign(layers.size(), 1e-5);
+        for (auto* v : {&norm_gain_, &norm_shift_, &norm_grads_, &pre_, &norm_stats_}) v->assign(layers.size(), DenseMatrix());
+        norm_grads_held_.assign(layers.size(), 0);
         bias_on_.assign(layers.size(), 0);
         bias_.assign(layers.size(), DenseMatrix());
         edge_bias_on_.assign(layers.size(), 0);
@@ -307,6 +331,57 @@ public:
         if (host == nullptr) throw hnh::Error("Error, GAT get_bias: null pointer!");
         if (!bias_on_[(size_t)i]) throw hnh::Error("Error, GAT layer " + std::to_string(i) + " has no bias: set_bias first!");
         bias_[(size_t)i].copy_to_host(host);
+    }
+
+    // Layer normalisation of layer i (include/hnh_gat_norm.h): HNH_GAT_NORM_NONE | HNH_GAT_NORM_LAYER with its eps (> 0, finite; kept while
+    // the norm is off).  gamma = 1 and beta = 0 until set_norm_weights.  A change invalidates the stored forward pass; a refused call leaves
+    // the object as it was.  Kept here, not in GATLayer, for set_activation's reason.
+    int norm(int i) const {
+        check_layer(i);
+        return norm_[(size_t)i];
+    }
+    double norm_eps(int i) const {
+        check_layer(i);
+        return norm_eps_[(size_t)i];
+    }
+    void set_norm(int i, int mode, double eps) {
+        check_layer(i);
+        if (mode != HNH_GAT_NORM_NONE && mode != HNH_GAT_NORM_LAYER)
+            throw hnh::Error("Error, unknown GAT norm mode " + std::to_string(mode) + " (none = 0, layer = 1)!");
+        if (!(eps > 0.0) || !std::isfinite(eps))
+            throw hnh::Error("Error, GAT set_norm of layer " + std::to_string(i) + " needs a positive finite eps, not " + std::to_string(eps) + "!");
+        if (mode == HNH_GAT_NORM_LAYER) ensure_norm_weights(i);
+        if (mode != norm_[(size_t)i] || eps != norm_eps_[(size_t)i]) {
+            invalidate_forward();
+            norm_grads_held_[(size_t)i] = 0;
+        }
+        norm_[(size_t)i] = mode;
+        norm_eps_[(size_t)i] = eps;
+    }
+    // gamma and beta of layer i: `n` = num_heads * features_per_head HOST entries each
+    void set_norm_weights(int i, const double* gamma, const double* beta, int64_t n) {
+        check_norm_vectors(i, gamma, beta, n, "set_norm_weights");
+        ensure_norm_weights(i);
+        norm_gain_[(size_t)i].copy_from_host(gamma);
+        norm_shift_[(size_t)i].copy_from_host(beta);
+        invalidate_forward();
+    }
+    void get_norm_weights(int i, double* gamma, double* beta, int64_t n) {
+        check_norm_vectors(i, gamma, beta, n, "get_norm_weights");
+        ensure_norm_weights(i);
+        norm_gain_[(size_t)i].copy_to_host(gamma);
+        norm_shift_[(size_t)i].copy_to_host(beta);
+    }
+    // dL/dgamma and dL/dbeta of layer i from the last backwardPass (the same on every rank); refuses before one with the layer normalised
+    void get_norm_grad(int i, double* dgamma, double* dbeta, int64_t n) {
+        check_norm_vectors(i, dgamma, dbeta, n, "get_norm_grad");
+        const DenseMatrix& g = norm_grads_[(size_t)i];
+        if (norm_[(size_t)i] != HNH_GAT_NORM_LAYER || !norm_grads_held_[(size_t)i] || g.rows() != 2 || g.cols() != n)
+            throw hnh::Error("Error, no GAT norm gradient of layer " + std::to_string(i) + " yet: call backwardPass with set_norm(layer, layer) first!");
+        hnh::World* w = d_ops->world;
+        w->copy(dgamma, g.data(), sizeof(double) * (size_t)n, HNH_COPY_D2H, HNH_STREAM_COMPUTE);
+        w->copy(dbeta, g.data() + n, sizeof(double) * (size_t)n, HNH_COPY_D2H, HNH_STREAM_COMPUTE);
+        w->sync(HNH_STREAM_COMPUTE);
     }
 
     // The per-edge bias of layer i's logits (include/hnh_attn_edge.h; score TRANSFORMER only, checked by forwardPass): one finite value per
@@ -461,8 +536,11 @@ public:
         if (learns_vectors())
             for (size_t i = 0; i < layers.size(); i++) ensure_attn_vectors((int)i);  // (on the compute stream, before the marks below)
         if (std::getenv("HNH_GAT_SERIAL") != nullptr) {
-            for (size_t i = 0; i < layers.size(); i++)
+            for (size_t i = 0; i < layers.size(); i++) {
+                shape_pre((int)i);
                 for (int j = 0; j < layers[i].num_heads; j++) computeSelfAttentionHead((int)i, j);
+                norm_forward((int)i);
+            }
             return;
         }
         hnh::World* w = d_ops->world;
@@ -477,6 +555,7 @@ public:
                 if (additive) shape_scored((int)i, scored[b]);
             }
             shape_residual((int)i);
+            shape_pre((int)i);  // (a normalised layer's pre-normalisation rows: allocated before the mark below, for the same reason)
             drop_input((int)i);  // (Xd: allocated and made on the compute stream, before the mark below)
             // the layer's input is complete, and both product buffers are free, once the compute stream gets here
             w->event_record(ev_input, HNH_STREAM_COMPUTE);
@@ -498,6 +577,7 @@ public:
                 head_attention((int)i, j, additive ? scored[j % 2] : product[j % 2]);
                 w->event_record(ev_head[j % 2], HNH_STREAM_COMPUTE);
             }
+            norm_forward((int)i);  // (a normalised layer: pre_[i] -> buffers[i + 1] behind the last head, on the compute stream)
         }
         // every product was awaited by the compute stream: nothing is left on the auxiliary stream
         forward_valid_ = true;
@@ -674,12 +754,14 @@ public:
         const std::vector<Learned> learned = learned_parameters();
         for (const Learned& t : learned)
             if (t.g == nullptr) throw hnh::Error(t.refusal);
-        // the learned edge biases (PARAM_EDGE_BIAS_S / _ST) in a table and a call of their own: they are never decayed
+        // the learned edge biases (PARAM_EDGE_BIAS_S / _ST) and the norms' gamma and beta (PARAM_NORM_GAIN / _SHIFT) in a table and a call of
+        // their own: they are never decayed
         std::vector<hnh_optim_tensor> table, undecayed;
         for (const Learned& t : learned) {
             if (t.rows == 0) continue;  // (a rank without nonzeros holds none of a layer's bias)
             const Moments& m = ensure_moments(t);
-            const bool edge = std::get<0>(t.key) == PARAM_EDGE_BIAS_S || std::get<0>(t.key) == PARAM_EDGE_BIAS_ST;
+            const int kind = std::get<0>(t.key);
+            const bool edge = kind == PARAM_EDGE_BIAS_S || kind == PARAM_EDGE_BIAS_ST || kind == PARAM_NORM_GAIN || kind == PARAM_NORM_SHIFT;
             (edge ? undecayed : table).push_back({t.p, t.ld_p, t.g, t.ld_g, m.first.data(), m.second.data(), t.rows, t.cols});
         }
         optim_steps_++;
@@ -784,6 +866,13 @@ private:
     std::vector<DenseMatrix> bias_;
     std::vector<std::vector<DenseMatrix>> w_res_;
     DenseMatrix res_product_;
+    // layer normalisation (include/hnh_gat_norm.h): per layer the mode and eps, gamma and beta (H f x 1 each, allocated when the layer is
+    // first normalised or its weights are set), [dgamma; dbeta] (2 x H f) with whether a backward pass has filled it since the layer's norm
+    // last changed, and of the stored forward pass the pre-normalisation rows z (rows x H f) and the rows' (mu, 1 / sigma) (rows x 2)
+    std::vector<int> norm_;
+    std::vector<double> norm_eps_;
+    std::vector<DenseMatrix> norm_gain_, norm_shift_, norm_grads_, pre_, norm_stats_;
+    std::vector<char> norm_grads_held_;
     // the per-edge bias (include/hnh_attn_edge.h) of every layer: [0] in S's order, [1] in S^T's, with its enabled bit (kept here, not in
     // GATLayer, for act_'s reason)
     std::vector<char> edge_bias_on_;
@@ -823,7 +912,8 @@ private:
     hnh_optim optim_ = {};
     int64_t optim_steps_ = 0;
     // Every learned tensor of the model is one row of optimizer_step's table (learned_parameters()); its moments live under its key.
-    enum ParamKind { PARAM_W, PARAM_A1, PARAM_A2, PARAM_BIAS, PARAM_W_RES, PARAM_W_Q, PARAM_W_K, PARAM_EDGE_BIAS_S, PARAM_EDGE_BIAS_ST };
+    enum ParamKind { PARAM_W, PARAM_A1, PARAM_A2, PARAM_BIAS, PARAM_W_RES, PARAM_W_Q, PARAM_W_K, PARAM_EDGE_BIAS_S, PARAM_EDGE_BIAS_ST,
+                     PARAM_NORM_GAIN, PARAM_NORM_SHIFT };
     typedef std::tuple<int, int, int> ParamKey;            // (kind, layer, head; head 0 for a tensor of the whole layer)
     typedef std::pair<DenseMatrix, DenseMatrix> Moments;   // (first moment: Adam only, SGD keeps none; second moment, or SGD's momentum buffer)
     struct Learned {
@@ -839,7 +929,8 @@ private:
     // The table's rows in order: per layer W_0 .. W_{H-1}, then a1, then a2 (score ADDITIVE; GATV2 learns a1 alone); after all layers, per
     // layer the enabled bias, then W_res_0 .. W_res_{H-1} of a projection (include/hnh_gat_skip.h), then with score TRANSFORMER W_q_0 ..
     // W_q_{H-1} and W_k_0 .. W_k_{H-1}, then a learned edge bias in S's and in S^T's order (one nnz x 1 tensor each, behind every other
-    // entry of the layer).  Weight decay applies to all alike but the edge bias, which optimizer_step never decays.
+    // entry of the layer), then gamma and beta of a normalised layer (PARAM_NORM_GAIN / _SHIFT, H f x 1 each, behind every other entry of the
+    // layer).  Weight decay applies to all alike but the edge bias, gamma and beta, which optimizer_step never decays (undecayed()).
     std::vector<Learned> learned_parameters() {
         std::vector<Learned> all;
         const size_t n = layers.size();
@@ -876,20 +967,26 @@ private:
                 for (int h = 0; h < L.num_heads; h++)
                     add(PARAM_W_RES, i, h, w_res_[i][(size_t)h].data(), f, k, f, held(res_weight_grads, i, k, hf), (int64_t)h * f,
                         "Error, GAT optimizer_step needs the residual-weight gradient of a backwardPass since set_residual!");
-            if (score_ != HNH_GAT_SCORE_TRANSFORMER) continue;
-            ensure_qk_weights((int)i);
-            for (int which = 0; which < 2; which++)
-                for (int h = 0; h < L.num_heads; h++)
-                    add(which == 0 ? PARAM_W_Q : PARAM_W_K, i, h, w_qk_[which][i][(size_t)h].data(), f, k, f, held(qk_weight_grads[which], i, k, hf),
-                        (int64_t)h * f, "Error, GAT optimizer_step needs the query and key weight gradients of a backwardPass with score transformer!");
-            if (!edge_bias_learned_[i]) continue;
-            for (int which = 0; which < 2; which++) {
-                VectorXd& b = edge_bias_[which][i];
-                const VectorXd& g = dbias_[which][i];
-                const bool held = dbias_held_[i] && g.size() == b.size();
-                all.push_back({ParamKey(which == 0 ? PARAM_EDGE_BIAS_S : PARAM_EDGE_BIAS_ST, (int)i, 0), b.data(), 1, held ? g.data() : nullptr, 1,
-                               (int64_t)b.size(), 1, "Error, GAT optimizer_step needs the edge-bias gradient of a backwardPass since set_edge_bias_learned!"});
+            if (score_ == HNH_GAT_SCORE_TRANSFORMER) {
+                ensure_qk_weights((int)i);
+                for (int which = 0; which < 2; which++)
+                    for (int h = 0; h < L.num_heads; h++)
+                        add(which == 0 ? PARAM_W_Q : PARAM_W_K, i, h, w_qk_[which][i][(size_t)h].data(), f, k, f, held(qk_weight_grads[which], i, k, hf),
+                            (int64_t)h * f, "Error, GAT optimizer_step needs the query and key weight gradients of a backwardPass with score transformer!");
+                for (int which = 0; which < 2 && edge_bias_learned_[i]; which++) {
+                    VectorXd& b = edge_bias_[which][i];
+                    const VectorXd& g = dbias_[which][i];
+                    const bool held = dbias_held_[i] && g.size() == b.size();
+                    all.push_back({ParamKey(which == 0 ? PARAM_EDGE_BIAS_S : PARAM_EDGE_BIAS_ST, (int)i, 0), b.data(), 1, held ? g.data() : nullptr, 1,
+                                   (int64_t)b.size(), 1, "Error, GAT optimizer_step needs the edge-bias gradient of a backwardPass since set_edge_bias_learned!"});
+                }
             }
+            if (norm_[i] != HNH_GAT_NORM_LAYER) continue;
+            const DenseMatrix& g = norm_grads_[i];  // (2 x H f: dgamma, then dbeta)
+            const bool have = norm_grads_held_[i] && g.rows() == 2 && g.cols() == hf;
+            const char* refusal = "Error, GAT optimizer_step needs the norm gradient of a backwardPass since set_norm!";
+            all.push_back({ParamKey(PARAM_NORM_GAIN, (int)i, 0), norm_gain_[i].data(), 1, have ? g.data() : nullptr, 1, hf, 1, refusal});
+            all.push_back({ParamKey(PARAM_NORM_SHIFT, (int)i, 0), norm_shift_[i].data(), 1, have ? g.data() + hf : nullptr, 1, hf, 1, refusal});
         }
         return all;
     }
@@ -1053,7 +1150,7 @@ private:
     // workspace of every X^T D product of gemm_tn, and SC_PACKED, the packed P = [A | dZ | lse delta] of the fused and the gatv2 backward.
     enum ScratchRole { SC_DA_ALL, SC_WT, SC_A, SC_DZ, SC_DA_ROW, SC_T1, SC_T2, SC_TN_WORK, SC_DELTA, SC_PACKED, SC_ADD_M, SC_ADD_Q, SC_ADD_D, SC_ADD_DAGG,
                        SC_ADD_TN_WORK, SC_XENT_WORK, SC_V2_R, SC_V2_C, SC_V2_DAGG, SC_V2_WORK, SC_COEF_A, SC_COEF_S, SC_COEF_T, SC_RES_PRODUCT, SC_DZ_ALL,
-                       SC_COLSUM_WORK, SC_DX_RES, SC_QKV_Q, SC_QKV_K, SC_QKV_KV, SC_QKV_P, SC_QKV_DQ, SC_QKV_DK, SC_QKV_DX };
+                       SC_COLSUM_WORK, SC_DX_RES, SC_QKV_Q, SC_QKV_K, SC_QKV_KV, SC_QKV_P, SC_QKV_DQ, SC_QKV_DK, SC_QKV_DX, SC_NORM_G, SC_NORM_WORK };
     std::map<std::tuple<int, int64_t, int64_t>, DenseMatrix> scratch_;
 
     // m at rows x cols: allocated anew (on the compute stream) unless it has that shape already
@@ -1131,11 +1228,63 @@ private:
     }
 
     static const char* activation_name(int mode) { return mode == HNH_GAT_ACT_ELU ? "elu" : (mode == HNH_GAT_ACT_IDENTITY ? "identity" : "relu"); }
-    // the finishing call's flag of layer i's activation (include/hnh_attention.h); 0 for relu
+    // the finishing call's flag of layer i's activation (include/hnh_attention.h); 0 for relu; identity for a normalised layer, whose
+    // activation follows the normalisation
     unsigned activation_flag(int i) const {
-        const int m = act_[(size_t)i];
+        const int m = head_act(i);
         return m == HNH_GAT_ACT_ELU ? HNH_ATTN_ACT_ELU : (m == HNH_GAT_ACT_IDENTITY ? HNH_ATTN_ACT_IDENTITY : 0u);
     }
+    // ---- layer normalisation (include/hnh_gat_norm.h)
+    bool normed(int i) const { return norm_[(size_t)i] == HNH_GAT_NORM_LAYER; }
+    // where the heads of layer i write and what the backward pass reads as the layer's stored output: the pre-normalisation rows of a
+    // normalised layer, the layer's output buffer otherwise; and the activation those rows went through: none for a normalised layer
+    DenseMatrix& head_target(int i) { return normed(i) ? pre_[(size_t)i] : buffers[(size_t)i + 1]; }
+    int head_act(int i) const { return normed(i) ? HNH_GAT_ACT_IDENTITY : act_[(size_t)i]; }
+    void ensure_norm_weights(int i) {
+        const int64_t hf = (int64_t)layers[(size_t)i].num_heads * layers[(size_t)i].features_per_head;
+        if (norm_gain_[(size_t)i].rows() != hf) norm_gain_[(size_t)i] = DenseMatrix::Constant(hf, 1, 1.0);
+        if (norm_shift_[(size_t)i].rows() != hf) norm_shift_[(size_t)i] = DenseMatrix::Constant(hf, 1, 0.0);
+    }
+    void check_norm_vectors(int i, const double* a, const double* b, int64_t n, const char* who) const {
+        check_layer(i);
+        if (a == nullptr || b == nullptr) throw hnh::Error(std::string("Error, GAT ") + who + ": null pointer!");
+        const int64_t hf = (int64_t)layers[(size_t)i].num_heads * layers[(size_t)i].features_per_head;
+        if (n != hf)
+            throw hnh::Error(std::string("Error, GAT ") + who + " of layer " + std::to_string(i) + " needs gamma and beta of num_heads * features_per_head = " +
+                             std::to_string(hf) + " entries each, not " + std::to_string(n) + "!");
+    }
+    // pre_[i] and the stats of a normalised layer, on the compute stream (before the layer's ev_input mark)
+    void shape_pre(int i) {
+        if (!normed(i)) return;
+        const DenseMatrix& out = buffers[(size_t)i + 1];
+        shaped(pre_[(size_t)i], out.rows(), out.cols());
+        shaped(norm_stats_[(size_t)i], out.rows(), 2);
+    }
+    // buffers[i + 1] = phi_i(gamma o xh + beta) from pre_[i], on the compute stream behind the layer's last head; nothing for a layer without
+    void norm_forward(int i) {
+        if (!normed(i)) return;
+        DenseMatrix &out = buffers[(size_t)i + 1], &z = pre_[(size_t)i];
+        HNH_GAT_CALL(hnh_layernorm_fwd_f64, out.data(), out.cols(), z.data(), z.cols(), norm_stats_[(size_t)i].data(), norm_gain_[(size_t)i].data(),
+                     norm_shift_[(size_t)i].data(), z.rows(), z.cols(), norm_eps_[(size_t)i], kernel_activation(act_[(size_t)i]), HNH_STREAM_COMPUTE);
+    }
+    // G' = dL/d(pre_[i]) from G = dL/d(buffers[i + 1]) into its scratch, and norm_grads_[i] = [dgamma; dbeta] summed over the world
+    const DenseMatrix& norm_backward(int i, const DenseMatrix& G) {
+        const int S0 = HNH_STREAM_COMPUTE;
+        const DenseMatrix& z = pre_[(size_t)i];
+        const int64_t rows = z.rows(), hf = z.cols();
+        if (G.rows() != rows || G.cols() != hf || norm_stats_[(size_t)i].rows() != rows)
+            throw hnh::Error("Error, GAT backwardPass: the normalised layer's stored rows do not have the layer's shape!");
+        DenseMatrix& Gp = scratch(SC_NORM_G, rows, hf);
+        DenseMatrix& dgb = shaped(norm_grads_[(size_t)i], 2, hf);
+        const int64_t need = d_ops->world->be->hnh_layernorm_bwd_workspace(rows, hf);
+        double* work = need > 0 ? scratch(SC_NORM_WORK, need, 1).data() : nullptr;
+        HNH_GAT_CALL(hnh_layernorm_bwd_f64, Gp.data(), hf, dgb.data(), dgb.data() + hf, G.data(), hf, z.data(), hf, norm_stats_[(size_t)i].data(),
+                     norm_gain_[(size_t)i].data(), norm_shift_[(size_t)i].data(), rows, hf, kernel_activation(act_[(size_t)i]), work, need, S0);
+        sum_over_world(dgb);
+        norm_grads_held_[(size_t)i] = 1;
+        return Gp;
+    }
+
     // ---- bias and skip connections (include/hnh_gat_skip.h)
     bool has_addend(int i) const { return bias_on_[(size_t)i] != 0 || res_mode_[(size_t)i] != HNH_GAT_RESIDUAL_NONE; }
     // the finishing call's HNH_ATTN_ADDEND of a layer whose heads have an addend; 0 without: today's launches
@@ -1203,10 +1352,11 @@ private:
     const double* head_bias(int i, int h) const {
         return bias_on_[(size_t)i] ? bias_[(size_t)i].data() + (int64_t)h * layers[(size_t)i].features_per_head : nullptr;
     }
-    // the addend r + b of (layer i, head j) into the head's column block of buffers[i + 1], on `stream`; nothing for a layer without
+    // the addend r + b of (layer i, head j) into the head's column block of buffers[i + 1] (pre_[i] of a normalised layer), on `stream`;
+    // nothing for a layer without
     void head_addend(int i, int j, int stream) {
         if (!has_addend(i)) return;
-        DenseMatrix& out = buffers[(size_t)i + 1];
+        DenseMatrix& out = head_target(i);
         const int64_t f = layers[(size_t)i].features_per_head;
         const Operand res = residual_operand(i, j, stream, res_product_);
         HNH_GAT_CALL(hnh_skip_addend_cols_f64, out.data(), out.cols(), (int64_t)j * f, res.data, res.ld, head_bias(i, j), out.rows(), f, stream);
@@ -1257,6 +1407,23 @@ private:
             const std::string what = std::string("activation ") + activation_name(act_[i]) + " of layer " + std::to_string(i);
             require_softmax(what, ": its passes end in a ReLU", "include/hnh_attention.h");
             require_own_rows(what);
+            require_kernels(what, "include/hnh_grad.h", {HNH_GAT_KERNEL(hnh_act_grad_cols_f64)});
+        }
+    }
+    // A normalised layer: its heads end in the identity flag of the softmax passes' finishing launch and its backward pass in
+    // hnh_act_grad_cols_f64's identity, so it is supported where the activations are; the row width; its kernel group.
+    void check_norm_supported() {
+        for (size_t i = 0; i < layers.size(); i++) {
+            if (!normed((int)i)) continue;
+            const std::string what = "norm layer of layer " + std::to_string(i);
+            require_softmax(what, ": its passes end in a ReLU", "include/hnh_gat_norm.h");
+            require_own_rows(what);
+            const int64_t hf = (int64_t)layers[i].num_heads * layers[i].features_per_head;
+            if (hf > HNH_NORM_MAX_COLS)
+                throw hnh::Error("Error, GAT " + what + " supports rows of at most " + std::to_string(HNH_NORM_MAX_COLS) + " values (num_heads * features_per_head), not " +
+                                 std::to_string(hf) + " (include/hnh_gat_norm.h)");
+            require_kernels(what, "include/hnh_gat_norm.h",
+                            {HNH_GAT_KERNEL(hnh_layernorm_fwd_f64), HNH_GAT_KERNEL(hnh_layernorm_bwd_workspace), HNH_GAT_KERNEL(hnh_layernorm_bwd_f64)});
             require_kernels(what, "include/hnh_grad.h", {HNH_GAT_KERNEL(hnh_act_grad_cols_f64)});
         }
     }
@@ -1356,7 +1523,7 @@ private:
         require_kernels("softmax attention", "include/hnh_attention.h", {HNH_GAT_KERNEL(hnh_attn_softmax_csr_p)});
     }
     // What an entry point refuses, in one order: the training state (labels, optimizer, training kernels, output width, whole rows), then
-    // dropout, the activations, bias and skip connections, the edge bias, then the backward pass's conditions or, for a forward pass, the score's own.  The
+    // dropout, the activations, the norms, bias and skip connections, the edge bias, then the backward pass's conditions or, for a forward pass, the score's own.  The
     // stored forward pass and the shapes of the arguments are the entry point's own checks, afterwards.
     enum Op { OP_FORWARD, OP_BACKWARD, OP_TRAIN_STEP, OP_EVALUATE, OP_LOSS };
     void check_supported(Op op) {
@@ -1364,6 +1531,7 @@ private:
         if (op == OP_LOSS) return;
         check_dropout_supported();
         check_activation_supported();
+        check_norm_supported();
         check_skip_supported();
         check_edge_bias_supported(op == OP_BACKWARD || op == OP_TRAIN_STEP);
         if (op == OP_BACKWARD || op == OP_TRAIN_STEP) check_backward_supported();
@@ -1382,9 +1550,9 @@ private:
     // included, and dZ also into the head's column block of dZ_all.
     void head_dz(int i, int h, const DenseMatrix& G, DenseMatrix& dZ, DenseMatrix* dZ_all) {
         const int S0 = HNH_STREAM_COMPUTE;
-        const DenseMatrix& out = buffers[(size_t)i + 1];
+        const DenseMatrix& out = head_target(i);  // (a normalised layer: G is dL/d(pre_[i]) and the activation is the identity)
         const int64_t rows = dZ.rows(), f = dZ.cols(), hf = out.cols(), at = (int64_t)h * f;
-        const int act = act_[(size_t)i];
+        const int act = head_act(i);
         if (dZ_all != nullptr) {
             const Operand res = residual_operand(i, h, S0, scratch_slot(SC_RES_PRODUCT, rows, f));
             shaped(act_delta_, rows, 1);
@@ -1398,10 +1566,12 @@ private:
         }
     }
     // one layer of the backward pass: G = dL/d(buffers[i + 1]) -> weight_grads[i], input_grads[i]
-    void backward_layer(int i, const DenseMatrix& G) {
+    void backward_layer(int i, const DenseMatrix& G_out) {
         const int S0 = HNH_STREAM_COMPUTE;
         DenseMatrix& X = layer_input(i);  // (Xd with feature dropout: the forward pass's products used it)
-        const DenseMatrix& out = buffers[(size_t)i + 1];
+        const DenseMatrix& out = head_target(i);
+        // a normalised layer: everything below differentiates the pre-normalisation rows, from G' = dL/d(pre_[i])
+        const DenseMatrix& G = normed(i) ? norm_backward(i, G_out) : G_out;
         const int H = layers[(size_t)i].num_heads, f = layers[(size_t)i].features_per_head;
         const int64_t rows = X.rows(), k = X.cols(), hf = (int64_t)H * f;
         if (out.rows() != rows || out.cols() != hf || G.rows() != rows || G.cols() != hf)
@@ -1478,12 +1648,12 @@ private:
     // non-ReLU layer or a layer with an addend it is what head_dz's launch for this head left in act_delta_ (a buffer of its own, which
     // nothing else writes)
     DenseMatrix& head_delta(int i, int h, const DenseMatrix& dZ) {
-        if (act_[(size_t)i] != HNH_GAT_ACT_RELU || has_addend(i)) {
+        if (head_act(i) != HNH_GAT_ACT_RELU || has_addend(i)) {
             if (act_delta_.rows() != dZ.rows() || act_delta_.cols() != 1)
                 throw hnh::Error("Error, GAT backwardPass: the activation's delta does not have the head's rows!");
             return act_delta_;
         }
-        const DenseMatrix& out = buffers[(size_t)i + 1];
+        const DenseMatrix& out = buffers[(size_t)i + 1];  // (a plain ReLU layer: never a normalised one)
         const int64_t f = dZ.cols();
         DenseMatrix& delta = scratch(SC_DELTA, dZ.rows(), 1);
         HNH_GAT_CALL(hnh_rowdot_cols_f64, delta.data(), dZ.data(), f, out.data(), out.cols(), (int64_t)h * f, dZ.rows(), f, HNH_STREAM_COMPUTE);
@@ -1808,7 +1978,7 @@ private:
         }
     };
     SoftmaxHead softmax_head(int i, int j, int64_t rows, int64_t carrier_cols) {
-        DenseMatrix& out = buffers[i + 1];
+        DenseMatrix& out = head_target(i);
         const int f = layers[i].features_per_head;
         double* lse = softmax_row_state(i, j, rows).data();
         return {DenseMatrix(rows, carrier_cols), lse, row_max_.data(), row_sum_.data(), out.data() + (int64_t)j * f, out.cols(), f, leaky_relu_alpha,

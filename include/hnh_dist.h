@@ -335,6 +335,26 @@ int hnh_gat_get_residual_weight_grad(hnh_gat* g, int layer, double* host);
 int hnh_gat_set_bias(hnh_gat* g, int layer, const double* host_or_null);
 int hnh_gat_get_bias(hnh_gat* g, int layer, double* host);
 int hnh_gat_get_bias_grad(hnh_gat* g, int layer, double* host);
+/* Layer normalisation of a layer (an addition; kernels: include/hnh_gat_norm.h, an optional group).  With mode LAYER the layer's output becomes
+ * out = act(gamma o xh + beta), xh = (z - mean(z)) / sqrt(var(z) + eps) over the WHOLE row z = o + r + b (all heads side by side, num_heads *
+ * features_per_head values; the variance is the biased one): the post-norm block of the transformer, LayerNorm then the activation as in
+ * TransformerConv / UniMP.  NONE is the default on every layer and launches what the layer launched before, bit for bit.  eps > 0 and finite
+ * (1e-5 is customary); gamma = 1 and beta = 0 until hnh_gat_set_norm_weights, whose arrays (and the getters') are HOST memory of n = num_heads *
+ * features_per_head doubles each; any other n fails.  Both are learned: after hnh_gat_backward, hnh_gat_get_norm_grad reads dL/dgamma and
+ * dL/dbeta (summed over all ranks like dW, the same on every rank; it fails before a backward pass with the layer normalised), and
+ * hnh_gat_optimizer_step / hnh_gat_train_step update them with the other parameters' step count and hyper-parameters but NEVER with weight
+ * decay, which would pull gamma to 0.  A normalised layer keeps one more matrix of the layer output's size (the pre-normalisation rows) and two
+ * doubles per row between the passes.  Supported where the activations are: attention SOFTMAX (every score, both backward modes, any dropout
+ * the score allows, bias and both residuals) on 15d_fusion2 with c = 1, rows of at most HNH_NORM_MAX_COLS values; hnh_gat_forward /
+ * hnh_gat_backward / hnh_gat_train_step / hnh_gat_evaluate fail elsewhere before anything is launched, naming the layer and the mode, the
+ * schedule, the width, or the missing symbol when the kernel library lacks the group.  Every setter invalidates the stored forward pass; a
+ * refused call leaves the object as it was. */
+#define HNH_GAT_NORM_NONE 0
+#define HNH_GAT_NORM_LAYER 1
+int hnh_gat_set_norm(hnh_gat* g, int layer, int mode, double eps);
+int hnh_gat_set_norm_weights(hnh_gat* g, int layer, const double* gamma_host, const double* beta_host, int64_t n);
+int hnh_gat_get_norm_weights(hnh_gat* g, int layer, double* gamma_host, double* beta_host, int64_t n);
+int hnh_gat_get_norm_grad(hnh_gat* g, int layer, double* dgamma_host, double* dbeta_host, int64_t n);
 int hnh_gat_set_attn_vectors(hnh_gat* g, int layer, int head, const double* a1_host, const double* a2_host);
 int hnh_gat_get_attn_grads(hnh_gat* g, int layer, int head, double* da1_host, double* da2_host);
 

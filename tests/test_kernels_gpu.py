@@ -3,6 +3,9 @@ CPU oracle (oracle/oracle.py: sddmm_local = sparse_kernels.cpp:44-55, spmm_local
 
 Tolerance (BASELINE.md / SURVEY §8d): fp64, only the summation order differs ->
     max|x - x_ref| <= 1e-11 * max|x_ref|.
+
+tests/test_row_instances_gpu.py checks SDDMM, SpMM and the fused pass once more at every kernel instance with integer data (bit equality
+instead of this tolerance) and guard zones round every device array.
 """
 import ctypes as C
 

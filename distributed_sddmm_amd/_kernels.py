@@ -233,6 +233,14 @@ XENT_MAX_WIDTH = 4096  # HNH_XENT_MAX_WIDTH
 OPTIM_ADAM, OPTIM_SGD, OPTIM_MAX_TENSORS = 0, 1, 32  # HNH_OPTIM_*
 
 
+# include/hnh_train_multilabel.h: the multi-label (sigmoid) head of the training step; a further OPTIONAL group bound only for the product
+# library
+MULTILABEL_SIGNATURES = {
+    "hnh_bce_rows_f64_workspace": (_i64, [_i64]),
+    "hnh_bce_rows_f64": (_i32, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _dbl, _vp, _i64, _vp, _vp, _i64, _i32]),
+}
+
+
 class OptimTensor(C.Structure):
     """struct hnh_optim_tensor"""
     _fields_ = [("p", _vp), ("ld_p", _i64), ("g", _vp), ("ld_g", _i64), ("m", _vp), ("v", _vp), ("rows", _i64), ("cols", _i64)]
@@ -406,7 +414,7 @@ def load(path: str | None = None) -> C.CDLL:
                 list(ATTN_ADD_SIGNATURES.items()) + list(ATTN_DROP_SIGNATURES.items()) + list(TRAIN_SIGNATURES.items()) + \
                 list(V2_SIGNATURES.items()) + list(ATTN_COEF_SIGNATURES.items()) + list(SKIP_SIGNATURES.items()) + \
                 list(QKV_SIGNATURES.items()) + list(EDGE_SIGNATURES.items()) + list(EDGE_GRAD_SIGNATURES.items()) + \
-                list(NORM_SIGNATURES.items()):
+                list(NORM_SIGNATURES.items()) + list(MULTILABEL_SIGNATURES.items()):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
     if path is None:

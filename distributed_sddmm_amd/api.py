@@ -161,6 +161,8 @@ SIGNATURES = {
     "hnh_gat_get_weight": (_i32, [_vp, _i32, _i32, _vp]),
     "hnh_gat_get_attn_vectors": (_i32, [_vp, _i32, _i32, _vp, _vp]),
     "hnh_gat_set_labels": (_i32, [_vp, _vp, _vp, _i64, _i32]),
+    "hnh_gat_set_multilabel_targets": (_i32, [_vp, _vp, _i64, _i32, _vp, _i64, _i32, _vp]),
+    "hnh_gat_multilabel_counts": (_i32, [_vp, _pdbl, _pdbl, _pdbl]),
     "hnh_gat_loss": (_i32, [_vp, _vp, _i64, _vp, _pdbl, _pdbl]),
     "hnh_gat_set_optimizer": (_i32, [_vp, _i32, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl]),
     "hnh_gat_optimizer_step": (_i32, [_vp]),
@@ -1188,10 +1190,47 @@ class GAT:
             raise ValueError("labels and train_mask differ in length: %d and %d" % (len(lab), n))
         _check(lib().hnh_gat_set_labels(self.h, lab.ctypes.data, None if m is None else m.ctypes.data, len(lab), self.HEADS[heads]), "gat_set_labels")
 
+    def set_multilabel_targets(self, targets, train_mask=None, heads: str = "mean", pos_weight=None):
+        """Multi-label targets: a bool or 0/1 host array of shape (M, classes) in the operator's global row numbering, where classes is
+        what `heads` gives ("mean": the last layer's features_per_head; "concat": num_heads * features_per_head); train_mask selects the
+        rows of the loss (None: every row); pos_weight holds one weight >= 0 per class for its positive term (None: 1), as in
+        BCEWithLogitsLoss(pos_weight=...).  Afterwards loss / train_step / evaluate use the sigmoid head (include/hnh_train_multilabel.h)
+        until the next set_labels: the most recent of the two calls decides.  Each rank keeps its rows' bits on the device; collective.
+        Any other target value, a class count that does not match, a mask that selects no row or a bad weight raises and leaves the
+        object as it was."""
+        if heads not in self.HEADS:
+            raise ValueError("heads must be one of %s, not %r" % (sorted(self.HEADS), heads))
+        t = np.asarray(targets)
+        if t.ndim != 2:
+            raise ValueError("targets is a two-dimensional array of shape (global rows, classes)")
+        bad = np.argwhere(~((t == 0) | (t == 1)))  # (before the cast to bytes, which would fold 256 onto 0; the host layer checks the bytes again)
+        if len(bad):
+            raise ValueError("target %r of row %d, class %d is neither 0 nor 1" % (t[tuple(bad[0])].item(), bad[0][0], bad[0][1]))
+        t = np.ascontiguousarray(t, dtype=np.uint8)
+        m, n = self._mask(train_mask)
+        if m is not None and n != t.shape[0]:
+            raise ValueError("targets and train_mask differ in length: %d and %d" % (t.shape[0], n))
+        pw = None
+        if pos_weight is not None:
+            pw = np.ascontiguousarray(pos_weight, dtype=np.float64)
+            if pw.shape != (t.shape[1],):
+                raise ValueError("pos_weight needs one entry per class: shape (%d,), not %r" % (t.shape[1], pw.shape))
+        _check(lib().hnh_gat_set_multilabel_targets(self.h, t.ctypes.data, t.size, t.shape[1], None if m is None else m.ctypes.data, n, self.HEADS[heads],
+                                                    None if pw is None else pw.ctypes.data), "gat_set_multilabel_targets")
+
+    def multilabel_counts(self):
+        """(tp, fp, fn) of the last loss / evaluate / train_step under the sigmoid head: exact counts of (row, class) pairs over the whole
+        world, the prediction being logit > 0."""
+        tp, fp, fn = C.c_double(), C.c_double(), C.c_double()
+        _check(lib().hnh_gat_multilabel_counts(self.h, C.byref(tp), C.byref(fp), C.byref(fn)), "gat_multilabel_counts")
+        return int(tp.value), int(fp.value), int(fn.value)
+
     def loss(self, mask=None, grad_out: Dense | None = None):
-        """(loss, accuracy) of the stored forward pass over the labelled rows of `mask` (None: the training rows): the mean softmax
-        cross-entropy and the share of rows whose argmax is the label, over the whole world.  grad_out receives dL/d(output), which
-        backwardPass takes."""
+        """The pair of the stored forward pass over the rows of `mask` (None: the training rows), over the whole world.  After set_labels:
+        (loss, accuracy), the mean softmax cross-entropy over the labelled rows and the share of them whose argmax is the label.  After
+        set_multilabel_targets: (loss, micro-F1), the mean weighted sigmoid cross-entropy over selected rows x classes and 2 tp / (2 tp +
+        fp + fn) of the prediction logit > 0 (0.0 when the denominator is 0; multilabel_counts() has the counts).  grad_out receives
+        dL/d(output), which backwardPass takes."""
         m, n = self._mask(mask)
         lo, acc = C.c_double(), C.c_double()
         _check(lib().hnh_gat_loss(self.h, None if m is None else m.ctypes.data, n, grad_out.h if grad_out is not None else None, C.byref(lo), C.byref(acc)),
@@ -1213,16 +1252,18 @@ class GAT:
         _check(lib().hnh_gat_optimizer_step(self.h), "gat_optimizer_step")
 
     def train_step(self):
-        """Forward pass, loss over the training rows, backward pass and optimizer step on the device; returns (loss, accuracy) of the
-        parameters before the update, the call's only host synchronisation.  With a nonzero dropout rate the seed advances by one
-        first: step t of a run uses the masks of seed + t."""
+        """Forward pass, loss over the training rows, backward pass and optimizer step on the device; returns the pair of the parameters
+        before the update, the call's only host synchronisation: (loss, accuracy) after set_labels, (loss, micro-F1) after
+        set_multilabel_targets, as loss() defines them.  With a nonzero dropout rate the seed advances by one first: step t of a run
+        uses the masks of seed + t."""
         lo, acc = C.c_double(), C.c_double()
         _check(lib().hnh_gat_train_step(self.h, C.byref(lo), C.byref(acc)), "gat_train_step")
         return lo.value, acc.value
 
     def evaluate(self, mask=None):
-        """(loss, accuracy) over the labelled rows of `mask` from a forward pass without dropout and without a gradient; rates and seed
-        are as before afterwards."""
+        """The pair over the rows of `mask` (None: the training rows) from a forward pass without dropout and without a gradient:
+        (loss, accuracy) over the labelled rows after set_labels, (loss, micro-F1) over the selected rows x classes after
+        set_multilabel_targets, as loss() defines them; rates and seed are as before afterwards."""
         m, n = self._mask(mask)
         lo, acc = C.c_double(), C.c_double()
         _check(lib().hnh_gat_evaluate(self.h, None if m is None else m.ctypes.data, n, C.byref(lo), C.byref(acc)), "gat_evaluate")

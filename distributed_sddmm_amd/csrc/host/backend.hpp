@@ -20,6 +20,7 @@
 #include "hnh_grad.h"
 #include "hnh_kernels.h"
 #include "hnh_train.h"
+#include "hnh_train_multilabel.h"
 #ifdef HNH_MEASUREMENT_AIDS
 #include "hnh_measurement_aids.h"
 #endif
@@ -84,6 +85,8 @@ struct Backend {
     HNH_FN(hnh_skip_addend_cols_f64) HNH_FN(hnh_skip_grad_cols_f64) HNH_FN(hnh_colsum_f64_workspace) HNH_FN(hnh_colsum_f64)
     // OPTIONAL group (include/hnh_gat_norm.h), bound the same way: only a normalised GAT layer needs it
     HNH_FN(hnh_layernorm_fwd_f64) HNH_FN(hnh_layernorm_bwd_workspace) HNH_FN(hnh_layernorm_bwd_f64)
+    // OPTIONAL group (include/hnh_train_multilabel.h), bound the same way: only the GAT's multi-label (sigmoid) head needs it
+    HNH_FN(hnh_bce_rows_f64_workspace) HNH_FN(hnh_bce_rows_f64)
 #ifdef HNH_MEASUREMENT_AIDS
     HNH_FN(hnh_stream_delay_us) HNH_FN(hnh_stream_paced_copy) HNH_FN(hnh_stream_pace_begin) HNH_FN(hnh_stream_pace_end)
 #endif

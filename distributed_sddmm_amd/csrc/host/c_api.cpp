@@ -926,6 +926,16 @@ int hnh_gat_get_attn_vectors(hnh_gat* g, int layer, int head, double* a1_host, d
 int hnh_gat_set_labels(hnh_gat* g, const int32_t* labels, const uint8_t* mask_or_null, int64_t n, int heads_mode) {
     return guarded(g->w, [&] { g->g->set_labels(labels, mask_or_null, n, heads_mode); });
 }
+int hnh_gat_set_multilabel_targets(hnh_gat* g, const uint8_t* targets, int64_t n, int classes, const uint8_t* mask_or_null, int64_t mask_n,
+                                   int heads_mode, const double* pos_weight_or_null) {
+    return guarded(g->w, [&] { g->g->set_multilabel_targets(targets, n, classes, mask_or_null, mask_n, heads_mode, pos_weight_or_null); });
+}
+int hnh_gat_multilabel_counts(hnh_gat* g, double* tp, double* fp, double* fn) {
+    return guarded(g->w, [&] {
+        if (!tp || !fp || !fn) throw hnh::Error("Error, hnh_gat_multilabel_counts: null pointer!");
+        g->g->multilabel_counts(tp, fp, fn);
+    });
+}
 int hnh_gat_loss(hnh_gat* g, const uint8_t* mask_or_null, int64_t n, hnh_dense* grad_out_or_null, double* loss, double* accuracy) {
     return guarded(g->w, [&] {
         const std::pair<double, double> r = g->g->loss(mask_or_null, n, grad_out_or_null ? &grad_out_or_null->m : nullptr);

@@ -97,6 +97,13 @@
 // without a broadcast.  train_step() = [seed + 1 when a dropout rate is nonzero] forwardPass, loss into an internal G, backwardPass,
 // optimizer_step, all on the compute stream; the host waits once, for the two scalars (of the parameters BEFORE the update).
 //
+// The multi-label head (an addition; include/hnh_train_multilabel.h).  set_multilabel_targets keeps this rank's rows of the M x classes
+// 0/1 targets bit-packed on the device with its rows of the mask and the class weights, and sums the selected row count over the world once.
+// Until the next set_labels, loss / train_step / evaluate then run ONE pass of hnh_bce_rows_f64 in place of hnh_xent_rows_f64: the weighted
+// sigmoid cross-entropy of z (heads as above), mean over selected rows x classes, with tp / fp / fn of the prediction z > 0 and G from the
+// same read; the four sums are all-reduced, the pair's second value is micro-F1 = 2 tp / (2 tp + fp + fn), and multilabel_counts() hands out
+// the counts.  No row is staged, so HNH_XENT_MAX_WIDTH does not apply.  A model that never calls it launches what it launched before.
+//
 // Output activation (an addition; set_activation(layer, mode), HNH_GAT_ACT_RELU on every layer by default, which launches exactly the kernels
 // above).  out[:, h f ..] = phi_l(o) with phi in {relu, elu, identity} leaves the finishing launch of the softmax and additive forward passes
 // (the HNH_ATTN_ACT_* flags of include/hnh_attention.h).  The backward pass keeps no pre-activation: for a non-ReLU layer ONE pass
@@ -706,6 +713,71 @@ public:
         }
         train_mask_.swap(keep_mask);
         labels_set_ = true;
+        multilabel_ = false;  // the most recent of set_labels / set_multilabel_targets decides the head
+    }
+
+    // ---- the multi-label head (include/hnh_train_multilabel.h)
+    // Targets as a HOST array of d_ops->M x classes values in {0, 1} (row-major, the operator's global row numbering), a training mask of
+    // mask_n = d_ops->M bytes (nullptr: every row) and `classes` class weights (nullptr: every weight 1; the pos_weight of the weighted
+    // sigmoid cross-entropy).  classes must be what heads_mode gives: the last layer's features_per_head (MEAN) or num_heads *
+    // features_per_head (CONCAT).  Afterwards loss / train_step / evaluate use the sigmoid head: the loss is the mean over selected rows x
+    // classes, the pair's second value micro-F1.  Each rank packs its own rows' bits and keeps them with its rows of the mask on the device.
+    // Collective: the selected row count is summed over the world.  Every refusal comes before anything is launched and leaves the object
+    // as it was.
+    void set_multilabel_targets(const uint8_t* targets, int64_t n, int classes, const uint8_t* mask, int64_t mask_n, int heads_mode,
+                                const double* pos_weight) {
+        if (heads_mode != HNH_GAT_HEADS_MEAN && heads_mode != HNH_GAT_HEADS_CONCAT)
+            throw hnh::Error("Error, unknown GAT label heads mode " + std::to_string(heads_mode) + " (mean = 0, concat = 1)!");
+        if (targets == nullptr) throw hnh::Error("Error, GAT set_multilabel_targets: null targets!");
+        const int want = classes_of(heads_mode);
+        if (classes != want)
+            throw hnh::Error("Error, GAT set_multilabel_targets: " + std::to_string(classes) + " classes, but heads mode " + std::to_string(heads_mode) +
+                             " of the last layer gives " + std::to_string(want) + "!");
+        const int64_t M = d_ops->M;
+        if (n != M * classes)
+            throw hnh::Error("Error, GAT set_multilabel_targets needs " + std::to_string(M) + " x " + std::to_string(classes) + " = " + std::to_string(M * classes) +
+                             " targets, not " + std::to_string(n) + "!");
+        if (mask != nullptr && mask_n != M)
+            throw hnh::Error("Error, GAT set_multilabel_targets: the mask needs " + std::to_string(M) + " entries, not " + std::to_string(mask_n) + "!");
+        check_whole_rows("set_multilabel_targets");
+        for (int64_t i = 0; i < n; i++)
+            if (targets[i] > 1)
+                throw hnh::Error("Error, GAT multi-label target " + std::to_string((int)targets[i]) + " of row " + std::to_string(i / classes) + ", class " +
+                                 std::to_string(i % classes) + " is neither 0 nor 1!");
+        for (int c = 0; pos_weight != nullptr && c < classes; c++)
+            if (!(pos_weight[c] >= 0.0) || !std::isfinite(pos_weight[c]))
+                throw hnh::Error("Error, GAT multi-label pos_weight " + std::to_string(pos_weight[c]) + " of class " + std::to_string(c) +
+                                 " is negative or not finite!");
+        // the new state in temporaries: a refusal of make_target_set leaves the object as it was
+        TargetSet set = make_target_set(mask);
+        hnh::World* w = d_ops->world;
+        const int64_t rows = buffers.back().rows(), top = d_ops->aSubmatrices[0].topRow, words = ((int64_t)classes + 31) / 32;
+        std::vector<uint32_t> bits((size_t)(rows * words), 0u);
+        for (int64_t r = 0; r < rows && top + r < M; r++)
+            for (int c = 0; c < classes; c++)
+                if (targets[(top + r) * classes + c]) bits[(size_t)(r * words + c / 32)] |= 1u << (c % 32);
+        hnh::DeviceArray dbits(w, (size_t)(rows * words) * sizeof(uint32_t));
+        if (rows > 0) w->copy(dbits.ptr(), bits.data(), (size_t)(rows * words) * sizeof(uint32_t), HNH_COPY_H2D, HNH_STREAM_COMPUTE);
+        DenseMatrix weights;
+        if (pos_weight != nullptr) {
+            weights = DenseMatrix(classes, 1);
+            w->copy(weights.data(), pos_weight, (size_t)classes * sizeof(double), HNH_COPY_H2D, HNH_STREAM_COMPUTE);
+        }
+        w->sync(HNH_STREAM_COMPUTE);  // (`bits` and the caller's weights have been read)
+        ml_bits_ = std::move(dbits);
+        ml_weights_ = std::move(weights);
+        ml_train_set_ = std::move(set);
+        ml_words_ = words;
+        ml_heads_ = heads_mode;
+        ml_counts_[0] = ml_counts_[1] = ml_counts_[2] = 0.0;
+        multilabel_ = true;
+    }
+    // (tp, fp, fn) of the last loss / evaluate / train_step under the sigmoid head, summed over the world: counts of (row, class) pairs
+    void multilabel_counts(double* tp, double* fp, double* fn) const {
+        if (!multilabel_) throw hnh::Error("Error, GAT multilabel_counts needs set_multilabel_targets first (and no set_labels since)!");
+        *tp = ml_counts_[0];
+        *fp = ml_counts_[1];
+        *fn = ml_counts_[2];
     }
 
     // (loss, accuracy) of the stored forward pass over the rows of `mask` (HOST, global numbering; nullptr: the training rows of set_labels);
@@ -717,6 +789,13 @@ public:
         const DenseMatrix& last = buffers.back();
         if (grad_out != nullptr && (grad_out->rows() != last.rows() || grad_out->cols() != last.cols()))
             throw hnh::Error("Error, GAT loss: the output gradient has the wrong shape!");
+        if (multilabel_) {  // (loss, micro-F1) of the sigmoid head
+            TargetSet other_rows;
+            if (mask != nullptr) other_rows = make_target_set(mask);
+            const TargetSet& ts = mask != nullptr ? other_rows : ml_train_set_;
+            bce_enqueue(ts, grad_out);
+            return bce_read(ts);
+        }
         LabelSet other;
         if (mask != nullptr) other = make_label_set(mask);
         const LabelSet& ls = mask != nullptr ? other : train_set_;
@@ -788,14 +867,15 @@ public:
             forwardPass();
             const DenseMatrix& last = buffers.back();
             if (train_grad_.rows() != last.rows() || train_grad_.cols() != last.cols()) train_grad_ = DenseMatrix(last.rows(), last.cols());
-            loss_enqueue(train_set_, &train_grad_);
+            if (multilabel_) bce_enqueue(ml_train_set_, &train_grad_);
+            else loss_enqueue(train_set_, &train_grad_);
             backwardPass(train_grad_);
             optimizer_step();
         } catch (...) {  // (a step that did not update leaves seed and step count as they were: step t keeps seed0 + t)
             if (optim_steps_ == steps0) seed_ = seed0;
             throw;
         }
-        return loss_read(train_set_);
+        return multilabel_ ? bce_read(ml_train_set_) : loss_read(train_set_);
     }
 
     // (loss, accuracy) over the rows of `mask` (nullptr: the training rows) from a forward pass without dropout and without a gradient.
@@ -804,15 +884,23 @@ public:
         check_supported(OP_EVALUATE);
         if (mask != nullptr && n != d_ops->M) throw hnh::Error("Error, GAT evaluate: the mask needs " + std::to_string(d_ops->M) + " entries, not " + std::to_string(n) + "!");
         LabelSet other;
-        if (mask != nullptr) other = make_label_set(mask);
+        TargetSet other_rows;
+        if (mask != nullptr && multilabel_) other_rows = make_target_set(mask);
+        else if (mask != nullptr) other = make_label_set(mask);
         const LabelSet& ls = mask != nullptr ? other : train_set_;
+        const TargetSet& ts = mask != nullptr ? other_rows : ml_train_set_;
         const double ap = attn_p_, fp = feat_p_;
         attn_p_ = feat_p_ = 0.0;
         std::pair<double, double> res;
         try {
             forwardPass();
-            loss_enqueue(ls, nullptr);
-            res = loss_read(ls);
+            if (multilabel_) {
+                bce_enqueue(ts, nullptr);
+                res = bce_read(ts);
+            } else {
+                loss_enqueue(ls, nullptr);
+                res = loss_read(ls);
+            }
         } catch (...) {
             attn_p_ = ap;
             feat_p_ = fp;
@@ -909,6 +997,20 @@ private:
     std::vector<uint8_t> train_mask_;
     LabelSet train_set_;
     DenseMatrix train_grad_, loss_result_;
+    // the multi-label head (include/hnh_train_multilabel.h): whether it is the head in use (the most recent of set_labels /
+    // set_multilabel_targets decides), this rank's rows of the bit-packed targets (ml_words_ words a row) and of a mask with the world's
+    // selected row count, the class weights (empty: none), the heads mode, and (tp, fp, fn) of the last loss
+    struct TargetSet {
+        hnh::DeviceArray mask;
+        double count = 0.0;
+    };
+    bool multilabel_ = false;
+    int ml_heads_ = HNH_GAT_HEADS_MEAN;
+    int64_t ml_words_ = 0;
+    hnh::DeviceArray ml_bits_;
+    DenseMatrix ml_weights_, ml_result_;
+    TargetSet ml_train_set_;
+    double ml_counts_[3] = {0.0, 0.0, 0.0};
     hnh_optim optim_ = {};
     int64_t optim_steps_ = 0;
     // Every learned tensor of the model is one row of optimizer_step's table (learned_parameters()); its moments live under its key.
@@ -1023,10 +1125,11 @@ private:
             for (int h = 0; h < L.num_heads; h++) w.push_back(DenseMatrix::Constant(L.wMats[(size_t)h].rows(), L.wMats[(size_t)h].cols(), 0.0));
         }
     }
-    int label_classes() const {
+    int classes_of(int heads_mode) const {
         const GATLayer& L = layers.back();
-        return label_heads_ == HNH_GAT_HEADS_MEAN ? L.features_per_head : L.num_heads * L.features_per_head;
+        return heads_mode == HNH_GAT_HEADS_MEAN ? L.features_per_head : L.num_heads * L.features_per_head;
     }
+    int label_classes() const { return classes_of(label_heads_); }
     // one dense block of whole rows per rank: the output's side, and with `input_too` the side of buffers[0], which is laid out like B
     bool whole_rows(bool input_too) const {
         return !d_ops->r_split && d_ops->aSubmatrices.size() == 1 && d_ops->aSubmatrices[0].leftCol == 0 &&
@@ -1069,8 +1172,14 @@ private:
     };
     // Refuses before anything is launched: labels (and the optimizer) not set, then the kernel group, then the row width.
     void check_train_supported(bool need_optimizer) {
-        if (!labels_set_) throw hnh::Error("Error, GAT loss / train_step / evaluate need set_labels first!");
+        if (!labels_set_ && !multilabel_) throw hnh::Error("Error, GAT loss / train_step / evaluate need set_labels first!");
         if (need_optimizer && !optimizer_set_) throw hnh::Error("Error, GAT train_step needs set_optimizer first!");
+        if (multilabel_) {  // the sigmoid head: its own kernel group, and no limit on the row width (no row is staged)
+            require_kernels("training", "include/hnh_train_multilabel.h", {HNH_GAT_KERNEL(hnh_bce_rows_f64_workspace), HNH_GAT_KERNEL(hnh_bce_rows_f64)});
+            if (need_optimizer) require_kernels("training", "include/hnh_train.h", {HNH_GAT_KERNEL(hnh_optim_step_f64)});
+            check_whole_rows("loss");
+            return;
+        }
         require_kernels("training", "include/hnh_train.h", {HNH_GAT_KERNEL(hnh_xent_rows_f64_workspace), HNH_GAT_KERNEL(hnh_xent_rows_f64)});
         if (need_optimizer) require_kernels("training", "include/hnh_train.h", {HNH_GAT_KERNEL(hnh_optim_step_f64)});
         const int64_t width = (int64_t)layers.back().num_heads * layers.back().features_per_head;
@@ -1139,6 +1248,62 @@ private:
             throw hnh::Error("Error, GAT loss is not a number: the device met a label outside its classes, or the output holds NaN!");
         return {r[0] / ls.count, r[1] / ls.count};
     }
+    // This rank's rows of `mask` (nullptr: every row) as bytes on the device, and the selected row count of the world.  Every rank sees
+    // the same host array, so a refusal is the same on all of them and happens before the collective.
+    TargetSet make_target_set(const uint8_t* mask) {
+        const int64_t M = d_ops->M;
+        int64_t global = M;
+        if (mask != nullptr) {
+            global = 0;
+            for (int64_t r = 0; r < M; r++) global += mask[r] ? 1 : 0;
+        }
+        if (global == 0) throw hnh::Error("Error, the GAT multi-label mask selects no row!");
+        hnh::World* w = d_ops->world;
+        const int64_t rows = buffers.back().rows(), top = d_ops->aSubmatrices[0].topRow;
+        std::vector<uint8_t> local((size_t)rows, 0);
+        double mine = 0.0;
+        for (int64_t r = 0; r < rows && top + r < M; r++) {
+            if (mask != nullptr && !mask[top + r]) continue;
+            local[(size_t)r] = 1;
+            mine += 1.0;
+        }
+        TargetSet ts;
+        ts.mask = hnh::DeviceArray(w, (size_t)rows);
+        if (rows > 0) w->copy(ts.mask.ptr(), local.data(), (size_t)rows, HNH_COPY_H2D, HNH_STREAM_COMPUTE);
+        DenseMatrix cnt(1, 1);
+        w->copy(cnt.data(), &mine, sizeof(double), HNH_COPY_H2D, HNH_STREAM_COMPUTE);
+        w->allreduce_f64(w->world_comm(), cnt.data(), 1, HNH_STREAM_COMPUTE);
+        w->copy(&ts.count, cnt.data(), sizeof(double), HNH_COPY_D2H, HNH_STREAM_COMPUTE);
+        w->sync(HNH_STREAM_COMPUTE);  // (also: `local` and `mine` have been read)
+        if (ts.count != (double)global)
+            throw hnh::Error("Error, GAT multi-label targets: the ranks' rows hold " + std::to_string((int64_t)ts.count) + " selected rows, the global mask " +
+                             std::to_string(global) + "!");
+        return ts;
+    }
+    // the sigmoid head's loss pass and the all-reduce of its four sums on the compute stream; G == nullptr: no gradient
+    void bce_enqueue(const TargetSet& ts, DenseMatrix* G) {
+        const DenseMatrix& out = buffers.back();
+        const int classes = classes_of(ml_heads_);
+        const int heads = ml_heads_ == HNH_GAT_HEADS_MEAN ? layers.back().num_heads : 1;
+        if (ml_result_.size() != 4) ml_result_ = DenseMatrix(4, 1);
+        const int64_t need = d_ops->world->be->hnh_bce_rows_f64_workspace(out.rows());
+        DenseMatrix& work = scratch(SC_BCE_WORK, need, 1);
+        HNH_GAT_CALL(hnh_bce_rows_f64, out.data(), out.cols(), (const uint32_t*)ml_bits_.ptr(), ml_words_, (const uint8_t*)ts.mask.ptr(),
+                     ml_weights_.size() ? ml_weights_.data() : nullptr, out.rows(), heads, classes, 1.0 / (ts.count * classes), G ? G->data() : nullptr,
+                     out.cols(), ml_result_.data(), work.data(), need, HNH_STREAM_COMPUTE);
+        sum_over_world(ml_result_);
+    }
+    // (mean loss over selected rows x classes, micro-F1 = 2 tp / (2 tp + fp + fn), 0 when nothing is predicted or present); keeps the counts
+    std::pair<double, double> bce_read(const TargetSet& ts) {
+        hnh::World* w = d_ops->world;
+        double r[4] = {0.0, 0.0, 0.0, 0.0};
+        w->copy(r, ml_result_.data(), sizeof(r), HNH_COPY_D2H, HNH_STREAM_COMPUTE);
+        w->sync(HNH_STREAM_COMPUTE);
+        if (std::isnan(r[0])) throw hnh::Error("Error, GAT loss is not a number: the output holds NaN!");
+        for (int k = 0; k < 3; k++) ml_counts_[k] = r[k + 1];
+        const double denom = 2.0 * r[1] + r[2] + r[3];
+        return {r[0] / (ts.count * classes_of(ml_heads_)), denom > 0.0 ? 2.0 * r[1] / denom : 0.0};
+    }
     DenseMatrix scored[2];  // score ADDITIVE: [A (0) | s t] of the head in flight and of the next one (include/hnh_attn_additive.h)
     // softmax attention: the rows' running max / sum (reused by every head, which run one after the other on the compute stream), the
     // log-sum-exp of every (layer, head), and for the backward pass a column of ones and the broadcasts of lse and delta onto the nonzeros
@@ -1150,7 +1315,7 @@ private:
     // workspace of every X^T D product of gemm_tn, and SC_PACKED, the packed P = [A | dZ | lse delta] of the fused and the gatv2 backward.
     enum ScratchRole { SC_DA_ALL, SC_WT, SC_A, SC_DZ, SC_DA_ROW, SC_T1, SC_T2, SC_TN_WORK, SC_DELTA, SC_PACKED, SC_ADD_M, SC_ADD_Q, SC_ADD_D, SC_ADD_DAGG,
                        SC_ADD_TN_WORK, SC_XENT_WORK, SC_V2_R, SC_V2_C, SC_V2_DAGG, SC_V2_WORK, SC_COEF_A, SC_COEF_S, SC_COEF_T, SC_RES_PRODUCT, SC_DZ_ALL,
-                       SC_COLSUM_WORK, SC_DX_RES, SC_QKV_Q, SC_QKV_K, SC_QKV_KV, SC_QKV_P, SC_QKV_DQ, SC_QKV_DK, SC_QKV_DX, SC_NORM_G, SC_NORM_WORK };
+                       SC_COLSUM_WORK, SC_DX_RES, SC_QKV_Q, SC_QKV_K, SC_QKV_KV, SC_QKV_P, SC_QKV_DQ, SC_QKV_DK, SC_QKV_DX, SC_NORM_G, SC_NORM_WORK, SC_BCE_WORK };
     std::map<std::tuple<int, int64_t, int64_t>, DenseMatrix> scratch_;
 
     // m at rows x cols: allocated anew (on the compute stream) unless it has that shape already

@@ -136,6 +136,7 @@ Backend* load_backend(const char* path_c) {
     HNH_BIND_OPTIONAL(hnh_skip_addend_cols_f64) HNH_BIND_OPTIONAL(hnh_skip_grad_cols_f64) HNH_BIND_OPTIONAL(hnh_colsum_f64_workspace)
     HNH_BIND_OPTIONAL(hnh_colsum_f64)
     HNH_BIND_OPTIONAL(hnh_layernorm_fwd_f64) HNH_BIND_OPTIONAL(hnh_layernorm_bwd_workspace) HNH_BIND_OPTIONAL(hnh_layernorm_bwd_f64)
+    HNH_BIND_OPTIONAL(hnh_bce_rows_f64_workspace) HNH_BIND_OPTIONAL(hnh_bce_rows_f64)
 #undef HNH_BIND_OPTIONAL
 #ifdef HNH_MEASUREMENT_AIDS
     HNH_BIND(hnh_stream_delay_us) HNH_BIND(hnh_stream_paced_copy) HNH_BIND(hnh_stream_pace_begin) HNH_BIND(hnh_stream_pace_end)

@@ -403,6 +403,23 @@ int hnh_gat_train_step(hnh_gat* g, double* loss, double* accuracy);
 /* Loss and accuracy over the mask's rows (NULL: the training rows) from a forward pass with both dropout rates 0 and no gradient.  Rates
  * and seed are restored; the stored forward pass stays invalid whenever a rate was nonzero. */
 int hnh_gat_evaluate(hnh_gat* g, const uint8_t* mask_or_null, int64_t n, double* loss, double* accuracy);
+/* The multi-label head (an addition; kernels: include/hnh_train_multilabel.h, an optional group — a kernel library without it makes
+ * hnh_gat_loss, hnh_gat_train_step and hnh_gat_evaluate fail under this head with an error naming the missing symbol).  targets: n = M x
+ * classes host bytes in {0, 1}, row-major, in the operator's global row numbering; classes must be what heads_mode gives (MEAN: the last
+ * layer's features_per_head; CONCAT: num_heads * features_per_head).  mask_or_null: mask_n = M bytes, a row whose byte is 0 is not in the
+ * loss (NULL: every row is).  pos_weight_or_null: `classes` doubles >= 0, the weight of a class's positive term (NULL: 1).  Afterwards
+ * hnh_gat_loss / hnh_gat_train_step / hnh_gat_evaluate use the sigmoid head until the next hnh_gat_set_labels (the most recent of the two
+ * calls decides): *loss = the mean over selected rows x classes of -w y log s(z) - (1 - y) log(1 - s(z)), z as under hnh_gat_set_labels,
+ * and *accuracy = micro-averaged F1 = 2 tp / (2 tp + fp + fn) of the prediction z > 0 (0.0 when the denominator is 0), both over the whole
+ * world; a mask given to hnh_gat_loss / hnh_gat_evaluate selects other rows of the same targets.  No limit on the row width applies.  Each
+ * rank keeps its rows' bits on the device; the selected row count is summed over the world once (collective).  Any other target value
+ * (named with its row and class), a wrong n or mask_n, a class count that does not match, a mask that selects no row or a weight that is
+ * negative or not finite fails before anything is launched and leaves the object as it was. */
+int hnh_gat_set_multilabel_targets(hnh_gat* g, const uint8_t* targets, int64_t n, int classes, const uint8_t* mask_or_null, int64_t mask_n,
+                                   int heads_mode, const double* pos_weight_or_null);
+/* (tp, fp, fn) of the last hnh_gat_loss / hnh_gat_evaluate / hnh_gat_train_step under the sigmoid head: counts of (row, class) pairs over
+ * the whole world, exact.  Fails when the sigmoid head is not the one in use. */
+int hnh_gat_multilabel_counts(hnh_gat* g, double* tp, double* fp, double* fn);
 
 #ifdef __cplusplus
 }

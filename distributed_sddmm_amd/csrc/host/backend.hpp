@@ -1,7 +1,8 @@
 // Function table over the C ABI of include/hnh_kernels.h.  The host layer never links the HIP library:
 // it dlopen()s it (default: libhnh_kernels.so next to this library) and fails loudly if that is not
 // possible.  There is NO built-in CPU implementation; the only other implementation of this ABI in the
-// repository is the test double under oracle/, which tests load explicitly by path.
+// repository is the test double under oracle/ (built twice: with and without four of the optional groups), which tests load
+// explicitly by path.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -52,7 +53,8 @@ struct Backend {
     HNH_FN(hnh_ipc_export) HNH_FN(hnh_ipc_open) HNH_FN(hnh_ipc_close) HNH_FN(hnh_ipc_pull) HNH_FN(hnh_ipc_flags_register) HNH_FN(hnh_ipc_flags_unregister)
     HNH_FN(hnh_stream_write_flag) HNH_FN(hnh_stream_wait_flag)
     HNH_FN(hnh_csr_plan_create) HNH_FN(hnh_csr_plan_destroy) HNH_FN(hnh_sddmm_csr_p) HNH_FN(hnh_sddmm_csr_ps) HNH_FN(hnh_spmm_csr_p) HNH_FN(hnh_spmm_csr_pf) HNH_FN(hnh_fused_sddmm_spmm_csr_p)
-    // OPTIONAL group (include/hnh_grad.h): bound when the library exports it, null otherwise (the CPU test double does not);
+    // OPTIONAL group (include/hnh_grad.h): bound when the library exports it, null otherwise (the plain CPU test double does not, oracle/liboracle_backend_gat.so does:
+    // that one has this group and those of hnh_attention.h, hnh_attn_grad.h and hnh_train.h);
     // only GAT::backwardPass needs it, and it fails with an error naming the missing symbol
     HNH_FN(hnh_gemm_tn_f64_workspace) HNH_FN(hnh_gemm_tn_f64) HNH_FN(hnh_leaky_relu_grad_f64) HNH_FN(hnh_relu_grad_cols_f64)
     HNH_FN(hnh_sum3_cols_f64) HNH_FN(hnh_transpose_into_f64)

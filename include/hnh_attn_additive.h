@@ -3,7 +3,7 @@
  * exported by libhnh_kernels.so.
  *
  * An OPTIONAL group of the kernel ABI, like include/hnh_grad.h, include/hnh_attention.h and include/hnh_attn_grad.h: the host layer
- * binds it with dlsym and leaves it null when a kernel library does not export it (the CPU test double under oracle/ does not); the
+ * binds it with dlsym and leaves it null when a kernel library does not export it (neither CPU test double under oracle/ does); the
  * additive score then fails with an error naming the missing symbol, and nothing else needs it.  Conventions as in hnh_kernels.h:
  * device pointers, row-major fp64, int status, asynchronous.
  *

@@ -3,7 +3,7 @@
  * mode, exported by libhnh_kernels.so.
  *
  * An OPTIONAL group of the kernel ABI, like include/hnh_attn_v2.h: the host layer binds it with dlsym and leaves it null when a kernel
- * library does not export it (the CPU test double under oracle/ does not); the export then fails with an error naming the missing
+ * library does not export it (neither CPU test double under oracle/ does); the export then fails with an error naming the missing
  * symbol, and nothing else needs it.  Conventions as in hnh_kernels.h: device pointers, row-major fp64, int status, asynchronous.
  *
  * Per head, with A = X W_h (rows x f), alpha the LeakyReLU slope and lse_i the log-sum-exp that a finished forward pass stored, for every

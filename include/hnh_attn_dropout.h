@@ -4,8 +4,7 @@
  * libhnh_kernels.so.
  *
  * An OPTIONAL group of the kernel ABI, like include/hnh_grad.h, include/hnh_attention.h, include/hnh_attn_grad.h and
- * include/hnh_attn_additive.h: the host layer binds it with dlsym and leaves it null when a kernel library does not export it (the CPU
- * test double under oracle/ does not); dropout then fails with an error naming the missing symbol, and nothing else needs it.
+ * include/hnh_attn_additive.h: the host layer binds it with dlsym and leaves it null when a kernel library does not export it (neither CPU test double under oracle/ does); dropout then fails with an error naming the missing symbol, and nothing else needs it.
  *
  * The mask.  Philox-4x32 with 10 rounds (multipliers 0xD2511F53, 0xCD9E8D57; key increments 0x9E3779B9, 0xBB67AE85):
  *     key     = (seed & 0xffffffff, seed >> 32)                      for a 64-bit seed

@@ -3,7 +3,7 @@
  * csrc/host/gat.hpp), forward and backward, exported by libhnh_kernels.so.
  *
  * An OPTIONAL group of the kernel ABI, like include/hnh_attn_qkv.h, whose three passes these are with one more operand: the host layer
- * binds it with dlsym and leaves it null when a kernel library does not export it (the CPU test double under oracle/ does not); a GAT layer
+ * binds it with dlsym and leaves it null when a kernel library does not export it (neither CPU test double under oracle/ does); a GAT layer
  * with an edge bias then fails with an error naming the missing symbol, and nothing else needs it.
  *
  * bias holds one FINITE fp64 value per nonzero of the block, b_e for entry e of the block's CSR order.  It belongs to the entry, not to the

@@ -4,7 +4,7 @@
  * libhnh_kernels.so.
  *
  * An OPTIONAL group of the kernel ABI, like include/hnh_attn_edge.h: the host layer binds it with dlsym and leaves it null when a kernel
- * library does not export it (the CPU test double under oracle/ does not); a GAT layer whose edge bias is learned then fails with an error
+ * library does not export it (neither CPU test double under oracle/ does); a GAT layer whose edge bias is learned then fails with an error
  * naming the missing symbol, and nothing else needs it.
  *
  * With the definitions of hnh_attn_qkv.h and hnh_attn_edge.h, for ONE head

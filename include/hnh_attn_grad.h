@@ -3,7 +3,7 @@
  * libhnh_kernels.so.
  *
  * An OPTIONAL group of the kernel ABI, like include/hnh_grad.h and include/hnh_attention.h: the host layer binds it with dlsym and
- * leaves it null when a kernel library does not export it (the CPU test double under oracle/ does not); the fused backward mode then
+ * leaves it null when a kernel library does not export it (the plain CPU test double, oracle/liboracle_backend.so, does not; the second one, oracle/liboracle_backend_gat.so, does); the fused backward mode then
  * fails with an error naming the missing symbol, and nothing else needs it.  Conventions as in hnh_kernels.h: device pointers,
  * row-major fp64, int status, asynchronous.
  *

@@ -2,7 +2,7 @@
  * hnh_gat_norm.h — layer normalisation of the GAT layers (GAT::set_norm, csrc/host/gat.hpp), exported by libhnh_kernels.so.
  *
  * An OPTIONAL group of the kernel ABI, like include/hnh_gat_skip.h: the host layer binds it with dlsym and leaves it null when a kernel
- * library does not export it (the CPU test double under oracle/ does not); a normalised layer then fails with an error naming the
+ * library does not export it (neither CPU test double under oracle/ does); a normalised layer then fails with an error naming the
  * missing symbol, and nothing else needs it.  Conventions as in hnh_kernels.h: device pointers, row-major fp64, int status, asynchronous.
  *
  * A normalised layer's output is out = phi(gamma o xh + beta) with, per WHOLE output row z_r = o_r + r_r + b (all heads side by side,

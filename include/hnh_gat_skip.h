@@ -3,7 +3,7 @@
  * libhnh_kernels.so.
  *
  * An OPTIONAL group of the kernel ABI, like include/hnh_grad.h: the host layer binds it with dlsym and leaves it null when a kernel
- * library does not export it (the CPU test double under oracle/ does not); a layer with a bias or a residual then fails with an error
+ * library does not export it (neither CPU test double under oracle/ does); a layer with a bias or a residual then fails with an error
  * naming the missing symbol, and nothing else needs it.  Conventions as in hnh_kernels.h: device pointers, row-major fp64, int status,
  * asynchronous.
  *

@@ -2,7 +2,7 @@
  * hnh_grad.h — dense kernels of the GAT backward pass (GAT::backwardPass in csrc/host/gat.hpp), exported by libhnh_kernels.so.
  *
  * An OPTIONAL group of the kernel ABI: the host layer binds it with dlsym and leaves it null when a kernel library does not export
- * it (the CPU test double under oracle/ does not), and GAT::backwardPass then fails with an error naming the missing symbol.  The
+ * it (the plain CPU test double, oracle/liboracle_backend.so, does not; the second one, oracle/liboracle_backend_gat.so, does), and GAT::backwardPass then fails with an error naming the missing symbol.  The
  * forward pass and every other operation never need it.  No counterpart in the reference (its gat.hpp:43-48 leaves the backward
  * pass as work in progress).  Conventions as in hnh_kernels.h: device pointers, row-major fp64, int status, asynchronous.
  */

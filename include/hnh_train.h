@@ -5,7 +5,7 @@
  *
  * An OPTIONAL group of the kernel ABI, like include/hnh_grad.h, include/hnh_attention.h, include/hnh_attn_grad.h,
  * include/hnh_attn_additive.h and include/hnh_attn_dropout.h: the host layer binds it with dlsym and leaves it null when a kernel library
- * does not export it (the CPU test double under oracle/ does not); the training calls then fail with an error naming the missing symbol,
+ * does not export it (the plain CPU test double, oracle/liboracle_backend.so, does not; the second one, oracle/liboracle_backend_gat.so, does); the training calls then fail with an error naming the missing symbol,
  * and nothing else needs it.  Conventions as in hnh_kernels.h: device pointers, row-major fp64, int status, asynchronous on the given
  * stream.  No floating-point atomics: every result is bit-identical run to run.
  *

@@ -4,7 +4,7 @@
  * libhnh_kernels.so.
  *
  * An OPTIONAL group of the kernel ABI, like include/hnh_train.h: the host layer binds it with dlsym and leaves it null when a kernel
- * library does not export it (the CPU test double under oracle/ does not); loss / train_step / evaluate under the sigmoid head then fail
+ * library does not export it (neither CPU test double under oracle/ does); loss / train_step / evaluate under the sigmoid head then fail
  * with an error naming the missing symbol, and nothing else needs it.  Conventions as in hnh_train.h: device pointers, row-major fp64, int
  * status, asynchronous on the given stream.  No floating-point atomics: every result is bit-identical run to run.
  *

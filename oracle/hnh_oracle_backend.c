@@ -47,7 +47,12 @@ static int fail(hnh_ctx* c, int code, const char* msg) {
     return code;
 }
 
+/* -DHNH_ORACLE_GAT_GROUPS: the second double (liboracle_backend_gat.so), with the optional groups of hnh_oracle_gat_groups.h */
+#ifdef HNH_ORACLE_GAT_GROUPS
+const char* hnh_backend_name(void) { return "oracle-cpu-test-double-gat"; }
+#else
 const char* hnh_backend_name(void) { return "oracle-cpu-test-double"; }
+#endif
 
 static pthread_mutex_t g_mu = PTHREAD_MUTEX_INITIALIZER;
 int hnh_ctx_create(int device, hnh_ctx** out) {
@@ -97,6 +102,7 @@ static int hb_op_begin(hnh_ctx* c, int stream, const char* name) {
     pthread_mutex_unlock(&g_mu);
     hb_cur.name = name;
     hb_cur.strict = c->hb_blocks > 0;
+    hb_cur.overrun = 0;
     return 1;
 }
 static void hb_op_end(int* opened) {
@@ -114,6 +120,7 @@ static void hb_access_at(const void* p, size_t bytes, int write, int where) {
         uint64_t lo = (uint64_t)((const char*)p - b->base), hi = lo + bytes;
         if (hi > b->bytes) {  /* the ranges are exact (index streams are scanned): this call runs past the end of its operand */
             hb_note_misuse(hb_cur.name, write, "runs past the end of its block", p, bytes);
+            hb_cur.overrun++;
             hi = b->bytes;
         }
         hb_touch(&b->recs, &b->nrec, &b->cap, b->base, lo, hi, write, hb_cur.t, hb_cur.name);
@@ -1577,3 +1584,8 @@ int hnh_fused_sddmm_spmm_csr_p(hnh_ctx* c, const hnh_csr_block* b, double* value
     return hnh_fused_sddmm_spmm_csr_w(c, b->rows, b->rowptr, b->col_idx, values, svalues, X, Y, Out, R, flags, b->nnz, b->max_row_nnz, ex,
                                       w ? w : &whole_block, stream);
 }
+
+/* ---- the GAT's backward, softmax attention, fused backward and training groups: only in the second double */
+#ifdef HNH_ORACLE_GAT_GROUPS
+#include "hnh_oracle_gat_groups.h"
+#endif

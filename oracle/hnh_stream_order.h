@@ -53,7 +53,7 @@ static long hb_races = 0, hb_checked = 0;
 static long hb_wait_count = 0, hb_wait_drop = -1;   /* single-fault injection of the checker's own tests */
 static char hb_report[HB_REPORT_BYTES];
 static size_t hb_report_len = 0;
-static __thread struct { int depth, t, strict; const char* name; } hb_cur;
+static __thread struct { int depth, t, strict, overrun; const char* name; } hb_cur;  /* overrun: accesses of this call past the end of their block */
 
 /* a process that ends with unreported races says so and fails (a pytest session drains the report first: tests/conftest.py) */
 static void hb_at_exit(void) {

@@ -14,6 +14,8 @@ from oracle import oracle as O
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 ORACLE_BACKEND = os.path.join(ROOT, "oracle", "liboracle_backend.so")
+# the same double with the GAT's optional groups (oracle/hnh_oracle_gat_groups.h): backward, softmax attention, fused backward, training
+ORACLE_GAT_BACKEND = os.path.join(ROOT, "oracle", "liboracle_backend_gat.so")
 TOL = 1e-11  # fp64, summation order only
 
 DENSE_OUT = ("spmmA", "spmmB", "fusedA", "fusedB")

@@ -90,8 +90,12 @@ def test_an_unordered_pair_is_a_race_and_an_event_orders_it(checker):
 
 STREAM_HEAVY = [("15d_fusion2", 4, 1, {}), ("15d_fusion2", 8, 2, {"HNH_MESH_TAPER": "3,4,4,3,2,1,1"}), ("15d_fusion2", 4, 1, {"HNH_RING_MODE": "relay"}),
                 ("15d_fusion1", 4, 1, {}), ("15d_fusion1", 8, 2, {"HNH_MESH_TAPER": "2,1"}),  # row-merged layout: row-range passes, mesh reduce-scatter
-                ("15d_fusion1", 4, 1, {"HNH_FUSION1_MESH": "0"}), ("15d_fusion1", 6, 2, {"HNH_FUSION1_MESH": "0", "HNH_ACC_HALVES": "0"}),  # the rings ("15d_sparse", 4, 1, {"HNH_SHIP_INDICES": "1"}),
-                ("25d_dense_replicate", 8, 2, {}), ("25d_sparse_replicate", 8, 2, {"HNH_BORROW": "force"}), ("25d_dense_replicate", 16, 4, {})]
+                # the rings
+                ("15d_fusion1", 4, 1, {"HNH_FUSION1_MESH": "0"}), ("15d_fusion1", 6, 2, {"HNH_FUSION1_MESH": "0", "HNH_ACC_HALVES": "0"}),
+                ("25d_dense_replicate", 8, 2, {}), ("25d_sparse_replicate", 8, 2, {"HNH_BORROW": "force"}), ("25d_dense_replicate", 16, 4, {}),
+                # travelling sparse blocks with their index arrays, with and without the perf counters: both branches of phase_end_mark
+                # (at the end of the list: the cases before them keep their numbered ids)
+                ("15d_sparse", 4, 1, {"HNH_SHIP_INDICES": "1"}), ("15d_sparse", 4, 1, {"HNH_SHIP_INDICES": "1", "HNH_PERF_COUNTERS": "0"})]
 
 
 @pytest.mark.parametrize("alg,p,c,env", STREAM_HEAVY)

@@ -9,7 +9,7 @@ build() {  # $1 = output name, rest = extra flags
     out="$1"; shift
     g++ -O2 -g -std=c++17 -fopenmp -fPIC -shared -Wall -Wno-sign-compare -Wno-unused-variable "$@" \
         -I"$ROOT/include" -I"$HERE/host" \
-        "$HERE/host/world.cpp" "$HERE/host/sparse_kernels.cpp" "$HERE/host/er_generator.cpp" "$HERE/host/c_api.cpp" \
+        "$HERE/host/world.cpp" "$HERE/host/sparse_kernels.cpp" "$HERE/host/attn_compat.cpp" "$HERE/host/er_generator.cpp" "$HERE/host/c_api.cpp" \
         -o "$HERE/../lib/$out" -ldl -lpthread -lrt -Wl,-Bsymbolic
 }
 build libhnh_host.so &

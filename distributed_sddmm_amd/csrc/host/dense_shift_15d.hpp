@@ -299,142 +299,28 @@ public:
         return true;
     }
 
-    // One pass of the fused attention backward (include/hnh_attn_grad.h): the row pass over S (`moving` = A, this->R = f wide) or, with
-    // `column_side`, the column pass over S^T (`moving` = the packed operand, this->R = its width: the caller sets the schedule's R to
-    // the MOVING operand's width, which is what the landing buffers and the fetch are sized by; the row operand and the output are
-    // narrower and addressed through args' leading dimensions).  The own block runs first, then the fetched blocks window by window or
-    // in adaptive groups as their chunks land, exactly as the fused forward pass.  `overwrite`: the output rows start from zero.
-    // Returns false, having done nothing, where a rank's own launches do not see all of a row's nonzeros (only approach 2 with c = 1).
-    // Not a virtual of Distributed_Sparse, for fusedSoftmax_out's reason.
-    bool attnGrad_pass(bool column_side, DenseMatrix& moving, const hnh_attn_grad& args, int64_t out_rows, bool overwrite) {
+    // One attention pass (hnh::AttnPass, sparse_kernels.hpp) of any family: passes 0 (a forward pass, or the export of the coefficients) and 1
+    // (the backward row pass) over S, pass 2 (the backward column pass) over S^T.  `moving` is the gathered operand of the pass (include/
+    // hnh_attn_grad.h, _additive.h, _dropout.h, _v2.h, _qkv.h, _coef.h say which: A, the scored M / M', the packed Q / Q' / P, [K | V], the
+    // pair [t | id]) and the caller sets the schedule's R to ITS width, which is what the landing buffers and the fetch are sized by; the
+    // row operand and the outputs are addressed through the arguments' leading dimensions.  The own block runs first, then the fetched
+    // blocks window by window or in adaptive groups as their chunks land, exactly as the fused forward pass.  `overwrite`: the output rows
+    // start from zero.  A forward pass makes its first call (the state reset) and its closing call (the finish, with pass.finish_flags)
+    // also for an absent block, like fusedSoftmax_out.  With dropout `moving`'s rows carry their global ids and pass.drop->row_id0 is the
+    // global id of this rank's row 0 (the same for every block: a block's rows are the rank's rows).
+    // pass.bias / pass.dbias / pass.coef: one value per nonzero in the like_S_values layout (passes 0 and 1) or the like_ST_values layout
+    // (pass 2), lent to the blocks for the pass (lend_slices).  Every nonzero's entry of dbias or coef is overwritten or, dbias with
+    // pass.accumulate, added to; entries of absent blocks are not touched.
+    // Returns false, having done nothing, where a rank's own launches do not see all of a row's nonzeros (only approach 2 with c = 1 has
+    // such a pass).  Not a virtual of Distributed_Sparse, for fusedSoftmax_out's reason.
+    bool attn_pass(const hnh::AttnPass& pass, DenseMatrix& moving, int64_t out_rows, bool overwrite) {
         if (fusionApproach != 2 || c != 1) return false;
-        if (moving.cols() != R) hnh::fatal("Error, attnGrad_pass: the schedule's R must be the moving operand's width!");
-        attn_walk(column_side ? ST.get() : S.get(), moving, args, overwrite, false,
-                  "Error, the kernel implementation has no fused attention backward pass (KernelImplementation::attn_grad_local)!",
-                  [&](SpmatLocal& choice, int block_id, const hnh_attn_grad& a, unsigned flags, bool) {
-                      return kernel->attn_grad_local(choice, block_id, a, column_side, flags, out_rows);
-                  });
-        return true;
-    }
-
-    // One pass of the additive-score attention (include/hnh_attn_additive.h): pass 0 = the forward pass over S (`moving` = the scored
-    // operand M), 1 = the backward row pass over S (M again), 2 = the backward column pass over S^T (`moving` = the packed operand Q).
-    // As for attnGrad_pass the schedule's R must be the MOVING operand's width; everything else is addressed through args.  The forward
-    // pass makes its first call (the state reset) and its closing call (the finish) also for an absent block, like fusedSoftmax_out.
-    // Returns false, having done nothing, where a rank's own launches do not see all of a row's nonzeros (only approach 2 with c = 1).
-    // Not a virtual of Distributed_Sparse, for fusedSoftmax_out's reason.
-    // `drop` (include/hnh_attn_dropout.h): the passes' DROP instances; `moving` is then M' / Q', whose rows carry their global ids, and
-    // drop->row_id0 is the global id of this rank's row 0 (the same for every block: a block's rows are the rank's rows).
-    // `finish_flags`: HNH_ATTN_ACT_ELU / HNH_ATTN_ACT_IDENTITY (or 0: ReLU) for the forward pass's finishing call alone.
-    bool attnAdditive_pass(int pass, DenseMatrix& moving, const hnh_attn_add& args, int64_t out_rows, bool overwrite,
-                           const hnh_attn_drop* drop = nullptr, unsigned finish_flags = 0u) {
-        if (fusionApproach != 2 || c != 1) return false;
-        if (pass < 0 || pass > 2) hnh::fatal("Error, attnAdditive_pass: unknown pass!");
-        if (moving.cols() != R) hnh::fatal("Error, attnAdditive_pass: the schedule's R must be the moving operand's width!");
-        attn_walk(pass == 2 ? ST.get() : S.get(), moving, args, overwrite, pass == 0,
-                  "Error, the kernel implementation has no additive attention pass (KernelImplementation::attn_additive_local)!",
-                  [&](SpmatLocal& choice, int block_id, const hnh_attn_add& a, unsigned flags, bool finish) {
-                      return kernel->attn_additive_local(choice, block_id, a, pass, flags | (finish ? finish_flags : 0u), out_rows, finish, drop);
-                  });
-        return true;
-    }
-
-    // One pass of the GATv2 attention (include/hnh_attn_v2.h): pass 0 = the forward pass over S (`moving` = the head's product A), 1 = the
-    // backward row pass over S (A again), 2 = the backward column pass over S^T (`moving` = the packed operand of include/hnh_attn_grad.h).
-    // Everything as for attnAdditive_pass: the schedule's R must be the MOVING operand's width, the forward pass makes its first and its
-    // closing call also for an absent block, `finish_flags` go to the closing call alone.  Returns false, having done nothing, where a
-    // rank's own launches do not see all of a row's nonzeros.  Not a virtual of Distributed_Sparse, for fusedSoftmax_out's reason.
-    bool attnV2_pass(int pass, DenseMatrix& moving, const hnh_attn_v2& args, int64_t out_rows, bool overwrite, unsigned finish_flags = 0u) {
-        if (fusionApproach != 2 || c != 1) return false;
-        if (pass < 0 || pass > 2) hnh::fatal("Error, attnV2_pass: unknown pass!");
-        if (moving.cols() != R) hnh::fatal("Error, attnV2_pass: the schedule's R must be the moving operand's width!");
-        attn_walk(pass == 2 ? ST.get() : S.get(), moving, args, overwrite, pass == 0,
-                  "Error, the kernel implementation has no gatv2 attention pass (KernelImplementation::attn_v2_local)!",
-                  [&](SpmatLocal& choice, int block_id, const hnh_attn_v2& a, unsigned flags, bool finish) {
-                      return kernel->attn_v2_local(choice, block_id, a, pass, flags | (finish ? finish_flags : 0u), out_rows, finish);
-                  });
-        return true;
-    }
-
-    // One pass of the query/key/value attention (include/hnh_attn_qkv.h): pass 0 = the forward pass over S and 1 = the backward row pass
-    // over S (`moving` = the packed [K | V]), 2 = the backward column pass over S^T (`moving` = the packed [Q | dZ | lse delta]).  Everything
-    // as for attnV2_pass: the schedule's R must be the MOVING operand's packed width, the forward pass makes its first and its closing call
-    // also for an absent block, `finish_flags` go to the closing call alone.  Returns false, having done nothing, where a rank's own
-    // launches do not see all of a row's nonzeros.  Not a virtual of Distributed_Sparse, for fusedSoftmax_out's reason.
-    // `bias` (include/hnh_attn_edge.h): one value per nonzero in the like_S_values layout (passes 0 and 1) or the like_ST_values layout (pass
-    // 2); block i is lent its slice bias->data() + blockStarts[i] (CSRLocal::spmm_values: a value array that the pass reads in place), as
-    // attnCoef_pass lends its destination, and the slices are reclaimed before the pass returns.
-    // `dbias` (include/hnh_attn_edge_grad.h; passes 1 and 2 with a bias): the bias's gradient in the bias's layout, sliced per block in the
-    // same way (CSRLocal::sddmm_dst: a value array that the pass writes in place); every nonzero's entry is overwritten or, with
-    // `accumulate`, added to, and entries of absent blocks are not touched.
-    bool attnQKV_pass(int pass, DenseMatrix& moving, const hnh_attn_qkv& args, int64_t out_rows, bool overwrite, unsigned finish_flags = 0u,
-                      const VectorXd* bias = nullptr, VectorXd* dbias = nullptr, bool accumulate = false) {
-        if (fusionApproach != 2 || c != 1) return false;
-        if (pass < 0 || pass > 2) hnh::fatal("Error, attnQKV_pass: unknown pass!");
-        if (moving.cols() != R) hnh::fatal("Error, attnQKV_pass: the schedule's R must be the moving operand's width!");
-        SpmatLocal* s = pass == 2 ? ST.get() : S.get();
-        const char* missing = "Error, the kernel implementation has no transformer attention pass (KernelImplementation::attn_qkv_local)!";
-        if (dbias != nullptr && (bias == nullptr || pass == 0)) hnh::fatal("Error, attnQKV_pass: the bias's gradient belongs to a backward pass with a bias!");
-        if (bias == nullptr) {
-            attn_walk(s, moving, args, overwrite, pass == 0, missing,
-                      [&](SpmatLocal& choice, int block_id, const hnh_attn_qkv& a, unsigned flags, bool finish) {
-                          return kernel->attn_qkv_local(choice, block_id, a, pass, flags | (finish ? finish_flags : 0u), out_rows, finish);
-                      });
-            return true;
-        }
-        if (!s->blockStarts.empty() && (uint64_t)bias->size() < s->blockStarts.back()) hnh::fatal("Error, sparse value vector has the wrong length!");
-        if (dbias != nullptr && !s->blockStarts.empty() && (uint64_t)dbias->size() < s->blockStarts.back())
-            hnh::fatal("Error, sparse value vector has the wrong length!");
-        for (size_t i = 0; i + 1 < s->blockStarts.size(); i++) {
-            CSRLocal* blk = s->csr_blocks[i];
-            if (blk == nullptr) continue;
-            if (blk->shifting) hnh::fatal("Error, attnQKV_pass: a travelling block cannot borrow a value slice!");
-            blk->spmm_values = bias->data() + s->blockStarts[i];
-            if (dbias != nullptr) blk->sddmm_dst = dbias->data() + s->blockStarts[i];
-        }
-        struct Reclaim {
-            SpmatLocal* s;
-            ~Reclaim() { s->reclaimValueArrays(); }
-        } reclaim{s};
-        attn_walk(s, moving, args, overwrite, pass == 0, missing,
-                  [&](SpmatLocal& choice, int block_id, const hnh_attn_qkv& a, unsigned flags, bool finish) {
-                      const CSRLocal* blk = choice.csr_blocks[block_id];
-                      if (dbias != nullptr)
-                          return kernel->attn_qkv_local(choice, block_id, a, pass, flags, out_rows, finish, blk ? blk->spmm_values : nullptr,
-                                                        blk ? blk->sddmm_dst : nullptr, accumulate);
-                      return kernel->attn_qkv_local(choice, block_id, a, pass, flags | (finish ? finish_flags : 0u), out_rows, finish,
-                                                    blk ? blk->spmm_values : nullptr);
-                  });
-        return true;
-    }
-
-    // The export of the attention coefficients (include/hnh_attn_coef.h) over S: `moving` is the gathered operand (the head's product A for
-    // the scores dot and gatv2, the packed pair [t | id] for additive) and, as for attnV2_pass, the schedule's R must be its width.  The
-    // blocks are walked in attn_walk's order (the own block, then the fetched blocks by window or adaptive group, or the ring); block i
-    // stores its nonzeros' coefficients into out_values[blockStarts[i] ..), the like_S_values layout that lendSddmmTargets defines, and the
-    // lent slices are reclaimed before the pass returns.  Returns false, having done nothing, where a rank's own launches do not see all of
-    // a row's nonzeros (the stored lse belongs to whole rows).  Not a virtual of Distributed_Sparse, for fusedSoftmax_out's reason.
-    bool attnCoef_pass(DenseMatrix& moving, const hnh_attn_coef& args, VectorXd& out_values, const hnh_attn_drop* drop = nullptr) {
-        if (fusionApproach != 2 || c != 1) return false;
-        if (moving.cols() != R) hnh::fatal("Error, attnCoef_pass: the schedule's R must be the moving operand's width!");
-        SpmatLocal* s = S.get();
-        if (!s->blockStarts.empty() && (uint64_t)out_values.size() < s->blockStarts.back()) hnh::fatal("Error, sparse value vector has the wrong length!");
-        const int64_t rows = (int64_t)localArows * c;  // (every block of S holds the rank's rows)
-        for (size_t i = 0; i + 1 < s->blockStarts.size(); i++) {
-            CSRLocal* blk = s->csr_blocks[i];
-            if (blk == nullptr) continue;
-            if (blk->shifting) hnh::fatal("Error, attnCoef_pass: a travelling block cannot borrow a value slice!");
-            blk->sddmm_dst = out_values.data() + s->blockStarts[i];
-        }
-        struct Reclaim {
-            SpmatLocal* s;
-            ~Reclaim() { s->reclaimValueArrays(); }
-        } reclaim{s};
-        attn_walk(s, moving, args, false, false,
-                  "Error, the kernel implementation has no attention-coefficient export (KernelImplementation::attn_coef_local)!",
-                  [&](SpmatLocal& choice, int block_id, const hnh_attn_coef& a, unsigned, bool) {
-                      return kernel->attn_coef_local(choice, block_id, a, rows, drop);
-                  });
+        if (pass.pass < 0 || pass.pass > 2) hnh::fatal("Error, attn_pass: unknown pass!");
+        if (moving.cols() != R) hnh::fatal("Error, attn_pass: the schedule's R must be the moving operand's width!");
+        if (pass.dbias != nullptr && (pass.bias == nullptr || pass.pass == 0)) hnh::fatal("Error, attn_pass: the bias's gradient belongs to a backward pass with a bias!");
+        SpmatLocal* s = pass.pass == 2 ? ST.get() : S.get();
+        const LentSlices lent = lend_slices(s, pass.bias, pass.dbias ? pass.dbias : pass.coef);
+        attn_walk(s, moving, pass, out_rows, overwrite);
         return true;
     }
 
@@ -608,24 +494,49 @@ private:
         return done;
     }
 
-    // The walk of attnGrad_pass and attnAdditive_pass: the own block, then the fetched blocks window by window or in adaptive groups as
-    // their chunks land (merged layout), or the blocks of the ring.  call(choice, block, args with Y / ld_y = the block's gathered operand,
-    // flags, finish) is the pass on one block; it returns false when the kernel implementation has no such pass (`missing`).  The first
-    // call of an `overwrite` pass carries HNH_FUSED_OUT_OVERWRITE; an absent block is skipped unless its call is that one or, with
-    // `finishes`, the closing one (the forward pass's finish).
-    template <typename Args, typename Call>
-    void attn_walk(SpmatLocal* choice, DenseMatrix& moving, const Args& args, bool overwrite, bool finishes, const char* missing, Call&& call) {
+    // Block i of `s` reads `read` and writes `written` (each may be null) in place for one pass: its slice from blockStarts[i] on as
+    // CSRLocal::spmm_values / sddmm_dst, as lendCSRValues and lendSddmmTargets lend an operation's; reclaimed when the guard goes.
+    struct LentSlices {
+        SpmatLocal* s;
+        ~LentSlices() {
+            if (s != nullptr) s->reclaimValueArrays();
+        }
+    };
+    static LentSlices lend_slices(SpmatLocal* s, const VectorXd* read, VectorXd* written) {
+        if (read == nullptr && written == nullptr) return {nullptr};
+        for (const VectorXd* v : {read, (const VectorXd*)written})
+            if (v != nullptr && !s->blockStarts.empty() && (uint64_t)v->size() < s->blockStarts.back()) hnh::fatal("Error, sparse value vector has the wrong length!");
+        for (size_t i = 0; i + 1 < s->blockStarts.size(); i++) {
+            CSRLocal* blk = s->csr_blocks[i];
+            if (blk == nullptr) continue;
+            if (blk->shifting) hnh::fatal("Error, attn_pass: a travelling block cannot borrow a value slice!");
+            if (read != nullptr) blk->spmm_values = read->data() + s->blockStarts[i];
+            if (written != nullptr) blk->sddmm_dst = written->data() + s->blockStarts[i];
+        }
+        return {s};
+    }
+
+    // The walk of attn_pass: the own block, then the fetched blocks window by window or in adaptive groups as their chunks land (merged
+    // layout), or the blocks of the ring; the pass on one block is KernelImplementation::attn_local with Y / ld_y = the block's gathered
+    // operand.  The first call of an `overwrite` pass carries HNH_FUSED_OUT_OVERWRITE; an absent block is skipped unless its call is that
+    // one or a forward pass's closing one (the finish, which alone carries pass.finish_flags).
+    void attn_walk(SpmatLocal* choice, DenseMatrix& moving, const hnh::AttnPass& pass, int64_t out_rows, bool overwrite) {
         const int n = p / c;
         bool fresh = overwrite;
         auto on = [&](int block_id, DenseMatrix& Y, int window, int window_end, bool closing) {
             CSRLocal* blk = choice->csr_blocks[block_id];
-            const bool finish = finishes && closing;
+            const bool finish = pass.forward() && closing;
             if (blk == nullptr && !fresh && !finish) return;  // nothing to add
-            Args a = args;
-            a.Y = Y.data();
-            a.ld_y = Y.cols();
-            if (!in_window(blk, window, window_end, [&] { return call(*choice, block_id, a, fresh ? HNH_FUSED_OUT_OVERWRITE : 0u, finish); }))
-                throw hnh::Error(missing);
+            hnh::AttnPass a = pass;
+            std::visit(
+                [&](auto& g) {
+                    g.Y = Y.data();
+                    g.ld_y = Y.cols();
+                },
+                a.args);
+            const unsigned flags = (fresh ? HNH_FUSED_OUT_OVERWRITE : 0u) | (finish ? pass.finish_flags : 0u);
+            if (!in_window(blk, window, window_end, [&] { return kernel->attn_local(*choice, block_id, a, flags, out_rows, finish); }))
+                throw hnh::Error(KernelImplementation::attn_missing(pass));
             fresh = false;
         };
         if (merged) {

@@ -650,8 +650,8 @@ public:
         GATLayer& L = layers[(size_t)i];
         const int f = L.features_per_head;
         const bool additive = score_ == HNH_GAT_SCORE_ADDITIVE;
-        require_kernels(what, "include/hnh_attn_coef.h", {HNH_GAT_KERNEL(hnh_attn_coef_csr_p)});
-        if (additive) require_kernels(what, "include/hnh_attn_coef.h", {HNH_GAT_KERNEL(hnh_attn_coef_scores_f64)});
+        require_kernels(what, {HNH_GAT_KERNEL(hnh_attn_coef_csr_p)});
+        if (additive) require_kernels(what, {HNH_GAT_KERNEL(hnh_attn_coef_scores_f64)});
         if (!forward_valid_ || lse_.size() != layers.size() || lse_[(size_t)i].size() != (size_t)L.num_heads)
             throw hnh::Error("Error, GAT " + what + " needs a forwardPass first (and a new one after set_weight / set_input / optimizer_step)!");
         const int S0 = HNH_STREAM_COMPUTE;
@@ -675,14 +675,18 @@ public:
             const bool drop = dropped && attn_p_ > 0.0;
             const hnh_attn_drop dr = attn_drop_args(i, h);
             ScheduleWidth width(d_ops, HNH_ATTN_COEF_PAIR_WIDTH, r0);
-            ok = ds->attnCoef_pass(T, g, out, drop ? &dr : nullptr);
+            hnh::AttnPass pass = {0, g, drop ? &dr : nullptr};
+            pass.coef = &out;
+            ok = ds->attn_pass(pass, T, rows, false);
         } else {
             g.score = score_ == HNH_GAT_SCORE_GATV2 ? HNH_ATTN_COEF_GATV2 : HNH_ATTN_COEF_DOT;
             g.X = A.data();
             g.ld_x = f;
             g.a = score_ == HNH_GAT_SCORE_GATV2 ? attn_vector(i, h, 0) : nullptr;
             ScheduleWidth width(d_ops, f, r0);
-            ok = ds->attnCoef_pass(A, g, out);
+            hnh::AttnPass pass = {0, g};
+            pass.coef = &out;
+            ok = ds->attn_pass(pass, A, rows, false);
         }
         require_own_rows(what, !ok);
     }
@@ -827,7 +831,7 @@ public:
     // forward pass.  No host synchronisation.
     void optimizer_step() {
         if (!optimizer_set_) throw hnh::Error("Error, GAT optimizer_step needs set_optimizer first!");
-        require_kernels("training", "include/hnh_train.h", {HNH_GAT_KERNEL(hnh_optim_step_f64)});
+        require_kernels("training", {HNH_GAT_KERNEL(hnh_optim_step_f64)});
         if (!grads_fresh_ || weight_grads.size() != layers.size() || (learns_vectors() && attn_grads.size() != layers.size()))
             throw hnh::Error("Error, GAT optimizer_step needs the gradients of a backwardPass since the last step!");
         const std::vector<Learned> learned = learned_parameters();
@@ -1140,13 +1144,11 @@ private:
         if (!whole_rows(false))
             throw hnh::Error(std::string("Error, GAT ") + what + " needs one dense block of whole rows per rank, which " + d_ops->algorithm_name + " does not have!");
     }
-    // Refuses with the first kernel of an optional group that the library lacks: `what` are the words after "GAT", `header` the group's;
-    // HNH_GAT_KERNEL(name) is an entry of the list.
-    void require_kernels(const std::string& what, const char* header, std::initializer_list<std::pair<const void*, const char*>> need) const {
+    // Refuses with the first kernel of the list that the library lacks (Backend::missing_kernel, which knows the kernel's header): `what`
+    // are the words after "GAT"; HNH_GAT_KERNEL(name) is an entry of the list.
+    void require_kernels(const std::string& what, std::initializer_list<std::pair<const void*, const char*>> need) const {
         for (const auto& n : need)
-            if (n.first == nullptr)
-                throw hnh::Error("Error, GAT " + what + " needs the kernel " + n.second + ", which the kernel library " + d_ops->world->be->path +
-                                 " does not export (" + header + ")");
+            if (n.first == nullptr) throw hnh::Error(d_ops->world->be->missing_kernel("GAT " + what, n.second));
     }
     // Refuses a schedule on which a rank's own launches do not see all of a row's nonzeros, or an output row is summed across ranks: all
     // but 15d_fusion2 with c = 1 (15d_fusion1 reduce-scatters over the mesh; c > 1, the 2.5D schedules and the sparse shift reduce across
@@ -1175,13 +1177,13 @@ private:
         if (!labels_set_ && !multilabel_) throw hnh::Error("Error, GAT loss / train_step / evaluate need set_labels first!");
         if (need_optimizer && !optimizer_set_) throw hnh::Error("Error, GAT train_step needs set_optimizer first!");
         if (multilabel_) {  // the sigmoid head: its own kernel group, and no limit on the row width (no row is staged)
-            require_kernels("training", "include/hnh_train_multilabel.h", {HNH_GAT_KERNEL(hnh_bce_rows_f64_workspace), HNH_GAT_KERNEL(hnh_bce_rows_f64)});
-            if (need_optimizer) require_kernels("training", "include/hnh_train.h", {HNH_GAT_KERNEL(hnh_optim_step_f64)});
+            require_kernels("training", {HNH_GAT_KERNEL(hnh_bce_rows_f64_workspace), HNH_GAT_KERNEL(hnh_bce_rows_f64)});
+            if (need_optimizer) require_kernels("training", {HNH_GAT_KERNEL(hnh_optim_step_f64)});
             check_whole_rows("loss");
             return;
         }
-        require_kernels("training", "include/hnh_train.h", {HNH_GAT_KERNEL(hnh_xent_rows_f64_workspace), HNH_GAT_KERNEL(hnh_xent_rows_f64)});
-        if (need_optimizer) require_kernels("training", "include/hnh_train.h", {HNH_GAT_KERNEL(hnh_optim_step_f64)});
+        require_kernels("training", {HNH_GAT_KERNEL(hnh_xent_rows_f64_workspace), HNH_GAT_KERNEL(hnh_xent_rows_f64)});
+        if (need_optimizer) require_kernels("training", {HNH_GAT_KERNEL(hnh_optim_step_f64)});
         const int64_t width = (int64_t)layers.back().num_heads * layers.back().features_per_head;
         if (width > HNH_XENT_MAX_WIDTH)
             throw hnh::Error("Error, GAT loss supports output rows of at most " + std::to_string(HNH_XENT_MAX_WIDTH) + " values, not " + std::to_string(width) +
@@ -1386,10 +1388,9 @@ private:
         if (feat_p_ > 0.0 && !whole_rows(true))
             throw hnh::Error("Error, GAT feature dropout needs one dense block of whole rows per rank, which " + d_ops->algorithm_name + " does not have!");
         if (attn_p_ > 0.0)
-            require_kernels("dropout", "include/hnh_attn_dropout.h",
-                            {HNH_GAT_KERNEL(hnh_attn_drop_fwd_csr_p), HNH_GAT_KERNEL(hnh_attn_drop_row_csr_p), HNH_GAT_KERNEL(hnh_attn_drop_col_csr_p),
+            require_kernels("dropout", {HNH_GAT_KERNEL(hnh_attn_drop_fwd_csr_p), HNH_GAT_KERNEL(hnh_attn_drop_row_csr_p), HNH_GAT_KERNEL(hnh_attn_drop_col_csr_p),
                              HNH_GAT_KERNEL(hnh_attn_drop_scores_f64), HNH_GAT_KERNEL(hnh_attn_drop_pack_f64)});
-        if (feat_p_ > 0.0) require_kernels("dropout", "include/hnh_attn_dropout.h", {HNH_GAT_KERNEL(hnh_feat_drop_f64)});
+        if (feat_p_ > 0.0) require_kernels("dropout", {HNH_GAT_KERNEL(hnh_feat_drop_f64)});
     }
 
     static const char* activation_name(int mode) { return mode == HNH_GAT_ACT_ELU ? "elu" : (mode == HNH_GAT_ACT_IDENTITY ? "identity" : "relu"); }
@@ -1559,8 +1560,7 @@ private:
                                      std::to_string(X.cols()) + " and " + std::to_string(out.rows()) + " x " + std::to_string(out.cols()) +
                                      ": use residual projection!");
             }
-            require_kernels(what, "include/hnh_gat_skip.h",
-                            {HNH_GAT_KERNEL(hnh_skip_addend_cols_f64), HNH_GAT_KERNEL(hnh_skip_grad_cols_f64), HNH_GAT_KERNEL(hnh_colsum_f64_workspace),
+            require_kernels(what, {HNH_GAT_KERNEL(hnh_skip_addend_cols_f64), HNH_GAT_KERNEL(hnh_skip_grad_cols_f64), HNH_GAT_KERNEL(hnh_colsum_f64_workspace),
                              HNH_GAT_KERNEL(hnh_colsum_f64)});
         }
     }
@@ -1572,7 +1572,7 @@ private:
             const std::string what = std::string("activation ") + activation_name(act_[i]) + " of layer " + std::to_string(i);
             require_softmax(what, ": its passes end in a ReLU", "include/hnh_attention.h");
             require_own_rows(what);
-            require_kernels(what, "include/hnh_grad.h", {HNH_GAT_KERNEL(hnh_act_grad_cols_f64)});
+            require_kernels(what, {HNH_GAT_KERNEL(hnh_act_grad_cols_f64)});
         }
     }
     // A normalised layer: its heads end in the identity flag of the softmax passes' finishing launch and its backward pass in
@@ -1587,9 +1587,8 @@ private:
             if (hf > HNH_NORM_MAX_COLS)
                 throw hnh::Error("Error, GAT " + what + " supports rows of at most " + std::to_string(HNH_NORM_MAX_COLS) + " values (num_heads * features_per_head), not " +
                                  std::to_string(hf) + " (include/hnh_gat_norm.h)");
-            require_kernels(what, "include/hnh_gat_norm.h",
-                            {HNH_GAT_KERNEL(hnh_layernorm_fwd_f64), HNH_GAT_KERNEL(hnh_layernorm_bwd_workspace), HNH_GAT_KERNEL(hnh_layernorm_bwd_f64)});
-            require_kernels(what, "include/hnh_grad.h", {HNH_GAT_KERNEL(hnh_act_grad_cols_f64)});
+            require_kernels(what, {HNH_GAT_KERNEL(hnh_layernorm_fwd_f64), HNH_GAT_KERNEL(hnh_layernorm_bwd_workspace), HNH_GAT_KERNEL(hnh_layernorm_bwd_f64)});
+            require_kernels(what, {HNH_GAT_KERNEL(hnh_act_grad_cols_f64)});
         }
     }
     // The backward pass: the score's or the fused mode's own conditions first, then the plain pass's schedules and kernel groups.
@@ -1604,17 +1603,14 @@ private:
                              d_ops->algorithm_name);
         if (ds->fusionApproach == 2 && ds->c != 1)
             throw hnh::Error("Error, GAT backwardPass does not support 15d_fusion2 with c > 1 (its forward pass reproduces a quirk of the reference)");
-        require_kernels("backwardPass", "include/hnh_grad.h",
-                        {HNH_GAT_KERNEL(hnh_gemm_tn_f64_workspace), HNH_GAT_KERNEL(hnh_gemm_tn_f64), HNH_GAT_KERNEL(hnh_leaky_relu_grad_f64),
+        require_kernels("backwardPass", {HNH_GAT_KERNEL(hnh_gemm_tn_f64_workspace), HNH_GAT_KERNEL(hnh_gemm_tn_f64), HNH_GAT_KERNEL(hnh_leaky_relu_grad_f64),
                          HNH_GAT_KERNEL(hnh_relu_grad_cols_f64), HNH_GAT_KERNEL(hnh_sum3_cols_f64), HNH_GAT_KERNEL(hnh_transpose_into_f64)});
         if (attention_ == HNH_GAT_ATTENTION_SOFTMAX)
-            require_kernels("backwardPass with softmax attention", "include/hnh_attention.h",
-                            {HNH_GAT_KERNEL(hnh_softmax_gate_f64), HNH_GAT_KERNEL(hnh_rowdot_cols_f64)});
+            require_kernels("backwardPass with softmax attention", {HNH_GAT_KERNEL(hnh_softmax_gate_f64), HNH_GAT_KERNEL(hnh_rowdot_cols_f64)});
     }
     // The fused backward mode: its kernel group first.
     void check_fused_backward_supported() {
-        require_kernels("backwardPass in fused mode", "include/hnh_attn_grad.h",
-                        {HNH_GAT_KERNEL(hnh_attn_grad_row_csr_p), HNH_GAT_KERNEL(hnh_attn_grad_col_csr_p), HNH_GAT_KERNEL(hnh_attn_grad_pack_f64)});
+        require_kernels("backwardPass in fused mode", {HNH_GAT_KERNEL(hnh_attn_grad_row_csr_p), HNH_GAT_KERNEL(hnh_attn_grad_col_csr_p), HNH_GAT_KERNEL(hnh_attn_grad_pack_f64)});
         require_own_rows("fused backward");
         require_head_width("fused backward", HNH_ATTN_GRAD_MAX_F, "include/hnh_attn_grad.h");
     }
@@ -1622,8 +1618,7 @@ private:
         require_softmax("score additive", "", "include/hnh_attn_additive.h");
         require_own_rows("score additive");
         require_head_width("score additive", HNH_ATTN_ADD_MAX_F, "include/hnh_attn_additive.h");
-        require_kernels("score additive", "include/hnh_attn_additive.h",
-                        {HNH_GAT_KERNEL(hnh_attn_add_fwd_csr_p), HNH_GAT_KERNEL(hnh_attn_add_row_csr_p), HNH_GAT_KERNEL(hnh_attn_add_col_csr_p),
+        require_kernels("score additive", {HNH_GAT_KERNEL(hnh_attn_add_fwd_csr_p), HNH_GAT_KERNEL(hnh_attn_add_row_csr_p), HNH_GAT_KERNEL(hnh_attn_add_col_csr_p),
                          HNH_GAT_KERNEL(hnh_attn_add_scores_f64), HNH_GAT_KERNEL(hnh_attn_add_pack_f64), HNH_GAT_KERNEL(hnh_attn_add_update_f64)});
     }
     // The gatv2 score: no attention dropout (its passes have no mask); its kernel group and the pack kernel of the fused backward it reuses.
@@ -1634,10 +1629,9 @@ private:
         if (attn_p_ > 0.0)
             throw hnh::Error("Error, GAT score gatv2 does not support attention dropout (p = " + std::to_string(attn_p_) +
                              "): its passes have no mask (include/hnh_attn_v2.h)");
-        require_kernels("score gatv2", "include/hnh_attn_v2.h",
-                        {HNH_GAT_KERNEL(hnh_attn_v2_fwd_csr_p), HNH_GAT_KERNEL(hnh_attn_v2_row_csr_p), HNH_GAT_KERNEL(hnh_attn_v2_col_csr_p),
+        require_kernels("score gatv2", {HNH_GAT_KERNEL(hnh_attn_v2_fwd_csr_p), HNH_GAT_KERNEL(hnh_attn_v2_row_csr_p), HNH_GAT_KERNEL(hnh_attn_v2_col_csr_p),
                          HNH_GAT_KERNEL(hnh_attn_v2_finish_f64)});
-        require_kernels("score gatv2", "include/hnh_attn_grad.h", {HNH_GAT_KERNEL(hnh_attn_grad_pack_f64)});
+        require_kernels("score gatv2", {HNH_GAT_KERNEL(hnh_attn_grad_pack_f64)});
     }
     // The transformer score: no attention dropout (its passes have no mask); its kernel group and the pack kernel of the fused backward,
     // which builds all of its gathered operands.
@@ -1648,9 +1642,8 @@ private:
         if (attn_p_ > 0.0)
             throw hnh::Error("Error, GAT score transformer does not support attention dropout (p = " + std::to_string(attn_p_) +
                              "): its passes have no mask (include/hnh_attn_qkv.h)");
-        require_kernels("score transformer", "include/hnh_attn_qkv.h",
-                        {HNH_GAT_KERNEL(hnh_attn_qkv_fwd_csr_p), HNH_GAT_KERNEL(hnh_attn_qkv_row_csr_p), HNH_GAT_KERNEL(hnh_attn_qkv_col_csr_p)});
-        require_kernels("score transformer", "include/hnh_attn_grad.h", {HNH_GAT_KERNEL(hnh_attn_grad_pack_f64)});
+        require_kernels("score transformer", {HNH_GAT_KERNEL(hnh_attn_qkv_fwd_csr_p), HNH_GAT_KERNEL(hnh_attn_qkv_row_csr_p), HNH_GAT_KERNEL(hnh_attn_qkv_col_csr_p)});
+        require_kernels("score transformer", {HNH_GAT_KERNEL(hnh_attn_grad_pack_f64)});
     }
     // A layer with an edge bias: the transformer score's passes alone take one (its own conditions are check_transformer_supported's, which
     // follows); the kernel group.
@@ -1664,10 +1657,8 @@ private:
                 throw hnh::Error("Error, GAT " + what + " supports score transformer only, not score " + score_name(score_) +
                                  ": its passes have no bias operand (include/hnh_attn_edge.h)");
             if (backward && edge_bias_learned_[i])
-                require_kernels("learned edge bias", "include/hnh_attn_edge_grad.h",
-                                {HNH_GAT_KERNEL(hnh_attn_qkv_bias_grad_row_csr_p), HNH_GAT_KERNEL(hnh_attn_qkv_bias_grad_col_csr_p)});
-            require_kernels("edge bias", "include/hnh_attn_edge.h",
-                            {HNH_GAT_KERNEL(hnh_attn_qkv_bias_fwd_csr_p), HNH_GAT_KERNEL(hnh_attn_qkv_bias_row_csr_p),
+                require_kernels("learned edge bias", {HNH_GAT_KERNEL(hnh_attn_qkv_bias_grad_row_csr_p), HNH_GAT_KERNEL(hnh_attn_qkv_bias_grad_col_csr_p)});
+            require_kernels("edge bias", {HNH_GAT_KERNEL(hnh_attn_qkv_bias_fwd_csr_p), HNH_GAT_KERNEL(hnh_attn_qkv_bias_row_csr_p),
                              HNH_GAT_KERNEL(hnh_attn_qkv_bias_col_csr_p)});
         }
     }
@@ -1685,7 +1676,7 @@ private:
                 throw hnh::Error("Error, GAT softmax attention supports heads of at most 512 features (256 when odd), not " + std::to_string(f) +
                                  ": a row's softmax is one pass over its columns (include/hnh_attention.h)");
         }
-        require_kernels("softmax attention", "include/hnh_attention.h", {HNH_GAT_KERNEL(hnh_attn_softmax_csr_p)});
+        require_kernels("softmax attention", {HNH_GAT_KERNEL(hnh_attn_softmax_csr_p)});
     }
     // What an entry point refuses, in one order: the training state (labels, optimizer, training kernels, output width, whole rows), then
     // dropout, the activations, the norms, bias and skip connections, the edge bias, then the backward pass's conditions or, for a forward pass, the score's own.  The
@@ -1904,11 +1895,11 @@ private:
         g.f = f;
         g.softmax = softmax ? 1 : 0;
         g.leaky_alpha = leaky_relu_alpha;
-        bool ok = ds != nullptr && ds->attnGrad_pass(false, A, g, rows, true);  // row side: dA_i = sum_j de_ij A_j
+        bool ok = ds != nullptr && ds->attn_pass({1, g}, A, rows, true);  // row side: dA_i = sum_j de_ij A_j
         if (ok) {
             // column side onto the same rows; the moving operand is the packed one
             ScheduleWidth width(d_ops, pw, f);
-            ok = ds->attnGrad_pass(true, P, g, rows, false);
+            ok = ds->attn_pass({2, g}, P, rows, false);
         }
         require_own_rows("fused backward", !ok);
     }
@@ -1947,11 +1938,11 @@ private:
         if (ds != nullptr) {  // the moving operand is M, then Q
             ScheduleWidth width(d_ops, mw, f);
             g.vec = D.data();
-            ok = ds->attnAdditive_pass(1, M, g, rows, true, drop ? &dr : nullptr);  // row side: ds
+            ok = ds->attn_pass({1, g, drop ? &dr : nullptr}, M, rows, true);  // row side: ds
             if (ok) {
                 d_ops->setRValue(qw);
                 g.vec = D.data() + 1;
-                ok = ds->attnAdditive_pass(2, Q, g, rows, true, drop ? &dr : nullptr);  // column side: dAgg, dt
+                ok = ds->attn_pass({2, g, drop ? &dr : nullptr}, Q, rows, true);  // column side: dAgg, dt
             }
         }
         require_own_rows("score additive", !ok);
@@ -1989,14 +1980,14 @@ private:
         g.ld_out = fe;
         g.f = f;
         g.leaky_alpha = leaky_relu_alpha;
-        bool ok = ds != nullptr && ds->attnV2_pass(1, A, g, rows, true);  // row side: R
+        bool ok = ds != nullptr && ds->attn_pass({1, g}, A, rows, true);  // row side: R
         if (ok) {
             // column side: C and dAgg; the moving operand is the packed one
             ScheduleWidth width(d_ops, pw, f);
             g.Out = Cm.data();
             g.Out2 = dAgg.data();
             g.ld_out2 = fe;
-            ok = ds->attnV2_pass(2, P, g, rows, true);
+            ok = ds->attn_pass({2, g}, P, rows, true);
         }
         require_own_rows("score gatv2", !ok);
         HNH_GAT_CALL(hnh_attn_v2_finish_f64, dA_all.data(), hf, (int64_t)h * f, dAgg.data(), fe, Rm.data(), fe, Cm.data(), fe, A.data(), f, g.a,
@@ -2059,7 +2050,13 @@ private:
                     if (d.size() != edge_bias_[k][(size_t)i].size()) d = VectorXd(edge_bias_[k][(size_t)i].size());
                     db[k] = &d;
                 }
-            ok = ds->attnQKV_pass(1, KV, g, rows, true, 0u, biased ? &edge_bias_[0][(size_t)i] : nullptr, db[0], h > 0);  // row side: dQ
+            auto with_edge = [&](hnh::AttnPass pass, int k) {  // (S's order for the row pass, S^T's for the column pass)
+                pass.bias = biased ? &edge_bias_[k][(size_t)i] : nullptr;
+                pass.dbias = db[k];
+                pass.accumulate = h > 0;
+                return pass;
+            };
+            ok = ds->attn_pass(with_edge({1, g}, 0), KV, rows, true);  // row side: dQ
             if (ok) {
                 d_ops->setRValue(pw);
                 g.X = qk.K.data();
@@ -2068,7 +2065,7 @@ private:
                 g.Out = dK_all.data() + at;
                 g.Out2 = dA_all.data() + at;
                 g.ld_out2 = hf;
-                ok = ds->attnQKV_pass(2, P, g, rows, true, 0u, biased ? &edge_bias_[1][(size_t)i] : nullptr, db[1], h > 0);  // column side: dK, dV
+                ok = ds->attn_pass(with_edge({2, g}, 1), P, rows, true);  // column side: dK, dV
                 if (ok && learned && h + 1 == layers[(size_t)i].num_heads) dbias_held_[(size_t)i] = 1;
             }
         }
@@ -2169,7 +2166,7 @@ private:
             if (ds != nullptr) {
                 ScheduleWidth width(d_ops, (int)A.cols(), f);
                 const hnh_attn_drop dr = attn_drop_args(i, j);
-                ok = ds->attnAdditive_pass(0, A, g, A.rows(), true, attn_p_ > 0.0 ? &dr : nullptr, s.flags);
+                ok = ds->attn_pass({0, g, attn_p_ > 0.0 ? &dr : nullptr, s.flags}, A, A.rows(), true);
             }
             require_own_rows("score additive", !ok);
             return;
@@ -2182,7 +2179,7 @@ private:
             g.ld_x = A.cols();
             g.a = attn_vector(i, j, 0);
             s.fill(g);
-            require_own_rows("score gatv2", ds == nullptr || !ds->attnV2_pass(0, A, g, A.rows(), true, s.flags));
+            require_own_rows("score gatv2", ds == nullptr || !ds->attn_pass({0, g, nullptr, s.flags}, A, A.rows(), true));
             return;
         }
         if (score_ == HNH_GAT_SCORE_TRANSFORMER) {
@@ -2206,7 +2203,9 @@ private:
             bool ok = false;
             if (ds != nullptr) {
                 ScheduleWidth width(d_ops, (int)KV.cols(), f);
-                ok = ds->attnQKV_pass(0, KV, g, A.rows(), true, s.flags, edge_bias_on_[(size_t)i] ? &edge_bias_[0][(size_t)i] : nullptr);
+                hnh::AttnPass pass = {0, g, nullptr, s.flags};
+                pass.bias = edge_bias_on_[(size_t)i] ? &edge_bias_[0][(size_t)i] : nullptr;
+                ok = ds->attn_pass(pass, KV, A.rows(), true);
             }
             require_own_rows("score transformer", !ok);
             return;

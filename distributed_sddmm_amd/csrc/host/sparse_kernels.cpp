@@ -1,5 +1,5 @@
-#include <functional>
 #include "sparse_kernels.hpp"
+#include <type_traits>
 
 // SDDMM of operands up to this many columns goes through the nonzero-balanced COO kernel (StandardKernel::sddmm_local)
 static constexpr int64_t kCooSddmmMaxWidth = 16;
@@ -127,8 +127,7 @@ bool StandardKernel::softmax_block(SpmatLocal& S, DenseMatrix& A, DenseMatrix& B
                                    const hnh_attn_state& state, bool finish) {
     hnh::World* w = S.world;
     if (w->be->hnh_attn_softmax_csr_p == nullptr)
-        throw hnh::Error(std::string("Error, softmax attention needs the kernel hnh_attn_softmax_csr_p, which the kernel library ") + w->be->path +
-                         " does not export (include/hnh_attention.h)");
+        throw hnh::Error(w->be->missing_kernel("softmax attention", "hnh_attn_softmax_csr_p"));
     if (A.cols() != B.cols() || Out.cols() != A.cols()) hnh::fatal("Error, fused operands must have the same number of columns!");
     if (Out.rows() != A.rows()) hnh::fatal("Error, the softmax pass needs an output of the row operand's shape!");
     CSRLocal* blk = S.csr_blocks[block];
@@ -155,13 +154,12 @@ bool StandardKernel::softmax_block(SpmatLocal& S, DenseMatrix& A, DenseMatrix& B
     return true;
 }
 
-// The block and window handling that the attention passes share around their backend call `call(descriptor, window)`, `pass` in the complaints.
+// The block and window handling round an attention pass's backend call `call(descriptor, window)`, `pass` in the complaints.
 // An absent or empty block still gets the call, with the output's rows alone: an overwrite's zeroing, the state reset and the forward finish
 // apply to it too.  Otherwise the call runs between begin() and end(launches), the profile's event pair, with the panel count of a `width`
 // wide operand when no window is selected.  finish_text != nullptr: the call finishes a forward pass, which belongs to the block's last window.
-template <typename Call, typename Begin, typename End>
-static void attn_block_call(SpmatLocal& S, int block, int64_t rows, const std::string& pass, const char* finish_text, int width, bool profile,
-                            Call&& call, Begin&& begin, End&& end) {
+template <typename Call>
+void StandardKernel::attn_block_call(SpmatLocal& S, int block, int64_t rows, const std::string& pass, const char* finish_text, int width, Call&& call) {
     hnh::World* w = S.world;
     CSRLocal* blk = S.csr_blocks[block];
     if (blk == nullptr || blk->num_coords == 0) {
@@ -172,188 +170,144 @@ static void attn_block_call(SpmatLocal& S, int block, int64_t rows, const std::s
         return;
     }
     if (blk->transpose) hnh::fatal("Error, local matrix is transposed, can't perform " + pass);
-    begin();
+    begin(w);
     hnh_csr_window win;
     const hnh_csr_block desc = blk->block_args();
     if (desc.rows != rows) hnh::fatal("Error, " + pass + " needs an output of the block's rows!");
     const bool windowed = blk->window_args(&win);
     if (windowed && finish_text != nullptr && !win.last) hnh::fatal(finish_text);
     call(desc, windowed ? &win : nullptr);
-    end((profile && !windowed) ? w->be->hnh_panel_count(w->ctx, desc.rows, desc.nnz, desc.cols, width, desc.max_row_nnz) : 1);
+    end(w, (profile && !windowed) ? w->be->hnh_panel_count(w->ctx, desc.rows, desc.nnz, desc.cols, width, desc.max_row_nnz) : 1);
 }
 
-bool KernelImplementation::attn_grad_local(SpmatLocal& S, int block, const hnh_attn_grad& args, bool column_side, unsigned flags, int64_t rows) {
+// ---- the attention passes' entry points (include/hnh_attn_grad.h, _additive.h, _dropout.h, _v2.h, _qkv.h, _edge.h, _edge_grad.h, _coef.h):
+// one row each.  A further score is a further alternative of hnh::AttnPass::args, its rows here and its call in attn_block.
+using hnh::AttnPass;
+namespace {
+enum Variant { PLAIN, DROP, BIAS, BIAS_GRAD };  // the plain entry point; with attention dropout; with an edge bias; ... and its gradient
+Variant variant_of(const AttnPass& p) {
+    if (p.family() == AttnPass::QKV) return p.dbias ? BIAS_GRAD : (p.bias ? BIAS : PLAIN);
+    return (p.family() == AttnPass::ADDITIVE && p.drop) ? DROP : PLAIN;  // (the export takes `drop` as an argument of its one entry point)
+}
+// the gathered operand's width, which hnh_panel_count splits into column panels, from the head's f
+int w_head(const AttnPass& p) { return std::visit([](const auto& a) { return (int)a.f; }, p.args); }
+int w_pair(const AttnPass& p) { return 2 * w_head(p); }
+int w_scored(const AttnPass& p) { return HNH_ATTN_ADD_SCORED_WIDTH(w_head(p)); }
+int w_add_packed(const AttnPass& p) { return HNH_ATTN_ADD_PACKED_WIDTH(w_head(p)); }
+int w_kv(const AttnPass& p) { return HNH_ATTN_GRAD_PACKED_WIDTH(w_head(p), 0); }
+int w_packed(const AttnPass& p) { return HNH_ATTN_GRAD_PACKED_WIDTH(w_head(p), 1); }
+int w_coef(const AttnPass& p) { return std::get<hnh_attn_coef>(p.args).score == HNH_ATTN_COEF_ADDITIVE ? HNH_ATTN_COEF_PAIR_WIDTH : w_head(p); }
+
+struct AttnEntry {
+    AttnPass::Family family;
+    int pass;
+    Variant variant;
+    void* (*fn)(const hnh::Backend&);  // the Backend member
+    const char* symbol;
+    const char *feature, *label, *noun;  // "<feature> needs the kernel ..."; attn_block_call's complaints; "... has no <noun> (...)"
+    const char* finish_text;             // of a forward pass's closing call, or none
+    int (*width)(const AttnPass&);
+};
+#define HNH_ATTN_ENTRY(family, pass, variant, sym, ...) \
+    {AttnPass::family, pass, variant, [](const hnh::Backend& be) { return (void*)be.sym; }, #sym, __VA_ARGS__}
+#define GRAD_WORDS "the fused attention backward", "the fused attention backward", "fused attention backward pass"
+#define ADD_WORDS "the additive attention score", "the additive attention pass", "additive attention pass"
+#define V2_WORDS "the gatv2 attention score", "the gatv2 attention pass", "gatv2 attention pass"
+#define QKV_WORDS(with) "the transformer attention score" with, "the transformer attention pass" with, "transformer attention pass"
+#define COEF_WORDS "the export of the attention coefficients", "the attention-coefficient export", "attention-coefficient export"
+#define FINISH(score) "Error, the " score " forward finish belongs to the block's last window!"
+const AttnEntry kAttnEntries[] = {
+    HNH_ATTN_ENTRY(GRAD, 1, PLAIN, hnh_attn_grad_row_csr_p, GRAD_WORDS, nullptr, w_head),
+    HNH_ATTN_ENTRY(GRAD, 2, PLAIN, hnh_attn_grad_col_csr_p, GRAD_WORDS, nullptr, w_pair),
+    HNH_ATTN_ENTRY(ADDITIVE, 0, PLAIN, hnh_attn_add_fwd_csr_p, ADD_WORDS, FINISH("additive"), w_scored),
+    HNH_ATTN_ENTRY(ADDITIVE, 1, PLAIN, hnh_attn_add_row_csr_p, ADD_WORDS, nullptr, w_scored),
+    HNH_ATTN_ENTRY(ADDITIVE, 2, PLAIN, hnh_attn_add_col_csr_p, ADD_WORDS, nullptr, w_add_packed),
+    HNH_ATTN_ENTRY(ADDITIVE, 0, DROP, hnh_attn_drop_fwd_csr_p, ADD_WORDS, FINISH("additive"), w_add_packed),
+    HNH_ATTN_ENTRY(ADDITIVE, 1, DROP, hnh_attn_drop_row_csr_p, ADD_WORDS, nullptr, w_add_packed),
+    HNH_ATTN_ENTRY(ADDITIVE, 2, DROP, hnh_attn_drop_col_csr_p, ADD_WORDS, nullptr, w_add_packed),
+    HNH_ATTN_ENTRY(GATV2, 0, PLAIN, hnh_attn_v2_fwd_csr_p, V2_WORDS, FINISH("gatv2"), w_head),
+    HNH_ATTN_ENTRY(GATV2, 1, PLAIN, hnh_attn_v2_row_csr_p, V2_WORDS, nullptr, w_head),
+    HNH_ATTN_ENTRY(GATV2, 2, PLAIN, hnh_attn_v2_col_csr_p, V2_WORDS, nullptr, w_packed),
+    HNH_ATTN_ENTRY(QKV, 0, PLAIN, hnh_attn_qkv_fwd_csr_p, QKV_WORDS(""), FINISH("transformer"), w_kv),
+    HNH_ATTN_ENTRY(QKV, 1, PLAIN, hnh_attn_qkv_row_csr_p, QKV_WORDS(""), nullptr, w_kv),
+    HNH_ATTN_ENTRY(QKV, 2, PLAIN, hnh_attn_qkv_col_csr_p, QKV_WORDS(""), nullptr, w_packed),
+    HNH_ATTN_ENTRY(QKV, 0, BIAS, hnh_attn_qkv_bias_fwd_csr_p, QKV_WORDS(" with an edge bias"), FINISH("transformer"), w_kv),
+    HNH_ATTN_ENTRY(QKV, 1, BIAS, hnh_attn_qkv_bias_row_csr_p, QKV_WORDS(" with an edge bias"), nullptr, w_kv),
+    HNH_ATTN_ENTRY(QKV, 2, BIAS, hnh_attn_qkv_bias_col_csr_p, QKV_WORDS(" with an edge bias"), nullptr, w_packed),
+    HNH_ATTN_ENTRY(QKV, 1, BIAS_GRAD, hnh_attn_qkv_bias_grad_row_csr_p, QKV_WORDS(" with a learned edge bias"), nullptr, w_kv),
+    HNH_ATTN_ENTRY(QKV, 2, BIAS_GRAD, hnh_attn_qkv_bias_grad_col_csr_p, QKV_WORDS(" with a learned edge bias"), nullptr, w_packed),
+    HNH_ATTN_ENTRY(COEF, 0, PLAIN, hnh_attn_coef_csr_p, COEF_WORDS, nullptr, w_coef),
+};
+#undef HNH_ATTN_ENTRY
+#undef GRAD_WORDS
+#undef ADD_WORDS
+#undef V2_WORDS
+#undef QKV_WORDS
+#undef COEF_WORDS
+#undef FINISH
+// attn_block calls a row through the signature of ONE member per variant: the members that share a call must share their type
+template <typename F, typename... G>
+constexpr bool kSameSignature = (std::is_same_v<F, G> && ...);
+static_assert(kSameSignature<decltype(&::hnh_attn_grad_row_csr_p), decltype(&::hnh_attn_grad_col_csr_p)>);
+static_assert(kSameSignature<decltype(&::hnh_attn_add_fwd_csr_p), decltype(&::hnh_attn_add_row_csr_p), decltype(&::hnh_attn_add_col_csr_p)>);
+static_assert(kSameSignature<decltype(&::hnh_attn_drop_fwd_csr_p), decltype(&::hnh_attn_drop_row_csr_p), decltype(&::hnh_attn_drop_col_csr_p)>);
+static_assert(kSameSignature<decltype(&::hnh_attn_v2_fwd_csr_p), decltype(&::hnh_attn_v2_row_csr_p), decltype(&::hnh_attn_v2_col_csr_p)>);
+static_assert(kSameSignature<decltype(&::hnh_attn_qkv_fwd_csr_p), decltype(&::hnh_attn_qkv_row_csr_p), decltype(&::hnh_attn_qkv_col_csr_p)>);
+static_assert(kSameSignature<decltype(&::hnh_attn_qkv_bias_fwd_csr_p), decltype(&::hnh_attn_qkv_bias_row_csr_p), decltype(&::hnh_attn_qkv_bias_col_csr_p)>);
+static_assert(kSameSignature<decltype(&::hnh_attn_qkv_bias_grad_row_csr_p), decltype(&::hnh_attn_qkv_bias_grad_col_csr_p)>);
+const AttnEntry& attn_entry(const AttnPass& p) {
+    if (p.dbias != nullptr && p.pass == 0) hnh::fatal("Error, the edge bias's gradient belongs to the backward passes!");
+    for (const AttnEntry& e : kAttnEntries)
+        if (e.family == p.family() && e.pass == p.pass && e.variant == variant_of(p)) return e;
+    hnh::fatal("Error, attn_local: the family has no pass " + std::to_string(p.pass) + "!");
+    return kAttnEntries[0];
+}
+}  // namespace
+
+std::string KernelImplementation::attn_missing(const AttnPass& pass) {
+    return std::string("Error, the kernel implementation has no ") + attn_entry(pass).noun + " (KernelImplementation::attn_local)!";
+}
+
+bool KernelImplementation::attn_local(SpmatLocal& S, int block, const AttnPass& pass, unsigned flags, int64_t rows, bool finish) {
     StandardKernel* k = dynamic_cast<StandardKernel*>(this);
-    return k != nullptr && k->attn_grad_block(S, block, args, column_side, flags, rows);
+    return k != nullptr && k->attn_block(S, block, pass, flags, rows, finish);
 }
 
-// The two passes of the fused attention backward (include/hnh_attn_grad.h), next to fused_local: same block and window handling.
-bool StandardKernel::attn_grad_block(SpmatLocal& S, int block, const hnh_attn_grad& args, bool column_side, unsigned flags, int64_t rows) {
+// Every attention pass, next to fused_local: the entry point and its words from the table, the shared block and window handling, and the
+// one place where the families differ, their entry points' signatures.
+bool StandardKernel::attn_block(SpmatLocal& S, int block, const AttnPass& pass, unsigned flags, int64_t rows, bool finish) {
     hnh::World* w = S.world;
-    auto fn = column_side ? w->be->hnh_attn_grad_col_csr_p : w->be->hnh_attn_grad_row_csr_p;
-    const char* name = column_side ? "hnh_attn_grad_col_csr_p" : "hnh_attn_grad_row_csr_p";
-    if (fn == nullptr)
-        throw hnh::Error(std::string("Error, the fused attention backward needs the kernel ") + name + ", which the kernel library " + w->be->path +
-                         " does not export (include/hnh_attn_grad.h)");
-    attn_block_call(S, block, rows, "the fused attention backward", nullptr, column_side ? 2 * args.f : args.f, profile,
-                    [&](const hnh_csr_block& d, const hnh_csr_window* win) { w->check(fn(w->ctx, &d, &args, flags, win, HNH_STREAM_COMPUTE), name); },
-                    [&] { begin(w); }, [&](long launches) { end(w, launches); });
-    return true;
-}
-
-bool KernelImplementation::attn_additive_local(SpmatLocal& S, int block, const hnh_attn_add& args, int pass, unsigned flags, int64_t rows, bool finish) {
-    return attn_additive_local(S, block, args, pass, flags, rows, finish, nullptr);
-}
-
-bool KernelImplementation::attn_additive_local(SpmatLocal& S, int block, const hnh_attn_add& args, int pass, unsigned flags, int64_t rows, bool finish,
-                                               const hnh_attn_drop* drop) {
-    StandardKernel* k = dynamic_cast<StandardKernel*>(this);
-    return k != nullptr && k->attn_additive_block(S, block, args, pass, flags, rows, finish, drop);
-}
-
-// The three passes of the additive-score attention (include/hnh_attn_additive.h), next to attn_grad_block: same block and window handling.
-bool StandardKernel::attn_additive_block(SpmatLocal& S, int block, const hnh_attn_add& args, int pass, unsigned flags, int64_t rows, bool finish) {
-    return attn_additive_block(S, block, args, pass, flags, rows, finish, nullptr);
-}
-
-// ... and with `drop` their DROP instances (include/hnh_attn_dropout.h): the same calls with one more argument.
-bool StandardKernel::attn_additive_block(SpmatLocal& S, int block, const hnh_attn_add& args, int pass, unsigned flags, int64_t rows, bool finish,
-                                         const hnh_attn_drop* drop) {
-    hnh::World* w = S.world;
-    auto plain = pass == 0 ? w->be->hnh_attn_add_fwd_csr_p : (pass == 1 ? w->be->hnh_attn_add_row_csr_p : w->be->hnh_attn_add_col_csr_p);
-    auto masked = pass == 0 ? w->be->hnh_attn_drop_fwd_csr_p : (pass == 1 ? w->be->hnh_attn_drop_row_csr_p : w->be->hnh_attn_drop_col_csr_p);
-    const char* name = drop ? (pass == 0 ? "hnh_attn_drop_fwd_csr_p" : (pass == 1 ? "hnh_attn_drop_row_csr_p" : "hnh_attn_drop_col_csr_p"))
-                            : (pass == 0 ? "hnh_attn_add_fwd_csr_p" : (pass == 1 ? "hnh_attn_add_row_csr_p" : "hnh_attn_add_col_csr_p"));
-    if (drop ? masked == nullptr : plain == nullptr)
-        throw hnh::Error(std::string("Error, the additive attention score needs the kernel ") + name + ", which the kernel library " + w->be->path +
-                         " does not export (" + (drop ? "include/hnh_attn_dropout.h" : "include/hnh_attn_additive.h") + ")");
-    auto fn = [&](hnh_ctx* ctx, const hnh_csr_block* b, const hnh_attn_add* a, unsigned fl, const hnh_csr_window* win, int stream) {
-        return drop ? masked(ctx, b, a, drop, fl, win, stream) : plain(ctx, b, a, fl, win, stream);
-    };
-    const unsigned f = flags | ((pass == 0 && finish) ? HNH_ATTN_FINISH : 0u);
-    const char* finish_text = (pass == 0 && finish) ? "Error, the additive forward finish belongs to the block's last window!" : nullptr;
-    attn_block_call(S, block, rows, "the additive attention pass", finish_text, (pass == 2 || drop) ? HNH_ATTN_ADD_PACKED_WIDTH(args.f) : HNH_ATTN_ADD_SCORED_WIDTH(args.f),
-                    profile, [&](const hnh_csr_block& d, const hnh_csr_window* win) { w->check(fn(w->ctx, &d, &args, f, win, HNH_STREAM_COMPUTE), name); },
-                    [&] { begin(w); }, [&](long launches) { end(w, launches); });
-    return true;
-}
-
-bool KernelImplementation::attn_v2_local(SpmatLocal& S, int block, const hnh_attn_v2& args, int pass, unsigned flags, int64_t rows, bool finish) {
-    StandardKernel* k = dynamic_cast<StandardKernel*>(this);
-    return k != nullptr && k->attn_v2_block(S, block, args, pass, flags, rows, finish);
-}
-
-// The three sparse passes of the GATv2 attention (include/hnh_attn_v2.h), next to attn_additive_block: same block and window handling.
-bool StandardKernel::attn_v2_block(SpmatLocal& S, int block, const hnh_attn_v2& args, int pass, unsigned flags, int64_t rows, bool finish) {
-    hnh::World* w = S.world;
-    auto fn = pass == 0 ? w->be->hnh_attn_v2_fwd_csr_p : (pass == 1 ? w->be->hnh_attn_v2_row_csr_p : w->be->hnh_attn_v2_col_csr_p);
-    const char* name = pass == 0 ? "hnh_attn_v2_fwd_csr_p" : (pass == 1 ? "hnh_attn_v2_row_csr_p" : "hnh_attn_v2_col_csr_p");
-    if (fn == nullptr)
-        throw hnh::Error(std::string("Error, the gatv2 attention score needs the kernel ") + name + ", which the kernel library " + w->be->path +
-                         " does not export (include/hnh_attn_v2.h)");
-    const unsigned f = flags | ((pass == 0 && finish) ? HNH_ATTN_FINISH : 0u);
-    const char* finish_text = (pass == 0 && finish) ? "Error, the gatv2 forward finish belongs to the block's last window!" : nullptr;
-    attn_block_call(S, block, rows, "the gatv2 attention pass", finish_text, pass == 2 ? HNH_ATTN_GRAD_PACKED_WIDTH(args.f, 1) : args.f, profile,
-                    [&](const hnh_csr_block& d, const hnh_csr_window* win) { w->check(fn(w->ctx, &d, &args, f, win, HNH_STREAM_COMPUTE), name); },
-                    [&] { begin(w); }, [&](long launches) { end(w, launches); });
-    return true;
-}
-
-bool KernelImplementation::attn_qkv_local(SpmatLocal& S, int block, const hnh_attn_qkv& args, int pass, unsigned flags, int64_t rows, bool finish) {
-    StandardKernel* k = dynamic_cast<StandardKernel*>(this);
-    return k != nullptr && k->attn_qkv_block(S, block, args, pass, flags, rows, finish);
-}
-
-// The three sparse passes of the query/key/value attention (include/hnh_attn_qkv.h), next to attn_v2_block: same block and window handling;
-// the gathered width is the packed operand's of the pass.  `biased`: the entry points of include/hnh_attn_edge.h, which take the block's
-// slice of the bias vector behind the arguments; `graded`: those of include/hnh_attn_edge_grad.h (the backward passes alone), which also
-// take the block's slice of the bias's gradient and `accumulate`; every overload of attn_qkv_block is this one function.
-static bool attn_qkv_call(StandardKernel& k, SpmatLocal& S, int block, const hnh_attn_qkv& args, int pass, unsigned flags, int64_t rows, bool finish,
-                          bool biased, const double* bias, const std::function<void()>& begin, const std::function<void(long)>& end,
-                          bool graded = false, double* dbias = nullptr, bool accumulate = false) {
-    hnh::World* w = S.world;
-    const hnh::Backend* be = w->be;
-    auto plain = pass == 0 ? be->hnh_attn_qkv_fwd_csr_p : (pass == 1 ? be->hnh_attn_qkv_row_csr_p : be->hnh_attn_qkv_col_csr_p);
-    auto with_bias = pass == 0 ? be->hnh_attn_qkv_bias_fwd_csr_p : (pass == 1 ? be->hnh_attn_qkv_bias_row_csr_p : be->hnh_attn_qkv_bias_col_csr_p);
-    if (graded) {
-        if (pass != 1 && pass != 2) hnh::fatal("Error, the edge bias's gradient belongs to the backward passes!");
-        auto with_grad = pass == 1 ? be->hnh_attn_qkv_bias_grad_row_csr_p : be->hnh_attn_qkv_bias_grad_col_csr_p;
-        const char* gname = pass == 1 ? "hnh_attn_qkv_bias_grad_row_csr_p" : "hnh_attn_qkv_bias_grad_col_csr_p";
-        if (with_grad == nullptr)
-            throw hnh::Error(std::string("Error, the transformer attention score with a learned edge bias needs the kernel ") + gname +
-                             ", which the kernel library " + be->path + " does not export (include/hnh_attn_edge_grad.h)");
-        attn_block_call(S, block, rows, "the transformer attention pass with a learned edge bias", nullptr, HNH_ATTN_GRAD_PACKED_WIDTH(args.f, pass == 2 ? 1 : 0),
-                        k.profile,
-                        [&](const hnh_csr_block& d, const hnh_csr_window* win) {
-                            w->check(with_grad(w->ctx, &d, &args, bias, dbias, accumulate ? 1 : 0, flags, win, HNH_STREAM_COMPUTE), gname);
-                        },
-                        begin, end);
-        return true;
-    }
-    const std::string name = std::string(biased ? "hnh_attn_qkv_bias_" : "hnh_attn_qkv_") + (pass == 0 ? "fwd" : (pass == 1 ? "row" : "col")) + "_csr_p";
-    if (biased ? with_bias == nullptr : plain == nullptr)
-        throw hnh::Error(std::string("Error, the transformer attention score") + (biased ? " with an edge bias" : "") + " needs the kernel " + name +
-                         ", which the kernel library " + be->path + " does not export (" + (biased ? "include/hnh_attn_edge.h" : "include/hnh_attn_qkv.h") + ")");
-    const unsigned f = flags | ((pass == 0 && finish) ? HNH_ATTN_FINISH : 0u);
-    const char* finish_text = (pass == 0 && finish) ? "Error, the transformer forward finish belongs to the block's last window!" : nullptr;
-    attn_block_call(S, block, rows, biased ? "the transformer attention pass with an edge bias" : "the transformer attention pass", finish_text,
-                    HNH_ATTN_GRAD_PACKED_WIDTH(args.f, pass == 2 ? 1 : 0), k.profile,
-                    [&](const hnh_csr_block& d, const hnh_csr_window* win) {
-                        w->check(biased ? with_bias(w->ctx, &d, &args, bias, f, win, HNH_STREAM_COMPUTE) : plain(w->ctx, &d, &args, f, win, HNH_STREAM_COMPUTE),
-                                 name.c_str());
-                    },
-                    begin, end);
-    return true;
-}
-
-bool StandardKernel::attn_qkv_block(SpmatLocal& S, int block, const hnh_attn_qkv& args, int pass, unsigned flags, int64_t rows, bool finish) {
-    return attn_qkv_call(*this, S, block, args, pass, flags, rows, finish, false, nullptr, [&] { begin(S.world); }, [&](long n) { end(S.world, n); });
-}
-
-bool KernelImplementation::attn_qkv_local(SpmatLocal& S, int block, const hnh_attn_qkv& args, int pass, unsigned flags, int64_t rows, bool finish,
-                                          const double* bias) {
-    StandardKernel* k = dynamic_cast<StandardKernel*>(this);
-    return k != nullptr && k->attn_qkv_block(S, block, args, pass, flags, rows, finish, bias);
-}
-
-bool StandardKernel::attn_qkv_block(SpmatLocal& S, int block, const hnh_attn_qkv& args, int pass, unsigned flags, int64_t rows, bool finish,
-                                    const double* bias) {
-    return attn_qkv_call(*this, S, block, args, pass, flags, rows, finish, true, bias, [&] { begin(S.world); }, [&](long n) { end(S.world, n); });
-}
-
-bool KernelImplementation::attn_qkv_local(SpmatLocal& S, int block, const hnh_attn_qkv& args, int pass, unsigned flags, int64_t rows, bool finish,
-                                          const double* bias, double* dbias, bool accumulate) {
-    StandardKernel* k = dynamic_cast<StandardKernel*>(this);
-    return k != nullptr && k->attn_qkv_block(S, block, args, pass, flags, rows, finish, bias, dbias, accumulate);
-}
-
-bool StandardKernel::attn_qkv_block(SpmatLocal& S, int block, const hnh_attn_qkv& args, int pass, unsigned flags, int64_t rows, bool finish,
-                                    const double* bias, double* dbias, bool accumulate) {
-    return attn_qkv_call(*this, S, block, args, pass, flags, rows, finish, true, bias, [&] { begin(S.world); }, [&](long n) { end(S.world, n); }, true, dbias,
-                         accumulate);
-}
-
-bool KernelImplementation::attn_coef_local(SpmatLocal& S, int block, const hnh_attn_coef& args, int64_t rows, const hnh_attn_drop* drop) {
-    StandardKernel* k = dynamic_cast<StandardKernel*>(this);
-    return k != nullptr && k->attn_coef_block(S, block, args, rows, drop);
-}
-
-// The export of the attention coefficients (include/hnh_attn_coef.h), next to attn_v2_block: same block and window handling; the values go
-// where an SDDMM's would (a lent slice of the caller's vector, or the block's own array).
-bool StandardKernel::attn_coef_block(SpmatLocal& S, int block, const hnh_attn_coef& args, int64_t rows, const hnh_attn_drop* drop) {
-    hnh::World* w = S.world;
-    const char* name = "hnh_attn_coef_csr_p";
-    if (w->be->hnh_attn_coef_csr_p == nullptr)
-        throw hnh::Error(std::string("Error, the export of the attention coefficients needs the kernel ") + name + ", which the kernel library " +
-                         w->be->path + " does not export (include/hnh_attn_coef.h)");
-    CSRLocal* blk = S.csr_blocks[block];
-    double* dst = blk == nullptr ? nullptr : (blk->sddmm_dst ? blk->sddmm_dst : blk->getActive()->values);
-    attn_block_call(S, block, rows, "the attention-coefficient export", nullptr,
-                    args.score == HNH_ATTN_COEF_ADDITIVE ? HNH_ATTN_COEF_PAIR_WIDTH : args.f, profile,
-                    [&](const hnh_csr_block& d, const hnh_csr_window* win) {
-                        w->check(w->be->hnh_attn_coef_csr_p(w->ctx, &d, dst, &args, drop, 0u, win, HNH_STREAM_COMPUTE), name);
-                    },
-                    [&] { begin(w); }, [&](long launches) { end(w, launches); });
+    const AttnEntry& e = attn_entry(pass);
+    void* fn = e.fn(*w->be);
+    if (fn == nullptr) throw hnh::Error(w->be->missing_kernel(e.feature, e.symbol));
+    const bool closes = pass.forward() && finish;
+    const unsigned f = flags | (closes ? HNH_ATTN_FINISH : 0u);
+    CSRLocal* blk = S.csr_blocks[block];  // (its lent slices: see attn_local)
+    attn_block_call(S, block, rows, e.label, closes ? e.finish_text : nullptr, e.width(pass), [&](const hnh_csr_block& d, const hnh_csr_window* win) {
+        hnh_ctx* c = w->ctx;
+        const int s = HNH_STREAM_COMPUTE;
+        auto as = [fn](auto* member) { return reinterpret_cast<decltype(member)>(fn); };  // fn with a Backend member's signature, which a variant's passes share
+        const int rc = std::visit(
+            [&](const auto& a) -> int {
+                using Args = std::decay_t<decltype(a)>;
+                if constexpr (std::is_same_v<Args, hnh_attn_grad>) return as(&::hnh_attn_grad_row_csr_p)(c, &d, &a, f, win, s);
+                else if constexpr (std::is_same_v<Args, hnh_attn_add>)
+                    return e.variant == DROP ? as(&::hnh_attn_drop_fwd_csr_p)(c, &d, &a, pass.drop, f, win, s) : as(&::hnh_attn_add_fwd_csr_p)(c, &d, &a, f, win, s);
+                else if constexpr (std::is_same_v<Args, hnh_attn_v2>) return as(&::hnh_attn_v2_fwd_csr_p)(c, &d, &a, f, win, s);
+                else if constexpr (std::is_same_v<Args, hnh_attn_qkv>) {
+                    const double* bias = (blk && e.variant != PLAIN) ? blk->spmm_values : nullptr;
+                    double* dbias = (blk && e.variant == BIAS_GRAD) ? blk->sddmm_dst : nullptr;
+                    return e.variant == BIAS_GRAD ? as(&::hnh_attn_qkv_bias_grad_row_csr_p)(c, &d, &a, bias, dbias, pass.accumulate ? 1 : 0, f, win, s)
+                           : e.variant == BIAS    ? as(&::hnh_attn_qkv_bias_fwd_csr_p)(c, &d, &a, bias, f, win, s)
+                                                  : as(&::hnh_attn_qkv_fwd_csr_p)(c, &d, &a, f, win, s);
+                } else {  // the coefficients go where an SDDMM's values would: the lent slice, or the block's own array
+                    double* coef = blk == nullptr ? nullptr : (blk->sddmm_dst ? blk->sddmm_dst : blk->getActive()->values);
+                    return as(&::hnh_attn_coef_csr_p)(c, &d, coef, &a, pass.drop, f, win, s);
+                }
+            },
+            pass.args);
+        w->check(rc, e.symbol);
+    });
     return true;
 }
 

@@ -9,6 +9,7 @@
 // issues per visiting block (15D_dense_shift.hpp:203-217).  The default implementation is literally that
 // pair of virtual calls; StandardKernel overrides it with the single-pass HIP kernel.
 #pragma once
+#include <variant>
 #include <vector>
 
 #include "common.hpp"
@@ -17,6 +18,29 @@
 
 using hnh::DenseMatrix;
 using hnh::VectorXd;
+
+namespace hnh {
+// One attention pass of the GAT, from the GAT to the kernel (Sparse15D_Dense_Shift::attn_pass, KernelImplementation::attn_local): which
+// family (the alternative that `args` holds, in this order), which pass and with what.
+struct AttnPass {
+    enum Family { GRAD, ADDITIVE, GATV2, QKV, COEF };  // fused backward, score additive, score gatv2, score transformer, coefficient export
+    int pass = 0;  // 0 = forward (and the export), 1 = backward row pass, both over S; 2 = backward column pass over S^T
+    std::variant<hnh_attn_grad, hnh_attn_add, hnh_attn_v2, hnh_attn_qkv, hnh_attn_coef> args;  // all five have f and Y / ld_y, which the walk writes
+    // (callers give the first four in this order and set the per-edge members below by name)
+    const hnh_attn_drop* drop = nullptr;  // ADDITIVE, COEF of score additive: attention dropout (include/hnh_attn_dropout.h)
+    unsigned finish_flags = 0u;           // HNH_ATTN_ACT_* / HNH_ATTN_ADDEND for a forward pass's closing call alone
+    // QKV: the per-edge bias (include/hnh_attn_edge.h) and, in the backward passes, its gradient (include/hnh_attn_edge_grad.h), set or with
+    // `accumulate` added to; COEF: the coefficients' destination.  One value per nonzero in the like_S_values layout (like_ST_values for pass 2).
+    const VectorXd* bias = nullptr;
+    VectorXd* dbias = nullptr;
+    bool accumulate = false;
+    VectorXd* coef = nullptr;
+
+    Family family() const { return (Family)args.index(); }
+    // a forward pass carries the rows' running state: its first call resets and its closing call finishes them (the export reads the stored lse)
+    bool forward() const { return pass == 0 && family() != COEF; }
+};
+}  // namespace hnh
 
 class KernelImplementation {
 public:
@@ -65,53 +89,18 @@ public:
     bool softmax_local(SpmatLocal& S, DenseMatrix& A, DenseMatrix& B, DenseMatrix& Out, int block, unsigned flags, const hnh_attn_state& state,
                        bool finish);
 
-    // One pass of the fused attention backward (include/hnh_attn_grad.h, the GAT's fused backward mode) on one block, or the selected
-    // window(s) of it: the row pass over a block of S, or with `column_side` the column pass over a block of S^T whose gathered operand
-    // is the packed one.  `args` carries the operands with their leading dimensions (args.Y = the gathered operand the schedule hands
-    // in); rows = the rows of the output (used when the block is absent: HNH_FUSED_OUT_OVERWRITE still has to leave zeros).  Returns
-    // false, having done nothing, when the implementation has no such pass.  NOT virtual, for softmax_local's reason.
-    bool attn_grad_local(SpmatLocal& S, int block, const hnh_attn_grad& args, bool column_side, unsigned flags, int64_t rows);
-
-    // One pass of the additive-score attention (include/hnh_attn_additive.h, the GAT's score "additive") on one block, or the selected
-    // window(s) of it: pass 0 = forward over a block of S (continues the rows' running state; `finish` = the pass's last call, which a
-    // schedule makes also when the block is absent), 1 = backward row pass over a block of S, 2 = backward column pass over a block of
-    // S^T.  `args` carries the operands with their leading dimensions (args.Y = the gathered operand the schedule hands in); rows =
-    // the rows of the output (used when the block is absent).  Returns false, having done nothing, when the implementation has no such
-    // pass.  NOT virtual, for softmax_local's reason.
-    bool attn_additive_local(SpmatLocal& S, int block, const hnh_attn_add& args, int pass, unsigned flags, int64_t rows, bool finish);
-    // The same pass with attention dropout (include/hnh_attn_dropout.h) when `drop` is not null: args.Y is then M' / Q', whose rows carry
-    // their global ids, and drop->row_id0 is the global id of the block's row 0.  An overload, not a changed signature and not a virtual:
-    // the symbol above stays, and no vtable changes.
-    bool attn_additive_local(SpmatLocal& S, int block, const hnh_attn_add& args, int pass, unsigned flags, int64_t rows, bool finish,
-                             const hnh_attn_drop* drop);
-
-    // One pass of the GATv2 attention (include/hnh_attn_v2.h, the GAT's score "gatv2") on one block, or the selected window(s) of it: pass
-    // 0 = forward over a block of S (continues the rows' running state; `finish` = the pass's last call, which a schedule makes also when
-    // the block is absent), 1 = backward row pass over a block of S, 2 = backward column pass over a block of S^T whose gathered operand
-    // is the packed one of include/hnh_attn_grad.h.  `args` and `rows` as for attn_additive_local.  Returns false, having done nothing,
-    // when the implementation has no such pass.  NOT virtual, for softmax_local's reason.
-    bool attn_v2_local(SpmatLocal& S, int block, const hnh_attn_v2& args, int pass, unsigned flags, int64_t rows, bool finish);
-
-    // One pass of the query/key/value attention (include/hnh_attn_qkv.h, the GAT's score "transformer") on one block, or the selected
-    // window(s) of it: pass 0 = forward over a block of S, 1 = backward row pass over a block of S (both gather the packed [K | V]), 2 =
-    // backward column pass over a block of S^T (gathers the packed [Q | dZ | lse delta]).  `args`, `rows` and `finish` as for attn_v2_local.
-    // Returns false, having done nothing, when the implementation has no such pass.  NOT virtual, for softmax_local's reason.
-    bool attn_qkv_local(SpmatLocal& S, int block, const hnh_attn_qkv& args, int pass, unsigned flags, int64_t rows, bool finish);
-    // ... with a per-edge bias (include/hnh_attn_edge.h): `bias` is the block's slice, entry e of the block's CSR order at bias[e] (of S
-    // for passes 0 and 1, of S^T for pass 2); it may be null only for an absent or empty block.  An overload, not a default argument: the
-    // earlier symbol stays.
-    bool attn_qkv_local(SpmatLocal& S, int block, const hnh_attn_qkv& args, int pass, unsigned flags, int64_t rows, bool finish, const double* bias);
-    // ... and with the bias's gradient (include/hnh_attn_edge_grad.h; passes 1 and 2 alone): `dbias` is the block's slice like `bias`,
-    // dbias[e] = or, with `accumulate`, += dL/db_e of this head.  Another overload: the earlier symbols stay.
-    bool attn_qkv_local(SpmatLocal& S, int block, const hnh_attn_qkv& args, int pass, unsigned flags, int64_t rows, bool finish, const double* bias,
-                        double* dbias, bool accumulate);
-
-    // The export of the attention coefficients (include/hnh_attn_coef.h) on one block of S, or the selected window(s) of it: every nonzero
-    // of the call gets its coefficient in the block's value slice, which the schedule has lent from the caller's vector (CSRLocal::sddmm_dst)
-    // as for an SDDMM; without a lent slice the block's own value array takes them.  An absent or empty block has nothing to store.  `rows`
-    // as for attn_additive_local; `drop` (score additive only) or nullptr.  Returns false, having done nothing, when the implementation has
-    // no such pass.  NOT virtual, for softmax_local's reason.
-    bool attn_coef_local(SpmatLocal& S, int block, const hnh_attn_coef& args, int64_t rows, const hnh_attn_drop* drop);
+    // One attention pass (hnh::AttnPass above) on one block, or the selected window(s) of it: a block of S for passes 0 and 1, of S^T for
+    // pass 2.  The family's arguments carry the operands with their leading dimensions (Y = the gathered operand the schedule hands in);
+    // flags: as fused_local's, plus the activation bits of a forward pass's closing call; rows = the rows of the output (used when the
+    // block is absent: HNH_FUSED_OUT_OVERWRITE still has to leave zeros, a forward pass still resets and finishes its rows); `finish` =
+    // the last call of a forward pass, which a schedule makes also when the block is absent.  The per-edge extras are read from the
+    // block's lent slices (CSRLocal::spmm_values = the bias, CSRLocal::sddmm_dst = its gradient or the coefficients' destination), which
+    // the schedule lends from pass.bias / pass.dbias / pass.coef; the bias may be null only for an absent or empty block, and without a
+    // lent destination the block's own value array takes the coefficients.  Returns false, having done nothing, when the implementation
+    // has no such pass.  NOT virtual, for softmax_local's reason.
+    bool attn_local(SpmatLocal& S, int block, const hnh::AttnPass& pass, unsigned flags, int64_t rows, bool finish);
+    // "Error, the kernel implementation has no ... pass (KernelImplementation::attn_local)!", the words from the table of attn_block
+    static std::string attn_missing(const hnh::AttnPass& pass);
 
     // Row windows (CSRLocal::window): a schedule may select one column range of a block before calling the kernels, to
     // work on data that arrives piece by piece.  An implementation that honours CSRLocal::window says so here; for the
@@ -189,21 +178,8 @@ public:
     // KernelImplementation::softmax_local's pass (non-virtual: see there)
     bool softmax_block(SpmatLocal& S, DenseMatrix& A, DenseMatrix& B, DenseMatrix& Out, int block, unsigned flags, const hnh_attn_state& state,
                        bool finish);
-    // KernelImplementation::attn_grad_local's pass (non-virtual: see there)
-    bool attn_grad_block(SpmatLocal& S, int block, const hnh_attn_grad& args, bool column_side, unsigned flags, int64_t rows);
-    // KernelImplementation::attn_additive_local's pass (non-virtual: see there)
-    bool attn_additive_block(SpmatLocal& S, int block, const hnh_attn_add& args, int pass, unsigned flags, int64_t rows, bool finish);
-    bool attn_additive_block(SpmatLocal& S, int block, const hnh_attn_add& args, int pass, unsigned flags, int64_t rows, bool finish,
-                             const hnh_attn_drop* drop);
-    // KernelImplementation::attn_v2_local's pass (non-virtual: see there)
-    bool attn_v2_block(SpmatLocal& S, int block, const hnh_attn_v2& args, int pass, unsigned flags, int64_t rows, bool finish);
-    // KernelImplementation::attn_qkv_local's pass (non-virtual: see there)
-    bool attn_qkv_block(SpmatLocal& S, int block, const hnh_attn_qkv& args, int pass, unsigned flags, int64_t rows, bool finish);
-    bool attn_qkv_block(SpmatLocal& S, int block, const hnh_attn_qkv& args, int pass, unsigned flags, int64_t rows, bool finish, const double* bias);
-    bool attn_qkv_block(SpmatLocal& S, int block, const hnh_attn_qkv& args, int pass, unsigned flags, int64_t rows, bool finish, const double* bias,
-                        double* dbias, bool accumulate);
-    // KernelImplementation::attn_coef_local's pass (non-virtual: see there)
-    bool attn_coef_block(SpmatLocal& S, int block, const hnh_attn_coef& args, int64_t rows, const hnh_attn_drop* drop);
+    // KernelImplementation::attn_local's pass (non-virtual: see there)
+    bool attn_block(SpmatLocal& S, int block, const hnh::AttnPass& pass, unsigned flags, int64_t rows, bool finish);
     ~StandardKernel() override;
 
 private:
@@ -213,4 +189,5 @@ private:
     hnh::World* evw_ = nullptr;
     void begin(hnh::World* w);
     void end(hnh::World* w, long launches = 1);
+    template <typename Call> void attn_block_call(SpmatLocal& S, int block, int64_t rows, const std::string& pass, const char* finish_text, int width, Call&& call);
 };

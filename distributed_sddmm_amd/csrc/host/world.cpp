@@ -95,48 +95,9 @@ Backend* load_backend(const char* path_c) {
 #define HNH_BIND(sym)                                                                  \
     b->sym = (decltype(b->sym))dlsym(dl, #sym);                                        \
     if (!b->sym) fatal(std::string("Error, kernel library ") + path + " lacks symbol " #sym);
-    HNH_BIND(hnh_backend_name)
-    HNH_BIND(hnh_ctx_create) HNH_BIND(hnh_ctx_destroy) HNH_BIND(hnh_last_error) HNH_BIND(hnh_ctx_stream) HNH_BIND(hnh_ctx_device_identity)
-    HNH_BIND(hnh_malloc) HNH_BIND(hnh_free) HNH_BIND(hnh_memcpy) HNH_BIND(hnh_memset) HNH_BIND(hnh_stream_sync)
-    HNH_BIND(hnh_event_create) HNH_BIND(hnh_event_destroy) HNH_BIND(hnh_event_record) HNH_BIND(hnh_event_wait)
-    HNH_BIND(hnh_event_sync) HNH_BIND(hnh_event_query) HNH_BIND(hnh_event_elapsed_ms)
-    HNH_BIND(hnh_sddmm_coo) HNH_BIND(hnh_sddmm_csr) HNH_BIND(hnh_spmm_csr) HNH_BIND(hnh_fused_sddmm_spmm_csr)
-    HNH_BIND(hnh_sddmm_csr_ex) HNH_BIND(hnh_spmm_csr_ex) HNH_BIND(hnh_fused_sddmm_spmm_csr_ex) HNH_BIND(hnh_csr_max_row_nnz)
-    HNH_BIND(hnh_fused_sddmm_spmm_csr_x) HNH_BIND(hnh_row_epilogue_f64) HNH_BIND(hnh_row_epilogue_x) HNH_BIND(hnh_cg_step_f64)
-    HNH_BIND(hnh_tuples_sort) HNH_BIND(hnh_tuples_bucket_starts) HNH_BIND(hnh_tuples_transform) HNH_BIND(hnh_tuples_to_csr)
-    HNH_BIND(hnh_csr_window_bounds) HNH_BIND(hnh_sddmm_csr_w) HNH_BIND(hnh_spmm_csr_w) HNH_BIND(hnh_fused_sddmm_spmm_csr_w) HNH_BIND(hnh_tuples_remap_cols) HNH_BIND(hnh_tuples_dedup_max) HNH_BIND(hnh_tuples_take_strided)
-    HNH_BIND(hnh_panel_count) HNH_BIND(hnh_generate_er_keys) HNH_BIND(hnh_generate_rmat_keys) HNH_BIND(hnh_tuples_from_keys) HNH_BIND(hnh_tuples_relabel)
-    HNH_BIND(hnh_fill_f64) HNH_BIND(hnh_hadamard_f64) HNH_BIND(hnh_axpy_f64) HNH_BIND(hnh_expand_rowptr) HNH_BIND(hnh_sum_chunked_blocks_f64)
-    HNH_BIND(hnh_rowdot_f64) HNH_BIND(hnh_row_scale_add_f64) HNH_BIND(hnh_vec_add_scalar_f64) HNH_BIND(hnh_vec_div_f64) HNH_BIND(hnh_fill_hashed_f64)
-    HNH_BIND(hnh_gemm_f64) HNH_BIND(hnh_leaky_relu_f64) HNH_BIND(hnh_relu_store_cols_f64)
-    HNH_BIND(hnh_comm_unique_id) HNH_BIND(hnh_comm_init) HNH_BIND(hnh_comm_split) HNH_BIND(hnh_comm_destroy) HNH_BIND(hnh_comm_identity)
-    HNH_BIND(hnh_comm_sendrecv) HNH_BIND(hnh_comm_group_begin) HNH_BIND(hnh_comm_group_end) HNH_BIND(hnh_comm_allgather) HNH_BIND(hnh_comm_reduce_scatter_f64)
-    HNH_BIND(hnh_comm_allreduce_f64)
-    HNH_BIND(hnh_ipc_export) HNH_BIND(hnh_ipc_open) HNH_BIND(hnh_ipc_close) HNH_BIND(hnh_ipc_pull) HNH_BIND(hnh_ipc_flags_register) HNH_BIND(hnh_ipc_flags_unregister)
-    HNH_BIND(hnh_stream_write_flag) HNH_BIND(hnh_stream_wait_flag)
-    HNH_BIND(hnh_csr_plan_create) HNH_BIND(hnh_csr_plan_destroy) HNH_BIND(hnh_sddmm_csr_p) HNH_BIND(hnh_sddmm_csr_ps) HNH_BIND(hnh_spmm_csr_p) HNH_BIND(hnh_spmm_csr_pf) HNH_BIND(hnh_fused_sddmm_spmm_csr_p)
-#define HNH_BIND_OPTIONAL(sym) b->sym = (decltype(b->sym))dlsym(dl, #sym);
-    HNH_BIND_OPTIONAL(hnh_gemm_tn_f64_workspace) HNH_BIND_OPTIONAL(hnh_gemm_tn_f64) HNH_BIND_OPTIONAL(hnh_leaky_relu_grad_f64)
-    HNH_BIND_OPTIONAL(hnh_relu_grad_cols_f64) HNH_BIND_OPTIONAL(hnh_sum3_cols_f64) HNH_BIND_OPTIONAL(hnh_transpose_into_f64)
-    HNH_BIND_OPTIONAL(hnh_act_grad_cols_f64)
-    HNH_BIND_OPTIONAL(hnh_attn_softmax_csr_p) HNH_BIND_OPTIONAL(hnh_softmax_gate_f64) HNH_BIND_OPTIONAL(hnh_rowdot_cols_f64)
-    HNH_BIND_OPTIONAL(hnh_attn_grad_row_csr_p) HNH_BIND_OPTIONAL(hnh_attn_grad_col_csr_p) HNH_BIND_OPTIONAL(hnh_attn_grad_pack_f64)
-    HNH_BIND_OPTIONAL(hnh_attn_add_fwd_csr_p) HNH_BIND_OPTIONAL(hnh_attn_add_row_csr_p) HNH_BIND_OPTIONAL(hnh_attn_add_col_csr_p)
-    HNH_BIND_OPTIONAL(hnh_attn_add_scores_f64) HNH_BIND_OPTIONAL(hnh_attn_add_pack_f64) HNH_BIND_OPTIONAL(hnh_attn_add_update_f64)
-    HNH_BIND_OPTIONAL(hnh_attn_drop_fwd_csr_p) HNH_BIND_OPTIONAL(hnh_attn_drop_row_csr_p) HNH_BIND_OPTIONAL(hnh_attn_drop_col_csr_p)
-    HNH_BIND_OPTIONAL(hnh_attn_drop_scores_f64) HNH_BIND_OPTIONAL(hnh_attn_drop_pack_f64) HNH_BIND_OPTIONAL(hnh_feat_drop_f64)
-    HNH_BIND_OPTIONAL(hnh_dropout_words_u32)
-    HNH_BIND_OPTIONAL(hnh_xent_rows_f64_workspace) HNH_BIND_OPTIONAL(hnh_xent_rows_f64) HNH_BIND_OPTIONAL(hnh_optim_step_f64)
-    HNH_BIND_OPTIONAL(hnh_attn_v2_fwd_csr_p) HNH_BIND_OPTIONAL(hnh_attn_v2_row_csr_p) HNH_BIND_OPTIONAL(hnh_attn_v2_col_csr_p)
-    HNH_BIND_OPTIONAL(hnh_attn_v2_finish_f64)
-    HNH_BIND_OPTIONAL(hnh_attn_qkv_fwd_csr_p) HNH_BIND_OPTIONAL(hnh_attn_qkv_row_csr_p) HNH_BIND_OPTIONAL(hnh_attn_qkv_col_csr_p)
-    HNH_BIND_OPTIONAL(hnh_attn_qkv_bias_fwd_csr_p) HNH_BIND_OPTIONAL(hnh_attn_qkv_bias_row_csr_p) HNH_BIND_OPTIONAL(hnh_attn_qkv_bias_col_csr_p)
-    HNH_BIND_OPTIONAL(hnh_attn_qkv_bias_grad_row_csr_p) HNH_BIND_OPTIONAL(hnh_attn_qkv_bias_grad_col_csr_p)
-    HNH_BIND_OPTIONAL(hnh_attn_coef_csr_p) HNH_BIND_OPTIONAL(hnh_attn_coef_scores_f64)
-    HNH_BIND_OPTIONAL(hnh_skip_addend_cols_f64) HNH_BIND_OPTIONAL(hnh_skip_grad_cols_f64) HNH_BIND_OPTIONAL(hnh_colsum_f64_workspace)
-    HNH_BIND_OPTIONAL(hnh_colsum_f64)
-    HNH_BIND_OPTIONAL(hnh_layernorm_fwd_f64) HNH_BIND_OPTIONAL(hnh_layernorm_bwd_workspace) HNH_BIND_OPTIONAL(hnh_layernorm_bwd_f64)
-    HNH_BIND_OPTIONAL(hnh_bce_rows_f64_workspace) HNH_BIND_OPTIONAL(hnh_bce_rows_f64)
+    HNH_MANDATORY_KERNELS(HNH_BIND)
+#define HNH_BIND_OPTIONAL(header, sym) b->sym = (decltype(b->sym))dlsym(dl, #sym);
+    HNH_OPTIONAL_KERNELS(HNH_BIND_OPTIONAL)
 #undef HNH_BIND_OPTIONAL
 #ifdef HNH_MEASUREMENT_AIDS
     HNH_BIND(hnh_stream_delay_us) HNH_BIND(hnh_stream_paced_copy) HNH_BIND(hnh_stream_pace_begin) HNH_BIND(hnh_stream_pace_end)
@@ -146,6 +107,14 @@ Backend* load_backend(const char* path_c) {
     g_backends[path] = b;
     g_default = b;
     return b;
+}
+
+std::string Backend::missing_kernel(const std::string& who, const char* symbol) const {
+    const char* group = "not an optional kernel";
+#define HNH_HEADER_OF(header, sym) if (std::strcmp(symbol, #sym) == 0) group = header;
+    HNH_OPTIONAL_KERNELS(HNH_HEADER_OF)
+#undef HNH_HEADER_OF
+    return "Error, " + who + " needs the kernel " + symbol + ", which the kernel library " + path + " does not export (" + group + ")";
 }
 
 Backend* default_backend() {

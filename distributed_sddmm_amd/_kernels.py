@@ -241,6 +241,16 @@ MULTILABEL_SIGNATURES = {
 }
 
 
+# include/hnh_train_clip.h: gradient clipping by global norm and AdamW (the sum of squares of a table of gradients, and the optimizer step
+# with a clip coefficient from device memory); a further OPTIONAL group bound only for the product library
+TRAIN_CLIP_SIGNATURES = {
+    "hnh_grad_sumsq_f64_workspace": (_i64, [_vp, _i32]),
+    "hnh_grad_sumsq_f64": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, _i64, _i32]),
+    "hnh_optim_step_clip_f64": (_i32, [_vp, _vp, _i32, _vp, _vp, _i32, _dbl, _i32]),
+}
+OPTIM_ADAMW, CLIP_MAX_SUMS = 2, 8  # HNH_OPTIM_ADAMW, HNH_CLIP_MAX_SUMS
+
+
 class OptimTensor(C.Structure):
     """struct hnh_optim_tensor"""
     _fields_ = [("p", _vp), ("ld_p", _i64), ("g", _vp), ("ld_g", _i64), ("m", _vp), ("v", _vp), ("rows", _i64), ("cols", _i64)]
@@ -414,7 +424,7 @@ def load(path: str | None = None) -> C.CDLL:
                 list(ATTN_ADD_SIGNATURES.items()) + list(ATTN_DROP_SIGNATURES.items()) + list(TRAIN_SIGNATURES.items()) + \
                 list(V2_SIGNATURES.items()) + list(ATTN_COEF_SIGNATURES.items()) + list(SKIP_SIGNATURES.items()) + \
                 list(QKV_SIGNATURES.items()) + list(EDGE_SIGNATURES.items()) + list(EDGE_GRAD_SIGNATURES.items()) + \
-                list(NORM_SIGNATURES.items()) + list(MULTILABEL_SIGNATURES.items()):
+                list(NORM_SIGNATURES.items()) + list(MULTILABEL_SIGNATURES.items()) + list(TRAIN_CLIP_SIGNATURES.items()):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
     if path is None:

@@ -166,6 +166,11 @@ SIGNATURES = {
     "hnh_gat_loss": (_i32, [_vp, _vp, _i64, _vp, _pdbl, _pdbl]),
     "hnh_gat_set_optimizer": (_i32, [_vp, _i32, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl]),
     "hnh_gat_optimizer_step": (_i32, [_vp]),
+    "hnh_gat_set_grad_clip": (_i32, [_vp, _dbl]),
+    "hnh_gat_grad_norm": (_i32, [_vp, _pdbl]),
+    "hnh_gat_set_learning_rate": (_i32, [_vp, _dbl]),
+    "hnh_gat_learning_rate": (_i32, [_vp, _pdbl]),
+    "hnh_gat_set_lr_schedule": (_i32, [_vp, _i32, _i64, _i64, _dbl]),
     "hnh_gat_train_step": (_i32, [_vp, _pdbl, _pdbl]),
     "hnh_gat_evaluate": (_i32, [_vp, _vp, _i64, _pdbl, _pdbl]),
     "hnh_dropout_word": (C.c_uint32, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
@@ -746,7 +751,9 @@ class GAT:
 
     HEADS = {"mean": 0, "concat": 1}  # HNH_GAT_HEADS_MEAN / _CONCAT
 
-    OPTIMIZER = {"adam": 0, "sgd": 1}  # HNH_GAT_OPTIMIZER_ADAM / _SGD
+    OPTIMIZER = {"adam": 0, "sgd": 1, "adamw": 2}  # HNH_GAT_OPTIMIZER_ADAM / _SGD / _ADAMW (the last: include/hnh_train_clip.h)
+
+    LR_SCHEDULE = {"constant": 0, "linear": 1, "cosine": 2}  # HNH_GAT_LR_CONSTANT / _LINEAR / _COSINE
 
     def __init__(self, op: DistributedSparse, layers, leaky_relu_alpha: float = 0.2, attention: str = "none", backward: str = "unfused",
                  score: str = "dot", dropout=(0.0, 0.0), seed: int = 0, activation="relu", residual="none", bias=False, norm="none"):
@@ -1239,13 +1246,48 @@ class GAT:
 
     def set_optimizer(self, kind: str, lr: float, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8, momentum: float = 0.0,
                       weight_decay: float = 0.0):
-        """"adam" or "sgd" (with momentum) over every W, a1, a2 with score "additive", and every enabled bias and residual weight; weight
-        decay is added to the gradient of each of them.  A learned edge bias (set_edge_bias_learned) is updated too, but never decayed.
-        (Re)allocates zeroed moments and resets the step count."""
+        """"adam", "sgd" (with momentum) or "adamw" over every W, a1, a2 with score "additive", and every enabled bias and residual weight;
+        with "adam" and "sgd" weight decay is added to the gradient of each of them, with "adamw" it shrinks the parameter itself by
+        lr * weight_decay before Adam's update (torch.optim.AdamW; include/hnh_train_clip.h).  A learned edge bias
+        (set_edge_bias_learned) is updated too, but never decayed.  (Re)allocates zeroed moments and resets the step count; the clip
+        setting (set_grad_clip) and the schedule (set_lr_schedule) stay in place."""
         if kind not in self.OPTIMIZER:
             raise ValueError("optimizer must be one of %s, not %r" % (sorted(self.OPTIMIZER), kind))
         _check(lib().hnh_gat_set_optimizer(self.h, self.OPTIMIZER[kind], float(lr), float(beta1), float(beta2), float(eps), float(momentum),
                                            float(weight_decay)), "gat_set_optimizer")
+
+    def set_grad_clip(self, max_norm: float | None):
+        """Gradient clipping by global norm, on the device (include/hnh_train_clip.h): every later optimizer_step / train_step scales all
+        gradients by min(1, max_norm / (norm + 1e-6)), norm being the 2-norm over every learned tensor of the whole world, as
+        torch.nn.utils.clip_grad_norm_ does.  train_step keeps its single host synchronisation.  None or 0 switches clipping off (the
+        default); a value that is negative, NaN or infinite raises and leaves the object as it was."""
+        _check(lib().hnh_gat_set_grad_clip(self.h, 0.0 if max_norm is None else float(max_norm)), "gat_set_grad_clip")
+
+    def grad_norm(self) -> float:
+        """The global gradient norm, before clipping, of the most recent optimizer_step / train_step taken with clipping on (a copy
+        and a host synchronisation of its own).  Raises before the first such step."""
+        out = C.c_double()
+        _check(lib().hnh_gat_grad_norm(self.h, C.byref(out)), "gat_grad_norm")
+        return out.value
+
+    def set_learning_rate(self, lr: float):
+        """A new base learning rate; unlike set_optimizer it keeps the moments and the step count."""
+        _check(lib().hnh_gat_set_learning_rate(self.h, float(lr)), "gat_set_learning_rate")
+
+    def learning_rate(self) -> float:
+        """The rate the next optimizer_step / train_step will use: the base rate times the schedule's factor."""
+        out = C.c_double()
+        _check(lib().hnh_gat_learning_rate(self.h, C.byref(out)), "gat_learning_rate")
+        return out.value
+
+    def set_lr_schedule(self, kind: str = "constant", warmup_steps: int = 0, total_steps: int = 0, min_factor: float = 0.0):
+        """lr_t = lr * factor(t) for the 1-based step t: t / warmup_steps during the warm-up; afterwards "constant" gives 1 (total_steps
+        and min_factor are not used), "linear" 1 - (1 - min_factor) (t - W) / (T - W) and "cosine" min_factor + (1 - min_factor)
+        (1 + cos(pi (t - W) / (T - W))) / 2, and min_factor beyond total_steps.  "linear" and "cosine" need total_steps > warmup_steps
+        >= 0 and min_factor in [0, 1]; anything else raises.  set_optimizer restarts t and keeps the schedule."""
+        if kind not in self.LR_SCHEDULE:
+            raise ValueError("schedule must be one of %s, not %r" % (sorted(self.LR_SCHEDULE), kind))
+        _check(lib().hnh_gat_set_lr_schedule(self.h, self.LR_SCHEDULE[kind], int(warmup_steps), int(total_steps), float(min_factor)), "gat_set_lr_schedule")
 
     def optimizer_step(self):
         """One optimizer step from the gradients of the last backwardPass, on the device.  Invalidates the stored forward pass."""

@@ -375,6 +375,7 @@ int hnh_transpose_into_f64(hnh_ctx* ctx, double* dst, int64_t ld_dst, int64_t ro
 }  // extern "C"
 
 #include "hnh_train_kernels.hpp"  // the training step (include/hnh_train.h): cross-entropy head and optimizer
+#include "hnh_train_clip_kernels.hpp"  // gradient clipping and AdamW (include/hnh_train_clip.h): the sum of squares and the clipped optimizer step
 #include "hnh_gat_skip_kernels.hpp"  // bias and skip connections (include/hnh_gat_skip.h): the dense kernels
 #include "hnh_gat_norm_kernels.hpp"  // layer normalisation (include/hnh_gat_norm.h): the two dense row passes
 #include "hnh_multilabel_kernels.hpp"  // the multi-label head (include/hnh_train_multilabel.h): sigmoid cross-entropy and the micro-F1 counts

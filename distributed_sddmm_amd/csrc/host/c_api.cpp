@@ -946,6 +946,27 @@ int hnh_gat_loss(hnh_gat* g, const uint8_t* mask_or_null, int64_t n, hnh_dense* 
 int hnh_gat_set_optimizer(hnh_gat* g, int kind, double lr, double beta1, double beta2, double eps, double momentum, double weight_decay) {
     return guarded(g->w, [&] { g->g->set_optimizer(kind, lr, beta1, beta2, eps, momentum, weight_decay); });
 }
+int hnh_gat_set_grad_clip(hnh_gat* g, double max_norm) {
+    return guarded(g->w, [&] { g->g->set_grad_clip(max_norm); });
+}
+int hnh_gat_grad_norm(hnh_gat* g, double* norm) {
+    return guarded(g->w, [&] {
+        if (!norm) throw hnh::Error("Error, hnh_gat_grad_norm: null pointer!");
+        *norm = g->g->grad_norm();
+    });
+}
+int hnh_gat_set_learning_rate(hnh_gat* g, double lr) {
+    return guarded(g->w, [&] { g->g->set_learning_rate(lr); });
+}
+int hnh_gat_learning_rate(hnh_gat* g, double* lr) {
+    return guarded(g->w, [&] {
+        if (!lr) throw hnh::Error("Error, hnh_gat_learning_rate: null pointer!");
+        *lr = g->g->learning_rate();
+    });
+}
+int hnh_gat_set_lr_schedule(hnh_gat* g, int kind, int64_t warmup_steps, int64_t total_steps, double min_factor) {
+    return guarded(g->w, [&] { g->g->set_lr_schedule(kind, warmup_steps, total_steps, min_factor); });
+}
 int hnh_gat_optimizer_step(hnh_gat* g) {
     return guarded(g->w, [&] { g->g->optimizer_step(); });
 }

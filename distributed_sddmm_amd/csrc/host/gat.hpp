@@ -104,6 +104,14 @@
 // same read; the four sums are all-reduced, the pair's second value is micro-F1 = 2 tp / (2 tp + fp + fn), and multilabel_counts() hands out
 // the counts.  No row is staged, so HNH_XENT_MAX_WIDTH does not apply.  A model that never calls it launches what it launched before.
 //
+// Gradient clipping, AdamW and learning-rate schedules (an addition; include/hnh_train_clip.h; set_grad_clip, optimizer kind
+// HNH_OPTIM_ADAMW, set_learning_rate, set_lr_schedule; all off by default, which launches exactly the kernels above).  With clipping on,
+// optimizer_step first runs hnh_grad_sumsq_f64 over learned_parameters(): the replicated tensors into one sum without a collective (their
+// gradients are bit-equal on every rank), the S-order copy of every learned edge bias into a second one that is summed over the world;
+// the update then goes through hnh_optim_step_clip_f64, where every thread derives coef = min(1, max_norm / (norm + 1e-6)) from the two
+// sums in device memory.  No host synchronisation is added: train_step still waits once, and grad_norm() reads the sums lazily.  The
+// schedule is host arithmetic on the step's lr.
+//
 // Output activation (an addition; set_activation(layer, mode), HNH_GAT_ACT_RELU on every layer by default, which launches exactly the kernels
 // above).  out[:, h f ..] = phi_l(o) with phi in {relu, elu, identity} leaves the finishing launch of the softmax and additive forward passes
 // (the HNH_ATTN_ACT_* flags of include/hnh_attention.h).  The backward pass keeps no pre-activation: for a non-ReLU layer ONE pass
@@ -807,9 +815,12 @@ public:
         return loss_read(ls);
     }
 
-    // Sets the hyper-parameters, drops every moment and resets the step count.  kind: HNH_OPTIM_ADAM | HNH_OPTIM_SGD (include/hnh_train.h).
+    // Sets the hyper-parameters, drops every moment and resets the step count.  kind: HNH_OPTIM_ADAM | HNH_OPTIM_SGD (include/hnh_train.h) |
+    // HNH_OPTIM_ADAMW (include/hnh_train_clip.h).  The clip setting (set_grad_clip) and the schedule (set_lr_schedule) stay in place; lr
+    // becomes the schedule's base rate.
     void set_optimizer(int kind, double lr, double beta1, double beta2, double eps, double momentum, double weight_decay) {
-        if (kind != HNH_OPTIM_ADAM && kind != HNH_OPTIM_SGD) throw hnh::Error("Error, unknown GAT optimizer " + std::to_string(kind) + " (adam = 0, sgd = 1)!");
+        if (kind != HNH_OPTIM_ADAM && kind != HNH_OPTIM_SGD && kind != HNH_OPTIM_ADAMW)
+            throw hnh::Error("Error, unknown GAT optimizer " + std::to_string(kind) + " (adam = 0, sgd = 1, adamw = 2)!");
         if (!(lr >= 0.0) || !std::isfinite(lr) || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0) || !(eps >= 0.0) || !(momentum >= 0.0 && momentum < 1.0) ||
             !(weight_decay >= 0.0) || !std::isfinite(weight_decay) || !std::isfinite(eps))
             throw hnh::Error("Error, GAT set_optimizer needs lr, eps, weight_decay >= 0 and beta1, beta2, momentum in [0, 1)!");
@@ -827,11 +838,72 @@ public:
     }
     int64_t optimizer_steps() const { return optim_steps_; }
 
+    // ---- gradient clipping, learning rate and schedule (include/hnh_train_clip.h)
+    // Clipping by global norm: every later optimizer_step / train_step scales all gradients by min(1, max_norm / (norm + 1e-6)), norm =
+    // the 2-norm over every learned tensor of the whole world (torch.nn.utils.clip_grad_norm_).  0 switches it off (the default).
+    void set_grad_clip(double max_norm) {
+        if (!(max_norm >= 0.0) || !std::isfinite(max_norm))
+            throw hnh::Error("Error, GAT set_grad_clip needs a finite max_norm >= 0 (0: no clipping), not " + std::to_string(max_norm) + "!");
+        clip_max_ = max_norm;
+    }
+    // The global gradient norm, before clipping, of the most recent clipped optimizer_step / train_step: a copy and a host synchronisation
+    // of its own.
+    double grad_norm() {
+        if (clip_nsums_ == 0) throw hnh::Error("Error, GAT grad_norm needs an optimizer_step or train_step with clipping switched on (set_grad_clip) first!");
+        hnh::World* w = d_ops->world;
+        double s[2] = {0.0, 0.0};
+        w->copy(s, clip_sums_.data(), sizeof(double) * (size_t)clip_nsums_, HNH_COPY_D2H, HNH_STREAM_COMPUTE);
+        w->sync(HNH_STREAM_COMPUTE);
+        double total = 0.0;
+        for (int q = 0; q < clip_nsums_; q++) total += s[q];  // (the kernel's sum)
+        return std::sqrt(total);
+    }
+    // A new base rate; moments and step count stay.
+    void set_learning_rate(double lr) {
+        if (!optimizer_set_) throw hnh::Error("Error, GAT set_learning_rate needs set_optimizer first!");
+        if (!(lr >= 0.0) || !std::isfinite(lr)) throw hnh::Error("Error, GAT set_learning_rate needs a finite lr >= 0!");
+        optim_.lr = lr;
+    }
+    // lr_t = lr * factor(t) for the 1-based step t: t / W during a warm-up of W steps; then 1 (HNH_GAT_LR_CONSTANT, which ignores total and
+    // min_factor), or a linear / cosine descent to min_factor at step T = total, and min_factor from there on.
+    void set_lr_schedule(int kind, int64_t warmup, int64_t total, double min_factor) {
+        if (kind != HNH_GAT_LR_CONSTANT && kind != HNH_GAT_LR_LINEAR && kind != HNH_GAT_LR_COSINE)
+            throw hnh::Error("Error, unknown GAT learning-rate schedule " + std::to_string(kind) + " (constant = 0, linear = 1, cosine = 2)!");
+        if (warmup < 0 || total < 0 || !(min_factor >= 0.0 && min_factor <= 1.0))
+            throw hnh::Error("Error, GAT set_lr_schedule needs warmup_steps >= 0, total_steps >= 0 and min_factor in [0, 1]!");
+        if (kind != HNH_GAT_LR_CONSTANT && total <= warmup)
+            throw hnh::Error("Error, GAT set_lr_schedule: a linear or cosine schedule needs total_steps > warmup_steps, not " + std::to_string(total) + " and " +
+                             std::to_string(warmup) + "!");
+        sched_kind_ = kind;
+        sched_warmup_ = warmup;
+        sched_total_ = total;
+        sched_min_ = min_factor;
+    }
+    double lr_factor(int64_t t) const {
+        const double W = (double)sched_warmup_, T = (double)sched_total_, x = (double)t;
+        if (t <= sched_warmup_) return x / W;
+        if (sched_kind_ == HNH_GAT_LR_CONSTANT) return 1.0;
+        if (t > sched_total_) return sched_min_;
+        const double s = (x - W) / (T - W);
+        if (sched_kind_ == HNH_GAT_LR_LINEAR) return 1.0 - (1.0 - sched_min_) * s;
+        return sched_min_ + (1.0 - sched_min_) * 0.5 * (1.0 + std::cos(3.14159265358979323846 * s));
+    }
+    // the rate of the next step
+    double learning_rate() const {
+        if (!optimizer_set_) throw hnh::Error("Error, GAT learning_rate needs set_optimizer first!");
+        return optim_.lr * lr_factor(optim_steps_ + 1);
+    }
+
     // One optimizer step from the gradients of the last backwardPass over learned_parameters(), in one table.  Invalidates the stored
-    // forward pass.  No host synchronisation.
+    // forward pass.  No host synchronisation.  With clipping off and kind Adam or SGD: hnh_optim_step_f64, as ever.  With clipping on:
+    // hnh_grad_sumsq_f64 first, the replicated tensors into sums[0] (their gradients are bit-equal on every rank: no collective) and the
+    // S-order copy of every learned edge bias, which each rank holds for its own nonzeros, into sums[1], summed over the world; then both
+    // tables through hnh_optim_step_clip_f64 with the two sums, so every rank takes the same coefficient.  Kind AdamW always takes that
+    // entry point (a null sumsq without clipping).
     void optimizer_step() {
         if (!optimizer_set_) throw hnh::Error("Error, GAT optimizer_step needs set_optimizer first!");
         require_kernels("training", {HNH_GAT_KERNEL(hnh_optim_step_f64)});
+        require_clip_kernels();
         if (!grads_fresh_ || weight_grads.size() != layers.size() || (learns_vectors() && attn_grads.size() != layers.size()))
             throw hnh::Error("Error, GAT optimizer_step needs the gradients of a backwardPass since the last step!");
         const std::vector<Learned> learned = learned_parameters();
@@ -839,22 +911,45 @@ public:
             if (t.g == nullptr) throw hnh::Error(t.refusal);
         // the learned edge biases (PARAM_EDGE_BIAS_S / _ST) and the norms' gamma and beta (PARAM_NORM_GAIN / _SHIFT) in a table and a call of
         // their own: they are never decayed
-        std::vector<hnh_optim_tensor> table, undecayed;
+        std::vector<hnh_optim_tensor> table, undecayed, replicated, per_rank;  // (the last two: what the norm is made of)
+        bool edge_learned = false;
         for (const Learned& t : learned) {
+            const int kind = std::get<0>(t.key);
+            edge_learned = edge_learned || kind == PARAM_EDGE_BIAS_S;
             if (t.rows == 0) continue;  // (a rank without nonzeros holds none of a layer's bias)
             const Moments& m = ensure_moments(t);
-            const int kind = std::get<0>(t.key);
             const bool edge = kind == PARAM_EDGE_BIAS_S || kind == PARAM_EDGE_BIAS_ST || kind == PARAM_NORM_GAIN || kind == PARAM_NORM_SHIFT;
             (edge ? undecayed : table).push_back({t.p, t.ld_p, t.g, t.ld_g, m.first.data(), m.second.data(), t.rows, t.cols});
+            // the S^T-order copy of an edge bias holds the numbers of the S-order one: counted once
+            if (kind == PARAM_EDGE_BIAS_S) per_rank.push_back((edge ? undecayed : table).back());
+            else if (kind != PARAM_EDGE_BIAS_ST) replicated.push_back((edge ? undecayed : table).back());
+        }
+        const bool clip = clip_max_ > 0.0, through_clip = clip || optim_.kind == HNH_OPTIM_ADAMW;
+        const int nsums = edge_learned ? 2 : 1;
+        if (clip) {
+            if (clip_sums_.size() != 2) clip_sums_ = DenseMatrix(2, 1);
+            const std::vector<hnh_optim_tensor>* part[2] = {&replicated, &per_rank};
+            for (int q = 0; q < nsums; q++) {
+                const int64_t need = d_ops->world->be->hnh_grad_sumsq_f64_workspace(part[q]->data(), (int)part[q]->size());
+                if (need < 0) throw hnh::Error("Error, GAT optimizer_step: a gradient has a shape that hnh_grad_sumsq_f64 refuses!");
+                DenseMatrix& work = scratch(SC_SUMSQ_WORK, need, 1);
+                HNH_GAT_CALL(hnh_grad_sumsq_f64, part[q]->data(), (int)part[q]->size(), 0, clip_sums_.data() + q, work.data(), need, HNH_STREAM_COMPUTE);
+            }
+            if (edge_learned) sum_over_world(clip_sums_.data() + 1, 1);
+            clip_nsums_ = nsums;
         }
         optim_steps_++;
         hnh_optim hy = optim_;
+        hy.lr = optim_.lr * lr_factor(optim_steps_);  // (factor 1.0 without a schedule: the same bits)
         hy.bias1 = 1.0 - std::pow(hy.beta1, (double)optim_steps_);
         hy.bias2 = 1.0 - std::pow(hy.beta2, (double)optim_steps_);
-        HNH_GAT_CALL(hnh_optim_step_f64, table.data(), (int)table.size(), &hy, HNH_STREAM_COMPUTE);
+        const double* sums = clip ? clip_sums_.data() : nullptr;
+        if (through_clip) HNH_GAT_CALL(hnh_optim_step_clip_f64, table.data(), (int)table.size(), &hy, sums, nsums, clip_max_, HNH_STREAM_COMPUTE);
+        else HNH_GAT_CALL(hnh_optim_step_f64, table.data(), (int)table.size(), &hy, HNH_STREAM_COMPUTE);
         if (!undecayed.empty()) {
             hy.weight_decay = 0.0;
-            HNH_GAT_CALL(hnh_optim_step_f64, undecayed.data(), (int)undecayed.size(), &hy, HNH_STREAM_COMPUTE);
+            if (through_clip) HNH_GAT_CALL(hnh_optim_step_clip_f64, undecayed.data(), (int)undecayed.size(), &hy, sums, nsums, clip_max_, HNH_STREAM_COMPUTE);
+            else HNH_GAT_CALL(hnh_optim_step_f64, undecayed.data(), (int)undecayed.size(), &hy, HNH_STREAM_COMPUTE);
         }
         grads_fresh_ = false;
         invalidate_forward();
@@ -1017,6 +1112,15 @@ private:
     double ml_counts_[3] = {0.0, 0.0, 0.0};
     hnh_optim optim_ = {};
     int64_t optim_steps_ = 0;
+    // gradient clipping and the schedule (include/hnh_train_clip.h): max_norm (0: off); the sums of squares of the last clipped step on the
+    // device ([0]: the replicated tensors, [1]: the learned edge biases over the world) and how many of them it used (0: no clipped step
+    // yet); the schedule of set_lr_schedule over optim_.lr, the base rate
+    double clip_max_ = 0.0;
+    DenseMatrix clip_sums_;
+    int clip_nsums_ = 0;
+    int sched_kind_ = HNH_GAT_LR_CONSTANT;
+    int64_t sched_warmup_ = 0, sched_total_ = 0;
+    double sched_min_ = 0.0;
     // Every learned tensor of the model is one row of optimizer_step's table (learned_parameters()); its moments live under its key.
     enum ParamKind { PARAM_W, PARAM_A1, PARAM_A2, PARAM_BIAS, PARAM_W_RES, PARAM_W_Q, PARAM_W_K, PARAM_EDGE_BIAS_S, PARAM_EDGE_BIAS_ST,
                      PARAM_NORM_GAIN, PARAM_NORM_SHIFT };
@@ -1101,7 +1205,7 @@ private:
     const Moments& ensure_moments(const Learned& t) {
         Moments& m = moments_[t.key];
         if (m.second.rows() != t.rows || m.second.cols() != t.cols) {
-            if (optim_.kind == HNH_OPTIM_ADAM) m.first = DenseMatrix::Constant(t.rows, t.cols, 0.0);
+            if (optim_.kind != HNH_OPTIM_SGD) m.first = DenseMatrix::Constant(t.rows, t.cols, 0.0);
             m.second = DenseMatrix::Constant(t.rows, t.cols, 0.0);
         }
         return m;
@@ -1172,10 +1276,17 @@ private:
         ScheduleWidth(const ScheduleWidth&) = delete;
         ScheduleWidth& operator=(const ScheduleWidth&) = delete;
     };
+    // What an optimizer step under set_grad_clip or with kind AdamW needs of include/hnh_train_clip.h
+    void require_clip_kernels() const {
+        if (clip_max_ > 0.0)
+            require_kernels("gradient clipping", {HNH_GAT_KERNEL(hnh_grad_sumsq_f64_workspace), HNH_GAT_KERNEL(hnh_grad_sumsq_f64), HNH_GAT_KERNEL(hnh_optim_step_clip_f64)});
+        if (optimizer_set_ && optim_.kind == HNH_OPTIM_ADAMW) require_kernels("adamw", {HNH_GAT_KERNEL(hnh_optim_step_clip_f64)});
+    }
     // Refuses before anything is launched: labels (and the optimizer) not set, then the kernel group, then the row width.
     void check_train_supported(bool need_optimizer) {
         if (!labels_set_ && !multilabel_) throw hnh::Error("Error, GAT loss / train_step / evaluate need set_labels first!");
         if (need_optimizer && !optimizer_set_) throw hnh::Error("Error, GAT train_step needs set_optimizer first!");
+        if (need_optimizer) require_clip_kernels();
         if (multilabel_) {  // the sigmoid head: its own kernel group, and no limit on the row width (no row is staged)
             require_kernels("training", {HNH_GAT_KERNEL(hnh_bce_rows_f64_workspace), HNH_GAT_KERNEL(hnh_bce_rows_f64)});
             if (need_optimizer) require_kernels("training", {HNH_GAT_KERNEL(hnh_optim_step_f64)});
@@ -1317,7 +1428,7 @@ private:
     // workspace of every X^T D product of gemm_tn, and SC_PACKED, the packed P = [A | dZ | lse delta] of the fused and the gatv2 backward.
     enum ScratchRole { SC_DA_ALL, SC_WT, SC_A, SC_DZ, SC_DA_ROW, SC_T1, SC_T2, SC_TN_WORK, SC_DELTA, SC_PACKED, SC_ADD_M, SC_ADD_Q, SC_ADD_D, SC_ADD_DAGG,
                        SC_ADD_TN_WORK, SC_XENT_WORK, SC_V2_R, SC_V2_C, SC_V2_DAGG, SC_V2_WORK, SC_COEF_A, SC_COEF_S, SC_COEF_T, SC_RES_PRODUCT, SC_DZ_ALL,
-                       SC_COLSUM_WORK, SC_DX_RES, SC_QKV_Q, SC_QKV_K, SC_QKV_KV, SC_QKV_P, SC_QKV_DQ, SC_QKV_DK, SC_QKV_DX, SC_NORM_G, SC_NORM_WORK, SC_BCE_WORK };
+                       SC_COLSUM_WORK, SC_DX_RES, SC_QKV_Q, SC_QKV_K, SC_QKV_KV, SC_QKV_P, SC_QKV_DQ, SC_QKV_DK, SC_QKV_DX, SC_NORM_G, SC_NORM_WORK, SC_BCE_WORK, SC_SUMSQ_WORK };
     std::map<std::tuple<int, int64_t, int64_t>, DenseMatrix> scratch_;
 
     // m at rows x cols: allocated anew (on the compute stream) unless it has that shape already
@@ -1327,10 +1438,11 @@ private:
     }
     DenseMatrix& scratch_slot(ScratchRole role, int64_t rows, int64_t cols) { return scratch_[std::make_tuple((int)role, rows, cols)]; }  // (not shaped yet)
     DenseMatrix& scratch(ScratchRole role, int64_t rows, int64_t cols) { return shaped(scratch_slot(role, rows, cols), rows, cols); }
-    void sum_over_world(DenseMatrix& m) {
+    void sum_over_world(double* data, size_t n) {
         hnh::World* w = d_ops->world;
-        w->allreduce_f64(w->world_comm(), m.data(), (size_t)m.size(), HNH_STREAM_COMPUTE);
+        w->allreduce_f64(w->world_comm(), data, n, HNH_STREAM_COMPUTE);
     }
+    void sum_over_world(DenseMatrix& m) { sum_over_world(m.data(), (size_t)m.size()); }
     // C (m x n at pitch ldc) = A^T B over `rows` local rows on the compute stream, the split-K workspace of hnh_gemm_tn_f64 from the scratch
     void gemm_tn(int64_t m, int64_t n, int64_t rows, const double* A, int64_t lda, const double* B, int64_t ldb, double* C, int64_t ldc, ScratchRole work_role) {
         const int64_t need = d_ops->world->be->hnh_gemm_tn_f64_workspace(m, n, rows);

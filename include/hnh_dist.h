@@ -389,9 +389,15 @@ int hnh_gat_set_labels(hnh_gat* g, const int32_t* labels, const uint8_t* mask_or
  * the world.  grad_out_or_null receives dL/d(output) in the layout hnh_gat_backward takes. */
 int hnh_gat_loss(hnh_gat* g, const uint8_t* mask_or_null, int64_t n, hnh_dense* grad_out_or_null, double* loss, double* accuracy);
 /* kind ADAM: m = beta1 m + (1 - beta1) g', v = beta2 v + (1 - beta2) g'^2, p -= lr (m / (1 - beta1^t)) / (sqrt(v / (1 - beta2^t)) + eps);
- * SGD: v = momentum v + g', p -= lr v; g' = g + weight_decay p.  (Re)allocates zeroed moments and resets the step count t. */
+ * SGD: v = momentum v + g', p -= lr v; g' = g + weight_decay p.  (Re)allocates zeroed moments and resets the step count t.
+ * ADAMW (kernels: include/hnh_train_clip.h, an optional group — a kernel library without it makes hnh_gat_optimizer_step and
+ * hnh_gat_train_step fail under this kind with an error naming the missing symbol): p = p (1 - lr weight_decay), then ADAM with g' = g
+ * (torch.optim.AdamW).  The edge bias, gamma and beta are not decayed under any kind.
+ * The step count restarts; the clip setting (hnh_gat_set_grad_clip) and the schedule (hnh_gat_set_lr_schedule) stay in place, and lr becomes
+ * the schedule's base rate. */
 #define HNH_GAT_OPTIMIZER_ADAM 0
 #define HNH_GAT_OPTIMIZER_SGD 1
+#define HNH_GAT_OPTIMIZER_ADAMW 2
 int hnh_gat_set_optimizer(hnh_gat* g, int kind, double lr, double beta1, double beta2, double eps, double momentum, double weight_decay);
 /* Applies the optimizer to the gradients of the last hnh_gat_backward — every W, a1, a2 with score ADDITIVE, and every enabled bias and
  * residual weight (weight decay applies to them as to every other tensor) — in one table-driven launch, and invalidates the stored forward pass.  The gradients are the same on every rank, so the parameters stay equal bit for bit. */
@@ -420,6 +426,30 @@ int hnh_gat_set_multilabel_targets(hnh_gat* g, const uint8_t* targets, int64_t n
 /* (tp, fp, fn) of the last hnh_gat_loss / hnh_gat_evaluate / hnh_gat_train_step under the sigmoid head: counts of (row, class) pairs over
  * the whole world, exact.  Fails when the sigmoid head is not the one in use. */
 int hnh_gat_multilabel_counts(hnh_gat* g, double* tp, double* fp, double* fn);
+/* Gradient clipping by global norm (an addition; kernels: include/hnh_train_clip.h, an optional group — a kernel library without it makes
+ * hnh_gat_optimizer_step and hnh_gat_train_step fail while clipping is on, before anything is launched, with an error naming the missing
+ * symbol).  With max_norm > 0 every later step scales all gradients by min(1, max_norm / (norm + 1e-6)), norm = the 2-norm over every
+ * learned tensor (torch.nn.utils.clip_grad_norm_): the replicated tensors counted once, a learned edge bias summed over the ranks that
+ * hold its entries.  The norm and the coefficient stay on the device: hnh_gat_train_step keeps its single host synchronisation, and
+ * parameters stay bit-equal across ranks.  A norm that is not finite gets no special handling.  max_norm == 0 (the default) switches
+ * clipping off; a value that is negative, NaN or infinite fails and leaves the object as it was. */
+int hnh_gat_set_grad_clip(hnh_gat* g, double max_norm);
+/* *norm = the global gradient norm, before clipping, of the most recent step taken with clipping on; a device-to-host copy and a
+ * synchronisation of its own.  Fails before the first such step. */
+int hnh_gat_grad_norm(hnh_gat* g, double* norm);
+/* A new base learning rate; unlike hnh_gat_set_optimizer it keeps the moments and the step count.  *lr of hnh_gat_learning_rate is the
+ * rate the next step will use: base rate * factor(t), t = the 1-based number of that step.  Both need hnh_gat_set_optimizer first. */
+int hnh_gat_set_learning_rate(hnh_gat* g, double lr);
+int hnh_gat_learning_rate(hnh_gat* g, double* lr);
+/* The schedule, host arithmetic in double on every step's rate: factor(t) = t / warmup_steps for t <= warmup_steps; afterwards CONSTANT
+ * gives 1 (total_steps and min_factor are not used), LINEAR 1 - (1 - min_factor) (t - W) / (T - W) and COSINE min_factor + (1 - min_factor)
+ * (1 + cos(pi (t - W) / (T - W))) / 2 with W = warmup_steps and T = total_steps, and min_factor for t > T.  LINEAR and COSINE need
+ * T > W >= 0; min_factor must lie in [0, 1]; anything else fails and leaves the object as it was.  The default is CONSTANT without a
+ * warm-up.  hnh_gat_set_optimizer restarts t and leaves the schedule in place. */
+#define HNH_GAT_LR_CONSTANT 0
+#define HNH_GAT_LR_LINEAR 1
+#define HNH_GAT_LR_COSINE 2
+int hnh_gat_set_lr_schedule(hnh_gat* g, int kind, int64_t warmup_steps, int64_t total_steps, double min_factor);
 
 #ifdef __cplusplus
 }

@@ -251,6 +251,19 @@ TRAIN_CLIP_SIGNATURES = {
 OPTIM_ADAMW, CLIP_MAX_SUMS = 2, 8  # HNH_OPTIM_ADAMW, HNH_CLIP_MAX_SUMS
 
 
+# include/hnh_als_implicit.h: the Gram term and the guarded CG update of implicit-feedback ALS (api.ImplicitALS); a further OPTIONAL group
+# bound only for the product library
+ALS_IMPLICIT_SIGNATURES = {
+    "hnh_gram_rows_f64": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _i32]),
+}
+GRAM_MAX_R = 256  # HNH_GRAM_MAX_R
+
+
+class GramCg(C.Structure):
+    """struct hnh_gram_cg"""
+    _fields_ = [("x", _vp), ("r", _vp), ("p", _vp), ("rs", _vp)]
+
+
 class OptimTensor(C.Structure):
     """struct hnh_optim_tensor"""
     _fields_ = [("p", _vp), ("ld_p", _i64), ("g", _vp), ("ld_g", _i64), ("m", _vp), ("v", _vp), ("rows", _i64), ("cols", _i64)]
@@ -424,7 +437,8 @@ def load(path: str | None = None) -> C.CDLL:
                 list(ATTN_ADD_SIGNATURES.items()) + list(ATTN_DROP_SIGNATURES.items()) + list(TRAIN_SIGNATURES.items()) + \
                 list(V2_SIGNATURES.items()) + list(ATTN_COEF_SIGNATURES.items()) + list(SKIP_SIGNATURES.items()) + \
                 list(QKV_SIGNATURES.items()) + list(EDGE_SIGNATURES.items()) + list(EDGE_GRAD_SIGNATURES.items()) + \
-                list(NORM_SIGNATURES.items()) + list(MULTILABEL_SIGNATURES.items()) + list(TRAIN_CLIP_SIGNATURES.items()):
+                list(NORM_SIGNATURES.items()) + list(MULTILABEL_SIGNATURES.items()) + list(TRAIN_CLIP_SIGNATURES.items()) + \
+                list(ALS_IMPLICIT_SIGNATURES.items()):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
     if path is None:

@@ -120,6 +120,17 @@ SIGNATURES = {
     "hnh_als_cg_optimizer": (_i32, [_vp, _i32, _i32]),
     "hnh_als_run_cg": (_i32, [_vp, _i32]),
     "hnh_als_compute_residual": (_i32, [_vp, _pdbl]),
+    "hnh_ials_create": (_i32, [_vp, C.c_double, _u64, _pvp]),
+    "hnh_ials_destroy": (_i32, [_vp]),
+    "hnh_ials_set_confidence": (_i32, [_vp, _vp, _vp]),
+    "hnh_ials_initialize_embeddings": (_i32, [_vp]),
+    "hnh_ials_set_embeddings": (_i32, [_vp, _vp, _vp]),
+    "hnh_ials_get_embeddings": (_i32, [_vp, _vp, _vp]),
+    "hnh_ials_half_step": (_i32, [_vp, _i32, _i32]),
+    "hnh_ials_run": (_i32, [_vp, _i32, _i32]),
+    "hnh_ials_loss": (_i32, [_vp, _pdbl]),
+    "hnh_ials_gram": (_i32, [_vp, _i32, _vp]),
+    "hnh_ials_set_folded": (_i32, [_vp, _i32]),
     "hnh_gat_create": (_i32, [_vp, _i32, _pi32, _dbl, _pvp]),
     "hnh_gat_destroy": (_i32, [_vp]),
     "hnh_gat_weight_shape": (_i32, [_vp, _i32, _i32, _pi64]),
@@ -727,6 +738,56 @@ class DistributedALS:
     def free(self):
         if self.h:
             _check(lib().hnh_als_destroy(self.h), "als_destroy")
+            self.h = None
+
+
+class ImplicitALS:
+    """Implicit_ALS (csrc/host/als_implicit.hpp): implicit-feedback ALS with confidence weights on a 15d_fusion2 operator.  Preference 1
+    with confidence 1 + w on the stored pairs, 0 with confidence 1 everywhere else; every row solved by `iters` guarded CG iterations."""
+
+    def __init__(self, op: DistributedSparse, lam: float, seed: int = 2022):
+        self.op = op
+        self.h = _vp()
+        _check(lib().hnh_ials_create(op.h, float(lam), seed, C.byref(self.h)), "ials_create")
+
+    def set_confidence(self, w_s: Vec, w_st: Vec):
+        """w >= 0 per stored pair, in the like_S_values and the like_ST_values layouts"""
+        _check(lib().hnh_ials_set_confidence(self.h, w_s.h, w_st.h), "ials_set_confidence")
+
+    def initializeEmbeddings(self):
+        _check(lib().hnh_ials_initialize_embeddings(self.h), "ials_initialize_embeddings")
+
+    def set_embeddings(self, a: Dense, b: Dense):
+        _check(lib().hnh_ials_set_embeddings(self.h, a.h, b.h), "ials_set_embeddings")
+
+    def get_embeddings(self, a: Dense, b: Dense):
+        _check(lib().hnh_ials_get_embeddings(self.h, a.h, b.h), "ials_get_embeddings")
+
+    def half_step(self, matmode: int, iters: int):
+        _check(lib().hnh_ials_half_step(self.h, matmode, iters), "ials_half_step")
+
+    def run(self, steps: int, iters: int):
+        _check(lib().hnh_ials_run(self.h, steps, iters), "ials_run")
+
+    def loss(self) -> float:
+        out = C.c_double()
+        _check(lib().hnh_ials_loss(self.h, C.byref(out)), "ials_loss")
+        return out.value
+
+    def gram(self, matmode: int) -> np.ndarray:
+        """A^T A (AMAT) or B^T B (BMAT), summed over all ranks"""
+        r = self.op.info()["R"]
+        out = np.empty((r, r), dtype=np.float64)
+        _check(lib().hnh_ials_gram(self.h, matmode, out.ctypes.data), "ials_gram")
+        return out
+
+    def set_folded(self, folded: bool):
+        """True: one hnh_gram_rows_f64 launch adds the Gram term and updates the rows (R <= 256); False: the composed sequence"""
+        _check(lib().hnh_ials_set_folded(self.h, int(bool(folded))), "ials_set_folded")
+
+    def free(self):
+        if self.h:
+            _check(lib().hnh_ials_destroy(self.h), "ials_destroy")
             self.h = None
 
 

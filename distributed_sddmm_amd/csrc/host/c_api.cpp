@@ -8,6 +8,7 @@
 #include <string>
 
 #include "als_conjugate_gradients.hpp"
+#include "als_implicit.hpp"
 #include "cannon_dense_25d.hpp"
 #include "cannon_sparse_25d.hpp"
 #include "dense_shift_15d.hpp"
@@ -43,6 +44,11 @@ struct hnh_dist {
 struct hnh_als {
     hnh::World* w;
     std::unique_ptr<Distributed_ALS> a;
+};
+
+struct hnh_ials {
+    hnh::World* w;
+    std::unique_ptr<Implicit_ALS> a;
 };
 
 struct hnh_gat {
@@ -717,6 +723,49 @@ int hnh_als_run_cg(hnh_als* a, int steps) {
 }
 int hnh_als_compute_residual(hnh_als* a, double* out) {
     return guarded(a->w, [&] { *out = a->a->computeResidual(); });
+}
+
+// ------------------------------------------------------------------ implicit-feedback ALS
+int hnh_ials_create(hnh_dist* d, double lambda, uint64_t seed, hnh_ials** out) {
+    return guarded(d->w, [&] {
+        std::unique_ptr<hnh_ials> h(new hnh_ials());
+        h->w = d->w;
+        h->a.reset(new Implicit_ALS(d->d.get(), lambda, seed));
+        *out = h.release();
+    });
+}
+int hnh_ials_destroy(hnh_ials* a) {
+    return guarded(a ? a->w : nullptr, [&] { delete a; });
+}
+int hnh_ials_set_confidence(hnh_ials* a, hnh_vec* ws, hnh_vec* wst) {
+    return guarded(a->w, [&] { a->a->set_confidence(ws->v, wst->v); });
+}
+int hnh_ials_initialize_embeddings(hnh_ials* a) {
+    return guarded(a->w, [&] { a->a->initializeEmbeddings(); });
+}
+int hnh_ials_set_embeddings(hnh_ials* a, hnh_dense* A, hnh_dense* B) {
+    return guarded(a->w, [&] { a->a->set_embeddings(A->m, B->m); });
+}
+int hnh_ials_get_embeddings(hnh_ials* a, hnh_dense* A, hnh_dense* B) {
+    return guarded(a->w, [&] {
+        if (A) A->m = a->a->A;
+        if (B) B->m = a->a->B;
+    });
+}
+int hnh_ials_half_step(hnh_ials* a, int matmode, int cg_iters) {
+    return guarded(a->w, [&] { a->a->half_step(matmode == HNH_AMAT ? Amat : Bmat, cg_iters); });
+}
+int hnh_ials_run(hnh_ials* a, int steps, int cg_iters) {
+    return guarded(a->w, [&] { a->a->run(steps, cg_iters); });
+}
+int hnh_ials_loss(hnh_ials* a, double* out) {
+    return guarded(a->w, [&] { *out = a->a->loss(); });
+}
+int hnh_ials_gram(hnh_ials* a, int matmode, double* host) {
+    return guarded(a->w, [&] { a->a->gram(matmode == HNH_AMAT ? Amat : Bmat, host); });
+}
+int hnh_ials_set_folded(hnh_ials* a, int folded) {
+    return guarded(a->w, [&] { a->a->set_folded(folded != 0); });
 }
 
 // ------------------------------------------------------------------ GAT

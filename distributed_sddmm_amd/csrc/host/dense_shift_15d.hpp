@@ -21,6 +21,8 @@
 // the block decomposition and the arithmetic are those of the reference's cyclic shift; only the route
 // differs.  HNH_RING_MODE=relay|mesh selects it (default mesh); the read-write ring always relays.
 #pragma once
+#include <cxxabi.h>
+#include <typeinfo>
 #include "distributed_sparse.hpp"
 
 class ShardedBlockCyclicColumn : public NonzeroDistribution {
@@ -283,6 +285,48 @@ public:
         fused_pass(Xin, mode == Amat ? localB : localA, mode == Amat ? S.get() : ST.get(), &Out, leaky ? HNH_FUSED_LEAKY_RELU : 0u, &extras);
         return true;
     }
+
+    // The same pass with per-nonzero WEIGHTS on the SpMM half: Out_i = sum_e weights[e] <x_i, y_j> y_j (+ the extras' epilogue), the
+    // operator of implicit-feedback ALS (als_implicit.hpp).  `weights` has the like_S_values layout (mode Amat) or the like_ST_values
+    // layout (Bmat) and is lent to the blocks by block start for the call (CSRLocal::spmm_values); a slice that SpmatLocal::lendable()
+    // refuses is copied once to scratch of the schedule's, which is kept until forget_fused_weights() or another vector or width comes.
+    // Fusion approach 2 only, c = 1 and c > 1; the kernel implementation must borrow value arrays.  Not a virtual of Distributed_Sparse,
+    // for fusedSoftmax_out's reason.
+    void fusedSpMM_out(DenseMatrix& localA, DenseMatrix& localB, MatMode mode, DenseMatrix& Out, const hnh_fused_extras& extras, const VectorXd& weights) {
+        if (fusionApproach != 2) hnh::fatal("Error, fusedSpMM_out with weights requires fusion approach 2 (15d_fusion2)!");
+        if (!kernel->borrows_value_arrays()) {
+            int status = 0;
+            char* plain = abi::__cxa_demangle(typeid(*kernel).name(), nullptr, nullptr, &status);
+            const std::string name = (status == 0 && plain) ? plain : typeid(*kernel).name();
+            std::free(plain);
+            hnh::fatal("Error, fusedSpMM_out with weights needs a kernel implementation that borrows value arrays, which " + name +
+                       " does not (KernelImplementation::borrows_value_arrays)!");
+        }
+        if (extras.leaky_alpha != 0.0 || extras.relu_dst != nullptr) hnh::fatal("Error, fusedSpMM_out with weights takes x_scale, rowdot and cg only!");
+        DenseMatrix& Xin = (mode == Amat) ? localA : localB;
+        if (Out.rows() != Xin.rows() || Out.cols() != Xin.cols() || Out.data() == Xin.data())
+            hnh::fatal("Error, fusedSpMM_out needs a separate output of the input's shape!");
+        SpmatLocal* s = mode == Amat ? S.get() : ST.get();
+        FusedWeightScratch& fw = fused_weight_scratch[mode == Amat ? 0 : 1];
+        const bool fresh = fw.src != weights.data() || fw.R != R;
+        fw.src = weights.data();
+        fw.R = R;
+        s->lendFusedWeights(weights, R, borrow_mode, fw.copies, fresh);
+        const LentSlices lent = {s};
+        fused_pass(Xin, mode == Amat ? localB : localA, s, &Out, 0u, &extras);
+    }
+    // the weights' contents are about to change (or their vector to go): the next weighted call copies again what it cannot borrow
+    void forget_fused_weights() {
+        for (auto& fw : fused_weight_scratch) {
+            fw.src = nullptr;
+            fw.copies.clear();
+        }
+    }
+    struct FusedWeightScratch {
+        const double* src = nullptr;
+        int64_t R = -1;
+        std::vector<VectorXd> copies;
+    } fused_weight_scratch[2];  // [0]: weights over S, [1]: over S^T
 
     // Neighbourhood-softmax attention (include/hnh_attention.h) in one fused pass: Out's rows are the running accumulators, `state`
     // holds the rows' running max / sum, the log-sum-exp and the ReLU destination.  Returns false, having done nothing, where a row's

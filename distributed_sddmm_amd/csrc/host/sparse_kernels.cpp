@@ -96,19 +96,19 @@ size_t StandardKernel::fused_local(SpmatLocal& S, DenseMatrix& A, DenseMatrix& B
         return 0;
     }
     if (blk->transpose) hnh::fatal("Error, local matrix is transposed, can't perform the fused SDDMM+SpMM");
-    CSRHandle* active = blk->getActive();
+    CSRHandle* active = blk->getActive();  // (blk->spmm_values: null, or the lent per-nonzero weights of the SpMM half, lendFusedWeights)
     begin(w);
     hnh_csr_window win;
     const hnh_csr_block desc = blk->block_args();
     if (blk->window_args(&win)) {
         if (wants_epilogue(extras) && !win.last) hnh::fatal("Error, the row epilogue belongs to the block's last window!");
-        w->check(w->be->hnh_fused_sddmm_spmm_csr_p(w->ctx, &desc, active->values, nullptr, A.data(), B.data(), Out.data(), (int)A.cols(), flags, extras,
+        w->check(w->be->hnh_fused_sddmm_spmm_csr_p(w->ctx, &desc, active->values, blk->spmm_values, A.data(), B.data(), Out.data(), (int)A.cols(), flags, extras,
                                                    &win, HNH_STREAM_COMPUTE),
                  "hnh_fused_sddmm_spmm_csr_p");
         end(w);
         return 0;
     }
-    w->check(w->be->hnh_fused_sddmm_spmm_csr_p(w->ctx, &desc, active->values, nullptr, A.data(), B.data(), Out.data(), (int)A.cols(), flags, extras,
+    w->check(w->be->hnh_fused_sddmm_spmm_csr_p(w->ctx, &desc, active->values, blk->spmm_values, A.data(), B.data(), Out.data(), (int)A.cols(), flags, extras,
                                                nullptr, HNH_STREAM_COMPUTE),
              "hnh_fused_sddmm_spmm_csr_p");
     end(w, profile ? w->be->hnh_panel_count(w->ctx, desc.rows, desc.nnz, desc.cols, (int)A.cols(), desc.max_row_nnz) : 1);

@@ -87,7 +87,11 @@ public:
     //   spmm_values               the SpMM reads its nonzero values here — the copy of setCSRValues (SpmatLocal.hpp:571-579) is skipped;
     //   sddmm_dst / sddmm_scale   the SDDMM stores scale[e] * dot[e] into dst[e] (result and SValues slices) — the block's own values
     //                             and the closing Hadamard pass (15D_dense_shift.hpp:366) are not touched.
-    // Set through SpmatLocal::lendCSRValues / lendSddmmTargets, cleared by reclaimValueArrays() before the operation returns.
+    //                             In a FUSED pass the same pointer is the per-nonzero weight of the SpMM half (the `svalues` of
+    //                             hnh_fused_sddmm_spmm_csr_p: Out_i = sum_e w_e <x_i, y_j> y_j) — the confidence weights of Implicit_ALS,
+    //                             lent by lendFusedWeights.  It is this member and not a further one because drivers compiled against
+    //                             earlier headers construct CSRLocal themselves: the library may read only what their objects have.
+    // Set through SpmatLocal::lendCSRValues / lendSddmmTargets / lendFusedWeights, cleared by reclaimValueArrays() before the operation returns.
     const double* spmm_values = nullptr;
     double* sddmm_dst = nullptr;
     const double* sddmm_scale = nullptr;
@@ -868,6 +872,30 @@ public:
                 blk->sddmm_scale = scale;
                 borrow_stats[2]++;
             }
+        }
+    }
+
+    // for a fused pass with per-nonzero weights (Sparse15D_Dense_Shift::fusedSpMM_out with a weights vector): block i reads its slice of
+    // `weights` in place where lendable() allows, and otherwise the copy of that slice in scratch[i], which the caller keeps for as long
+    // as the weights stay the same (`fresh`: the copies have to be made now; a slice that can be lent needs none)
+    void lendFusedWeights(const hnh::VectorXd& weights, int64_t R, int mode, std::vector<hnh::VectorXd>& scratch, bool fresh) {
+        if (!blockStarts.empty() && (uint64_t)weights.size() < blockStarts.back()) hnh::fatal("Error, sparse value vector has the wrong length!");
+        if (scratch.size() + 1 < blockStarts.size()) scratch.resize(blockStarts.size() - 1);
+        for (size_t i = 0; i + 1 < blockStarts.size(); i++) {
+            CSRLocal* blk = csr_blocks[i];
+            if (blk == nullptr) continue;
+            if (blk->shifting) hnh::fatal("Error, a travelling block cannot borrow a weight slice!");
+            const double* src = weights.data() + blockStarts[i];
+            const int64_t n = (int64_t)(blockStarts[i + 1] - blockStarts[i]);
+            if (n == 0 || lendable(src, R, mode)) {
+                blk->spmm_values = src;
+                continue;
+            }
+            if (fresh || scratch[i].size() != n) {
+                scratch[i] = hnh::VectorXd(n);
+                world->copy(scratch[i].data(), src, sizeof(double) * (size_t)n, HNH_COPY_D2D, HNH_STREAM_COMPUTE);
+            }
+            blk->spmm_values = scratch[i].data();
         }
     }
 

@@ -216,6 +216,25 @@ int hnh_als_cg_optimizer(hnh_als* a, int matmode, int cg_max_iter);             
 int hnh_als_run_cg(hnh_als* a, int n_alternating_steps);                               /* run_cg (.cpp:235-263)      */
 int hnh_als_compute_residual(hnh_als* a, double* out);                                 /* computeResidual (.cpp:201-219) */
 
+/* ---- implicit-feedback ALS with confidence weights (an addition; csrc/host/als_implicit.hpp: Implicit_ALS).  The model of Hu, Koren and
+ * Volinsky: preference 1 with confidence 1 + w_e on the stored pairs, preference 0 with confidence 1 on every other pair, every row
+ * solved by a few guarded CG iterations.  Schedule 15d_fusion2 only (anything else is refused by name), lambda > 0.  Kernels: the Gram
+ * matrices need include/hnh_grad.h; folded mode needs include/hnh_als_implicit.h (both optional groups: a kernel library without one
+ * makes hnh_ials_half_step / _run / _loss / _gram fail with an error naming the missing symbol). */
+typedef struct hnh_ials hnh_ials; /* Implicit_ALS */
+int hnh_ials_create(hnh_dist* d, double lambda, uint64_t seed, hnh_ials** out);
+int hnh_ials_destroy(hnh_ials* a);
+/* w >= 0 and finite per stored pair, in the like_S_values and the like_ST_values layouts (copied in) */
+int hnh_ials_set_confidence(hnh_ials* a, hnh_vec* w_S_order, hnh_vec* w_ST_order);
+int hnh_ials_initialize_embeddings(hnh_ials* a);                      /* Distributed_ALS's hashed fill */
+int hnh_ials_set_embeddings(hnh_ials* a, hnh_dense* A, hnh_dense* B); /* copied in  */
+int hnh_ials_get_embeddings(hnh_ials* a, hnh_dense* A, hnh_dense* B); /* copied out */
+int hnh_ials_half_step(hnh_ials* a, int matmode, int cg_iters);       /* the factor `matmode` names, the other one fixed */
+int hnh_ials_run(hnh_ials* a, int n_alternating_steps, int cg_iters);
+int hnh_ials_loss(hnh_ials* a, double* out);                          /* the objective, the same number on every rank */
+int hnh_ials_gram(hnh_ials* a, int matmode, double* host_RxR);        /* A^T A or B^T B over all ranks, to host memory */
+int hnh_ials_set_folded(hnh_ials* a, int folded);                     /* 1: hnh_gram_rows_f64 with the update; 0: the composed sequence */
+
 /* ---- GAT forward pass (gat.hpp; BASELINE config 5's second application) */
 typedef struct hnh_gat hnh_gat; /* GAT */
 /* GAT(layers, d_ops) (gat.hpp:57-81): spec3 = {input_features, features_per_head, num_heads} per layer */

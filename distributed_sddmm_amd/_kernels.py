@@ -259,6 +259,17 @@ ALS_IMPLICIT_SIGNATURES = {
 GRAM_MAX_R = 256  # HNH_GRAM_MAX_R
 
 
+# include/hnh_topk.h: top-k recommendation for implicit-feedback ALS (api.ImplicitALS.recommend): scores and selection in one kernel, the
+# merge of lists and a row gather; a further OPTIONAL group bound only for the product library
+TOPK_SIGNATURES = {
+    "hnh_topk_rows_f64_workspace": (_i64, [_i64, _i64, _i32, _i32]),
+    "hnh_topk_rows_f64": (_i32, [_vp, _vp, _i64, _vp, _i64, _i32, _i64, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _i64, _i32]),
+    "hnh_topk_merge_f64": (_i32, [_vp, _vp, _vp, _i32, _i64, _i32, _vp, _vp, _i32]),
+    "hnh_take_rows_f64": (_i32, [_vp, _vp, _i64, _i32, _vp, _i64, _vp, _i32]),
+}
+TOPK_MAX_K, TOPK_MAX_R, TOPK_MAX_SPLITS = 128, 512, 1024  # HNH_TOPK_MAX_*
+
+
 class GramCg(C.Structure):
     """struct hnh_gram_cg"""
     _fields_ = [("x", _vp), ("r", _vp), ("p", _vp), ("rs", _vp)]
@@ -438,7 +449,7 @@ def load(path: str | None = None) -> C.CDLL:
                 list(V2_SIGNATURES.items()) + list(ATTN_COEF_SIGNATURES.items()) + list(SKIP_SIGNATURES.items()) + \
                 list(QKV_SIGNATURES.items()) + list(EDGE_SIGNATURES.items()) + list(EDGE_GRAD_SIGNATURES.items()) + \
                 list(NORM_SIGNATURES.items()) + list(MULTILABEL_SIGNATURES.items()) + list(TRAIN_CLIP_SIGNATURES.items()) + \
-                list(ALS_IMPLICIT_SIGNATURES.items()):
+                list(ALS_IMPLICIT_SIGNATURES.items()) + list(TOPK_SIGNATURES.items()):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
     if path is None:

@@ -131,6 +131,7 @@ SIGNATURES = {
     "hnh_ials_loss": (_i32, [_vp, _pdbl]),
     "hnh_ials_gram": (_i32, [_vp, _i32, _vp]),
     "hnh_ials_set_folded": (_i32, [_vp, _i32]),
+    "hnh_ials_recommend": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp, _vp]),
     "hnh_gat_create": (_i32, [_vp, _i32, _pi32, _dbl, _pvp]),
     "hnh_gat_destroy": (_i32, [_vp]),
     "hnh_gat_weight_shape": (_i32, [_vp, _i32, _i32, _pi64]),
@@ -784,6 +785,52 @@ class ImplicitALS:
     def set_folded(self, folded: bool):
         """True: one hnh_gram_rows_f64 launch adds the Gram term and updates the rows (R <= 256); False: the composed sequence"""
         _check(lib().hnh_ials_set_folded(self.h, int(bool(folded))), "ials_set_folded")
+
+    def recommend(self, users, k: int = 10, filter_seen: bool = True):
+        """The first k items of every user (global row numbers, repeats allowed) by <a_u, b_j>, score descending and then item id
+        ascending: (ids int64 [nq, k], scores float64 [nq, k]), the tail (-1, -inf) where fewer than k items are left.  filter_seen: the
+        items of the user's row of S are never returned.  Collective: every rank passes the same users and gets the same arrays."""
+        users = np.ascontiguousarray(np.asarray(users, dtype=np.int64).reshape(-1))
+        nq = len(users)
+        ids = np.empty((nq, int(k)) if k >= 1 else (nq, 0), dtype=np.int64)
+        scores = np.empty(ids.shape, dtype=np.float64)
+        _check(lib().hnh_ials_recommend(self.h, users.ctypes.data, nq, int(k), int(bool(filter_seen)), ids.ctypes.data, scores.ctypes.data), "ials_recommend")
+        return ids, scores
+
+    def ranking_metrics(self, test_rows, test_cols, k: int = 10, batch: int = 1024) -> dict:
+        """precision, map and ndcg at k (the definitions of the `implicit` package's ranking_metrics_at_k) on held-out pairs in global
+        coordinates, the same on every rank.  The users are those with a held-out pair; they are recommended in batches with
+        filter_seen=True and the sums are kept in numpy on the host.  For a user with held-out set L and list r_1 .. r_k, m = min(k, |L|):
+        precision = sum hits / sum m; map = mean of (sum_t [r_t in L] hits_<=t / t) / m; ndcg = mean of sum_t [r_t in L] / log2(t + 1)
+        over sum_{t <= m} 1 / log2(t + 1).  Entries with id -1 are misses."""
+        test_rows = np.asarray(test_rows, dtype=np.int64).reshape(-1)
+        test_cols = np.asarray(test_cols, dtype=np.int64).reshape(-1)
+        if len(test_rows) != len(test_cols) or batch < 1:
+            raise ValueError("ranking_metrics needs as many rows as columns and batch >= 1")
+        order = np.lexsort((test_cols, test_rows))
+        rows, cols = test_rows[order], test_cols[order]
+        users, starts = np.unique(rows, return_index=True)
+        ends = np.append(starts[1:], len(rows))
+        discount = 1.0 / np.log2(np.arange(2, k + 2))
+        hits_total, m_total, ap_sum, ndcg_sum = 0.0, 0.0, 0.0, 0.0
+        for b in range(0, len(users), batch):
+            ids, _ = self.recommend(users[b:b + batch], k, True)
+            for n, row in enumerate(ids):
+                liked = set(cols[starts[b + n]:ends[b + n]].tolist())
+                m = min(k, len(liked))
+                hits, ap, dcg = 0, 0.0, 0.0
+                for t, item in enumerate(row.tolist(), start=1):
+                    if item >= 0 and item in liked:
+                        hits += 1
+                        ap += hits / t
+                        dcg += discount[t - 1]
+                hits_total += hits
+                m_total += m
+                ap_sum += ap / m
+                ndcg_sum += dcg / discount[:m].sum()
+        n_users = len(users)
+        return dict(precision=float(hits_total / m_total) if m_total else 0.0, map=float(ap_sum / n_users) if n_users else 0.0,
+                    ndcg=float(ndcg_sum / n_users) if n_users else 0.0, users=n_users)
 
     def free(self):
         if self.h:

@@ -25,8 +25,18 @@
 // Both need hnh_gemm_tn_f64 of include/hnh_grad.h for the Gram matrices; a kernel library without a needed group is refused through
 // Backend::missing_kernel().  Schedule: 15d_fusion2 only (c = 1 and c > 1): its fused pass takes the weights, and its layout gives every
 // rank distinct rows of A and of B, so the Gram matrix is the sum of the ranks' own.
+//
+// Serving.  recommend() returns, for a batch of users, the k items with the largest <a_u, b_j> in the total order of include/hnh_topk.h
+// (score descending, then item id ascending), with or without the items of the user's row of S.  Every rank searches its own valid rows
+// of B with hnh_topk_rows_f64 (scores and selection in one kernel: no M x N product is stored anywhere), the ranks' lists are all-gathered
+// and merged by hnh_topk_merge_f64.  A score's bits depend on its two rows and R only, and the order is strict, so every rank count gives
+// the same bits.  The exclusion lists come from the GLOBAL coordinates of the rank's stored pairs, which the schedule does not keep: they
+// are read back once, by two SDDMM calls on probe matrices (row ids against ones, ones against column ids), and cached in the object.
 #pragma once
+#include <algorithm>
 #include <cmath>
+#include <cstring>
+#include <unordered_map>
 #include "dense_shift_15d.hpp"
 
 class Implicit_ALS {
@@ -203,8 +213,154 @@ public:
         return (sums[0] - sums[1]) + cross + lambda * norms;
     }
 
+    // The first k items of every user of `users` (nq global row numbers, repeats allowed) by <a_u, b_j>, best first: ids_host and
+    // scores_host receive nq x k entries, global item ids, the tail (-1, -infinity) where fewer than k items are left.  filter_seen: the
+    // items of the user's row of S are never returned (S's pattern is enough: set_confidence is not needed).  COLLECTIVE: every rank passes
+    // the same users and receives the same result.  There is no host fallback: a kernel library without include/hnh_topk.h is refused.
+    void recommend(const int64_t* users, int64_t nq, int k, bool filter_seen, int64_t* ids_host, double* scores_host) {
+        require_embeddings("recommend");
+        hnh::World* w = d_ops->world;
+        hnh::Backend* be = w->be;
+        const int R = (int)d_ops->R;
+        if (k < 1 || k > HNH_TOPK_MAX_K)
+            throw hnh::Error("Error, Implicit_ALS recommend needs 1 <= k <= HNH_TOPK_MAX_K = " + std::to_string(HNH_TOPK_MAX_K) + ", not k = " + std::to_string(k) + "!");
+        if (nq < 0 || (nq > 0 && (users == nullptr || ids_host == nullptr || scores_host == nullptr)))
+            throw hnh::Error("Error, Implicit_ALS recommend needs nq >= 0 and its three arrays!");
+        for (int64_t q = 0; q < nq; q++)
+            if (users[q] < 0 || users[q] >= d_ops->M)
+                throw hnh::Error("Error, Implicit_ALS recommend: user " + std::to_string(users[q]) + " is outside [0, M = " + std::to_string(d_ops->M) + ")!");
+        if (R > HNH_TOPK_MAX_R)
+            throw hnh::Error("Error, Implicit_ALS recommend supports R <= HNH_TOPK_MAX_R = " + std::to_string(HNH_TOPK_MAX_R) + ", not R = " + std::to_string(R) + "!");
+        if (be->hnh_topk_rows_f64 == nullptr || be->hnh_topk_rows_f64_workspace == nullptr || be->hnh_topk_merge_f64 == nullptr || be->hnh_take_rows_f64 == nullptr)
+            throw hnh::Error(be->missing_kernel("Implicit_ALS recommend", "hnh_topk_rows_f64"));
+        if (nq == 0) return;
+        const DenseSubmatrix& subA = d_ops->aSubmatrices[0];
+        const DenseSubmatrix& subB = d_ops->bSubmatrices[0];
+        const int64_t validB = std::max<int64_t>(0, std::min<int64_t>(subB.rowCount, d_ops->N - subB.topRow));
+
+        // the queries' rows of A, the same bits on every rank: each rank gathers the rows it owns into a zeroed matrix, and adding +0.0 is exact
+        std::vector<int64_t> idx((size_t)nq);
+        for (int64_t q = 0; q < nq; q++) {
+            const int64_t local = users[q] - subA.topRow;
+            idx[(size_t)q] = (local >= 0 && local < subA.rowCount) ? local : -1;
+        }
+        DenseMatrix idx_d(nq, 1), Qd(nq, R);  // (idx_d holds int64)
+        w->copy(idx_d.data(), idx.data(), (size_t)nq * sizeof(int64_t), HNH_COPY_H2D, HNH_STREAM_COMPUTE);
+        w->check(be->hnh_take_rows_f64(w->ctx, A.data(), subA.rowCount, R, reinterpret_cast<const int64_t*>(idx_d.data()), nq, Qd.data(), HNH_STREAM_COMPUTE),
+                 "hnh_take_rows_f64");
+        w->allreduce_f64(w->world_comm(), Qd.data(), (size_t)(nq * R), HNH_STREAM_COMPUTE);
+
+        // the exclusion lists of this rank's rows of B, as a CSR over the queries
+        DenseMatrix excl_ptr_d, excl_idx_d;
+        if (filter_seen) {
+            std::vector<int64_t> ptr;
+            std::vector<int32_t> items;
+            seen_lists(users, nq, subB.topRow, validB, ptr, items);
+            excl_ptr_d = DenseMatrix(nq + 1, 1);
+            excl_idx_d = DenseMatrix((int64_t)(items.size() / 2 + 1), 1);  // (int32, two to a double; never empty)
+            w->copy(excl_ptr_d.data(), ptr.data(), ptr.size() * sizeof(int64_t), HNH_COPY_H2D, HNH_STREAM_COMPUTE);
+            if (!items.empty()) w->copy(excl_idx_d.data(), items.data(), items.size() * sizeof(int32_t), HNH_COPY_H2D, HNH_STREAM_COMPUTE);
+        }
+        w->sync(HNH_STREAM_COMPUTE);  // the host arrays above may go
+
+        // this rank's list, then every rank's, then their merge: [scores | ids] in one buffer, downloaded once
+        const int64_t list = nq * k;
+        const int p = w->size;
+        DenseMatrix mine(2 * list, 1), merged(2 * list, 1);
+        const int64_t need = be->hnh_topk_rows_f64_workspace(nq, validB, R, k);
+        DenseMatrix work(std::max<int64_t>((need + 7) / 8, 2), 1);
+        DenseMatrix& local_out = p > 1 ? mine : merged;
+        w->check(be->hnh_topk_rows_f64(w->ctx, Qd.data(), nq, B.data(), validB, R, subB.topRow, filter_seen ? reinterpret_cast<const int64_t*>(excl_ptr_d.data()) : nullptr,
+                                       filter_seen ? reinterpret_cast<const int32_t*>(excl_idx_d.data()) : nullptr, k, 0, local_out.data(),
+                                       reinterpret_cast<int64_t*>(local_out.data() + list), work.data(), work.size() * 8, HNH_STREAM_COMPUTE),
+                 "hnh_topk_rows_f64");
+        if (p > 1) {
+            DenseMatrix all_s((int64_t)p * list, 1), all_i((int64_t)p * list, 1);
+            w->allgather(w->world_comm(), mine.data(), all_s.data(), (size_t)list * sizeof(double), HNH_STREAM_COMPUTE);
+            w->allgather(w->world_comm(), mine.data() + list, all_i.data(), (size_t)list * sizeof(int64_t), HNH_STREAM_COMPUTE);
+            w->check(be->hnh_topk_merge_f64(w->ctx, all_s.data(), reinterpret_cast<const int64_t*>(all_i.data()), p, nq, k, merged.data(),
+                                            reinterpret_cast<int64_t*>(merged.data() + list), HNH_STREAM_COMPUTE),
+                     "hnh_topk_merge_f64");
+            w->sync(HNH_STREAM_COMPUTE);  // (the gathered lists go out of scope)
+        }
+        std::vector<double> host((size_t)(2 * list));
+        merged.copy_to_host(host.data());
+        std::memcpy(scores_host, host.data(), (size_t)list * sizeof(double));
+        std::memcpy(ids_host, host.data() + list, (size_t)list * sizeof(int64_t));
+    }
+
 private:
     VectorXd w_S_, w_ST_, c_S_, c_ST_;
+    std::vector<int64_t> seen_rows_, seen_cols_;  // global coordinates of this rank's stored pairs (like_S_values order), read once
+    bool seen_cached_ = false;
+
+    // The global coordinates of the local stored pairs: sddmmA of (row id in column 0) against (1 in column 0) gives every pair its row,
+    // and the other way round its column (ids are exact in fp64).  Cached: S's pattern never changes.
+    void cache_seen_coordinates() {
+        if (seen_cached_) return;
+        const int64_t R = d_ops->R;
+        DenseMatrix PA = d_ops->like_A_matrix(0.0), PB = d_ops->like_B_matrix(0.0);
+        VectorXd ones = d_ops->like_S_values(1.0), s = d_ops->like_S_values(0.0);
+        std::vector<double> ha((size_t)(PA.rows() * R), 0.0), hb((size_t)(PB.rows() * R), 0.0);
+        const int64_t topA = d_ops->aSubmatrices[0].topRow, topB = d_ops->bSubmatrices[0].topRow;
+        for (int pass = 0; pass < 2; pass++) {
+            for (int64_t i = 0; i < PA.rows(); i++) ha[(size_t)(i * R)] = pass == 0 ? (double)(topA + i) : 1.0;
+            for (int64_t j = 0; j < PB.rows(); j++) hb[(size_t)(j * R)] = pass == 0 ? 1.0 : (double)(topB + j);
+            PA.copy_from_host(ha.data());
+            PB.copy_from_host(hb.data());
+            d_ops->sddmmA(PA, PB, ones, s);
+            const std::vector<double> got = s.to_host();
+            std::vector<int64_t>& dst = pass == 0 ? seen_rows_ : seen_cols_;
+            dst.resize(got.size());
+            for (size_t e = 0; e < got.size(); e++) dst[e] = (int64_t)std::llround(got[e]);
+        }
+        seen_cached_ = true;
+    }
+
+    // ptr / items: for every query q the rows j - topB of this rank's valid B rows whose item j the user has seen, ascending and without
+    // repeats.  With c > 1 a rank's block of S is not aligned with its rows of B, so the (query, item) pairs of all ranks are exchanged:
+    // one round of counts, one padded round of payload.
+    void seen_lists(const int64_t* users, int64_t nq, int64_t topB, int64_t validB, std::vector<int64_t>& ptr, std::vector<int32_t>& items) {
+        cache_seen_coordinates();
+        hnh::World* w = d_ops->world;
+        std::unordered_map<int64_t, std::vector<int64_t>> queries_of;  // a user may be asked for more than once
+        for (int64_t q = 0; q < nq; q++) queries_of[users[q]].push_back(q);
+        std::vector<int64_t> pairs;  // (query, item), ...
+        for (size_t e = 0; e < seen_rows_.size(); e++) {
+            auto it = queries_of.find(seen_rows_[e]);
+            if (it == queries_of.end()) continue;
+            for (int64_t q : it->second) {
+                pairs.push_back(q);
+                pairs.push_back(seen_cols_[e]);
+            }
+        }
+        const int p = w->size;
+        std::vector<int64_t> counts((size_t)p, 0);
+        const int64_t my_count = (int64_t)pairs.size();
+        w->host_allgather(&my_count, counts.data(), sizeof(int64_t));
+        const int64_t widest = *std::max_element(counts.begin(), counts.end());
+        std::vector<int64_t> all((size_t)p * (size_t)widest, 0);
+        if (widest > 0) {
+            pairs.resize((size_t)widest, 0);
+            w->host_allgather(pairs.data(), all.data(), (size_t)widest * sizeof(int64_t));
+        }
+        std::vector<std::pair<int64_t, int64_t>> mine;
+        for (int r = 0; r < p; r++)
+            for (int64_t x = 0; x + 1 < counts[(size_t)r]; x += 2) {
+                const int64_t q = all[(size_t)r * (size_t)widest + (size_t)x], j = all[(size_t)r * (size_t)widest + (size_t)x + 1] - topB;
+                if (j >= 0 && j < validB) mine.emplace_back(q, j);
+            }
+        std::sort(mine.begin(), mine.end());
+        mine.erase(std::unique(mine.begin(), mine.end()), mine.end());
+        ptr.assign((size_t)nq + 1, 0);
+        items.clear();
+        for (const auto& qj : mine) {
+            ptr[(size_t)qj.first + 1]++;
+            items.push_back((int32_t)qj.second);
+        }
+        for (int64_t q = 0; q < nq; q++) ptr[(size_t)q + 1] += ptr[(size_t)q];
+    }
+
     std::vector<double> w_host_;  // w in the like_S_values layout, for loss()
     bool confidence_set_ = false, folded_ = false;
 

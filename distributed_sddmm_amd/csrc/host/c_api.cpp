@@ -767,6 +767,9 @@ int hnh_ials_gram(hnh_ials* a, int matmode, double* host) {
 int hnh_ials_set_folded(hnh_ials* a, int folded) {
     return guarded(a->w, [&] { a->a->set_folded(folded != 0); });
 }
+int hnh_ials_recommend(hnh_ials* a, const int64_t* users, int64_t nq, int k, int filter_seen, int64_t* ids, double* scores) {
+    return guarded(a->w, [&] { a->a->recommend(users, nq, k, filter_seen != 0, ids, scores); });
+}
 
 // ------------------------------------------------------------------ GAT
 int hnh_gat_create(hnh_dist* d, int nlayers, const int* spec3, double alpha, hnh_gat** out) {

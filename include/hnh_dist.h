@@ -234,6 +234,11 @@ int hnh_ials_run(hnh_ials* a, int n_alternating_steps, int cg_iters);
 int hnh_ials_loss(hnh_ials* a, double* out);                          /* the objective, the same number on every rank */
 int hnh_ials_gram(hnh_ials* a, int matmode, double* host_RxR);        /* A^T A or B^T B over all ranks, to host memory */
 int hnh_ials_set_folded(hnh_ials* a, int folded);                     /* 1: hnh_gram_rows_f64 with the update; 0: the composed sequence */
+/* The first k items (1 <= k <= 128) of each of the nq users (global row numbers, repeats allowed) by <a_u, b_j>, score descending and then
+ * item id ascending: ids and scores are host arrays of nq x k, global item ids, the tail (-1, -infinity) where fewer than k items are
+ * left.  filter_seen != 0: the items of the user's row of S are never returned.  Collective: every rank passes the same users and gets
+ * the same result, bit-identical for every rank count.  Needs include/hnh_topk.h (an optional group; there is no host fallback). */
+int hnh_ials_recommend(hnh_ials* a, const int64_t* users, int64_t nq, int k, int filter_seen, int64_t* ids, double* scores);
 
 /* ---- GAT forward pass (gat.hpp; BASELINE config 5's second application) */
 typedef struct hnh_gat hnh_gat; /* GAT */

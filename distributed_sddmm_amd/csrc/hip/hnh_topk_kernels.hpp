@@ -395,6 +395,9 @@ int hnh_topk_rows_f64(hnh_ctx* ctx, const double* Q, int64_t nq, const double* Y
     if (const char* bad = topk_bad_shape(nq, n, R, k)) return hnh::fail(ctx, HNH_ERR_INVALID, std::string("hnh_topk_rows_f64: ") + bad);
     if (splits < 0 || splits > HNH_TOPK_MAX_SPLITS)
         return hnh::fail(ctx, HNH_ERR_INVALID, "hnh_topk_rows_f64: splits must be between 0 and HNH_TOPK_MAX_SPLITS = " + std::to_string(HNH_TOPK_MAX_SPLITS));
+    // -1 marks an empty entry and the merge takes every negative id for one: the ids id_base .. id_base + n - 1 must be real ones
+    if (id_base < 0 || id_base > INT64_MAX - n)
+        return hnh::fail(ctx, HNH_ERR_INVALID, "hnh_topk_rows_f64: id_base must be between 0 and INT64_MAX - n, not " + std::to_string(id_base));
     if (nq == 0) return HNH_OK;
     if (!Q || (n > 0 && !Y) || !out_scores || !out_ids || !work || (excl_ptr != nullptr && excl_idx == nullptr))
         return hnh::fail(ctx, HNH_ERR_INVALID, "hnh_topk_rows_f64: null pointer");

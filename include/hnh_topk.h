@@ -42,14 +42,15 @@ int64_t hnh_topk_rows_f64_workspace(int64_t nq, int64_t n, int R, int k);
  *   library choose, 1 .. HNH_TOPK_MAX_SPLITS forces it.  The result does not depend on it.
  *   work, work_bytes: scratch of at least hnh_topk_rows_f64_workspace() bytes, 16-byte aligned; its contents are undefined afterwards.
  * 1 <= k <= HNH_TOPK_MAX_K, 1 <= R <= HNH_TOPK_MAX_R, any nq >= 0 and n >= 0 (nq == 0: nothing is launched; n == 0: every entry is
- * empty); remainders in nq, n and R are handled, and 16-byte loads are used only where base and pitch allow.  Q, Y and the lists are
+ * empty), 0 <= id_base <= INT64_MAX - n (a negative id would read as an empty entry in a merged list); remainders in nq, n and R are handled, and 16-byte loads are used only where base and pitch allow.  Q, Y and the lists are
  * read only.  Anything else fails with HNH_ERR_INVALID and a message, and nothing is launched. */
 int hnh_topk_rows_f64(hnh_ctx* ctx, const double* Q, int64_t nq, const double* Y, int64_t n, int R, int64_t id_base, const int64_t* excl_ptr,
                       const int32_t* excl_idx, int k, int splits, double* out_scores, int64_t* out_ids, void* work, int64_t work_bytes, int stream);
 
-/* The first k of the union of `parts` lists per query in the total order: in_scores and in_ids are laid out [part][nq][k], entries with
- * id -1 are empty (their scores are ignored), all other ids of a query are distinct.  out_scores, out_ids: nq x k, best first, the tail
- * (-infinity, -1).  The outputs must not overlap the inputs.  parts >= 1, nq >= 0, 1 <= k <= HNH_TOPK_MAX_K. */
+/* The first k of the union of `parts` lists per query in the total order: in_scores and in_ids are laid out [part][nq][k], real ids are
+ * >= 0 and EVERY negative id is an empty entry (the lists of hnh_topk_rows_f64 use -1; the score of an empty entry is ignored, NaN
+ * included), all real ids of a query are distinct.  A score keeps its bits (the sign of a zero too).  out_scores, out_ids: nq x k, best
+ * first, the tail (-infinity, -1).  The outputs must not overlap the inputs.  parts >= 1, nq >= 0, 1 <= k <= HNH_TOPK_MAX_K. */
 int hnh_topk_merge_f64(hnh_ctx* ctx, const double* in_scores, const int64_t* in_ids, int parts, int64_t nq, int k, double* out_scores,
                        int64_t* out_ids, int stream);
 

@@ -1,6 +1,9 @@
 """Top-k recommendation and ranking metrics for implicit-feedback ALS without a GPU (api.ImplicitALS.recommend / ranking_metrics,
 csrc/host/als_implicit.hpp, include/hnh_topk.h; tests/als_topk_ref.py is the definition).
 
+The builders of hostile item orders (als_topk_common.ordered_case, used by tests/test_als_topk_edges_gpu.py): exact scores, the answers
+they are meant to have, one item per tile for "trickle", and an emulation of a lazily raised threshold (als_topk_common.lazy_cuts) that
+says at which (have, add) the candidate buffer is cut at the shapes the GPU tests use.
 The definition: topk() against a brute-force loop over the total order (with plenty of ties) and against torch.topk where no two scores
 are equal; the three metrics against values computed by hand on a six-user example (a user with more held-out items than k, a user whose
 list has -1 entries, a user with no hit).
@@ -15,6 +18,7 @@ import pytest
 import torch
 
 import als_implicit_ref as IR
+import als_topk_common as TC
 import als_topk_ref as TR
 import hnh_testlib as T
 from distributed_sddmm_amd import _kernels as K
@@ -101,6 +105,99 @@ def test_metrics_on_a_six_user_example():
     assert got["users"] == 6
     for name, value in want.items():
         assert abs(got[name] - value) <= 1e-15, (name, got[name], value)
+
+
+# ------------------------------------------------------------------------------------------------ the hostile item orders
+ORDERED_N = 16640  # the items of the GPU tests' long cases: 260 tiles
+
+
+@pytest.mark.parametrize("kind", TC.KINDS)
+def test_ordered_scores_are_exact_and_ordered_alike(kind):
+    nq, n, R = 5, 2000, 132
+    Q, Y = TC.ordered_case(kind, nq, n, R)
+    v = TC.ordered_values(kind, n)
+    assert Q.shape == (nq, R) and Y.shape == (n, R) and Q.flags.c_contiguous and Y.flags.c_contiguous
+    assert np.all((Q >= 1) & (Q <= 3) & (Q == np.rint(Q))) and np.array_equal(Y, np.outer(v, np.ones(R)))
+    S = Q @ Y.T
+    assert np.array_equal(S, np.outer(Q.sum(axis=1), v)) and np.array_equal(S, np.rint(S)), "every score is v_j * sum(Q[q]), an integer"
+    # ... and so is every partial sum, in any order of the products: |Q| <= 3 and the largest tested |v| bound them far below 2^53
+    assert 3 * 512 * (ORDERED_N + 1) < 2**53 and np.max(np.abs(TC.ordered_values(kind, ORDERED_N))) <= ORDERED_N
+    Q2, Y2 = TC.ordered_case(kind, nq, n, R)
+    assert Q2.tobytes() == Q.tobytes() and Y2.tobytes() == Y.tobytes(), "the builder is a function of its arguments"
+
+
+@pytest.mark.parametrize("k", [10, 64, 65, 128])
+def test_ordered_cases_have_the_answers_they_are_meant_to(k):
+    nq, n, R = 3, 2000, 4
+    rng = np.random.default_rng(k)
+    excluded = TC.random_lists(rng, nq, n)
+    excluded[0] = np.arange(n - 5, n)  # the five best of "ascending"
+    excluded[1] = np.arange(0, 7)      # the seven first of "flat"
+    for lists in (None, excluded):
+        left = [np.setdiff1d(np.arange(n), lists[q] if lists is not None else []) for q in range(nq)]
+        Q, Y = TC.ordered_case("ascending", nq, n, R)
+        ids, scores = TR.topk(Q, Y, k, 0, lists)
+        for q in range(nq):
+            assert np.array_equal(ids[q], left[q][::-1][:k]), "the last k ids that are left, descending"
+            assert np.array_equal(scores[q], ids[q] * Q[q].sum())
+        Q, Y = TC.ordered_case("flat", nq, n, R)
+        ids, scores = TR.topk(Q, Y, k, 0, lists)
+        for q in range(nq):
+            assert np.array_equal(ids[q], left[q][:k]) and np.all(scores[q] == 5 * Q[q].sum()), "the first k ids that are left"
+        Q, Y = TC.ordered_case("descending", nq, n, R)
+        ids, _ = TR.topk(Q, Y, k, 0, lists)
+        for q in range(nq):
+            assert np.array_equal(ids[q], left[q][:k])
+
+
+@pytest.mark.parametrize("k", [10, 64, 65, 100])
+def test_trickle_brings_one_item_per_tile(k):
+    n = ORDERED_N
+    v = TC.ordered_values("trickle", n)
+    tiles = n // TC.ITEM_TILE
+    spikes = np.array([TC.ITEM_TILE * t + (7 * t) % TC.ITEM_TILE for t in range(tiles)])
+    assert n % TC.ITEM_TILE == 0 and tiles == 260 and np.array_equal(v[spikes], np.arange(tiles) + 1) and np.all(np.delete(v, spikes) < 0)
+    assert len({int(s) % TC.ITEM_TILE for s in spikes[:64]}) == 64, "the spike visits every lane"
+    best = np.zeros(0, dtype=np.int64)  # the ids of the running first k, kept exactly: a sequential pass over the tiles
+    for t in range(tiles):
+        js = np.arange(TC.ITEM_TILE * t, TC.ITEM_TILE * (t + 1))
+        if t >= -(-k // TC.ITEM_TILE):  # from tile 1 on for k <= 64, from tile 2 on for k <= 128: before that there is no k-th best yet
+            kth = best[-1]  # (v has no ties: "ranks before" is v > v[kth])
+            assert len(best) == k and np.sum(v[js] > v[kth]) == 1 and v[spikes[t]] > v[kth], t
+        else:
+            assert len(best) < k
+        both = np.concatenate([best, js])
+        best = both[np.lexsort((both, -v[both]))][:k]
+    assert np.array_equal(best, spikes[::-1][:k]), "the top-k is the last k spikes"
+    Q, Y = TC.ordered_case("trickle", 2, n, 3)
+    ids, scores = TR.topk(Q, Y, k)
+    assert np.array_equal(ids, np.stack([spikes[::-1][:k]] * 2)) and np.array_equal(scores[1], v[ids[1]] * Q[1].sum())
+
+
+def test_the_orders_reach_the_cuts():
+    """If someone shrinks n or moves k, this says that the kernel's cut paths are no longer reached by the GPU tests' inputs."""
+    cap = lambda k: 128 if k <= 64 else 256  # noqa: E731  (topk_cap of hnh_topk_kernels.hpp)
+    trickle, ascending = TC.ordered_values("trickle", ORDERED_N), TC.ordered_values("ascending", ORDERED_N)
+    for k in (10, 64):
+        assert (128, 1) in TC.lazy_cuts(trickle, k, cap(k)), k
+    for k in (65, 100):
+        assert (256, 1) in TC.lazy_cuts(trickle, k, cap(k)), k
+    assert (128, 64) in TC.lazy_cuts(ascending, 64, cap(64)) and (128, 64) in TC.lazy_cuts(ascending, 10, cap(10))
+    assert (256, 64) in TC.lazy_cuts(ascending, 128, cap(128))
+    assert (193, 64) in TC.lazy_cuts(ascending, 65, cap(65)), "k + 2 tiles fit, the third does not"
+    # ascending cuts whenever the buffer is full, a last tile of 16 items included; descending and flat cut once: nothing passes the
+    # first threshold ...
+    assert TC.lazy_cuts(ascending[:2000], 64, 128) == {(128, 64), (128, 16)}
+    for kind in ("descending", "flat"):
+        assert TC.lazy_cuts(TC.ordered_values(kind, ORDERED_N), 10, 128) == {(128, 64)}, kind
+        assert TC.lazy_cuts(TC.ordered_values(kind, ORDERED_N), 100, 256) == {(256, 64)}, kind
+    # ... and the emulation itself on five tiles that can be followed by hand (k = 2, cap = 128; equal values: the smaller index first)
+    v = np.full(320, -1000)
+    v[[0, 1, 2]] = [5, 6, 7]  # tiles 0 and 1 fill the buffer; tile 2 cuts it at (128, 64) to {7, 6}, threshold (6, 1), and brings 64
+    v[192:255] = 100          # tile 3: 63 pass, 66 + 63 > 128: cut at (66, 63), the threshold stays (6, 1), have = 65
+    v[[260, 261]] = [6, 9]    # tile 4: 6 ties with the threshold at a larger index and fails, 9 passes, 66 fit
+    assert TC.lazy_cuts(v, 2, 128) == {(128, 64), (66, 63)}
+    assert TC.lazy_cuts(v[:192], 2, 128) == {(128, 64)} and TC.lazy_cuts(v[:128], 2, 128) == set()
 
 
 # ------------------------------------------------------------------------------------------------ the group and the host call

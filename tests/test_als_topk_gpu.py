@@ -8,7 +8,8 @@ item, fewer than k, exactly k, k + 1, either side of a 64-item tile, many tiles;
 16-byte loads), without lists and with random ones; with an empty list, a list that covers a whole item tile, one that leaves k - 1 items
 and one that excludes everything.  Guard zones around every buffer are intact and the inputs unchanged.  splits in {1, 2, 3, 7} and the
 library's choice, a query's position in a larger batch, and a second run all give the same bits.  Real operands pass check_topk at T.TOL.
-The merge and the gather on exact operands; the refusals by message.
+The merge and the gather on exact operands; the refusals by message.  (The helpers are in tests/als_topk_common.py; more splits, hostile
+item orders, odd bases and the larger merges: tests/test_als_topk_edges_gpu.py.)
 The operator on loopback ranks: every rank the same arrays, check_topk against numpy on the factors, p > 1 bit-identical to p = 1, no seen
 item with filter_seen, no padding id ever; ranking_metrics after two training steps on nine tenths of hub equals the definition."""
 import ctypes as C
@@ -22,6 +23,7 @@ import als_implicit_common as IC
 import als_implicit_ref as IR
 import als_topk_ref as TR
 import hnh_testlib as T
+from als_topk_common import Guarded, integers, random_lists, topk_rows
 from distributed_sddmm_amd import _kernels as K
 from distributed_sddmm_amd import api as H
 from gat_gpu_harness import ctx, hip_backend  # noqa: F401
@@ -36,76 +38,6 @@ KERNEL_CASES = [(0, 64, 2, 1), (1, 0, 8, 10), (15, 1, 17, 2), (16, 9, 8, 10), (1
                 (17, 65, 100, 64), (16, 1000, 128, 128), (70, 5000, 130, 10), (33, 1000, 256, 100), (15, 5000, 320, 10), (17, 1000, 512, 10),
                 (70, 5000, 8, 10), (1, 5000, 2, 1), (33, 65, 128, 128)]
 OPERATOR_CASES = [(8, 1, 1), (128, 1, 1), (128, 4, 1), (100, 5, 1), (100, 4, 2), (256, 4, 1)]
-GUARD = 128  # bytes in front of and behind every buffer (the buffers keep their alignment)
-FILL = 0xA5
-
-
-class Guarded:
-    """A device buffer of any dtype with guard bytes on both sides"""
-
-    def __init__(self, ctx, arr):
-        arr = np.ascontiguousarray(arr)
-        self.shape, self.dtype, self.nbytes = arr.shape, arr.dtype, arr.nbytes
-        flat = np.concatenate([np.full(GUARD, FILL, np.uint8), arr.reshape(-1).view(np.uint8), np.full(GUARD + (-arr.nbytes) % 16, FILL, np.uint8)])
-        self.dev = ctx.upload(flat)
-        self.ptr = self.dev.ptr + GUARD
-
-    def get(self):
-        flat = self.dev.get()
-        assert np.all(flat[:GUARD] == FILL) and np.all(flat[GUARD + self.nbytes:] == FILL), "guard bytes overwritten"
-        return flat[GUARD:GUARD + self.nbytes].view(self.dtype).reshape(self.shape).copy()
-
-    def free(self):
-        self.dev.free()
-
-
-def csr_of(excluded, nq):
-    ptr = np.zeros(nq + 1, dtype=np.int64)
-    for q in range(nq):
-        ptr[q + 1] = ptr[q] + len(excluded[q])
-    idx = np.concatenate([np.asarray(e, dtype=np.int32) for e in excluded] + [np.zeros(0, np.int32)]).astype(np.int32)
-    return ptr, idx
-
-
-def topk_rows(ctx, Q, Y, k, id_base=0, excluded=None, splits=0):
-    """hnh_topk_rows_f64 with guard zones around every buffer; checks that they are intact and the inputs unchanged"""
-    lib = K.load()
-    nq, R = Q.shape
-    n = Y.shape[0]
-    need = lib.hnh_topk_rows_f64_workspace(nq, n, R, k)
-    assert need >= 0
-    bufs = dict(Q=Guarded(ctx, Q if nq else np.zeros((1, R))), Y=Guarded(ctx, Y if n else np.zeros((1, R))),
-                s=Guarded(ctx, np.full((max(nq, 1), k), 7.5)), i=Guarded(ctx, np.full((max(nq, 1), k), -7, np.int64)),
-                work=Guarded(ctx, np.zeros(max(need, 16), np.uint8)))
-    ptr = idx = None
-    if excluded is not None:
-        ptr, idx = csr_of(excluded, nq)
-        bufs["ptr"], bufs["idx"] = Guarded(ctx, ptr), Guarded(ctx, idx if len(idx) else np.zeros(1, np.int32))
-    rc = lib.hnh_topk_rows_f64(ctx.h, bufs["Q"].ptr, nq, bufs["Y"].ptr, n, R, id_base, bufs["ptr"].ptr if excluded is not None else None,
-                               bufs["idx"].ptr if excluded is not None else None, k, splits, bufs["s"].ptr, bufs["i"].ptr, bufs["work"].ptr, need,
-                               K.STREAM_COMPUTE)
-    ctx.check(rc, "hnh_topk_rows_f64")
-    got = {name: b.get() for name, b in bufs.items()}
-    for b in bufs.values():
-        b.free()
-    if nq:
-        assert np.array_equal(got["Q"], Q)
-    else:
-        assert np.all(got["s"] == 7.5) and np.all(got["i"] == -7), "nothing is written without a query"
-    if n:
-        assert np.array_equal(got["Y"], Y)
-    if excluded is not None:
-        assert np.array_equal(got["ptr"], ptr) and (len(idx) == 0 or np.array_equal(got["idx"], idx))
-    return got["i"][:nq], got["s"][:nq]
-
-
-def integers(rng, shape):
-    return rng.integers(-4, 5, shape).astype(np.float64)
-
-
-def random_lists(rng, nq, n):
-    return [np.sort(rng.choice(n, size=int(rng.integers(0, n + 1)) if n < 40 else int(rng.integers(0, 40)), replace=False)) if n else np.zeros(0, np.int64)
-            for _ in range(nq)]
 
 
 # ------------------------------------------------------------------------------------------------ the kernel, exact

@@ -842,6 +842,10 @@ int hnh_vec_div_f64(hnh_ctx* c, double* out, const double* num, const double* de
 
 /* gat.hpp:88 (Eigen dense product), :96-97, :103 */
 int hnh_gemm_f64(hnh_ctx* c, int64_t M, int64_t N, int64_t K, const double* A, const double* B, double* C, int stream) {
+    /* the refusals of the HIP library, word for word; K = 0 stores zeros and reads neither operand (they may be null) */
+    if (M < 0 || N < 0 || K < 0) return fail(c, HNH_ERR_INVALID, "hnh_gemm_f64: negative size");
+    if (M == 0 || N == 0) return HNH_OK;
+    if (!C || (K > 0 && (!A || !B))) return fail(c, HNH_ERR_INVALID, "hnh_gemm_f64: null pointer");
     HB_OP(c, stream, "hnh_gemm_f64");
     HB_R(A, (size_t)M * K * sizeof(double));
     HB_R(B, (size_t)K * N * sizeof(double));

@@ -270,6 +270,18 @@ TOPK_SIGNATURES = {
 TOPK_MAX_K, TOPK_MAX_R, TOPK_MAX_SPLITS = 128, 512, 1024  # HNH_TOPK_MAX_*
 
 
+# include/hnh_rank.h: exact item ranks for implicit-feedback ALS (api.ImplicitALS.rank_of): counting on the score tile, the scores of single
+# pairs and the subtraction of excluded entries; a further OPTIONAL group bound only for the product library.  tgt_ptr of hnh_rank_rows_f64
+# is a HOST array.
+RANK_SIGNATURES = {
+    "hnh_pair_scores_f64": (_i32, [_vp, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _i64, _vp, _i32]),
+    "hnh_rank_rows_f64_workspace": (_i64, [_i64, _i64, _i64, _i32]),
+    "hnh_rank_rows_f64": (_i32, [_vp, _vp, _i64, _vp, _i64, _i32, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _i64, _i32]),
+    "hnh_rank_exclude_f64": (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32]),
+}
+RANK_MAX_R, RANK_MAX_TARGETS, RANK_MAX_SPLITS = 512, 16, 1024  # HNH_RANK_MAX_*
+
+
 class GramCg(C.Structure):
     """struct hnh_gram_cg"""
     _fields_ = [("x", _vp), ("r", _vp), ("p", _vp), ("rs", _vp)]
@@ -449,7 +461,7 @@ def load(path: str | None = None) -> C.CDLL:
                 list(V2_SIGNATURES.items()) + list(ATTN_COEF_SIGNATURES.items()) + list(SKIP_SIGNATURES.items()) + \
                 list(QKV_SIGNATURES.items()) + list(EDGE_SIGNATURES.items()) + list(EDGE_GRAD_SIGNATURES.items()) + \
                 list(NORM_SIGNATURES.items()) + list(MULTILABEL_SIGNATURES.items()) + list(TRAIN_CLIP_SIGNATURES.items()) + \
-                list(ALS_IMPLICIT_SIGNATURES.items()) + list(TOPK_SIGNATURES.items()):
+                list(ALS_IMPLICIT_SIGNATURES.items()) + list(TOPK_SIGNATURES.items()) + list(RANK_SIGNATURES.items()):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
     if path is None:

@@ -132,6 +132,7 @@ SIGNATURES = {
     "hnh_ials_gram": (_i32, [_vp, _i32, _vp]),
     "hnh_ials_set_folded": (_i32, [_vp, _i32]),
     "hnh_ials_recommend": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp, _vp]),
+    "hnh_ials_rank_of": (_i32, [_vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp]),
     "hnh_gat_create": (_i32, [_vp, _i32, _pi32, _dbl, _pvp]),
     "hnh_gat_destroy": (_i32, [_vp]),
     "hnh_gat_weight_shape": (_i32, [_vp, _i32, _i32, _pi64]),
@@ -831,6 +832,61 @@ class ImplicitALS:
         n_users = len(users)
         return dict(precision=float(hits_total / m_total) if m_total else 0.0, map=float(ap_sum / n_users) if n_users else 0.0,
                     ndcg=float(ndcg_sum / n_users) if n_users else 0.0, users=n_users)
+
+    def _rank_of(self, users, items, filter_seen):
+        users = np.ascontiguousarray(np.asarray(users, dtype=np.int64).reshape(-1))
+        items = np.ascontiguousarray(np.asarray(items, dtype=np.int64).reshape(-1))
+        if len(users) != len(items):
+            raise ValueError("rank_of needs as many users as items")
+        ranks, candidates, in_seen = (np.empty(len(users), dtype=np.int64) for _ in range(3))
+        _check(lib().hnh_ials_rank_of(self.h, users.ctypes.data, items.ctypes.data, len(users), int(bool(filter_seen)), ranks.ctypes.data,
+                                      candidates.ctypes.data, in_seen.ctypes.data), "ials_rank_of")
+        return ranks, candidates, in_seen
+
+    def rank_of(self, users, items, filter_seen: bool = True):
+        """The exact position of items[i] in users[i]'s full ordering of all N items by <a_u, b_j> (score descending, then item id
+        ascending: recommend's order), for pairs in global coordinates, repeats allowed: (ranks int64 [n], candidates int64 [n]).
+        ranks[i] counts the user's candidates other than items[i] that rank before it, 0-based: for an item the user has not seen it is
+        the item's index in recommend(user, k = all, filter_seen).  candidates[i] is N, or with filter_seen (the items of the user's row
+        of S are no candidates, the asked item always is) N - |seen_u \\ {items[i]}|: 0 <= ranks[i] < candidates[i].  Counted on the device
+        from the scores' own bits: no score matrix is formed anywhere.  Collective: every rank passes the same pairs and gets the same
+        arrays."""
+        return self._rank_of(users, items, filter_seen)[:2]
+
+    def rank_metrics(self, test_rows, test_cols, batch: int = 1024, filter_seen: bool = True) -> dict:
+        """mpr, auc and mrr of held-out pairs in global coordinates (duplicates are dropped), the same on every rank, from rank_of's
+        integers by host arithmetic; the users are ranked in batches of `batch`.  With L_u the held-out items of user u, h = |L_u|:
+        mpr = the mean over the pairs of rank / (candidates - 1), 0 where candidates == 1: the expected percentile rank of Hu, Koren and
+        Volinsky with r_ui = 1; 0 is best, 0.5 is random.
+        auc = the mean over the users of 1 - (sum_t rank_t - h (h - 1) / 2) / (h neg), neg = N - |seen_u \\ L_u| - h the items that are
+        neither seen nor held out (N - h without filter_seen): the share of (held-out, other) pairs that are ordered rightly.
+        mrr = the mean over the users of 1 / (1 + min_t rank_t).
+        A user with neg == 0 has nothing to be ranked against: it is left out of auc and mrr, and `users` counts the others; `pairs`
+        counts every distinct pair.  The three sums are exactly rounded (math.fsum): they do not depend on `batch` or the pairs' order."""
+        import math
+        test_rows = np.asarray(test_rows, dtype=np.int64).reshape(-1)
+        test_cols = np.asarray(test_cols, dtype=np.int64).reshape(-1)
+        if len(test_rows) != len(test_cols) or batch < 1:
+            raise ValueError("rank_metrics needs as many rows as columns and batch >= 1")
+        pairs = np.unique(np.stack([test_rows, test_cols], axis=1), axis=0) if len(test_rows) else np.zeros((0, 2), np.int64)
+        rows, cols = pairs[:, 0], pairs[:, 1]
+        users, starts = np.unique(rows, return_index=True)
+        ends = np.append(starts[1:], len(rows))
+        pr, auc, rr = [], [], []
+        for b in range(0, len(users), batch):
+            lo, hi = int(starts[b]), int(ends[min(b + batch, len(users)) - 1])
+            ranks, cand, in_seen = self._rank_of(rows[lo:hi], cols[lo:hi], filter_seen)
+            pr += [r / (c - 1) if c > 1 else 0.0 for r, c in zip(ranks.tolist(), cand.tolist())]
+            for u in range(b, min(b + batch, len(users))):
+                s, e = int(starts[u]) - lo, int(ends[u]) - lo
+                h = e - s
+                neg = int(cand[s] - in_seen[s] + in_seen[s:e].sum()) - h
+                if neg <= 0:
+                    continue
+                auc.append(1.0 - (int(ranks[s:e].sum()) - h * (h - 1) // 2) / (h * neg))
+                rr.append(1.0 / (1 + int(ranks[s:e].min())))
+        return dict(mpr=math.fsum(pr) / len(pr) if pr else 0.0, auc=math.fsum(auc) / len(auc) if auc else 0.0,
+                    mrr=math.fsum(rr) / len(rr) if rr else 0.0, users=len(auc), pairs=len(pr))
 
     def free(self):
         if self.h:

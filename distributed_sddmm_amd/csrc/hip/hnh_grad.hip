@@ -381,3 +381,4 @@ int hnh_transpose_into_f64(hnh_ctx* ctx, double* dst, int64_t ld_dst, int64_t ro
 #include "hnh_multilabel_kernels.hpp"  // the multi-label head (include/hnh_train_multilabel.h): sigmoid cross-entropy and the micro-F1 counts
 #include "hnh_als_implicit_kernels.hpp"  // implicit-feedback ALS (include/hnh_als_implicit.h): the Gram term and the guarded CG update of a row tile
 #include "hnh_topk_kernels.hpp"  // top-k recommendation (include/hnh_topk.h): fused scores and selection, the merge of lists, a row gather
+#include "hnh_rank_kernels.hpp"  // exact item ranks (include/hnh_rank.h): counting on the score tile, the scores of pairs, the subtraction of excluded entries

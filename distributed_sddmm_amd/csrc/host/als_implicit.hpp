@@ -32,6 +32,10 @@
 // and merged by hnh_topk_merge_f64.  A score's bits depend on its two rows and R only, and the order is strict, so every rank count gives
 // the same bits.  The exclusion lists come from the GLOBAL coordinates of the rank's stored pairs, which the schedule does not keep: they
 // are read back once, by two SDDMM calls on probe matrices (row ids against ones, ones against column ids), and cached in the object.
+//
+// Evaluation.  rank_of() returns the exact position of an item in a user's full ordering of all N items (the order of recommend) by
+// COUNTING on the device (include/hnh_rank.h: the top-k kernel's product loop with a counting epilogue, no score stored); the counts are
+// integers and additive over the ranks' rows of B, so every rank count gives the same numbers.  AUC, MPR and MRR are host arithmetic on them.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -287,6 +291,148 @@ public:
         merged.copy_to_host(host.data());
         std::memcpy(scores_host, host.data(), (size_t)list * sizeof(double));
         std::memcpy(ids_host, host.data() + list, (size_t)list * sizeof(int64_t));
+    }
+
+    // The exact position of items[i] in users[i]'s full ordering of the items, for n (user, item) pairs in global coordinates (repeats
+    // allowed): ranks_host[i] = the number of items that rank before items[i] in the total order of include/hnh_topk.h among the user's
+    // candidates other than the item itself, and candidates_host[i] = the number of those candidates plus the item: N, or with filter_seen
+    // N - |seen_u \ {item}| (the items of the user's row of S are no candidates, the asked item always is), so 0 <= rank < candidates.
+    // For an item the user has not seen this is its index in recommend(user, k = infinity, filter_seen), bit for bit: the target's score
+    // (hnh_pair_scores_f64) and the scores it is compared with (hnh_rank_rows_f64) carry the bits that hnh_topk_rows_f64 returns.
+    // in_seen_host (or null) receives 1 where filter_seen and the item is in the user's row of S, else 0.
+    // Every rank counts over its own valid rows of B; with filter_seen it scores its share of the users' seen items with
+    // hnh_pair_scores_f64 and subtracts those that rank before the target (hnh_rank_exclude_f64): the counting kernel searches nothing.
+    // The counts are summed over the ranks on the host, as doubles (they stay below 2^53).  COLLECTIVE: every rank passes the same pairs
+    // and receives the same arrays, the same integers for every rank count.  There is no host fallback: a kernel library without
+    // include/hnh_rank.h is refused.
+    void rank_of(const int64_t* users, const int64_t* items, int64_t n, bool filter_seen, int64_t* ranks_host, int64_t* candidates_host,
+                 int64_t* in_seen_host = nullptr) {
+        require_embeddings("rank_of");
+        hnh::World* w = d_ops->world;
+        hnh::Backend* be = w->be;
+        const int R = (int)d_ops->R;
+        if (n < 0 || (n > 0 && (users == nullptr || items == nullptr || ranks_host == nullptr || candidates_host == nullptr)))
+            throw hnh::Error("Error, Implicit_ALS rank_of needs n >= 0 and its four arrays!");
+        for (int64_t i = 0; i < n; i++) {
+            if (users[i] < 0 || users[i] >= d_ops->M)
+                throw hnh::Error("Error, Implicit_ALS rank_of: user " + std::to_string(users[i]) + " is outside [0, M = " + std::to_string(d_ops->M) + ")!");
+            if (items[i] < 0 || items[i] >= d_ops->N)
+                throw hnh::Error("Error, Implicit_ALS rank_of: item " + std::to_string(items[i]) + " is outside [0, N = " + std::to_string(d_ops->N) + ")!");
+        }
+        if (R > HNH_RANK_MAX_R)
+            throw hnh::Error("Error, Implicit_ALS rank_of supports R <= HNH_RANK_MAX_R = " + std::to_string(HNH_RANK_MAX_R) + ", not R = " + std::to_string(R) + "!");
+        if (be->hnh_rank_rows_f64 == nullptr || be->hnh_rank_rows_f64_workspace == nullptr || be->hnh_pair_scores_f64 == nullptr ||
+            be->hnh_rank_exclude_f64 == nullptr)
+            throw hnh::Error(be->missing_kernel("Implicit_ALS rank_of", "hnh_rank_rows_f64"));
+        if (be->hnh_take_rows_f64 == nullptr) throw hnh::Error(be->missing_kernel("Implicit_ALS rank_of", "hnh_take_rows_f64"));
+        if (n == 0) return;
+        const DenseSubmatrix& subA = d_ops->aSubmatrices[0];
+        const DenseSubmatrix& subB = d_ops->bSubmatrices[0];
+        const int64_t topB = subB.topRow;
+        const int64_t validB = std::max<int64_t>(0, std::min<int64_t>(subB.rowCount, d_ops->N - topB));
+
+        // the pairs grouped by user: target slot t holds pair order[t]; a user with more than HNH_RANK_MAX_TARGETS pairs gets several query rows
+        std::vector<int64_t> order((size_t)n);
+        for (int64_t i = 0; i < n; i++) order[(size_t)i] = i;
+        std::stable_sort(order.begin(), order.end(), [&](int64_t a, int64_t b) { return users[a] < users[b]; });
+        std::vector<int64_t> row_user, tgt_ptr(1, 0), tgt_id((size_t)n), pair_q((size_t)n), pair_j((size_t)n);
+        for (int64_t t = 0; t < n; t++) {
+            const int64_t i = order[(size_t)t];
+            if (t == 0 || users[i] != row_user.back() || t - tgt_ptr[tgt_ptr.size() - 2] == HNH_RANK_MAX_TARGETS) {
+                row_user.push_back(users[i]);
+                tgt_ptr.push_back(t);
+            }
+            tgt_ptr.back() = t + 1;
+            const int64_t local = items[i] - topB;
+            tgt_id[(size_t)t] = items[i];
+            pair_q[(size_t)t] = (int64_t)row_user.size() - 1;
+            pair_j[(size_t)t] = (local >= 0 && local < validB) ? local : -1;  // (an item of another rank scores +0.0 here)
+        }
+        const int64_t nq = (int64_t)row_user.size();
+
+        // the query rows of A, as in recommend: the same bits on every rank
+        std::vector<int64_t> idx((size_t)nq);
+        for (int64_t q = 0; q < nq; q++) {
+            const int64_t local = row_user[(size_t)q] - subA.topRow;
+            idx[(size_t)q] = (local >= 0 && local < subA.rowCount) ? local : -1;
+        }
+        auto upload = [&](const std::vector<int64_t>& host) {  // (a DenseMatrix that holds int64; never empty)
+            DenseMatrix dev(std::max<int64_t>((int64_t)host.size(), 1), 1);
+            if (!host.empty()) w->copy(dev.data(), host.data(), host.size() * sizeof(int64_t), HNH_COPY_H2D, HNH_STREAM_COMPUTE);
+            return dev;
+        };
+        DenseMatrix idx_d = upload(idx), Qd(nq, R);
+        w->check(be->hnh_take_rows_f64(w->ctx, A.data(), subA.rowCount, R, reinterpret_cast<const int64_t*>(idx_d.data()), nq, Qd.data(), HNH_STREAM_COMPUTE),
+                 "hnh_take_rows_f64");
+        w->allreduce_f64(w->world_comm(), Qd.data(), (size_t)(nq * R), HNH_STREAM_COMPUTE);
+
+        // the targets' scores: the rank that holds the item computes it, the others add +0.0 (at most the sign of a zero changes)
+        DenseMatrix tgt_ptr_d = upload(tgt_ptr), tgt_id_d = upload(tgt_id), pair_q_d = upload(pair_q), pair_j_d = upload(pair_j), tgt_score(n, 1), counts(n, 1);
+        w->check(be->hnh_pair_scores_f64(w->ctx, Qd.data(), nq, B.data(), validB, R, reinterpret_cast<const int64_t*>(pair_q_d.data()),
+                                         reinterpret_cast<const int64_t*>(pair_j_d.data()), n, tgt_score.data(), HNH_STREAM_COMPUTE),
+                 "hnh_pair_scores_f64");
+        w->allreduce_f64(w->world_comm(), tgt_score.data(), (size_t)n, HNH_STREAM_COMPUTE);
+
+        // the count over this rank's valid rows of B (the padding rows are never candidates)
+        const int64_t need = be->hnh_rank_rows_f64_workspace(nq, validB, n, 0);
+        if (need < 0) throw hnh::Error("Error, Implicit_ALS rank_of: hnh_rank_rows_f64_workspace refuses the shape!");
+        DenseMatrix work(std::max<int64_t>((need + 7) / 8, 2), 1);
+        w->check(be->hnh_rank_rows_f64(w->ctx, Qd.data(), nq, B.data(), validB, R, topB, tgt_ptr.data(), tgt_score.data(),
+                                       reinterpret_cast<const int64_t*>(tgt_id_d.data()), 0, reinterpret_cast<int64_t*>(counts.data()), work.data(),
+                                       work.size() * 8, HNH_STREAM_COMPUTE),
+                 "hnh_rank_rows_f64");
+
+        // [counts | is the item seen | the user's seen items], this rank's share of each, summed over the ranks below
+        std::vector<double> sums((size_t)(3 * n), 0.0);
+        if (filter_seen) {
+            std::vector<int64_t> ptr;
+            std::vector<int32_t> seen;
+            seen_lists(row_user.data(), nq, topB, validB, ptr, seen);
+            const int64_t ne = (int64_t)seen.size();
+            std::vector<int64_t> ex_q((size_t)ne), ex_j((size_t)ne), ex_id((size_t)ne);
+            for (int64_t q = 0; q < nq; q++)
+                for (int64_t e = ptr[(size_t)q]; e < ptr[(size_t)q + 1]; e++) {
+                    ex_q[(size_t)e] = q;
+                    ex_j[(size_t)e] = seen[(size_t)e];
+                    ex_id[(size_t)e] = topB + seen[(size_t)e];
+                }
+            if (ne > 0) {
+                DenseMatrix ptr_d = upload(ptr), ex_q_d = upload(ex_q), ex_j_d = upload(ex_j), ex_id_d = upload(ex_id), ex_score(ne, 1);
+                w->check(be->hnh_pair_scores_f64(w->ctx, Qd.data(), nq, B.data(), validB, R, reinterpret_cast<const int64_t*>(ex_q_d.data()),
+                                                 reinterpret_cast<const int64_t*>(ex_j_d.data()), ne, ex_score.data(), HNH_STREAM_COMPUTE),
+                         "hnh_pair_scores_f64");
+                w->check(be->hnh_rank_exclude_f64(w->ctx, nq, reinterpret_cast<const int64_t*>(ptr_d.data()), ex_score.data(),
+                                                  reinterpret_cast<const int64_t*>(ex_id_d.data()), reinterpret_cast<const int64_t*>(tgt_ptr_d.data()),
+                                                  tgt_score.data(), reinterpret_cast<const int64_t*>(tgt_id_d.data()),
+                                                  reinterpret_cast<int64_t*>(counts.data()), HNH_STREAM_COMPUTE),
+                         "hnh_rank_exclude_f64");
+                w->sync(HNH_STREAM_COMPUTE);  // (the uploaded lists go out of scope)
+            }
+            for (int64_t q = 0; q < nq; q++) {
+                const int32_t* first = seen.data() + ptr[(size_t)q];
+                const int32_t* last = seen.data() + ptr[(size_t)q + 1];
+                for (int64_t t = tgt_ptr[(size_t)q]; t < tgt_ptr[(size_t)q + 1]; t++) {
+                    const int64_t j = pair_j[(size_t)t];
+                    sums[(size_t)(n + t)] = (j >= 0 && std::binary_search(first, last, (int32_t)j)) ? 1.0 : 0.0;
+                    sums[(size_t)(2 * n + t)] = (double)(last - first);
+                }
+            }
+        }
+        std::vector<double> got((size_t)n);
+        counts.copy_to_host(got.data());  // (int64 in a DenseMatrix; waits for the stream: the host arrays above may go)
+        for (int64_t t = 0; t < n; t++) {
+            int64_t c;
+            std::memcpy(&c, &got[(size_t)t], sizeof(c));
+            sums[(size_t)t] = (double)c;
+        }
+        w->host_allreduce_sum(sums.data(), sums.size());
+        for (int64_t t = 0; t < n; t++) {
+            const int64_t i = order[(size_t)t];
+            const int64_t in_seen = (int64_t)std::llround(sums[(size_t)(n + t)]);
+            ranks_host[i] = (int64_t)std::llround(sums[(size_t)t]);
+            candidates_host[i] = d_ops->N - ((int64_t)std::llround(sums[(size_t)(2 * n + t)]) - in_seen);
+            if (in_seen_host != nullptr) in_seen_host[i] = in_seen;
+        }
     }
 
 private:

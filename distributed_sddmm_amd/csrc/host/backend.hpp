@@ -25,6 +25,7 @@
 #include "hnh_train_multilabel.h"
 #include "hnh_als_implicit.h"
 #include "hnh_topk.h"
+#include "hnh_rank.h"
 #ifdef HNH_MEASUREMENT_AIDS
 #include "hnh_measurement_aids.h"
 #endif
@@ -67,6 +68,7 @@
 //   hnh_train_clip.h: the GAT's gradient clipping and its AdamW optimizer
 //   hnh_als_implicit.h: Implicit_ALS in folded mode
 //   hnh_topk.h: Implicit_ALS::recommend
+//   hnh_rank.h: Implicit_ALS::rank_of
 #define HNH_OPTIONAL_KERNELS(X) \
     X("include/hnh_grad.h", hnh_gemm_tn_f64_workspace) X("include/hnh_grad.h", hnh_gemm_tn_f64) X("include/hnh_grad.h", hnh_leaky_relu_grad_f64) X("include/hnh_grad.h", hnh_relu_grad_cols_f64) \
     X("include/hnh_grad.h", hnh_sum3_cols_f64) X("include/hnh_grad.h", hnh_transpose_into_f64) X("include/hnh_grad.h", hnh_act_grad_cols_f64) \
@@ -87,7 +89,8 @@
     X("include/hnh_train_multilabel.h", hnh_bce_rows_f64_workspace) X("include/hnh_train_multilabel.h", hnh_bce_rows_f64) \
     X("include/hnh_train_clip.h", hnh_grad_sumsq_f64_workspace) X("include/hnh_train_clip.h", hnh_grad_sumsq_f64) X("include/hnh_train_clip.h", hnh_optim_step_clip_f64) \
     X("include/hnh_als_implicit.h", hnh_gram_rows_f64) \
-    X("include/hnh_topk.h", hnh_topk_rows_f64_workspace) X("include/hnh_topk.h", hnh_topk_rows_f64) X("include/hnh_topk.h", hnh_topk_merge_f64) X("include/hnh_topk.h", hnh_take_rows_f64)
+    X("include/hnh_topk.h", hnh_topk_rows_f64_workspace) X("include/hnh_topk.h", hnh_topk_rows_f64) X("include/hnh_topk.h", hnh_topk_merge_f64) X("include/hnh_topk.h", hnh_take_rows_f64) \
+    X("include/hnh_rank.h", hnh_pair_scores_f64) X("include/hnh_rank.h", hnh_rank_rows_f64_workspace) X("include/hnh_rank.h", hnh_rank_rows_f64) X("include/hnh_rank.h", hnh_rank_exclude_f64)
 
 namespace hnh {
 

@@ -770,6 +770,10 @@ int hnh_ials_set_folded(hnh_ials* a, int folded) {
 int hnh_ials_recommend(hnh_ials* a, const int64_t* users, int64_t nq, int k, int filter_seen, int64_t* ids, double* scores) {
     return guarded(a->w, [&] { a->a->recommend(users, nq, k, filter_seen != 0, ids, scores); });
 }
+int hnh_ials_rank_of(hnh_ials* a, const int64_t* users, const int64_t* items, int64_t n, int filter_seen, int64_t* ranks, int64_t* candidates,
+                     int64_t* in_seen) {
+    return guarded(a->w, [&] { a->a->rank_of(users, items, n, filter_seen != 0, ranks, candidates, in_seen); });
+}
 
 // ------------------------------------------------------------------ GAT
 int hnh_gat_create(hnh_dist* d, int nlayers, const int* spec3, double alpha, hnh_gat** out) {

@@ -239,6 +239,15 @@ int hnh_ials_set_folded(hnh_ials* a, int folded);                     /* 1: hnh_
  * left.  filter_seen != 0: the items of the user's row of S are never returned.  Collective: every rank passes the same users and gets
  * the same result, bit-identical for every rank count.  Needs include/hnh_topk.h (an optional group; there is no host fallback). */
 int hnh_ials_recommend(hnh_ials* a, const int64_t* users, int64_t nq, int k, int filter_seen, int64_t* ids, double* scores);
+/* The exact position of items[i] in users[i]'s full ordering of all N items (the order of hnh_ials_recommend), for n pairs in global
+ * coordinates, repeats allowed.  ranks[i]: the number of the user's candidates, other than items[i] itself, that rank before items[i],
+ * 0-based; for an item the user has not seen it is the item's index in hnh_ials_recommend's list with k = infinity.  candidates[i]: N, or
+ * with filter_seen != 0 (the items of the user's row of S are no candidates, the asked item always is) N - |seen_u \ {items[i]}|, so that
+ * 0 <= ranks[i] < candidates[i].  in_seen (or NULL): 1 where filter_seen != 0 and items[i] is in the user's row of S, else 0.  Host
+ * arrays of n int64.  Collective: every rank passes the same pairs and gets the same arrays, the same integers for every rank count.
+ * Needs include/hnh_rank.h (an optional group; there is no host fallback) and R <= HNH_RANK_MAX_R. */
+int hnh_ials_rank_of(hnh_ials* a, const int64_t* users, const int64_t* items, int64_t n, int filter_seen, int64_t* ranks, int64_t* candidates,
+                     int64_t* in_seen);
 
 /* ---- GAT forward pass (gat.hpp; BASELINE config 5's second application) */
 typedef struct hnh_gat hnh_gat; /* GAT */

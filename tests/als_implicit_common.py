@@ -73,8 +73,14 @@ def rank_run(world, c, case, folded, steps=STEPS, iters=ITERS):
 
 def run_case(g, R, p, c, folded):
     """One case on the loaded backend, held to the model at T.TOL; returns the assembled factors, Gram matrices and losses."""
+    return run_inputs(IR.inputs(g, R), IR.expected(g, R), p, c, folded, g)[0]
+
+
+def run_inputs(case, want, p, c, folded, g=None):
+    """run_case on given inputs and their expected results (tests/gram_cases.py varies the weights and the factors): returns (the
+    assembled results, every rank's own with its whole local blocks)."""
+    g, R = g or case["name"], case["R"]
     assert T.valid_config(ALG, p, c, R)
-    case, want = IR.inputs(g, R), IR.expected(g, R)
     per_rank = H.run_spmd(p, lambda w: rank_run(w, c, case, folded))
     got = dict(A=T.assemble_dense(per_rank, "A", "subA", case["M"], R), B=T.assemble_dense(per_rank, "B", "subB", case["N"], R),
                losses=per_rank[0]["losses"], gramA=per_rank[0]["gramA"], gramB=per_rank[0]["gramB"])
@@ -86,4 +92,4 @@ def run_case(g, R, p, c, folded):
         assert T.rel(o["gramA"], per_rank[0]["gramA"]) <= 1e-15 and T.rel(o["gramB"], per_rank[0]["gramB"]) <= 1e-15
     for name, e in errs.items():
         assert e <= T.TOL, (g, R, p, c, folded, name, e)
-    return got
+    return got, per_rank

@@ -80,8 +80,8 @@ class NormCase:
     the last row are guards), stats, dgamma, dbeta and work with a guard double on either side.  odd=True moves every matrix base by one
     element and makes the pitches odd: 8-byte lanes."""
 
-    def __init__(self, ctx, rows, cols, z, gamma, beta, g, odd):
-        self.ctx, self.rows, self.cols, self.odd = ctx, rows, cols, odd
+    def __init__(self, ctx, rows, cols, z, gamma, beta, g, odd, eps=EPS):
+        self.ctx, self.rows, self.cols, self.odd, self.eps = ctx, rows, cols, odd, eps
         pad = (lambda v: v + 1 - v % 2) if odd else (lambda v: v + v % 2)
         self.ld_z, self.ld_o, self.ld_g, self.ld_dz = pad(cols + 4), pad(cols + 6), pad(cols + 2), pad(cols + 8)
         self.off = 1 if odd else 0
@@ -123,7 +123,7 @@ class NormCase:
         lib, ctx = self.ctx.lib, self.ctx
         dst = "z" if in_place else "out"
         rc = lib.hnh_layernorm_fwd_f64(ctx.h, self.ptr(dst), self.ld(dst), self.ptr("z"), self.ld_z, self.ptr("stats"), self.ptr("gamma"), self.ptr("beta"),
-                                       self.rows, self.cols, EPS, R.ACT_CODE[act], K.STREAM_COMPUTE)
+                                       self.rows, self.cols, self.eps, R.ACT_CODE[act], K.STREAM_COMPUTE)
         assert rc == expect, (rc, lib.hnh_last_error(ctx.h))
         ctx.sync()
         out, ok = self.matrix(dst)
